@@ -1,8 +1,13 @@
 #!/usr/bin/env python3
 """bench.py -- full-feature extraction throughput of the fused HIP sweep on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the line; everything else it can measure (the CPU baselines, the
+secondary workloads, the measured read ceiling, the adjacency-collect time, the global pair-list gather of N > 1) runs only
+with --full.  --dump-outputs DIR writes what the last timed step computed -- the arrays SlabJob.result_arrays() hands a
+caller -- as DIR/<name>.npy in float64 (the inputs are seeded: the same arguments give the same inputs on every run).
 
 A "step" is one pass of the hot path over one synthetic labelled volume that is already resident
 in HBM: accumulator init + fused sweep + adjacency collection (+ for N > 1 the per-label RCCL
@@ -18,12 +23,13 @@ idled -- the synthetic volume is generated and the CPU baseline computed before 
 milliseconds of work to reach its sustained clock, and K steps of ~1 ms would otherwise measure the ramp.
 
 Rank 0 prints ONE JSON line (contract in the task description), with extra objects:
-  roofline     -- the sweep kernel's algorithmic bytes / its mean HIP-event duration vs 8 TB/s, plus
-                  `peak_measured`: what a trivial 16-B/lane read-reduce kernel reaches on the same buffer in this run
-  cpu_baseline -- the per-label scipy restatement of the reference (oracle/, 1 core) timed on a
+  roofline     -- the sweep kernel's algorithmic bytes / its mean HIP-event duration vs 8 TB/s (events of the timed steps);
+                  with --full also `peak_measured`: what a trivial 16-B/lane read-reduce kernel reaches on the same buffer
+                  in this run, and `adjacency_collect_ms`
+  cpu_baseline -- (--full) the per-label scipy restatement of the reference (oracle/, 1 core) timed on a
                   bounded crop of the same volume on this node's host (rank 0, N = 1 only); `best_effort`
                   inside it = the one-pass C restatement on 16 host processes (NOT the reference's algorithm)
-  secondary    -- (N = 1) the same volume WITHOUT the ellipsoid mask: tissue everywhere, ~50k labels present,
+  secondary    -- (--full; N = 1) the same volume WITHOUT the ellipsoid mask: tissue everywhere, ~50k labels present,
                   2.6x the event density of the headline workload (its fraction is also `roofline.frac_50k_labels`); the
                   headline workload with two steps in flight (what N > 1 runs), so that a scaling curve compares like with
                   like; `sorted_adjacency_ms`: what a caller of ta_adjacency_get pays on top of a step (device sort by
@@ -99,6 +105,22 @@ def pmc_traffic(config_name, kernel_name):
         return None, "pmc_traffic.json unreadable: %s" % type(exc).__name__
 
 
+DUMP_BYTES = 63 << 20     # --dump-outputs: at most 64 MB in all, with room for the .npy headers
+
+
+def dump_outputs(arrays, out_dir):
+    """Every array of `arrays` as <out_dir>/<name>.npy in float64 (the integers of C4 stay exact: all below 2^53).  When the
+    whole would pass DUMP_BYTES, every array keeps the same fixed, seeded sample of its rows, in their order."""
+    arrays = {k: v for k, v in arrays.items() if isinstance(v, np.ndarray)}
+    total = 8 * sum(a.size for a in arrays.values())
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in sorted(arrays.items()):
+        if total > DUMP_BYTES and a.shape[0] > 0:
+            keep = max(1, a.shape[0] * DUMP_BYTES // total)
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a.astype(np.float64))
+
+
 def _slab_worker(args):
     """Best-effort CPU: one Z-slab of the sample through the one-pass C restatement (own process: it keeps globals)."""
     from oracle import onepass_c
@@ -172,8 +194,14 @@ def main():
     ap.add_argument("--config", default=None, help="override: C2/C3/C4/C5 on one GPU")
     ap.add_argument("--features", type=lambda v: int(v, 0), default=None,
                     help="override the feature mask (e.g. 0x0f = everything but adjacency); not the headline metric")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the tissue-filled and the two-steps-in-flight figures")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: CPU baselines, secondary workloads, read "
+                         "ceiling, adjacency-collect time, global pair-list gather (N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays the last timed step computed to DIR/<name>.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-secondary", action="store_true",
+                    help="with --full: skip the tissue-filled, two-steps-in-flight and other secondary figures")
     ap.add_argument("--no-ellipsoid", action="store_true", help="tissue everywhere (not the headline workload)")
     ap.add_argument("--tile-planes", type=int, default=0)
     ap.add_argument("--dims", type=int, nargs=3, default=None, help="rehearsal: override the volume shape")
@@ -312,19 +340,25 @@ def main():
     # the dominant kernel's duration: HIP events of the launches of the timed region itself
     for cx in contexts:
         sweep_ms += cx.timing_series()
-    # what follows the sweep in a step (hot-row fold + adjacency collect), from three more steps with the step's
-    # begin / end events switched on
-    for cx in contexts:
-        cx.set_option(_capi.OPT_TIMING, 2)
-    for _ in range(3 * len(contexts)):
-        job.step()
-        job.finish()
-        torch.cuda.synchronize()
-        adj_ms.append(last_ctx().timing()["ms_adjacency"])
+    if args.dump_outputs:
+        arrays = job.result_arrays()                # (collective for N > 1: every rank asks, rank 0 writes)
+        if rank == 0:
+            dump_outputs(arrays, args.dump_outputs)
+        del arrays
     bytes_read = last_ctx().timing()["bytes_read"]
+    if args.full:
+        # what follows the sweep in a step (hot-row fold + adjacency collect), from three more steps with the step's
+        # begin / end events switched on
+        for cx in contexts:
+            cx.set_option(_capi.OPT_TIMING, 2)
+        for _ in range(3 * len(contexts)):
+            job.step()
+            job.finish()
+            torch.cuda.synchronize()
+            adj_ms.append(last_ctx().timing()["ms_adjacency"])
 
     gather_ms = None
-    if n > 1 and feats & _capi.F_ADJACENCY:
+    if args.full and n > 1 and feats & _capi.F_ADJACENCY:
         # the GLOBAL pair list is not part of a step (ranks keep private + travelling pairs): one collective assembly, timed
         barrier()
         t1 = time.perf_counter()
@@ -345,9 +379,6 @@ def main():
     if rank == 0:
         sweep = float(np.mean(sweep_ms))
         achieved = bytes_read / (sweep * 1e-3) / 1e9
-        owned = job.owned_view()
-        probe_ms = last_ctx().read_probe(owned.data_ptr(), owned.numel() * owned.element_size(), repeats=5)
-        peak_measured = owned.numel() * owned.element_size() / (probe_ms * 1e-3) / 1e9
         kernel_name = ((("scan_wide_kernel" if last_ctx().get_option(_capi.OPT_SWEEP_SHAPE_USED) else "scan_two_rows_kernel")
                         if dtype.itemsize == 4 else "scan_kernel") if feats & _capi.F_ADJACENCY else "scan_noadj_kernel")
         traffic, traffic_note = pmc_traffic(cfg["name"], kernel_name)
@@ -369,21 +400,25 @@ def main():
                        "pct_hbm_roofline": round(100.0 * achieved / HBM_PEAK_GBS, 2)},
             "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
-                         "peak_measured": round(peak_measured, 1), "frac_of_measured": round(achieved / peak_measured, 4),
                          "traffic_note": traffic_note, "kernel": kernel_name,
                          "kernel_ms": round(sweep, 4), "kernel_launches_timed": len(sweep_ms),
-                         "adjacency_collect_ms": round(float(np.mean(adj_ms)), 4),
                          "algorithmic_bytes_per_launch": int(bytes_read),
                          "tile_planes": int(last_ctx().get_option(_capi.OPT_TILE_PLANES))},
         }
+        if args.full:
+            owned = job.owned_view()
+            probe_ms = last_ctx().read_probe(owned.data_ptr(), owned.numel() * owned.element_size(), repeats=5)
+            peak_measured = owned.numel() * owned.element_size() / (probe_ms * 1e-3) / 1e9
+            out["roofline"].update(peak_measured=round(peak_measured, 1), frac_of_measured=round(achieved / peak_measured, 4),
+                                   adjacency_collect_ms=round(float(np.mean(adj_ms)), 4))
         if gather_ms is not None:
             out["secondary"] = {"global_adjacency_gather_ms": {"value": round(gather_ms, 3), "pairs": global_pairs,
                                 "what": "one SlabJob.result_arrays(): all-gather of the ranks' private pair lists + host merge; "
                                         "outside the timed steps"}}
-        if n == 1 and not args.no_cpu_baseline:     # (before the secondary figures release the volume)
+        if args.full and n == 1 and not args.no_cpu_baseline:     # (before the secondary figures release the volume)
             cpu_baseline_result = cpu_baseline(job.owned_view(), (a_hi - a_lo, dims[1], dims[2]), dtype)
             cpu_baseline_result["best_effort"] = cpu_best_effort(job.owned_view(), (a_hi - a_lo, dims[1], dims[2]), dtype, max_label)
-        if n == 1 and not args.no_secondary and not args.config and args.features is None and not args.dims \
+        if args.full and n == 1 and not args.no_secondary and not args.config and args.features is None and not args.dims \
                 and not args.no_ellipsoid:
             sec = {}
 
@@ -531,7 +566,7 @@ def main():
             except Exception as e:
                 sec["sparse_ids"] = {"skipped": "%s: %s" % (type(e).__name__, str(e)[:160])}
             out["secondary"] = sec
-        if n == 1 and not args.no_cpu_baseline:
+        if args.full and n == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline_result
         print(json.dumps(out), flush=True)
     if n > 1:

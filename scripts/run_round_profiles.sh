@@ -1,9 +1,10 @@
 #!/bin/bash
-# usage (GPU box): scripts/run_round_profiles.sh TAG
+# usage (GPU box): RESULTS=DIR scripts/run_round_profiles.sh TAG
 # everything profiles/ holds for a round: kernel stats + PMC of the default bench (run_profiles.sh), the moments-only
 # mask, the uint16 kernels, the bench lines of the other configurations, the ablation ladder (scratch/lib*.so when present).
 # Every step appends to a file under gpurun_out/ (a silent GPU call is taken to be hung after 7 minutes).
 TAG=$1
+RESULTS=${RESULTS:?set RESULTS to the directory the bench lines go to}; mkdir -p "$RESULTS"
 R=$GRAFT_REPO_ROOT
 export PYTHONPATH=$R
 bash $R/scripts/run_profiles.sh $TAG
@@ -19,10 +20,11 @@ rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_I
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $R/gpurun_out/prof_${TAG}_u16_fetch -- python3 $R/bench.py --config C2 --features 0x1f --steps 5 --warmup 1 --no-cpu-baseline --no-secondary > $R/gpurun_out/prof_${TAG}_u16_fetch.log 2>&1
 python3 $R/scripts/pmc_summary.py --kernel "scan_kernel|scan_noadj_kernel" $R/gpurun_out/prof_${TAG}_u16_sq $R/gpurun_out/prof_${TAG}_u16_fetch > $R/gpurun_out/prof_${TAG}_u16_pmc.txt 2>&1
 cd $R
-: > gpurun_out/${TAG}_bench.jsonl
-python3 bench.py 2>gpurun_out/${TAG}_bench_default.err | tail -1 >> gpurun_out/${TAG}_bench.jsonl
+# the bench lines: the default one with --full (cpu_baseline + secondary), the other configurations plain, into $RESULTS
+: > $RESULTS/${TAG}_bench.jsonl
+python3 bench.py --full 2>$RESULTS/${TAG}_bench_default.err | tail -1 >> $RESULTS/${TAG}_bench.jsonl
 for extra in "--config C3" "--config C2" "--config C2 --features 0x1f" "--config C1 --features 0x1f" "--features 0x0f" "--features 0x07" "--dims 1000 1000 1000"; do
-  python3 bench.py $extra --no-cpu-baseline --no-secondary 2>/dev/null | tail -1 >> gpurun_out/${TAG}_bench.jsonl
+  python3 bench.py $extra 2>/dev/null | tail -1 >> $RESULTS/${TAG}_bench.jsonl
 done
 # ablation builds (scripts/build_variant.py NAME -D...; results wrong by construction, only the time matters), a CUMULATIVE ladder
 # on the WIDE shape (--shape 1: the kernel the headline names):

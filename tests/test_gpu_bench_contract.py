@@ -12,7 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def test_bench_line_has_the_contract_fields():
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dims", "96", "128", "512", "--steps", "4", "--warmup", "1",
-                        "--no-secondary"], cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+                        "--full", "--no-secondary"], cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert p.returncode == 0, p.stderr.decode(errors="replace")[-2000:]
     lines = [l for l in p.stdout.decode().splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -41,7 +41,7 @@ def test_bench_two_ranks_rehearsal_runs_the_multi_gpu_path():
     env = dict(os.environ, TA_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                         "--master-port", str(29650 + os.getpid() % 300), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dims", "96", "64", "512",
-                        "--steps", "3", "--warmup", "1", "--settle-ms", "5"], cwd=ROOT, env=env, stdout=subprocess.PIPE,
+                        "--steps", "3", "--warmup", "1", "--settle-ms", "5", "--full"], cwd=ROOT, env=env, stdout=subprocess.PIPE,
                        stderr=subprocess.PIPE, timeout=300)
     assert p.returncode == 0, p.stderr.decode(errors="replace")[-2000:]
     lines = [l for l in p.stdout.decode().splitlines() if l.startswith("{")]
@@ -66,3 +66,33 @@ def test_bench_gpus_2_as_a_plain_command_starts_its_own_ranks():
     assert len(lines) == 1 and lines[0].startswith("{")
     d = json.loads(lines[0])
     assert d["n_gpus"] == 2 and d["config"]["steps_in_flight"] == 2 and d["roofline"]["frac"] > 0
+
+
+def test_plain_line_and_dumped_outputs_match_the_c_oracle(tmp_path):
+    """A plain run (no --full) prints the headline fields and none of the --full objects; --dump-outputs writes the arrays of
+    the last timed step in float64, equal to the C oracle on the same seeded volume (generated again here)."""
+    import numpy as np
+    from helpers import INT_KEYS, assert_same_accumulators
+    from oracle import onepass_c
+    from tissue_analysis_amd import device as dev, synth
+    dims = (96, 128, 512)
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dims"] + [str(d) for d in dims] +
+                       ["--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path)], cwd=ROOT, stdout=subprocess.PIPE,
+                       stderr=subprocess.PIPE, timeout=600)
+    assert p.returncode == 0, p.stderr.decode(errors="replace")[-2000:]
+    lines = [l for l in p.stdout.decode().splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "roofline"):
+        assert k in d, k
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["roofline"]["kernel_launches_timed"] == 3
+    assert "cpu_baseline" not in d and "secondary" not in d and "peak_measured" not in d["roofline"]
+    got = {f[:-4]: np.load(str(tmp_path / f)) for f in os.listdir(str(tmp_path))}
+    assert set(INT_KEYS) <= set(got) and all(a.dtype == np.float64 for a in got.values())
+    assert sum(a.nbytes for a in got.values()) <= 64 << 20
+    c = synth.CONFIGS["C4"]
+    ctx = dev.torch_context(0)
+    vol, L = dev.synth_slab(ctx, dims, np.dtype(c["dtype"]), c["n_cells"], c["seed"])
+    host = vol.cpu().numpy().view(np.dtype(c["dtype"]))
+    ctx.close()
+    assert_same_accumulators(got, onepass_c.extract(host, max_label=L), "bench --dump-outputs")
