@@ -38,6 +38,14 @@ SYMBOLS = (
     "ta_device_malloc", "ta_device_free", "ta_memcpy_d2h", "ta_memcpy_h2d",
 )
 
+# every symbol include/tissue_scan_signal.h declares (same library; kept apart from SYMBOLS, which is tissue_scan.h's list)
+SIGNAL_SYMBOLS = (
+    "ta_signal_set", "ta_signal_set_device", "ta_signal_extract", "ta_signal_get_labels", "ta_signal_get_walls",
+    "ta_signal_timing",
+)
+SIG_LABELS, SIG_WALLS = 1, 2           # TA_SIG_LABELS / TA_SIG_WALLS
+SIGNAL_DTYPES = (np.uint8, np.uint16)
+
 
 def exchange_words(capacity_pairs):
     """uint64 words of one exchange block (TA_EXCHANGE_WORDS in include/tissue_scan.h)."""
@@ -129,8 +137,14 @@ def load():
         "ta_device_free": (ci, [vp, vp]),
         "ta_memcpy_d2h": (ci, [vp, vp, vp, u64]),
         "ta_memcpy_h2d": (ci, [vp, vp, vp, u64]),
+        "ta_signal_set": (ci, [vp, vp, ci, P(i64), P(i64)]),
+        "ta_signal_set_device": (ci, [vp, vp, ci]),
+        "ta_signal_extract": (ci, [vp, u32]),
+        "ta_signal_get_labels": (ci, [vp, vp, vp, vp, vp, vp]),
+        "ta_signal_get_walls": (ci, [vp, vp, vp]),
+        "ta_signal_timing": (ci, [vp, P(ctypes.c_double)]),
     }
-    for name in SYMBOLS:
+    for name in SYMBOLS + SIGNAL_SYMBOLS:
         fn = getattr(lib, name)      # AttributeError here == the .so does not match the header
         fn.restype, fn.argtypes = sig[name]
     if lib.ta_version() != ABI_VERSION:
@@ -240,6 +254,7 @@ class Context(object):
             a = np.ascontiguousarray(a)
         _check(self._lib.ta_volume_set(self._h, ctypes.c_void_p(a.ctypes.data), a.dtype.itemsize,
                                        _i64x3(a.shape), _i64x3(a.strides)))
+        self._vol_layout = (tuple(a.shape), tuple(s // a.dtype.itemsize for s in a.strides))
         self._owned_planes = int(a.shape[int(np.argmax(a.strides))])         # planes of the slowest MEMORY axis
 
     def relabel(self, lut):
@@ -334,6 +349,8 @@ class Context(object):
     def set_volume_device(self, dev_ptr, itemsize, buf_dims, a0_origin=0, has_low_halo=False, keep=None):
         _check(self._lib.ta_volume_set_device(self._h, ctypes.c_void_p(int(dev_ptr)), int(itemsize),
                                               _i64x3(buf_dims), int(a0_origin), int(bool(has_low_halo))))
+        d = [int(x) for x in buf_dims]
+        self._vol_layout = (tuple(d), (d[1] * d[2], d[2], 1))
         self._keep = [keep]
         self._owned_planes = int(buf_dims[0]) - (1 if has_low_halo else 0)
         # a torch tensor that is a view of a larger storage: tell the library how many bytes are readable behind it
@@ -344,6 +361,59 @@ class Context(object):
                 self.set_option(OPT_VOLUME_SLACK, int(st.nbytes() - end))
         except AttributeError:
             pass
+
+    # -- signal image (include/tissue_scan_signal.h)
+    def set_signal(self, array):
+        """Upload a uint8 / uint16 intensity image of the label volume's shape.  One stored in another axis permutation than
+        the labels is copied into the labels' layout first."""
+        a = np.asarray(array)
+        if a.dtype not in SIGNAL_DTYPES:
+            raise TypeError("signal images must be uint8 or uint16, not %s" % a.dtype)
+        layout = getattr(self, "_vol_layout", None)
+        if layout is None:
+            raise ValueError("set a label volume before its signal")
+        shape, el = layout
+        if a.ndim == 2 and len(shape) == 3 and shape[2] == 1:
+            a = a[:, :, None]
+        if tuple(a.shape) != shape:
+            raise ValueError("the signal's shape %s differs from the label volume's %s" % (tuple(a.shape), shape))
+        same = all(n == 1 or st == e * a.dtype.itemsize for n, st, e in zip(a.shape, a.strides, el))
+        if not same:              # the labels' layout: a flat buffer viewed with their element strides
+            flat = np.empty(int(np.prod(shape)), dtype=a.dtype)
+            view = np.lib.stride_tricks.as_strided(flat, shape=shape, strides=[e * a.dtype.itemsize for e in el])
+            view[...] = a
+            a = view
+        _check(self._lib.ta_signal_set(self._h, ctypes.c_void_p(a.ctypes.data), a.dtype.itemsize, _i64x3(a.shape), _i64x3(a.strides)))
+
+    def set_signal_device(self, dev_ptr, itemsize, keep=None):
+        """Adopt a device-resident signal: dense C order with the label volume's buffer dims (halo plane included)."""
+        _check(self._lib.ta_signal_set_device(self._h, ctypes.c_void_p(int(dev_ptr)), int(itemsize)))
+        self._keep_sig = keep
+
+    def signal_extract(self, what=SIG_LABELS | SIG_WALLS):
+        """Enqueue the signal pass over the current extraction (SIG_LABELS | SIG_WALLS)."""
+        _check(self._lib.ta_signal_extract(self._h, int(what)))
+
+    def signal_labels(self):
+        """(n u64[R], sum u64[R], sumsq u64[R, 2] (lo, hi words), min u32[R], max u32[R]), rows as labels()."""
+        R = self._max_label + 1
+        n, s = np.zeros(R, dtype=np.uint64), np.zeros(R, dtype=np.uint64)
+        q = np.zeros((R, 2), dtype=np.uint64)
+        mn, mx = np.zeros(R, dtype=np.uint32), np.zeros(R, dtype=np.uint32)
+        _check(self._lib.ta_signal_get_labels(self._h, n.ctypes.data, s.ctypes.data, q.ctypes.data, mn.ctypes.data, mx.ctypes.data))
+        return n, s, q, mn, mx
+
+    def signal_walls(self):
+        """(side_lo u64[P], side_hi u64[P]), rows as adjacency()."""
+        P = self.adjacency_size()
+        lo, hi = np.zeros(P, dtype=np.uint64), np.zeros(P, dtype=np.uint64)
+        _check(self._lib.ta_signal_get_walls(self._h, lo.ctypes.data, hi.ctypes.data))
+        return lo, hi
+
+    def signal_timing(self):
+        ms = ctypes.c_double(0.0)
+        _check(self._lib.ta_signal_timing(self._h, ctypes.byref(ms)))
+        return ms.value
 
     def max_label(self):
         v = ctypes.c_uint32(0)

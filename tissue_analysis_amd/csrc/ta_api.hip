@@ -1,6 +1,7 @@
 // ta_api.hip -- the C ABI of include/tissue_scan.h on top of the gfx950 kernels.
-#include "../../include/tissue_scan.h"
+#include "../../include/tissue_scan_signal.h"
 #include "ta_kernels.h"
+#include "ta_signal.h"
 
 #include <algorithm>
 #include <cmath>
@@ -152,6 +153,19 @@ struct ta_ctx {
     int64_t npairs = 0;
     PinnedBuf h_pairs;                                  // sorted host copy for ta_adjacency_get: keys u64[n], then faces u64[n][3]
     bool host_pairs_ready = false;
+
+    // signal image (include/tissue_scan_signal.h): same buffer dims and layout as the label volume
+    const void* sig = nullptr;                          // device pointer (owned_sig.p or adopted), NULL = no signal
+    DevBuf owned_sig;
+    int sig_itemsize = 0;
+    int64_t sig_mdims[3] = {0, 0, 0};                   // the label buffer dims it was set for
+    DevBuf sig_out;                                     // flags u32[4] | n | sum | sumsq[2] | min | max | side_lo | side_hi
+    DevBuf sig_hash;                                    // pair -> row table of the sorted pair list: keys u64[cap] | rows u32[cap]
+    uint64_t sig_seq = 0;                               // extract_seq of the extraction the results belong to, 0 = none
+    uint32_t sig_what = 0;
+    uint32_t sig_rows = 0;                              // max_label + 1 of that extraction
+    int64_t sig_npairs = 0;
+    hipEvent_t sig_ev[2] = {nullptr, nullptr};
 };
 
 namespace {
@@ -175,6 +189,16 @@ void drop_census(ta_ctx* c) {          // (whenever the voxels change)
     c->tune_launched = 0;
     for (bool& d : c->tune_done) d = false;
     if (c->compact) { c->compact = false; c->extracted = c->checked = false; }
+}
+
+// a new label volume: the signal results are stale (extracted is false); a signal of other dims is dropped
+void signal_on_new_volume(ta_ctx* c) {
+    c->sig_seq = 0;
+    if (c->sig && (c->sig_mdims[0] != c->mdims[0] || c->sig_mdims[1] != c->mdims[1] || c->sig_mdims[2] != c->mdims[2])) {
+        c->sig = nullptr;
+        c->owned_sig.release();
+        c->sig_itemsize = 0;
+    }
 }
 
 int use_device(ta_ctx* c) {
@@ -515,6 +539,8 @@ TA_API int ta_ctx_destroy(ta_ctx* c) {
     c->wall_stage.release();
     c->wall_medians.release();
     c->census.release(); c->census_ids.release(); c->compact_vol.release(); c->census_list.release();
+    c->owned_sig.release(); c->sig_out.release(); c->sig_hash.release();
+    for (auto& e : c->sig_ev) if (e) (void)hipEventDestroy(e);
     if (c->h_small) (void)hipHostFree(c->h_small);
     for (auto& e : c->ev) if (e) (void)hipEventDestroy(e);
     for (auto& e : c->ring) if (e) (void)hipEventDestroy(e);
@@ -661,6 +687,7 @@ TA_API int ta_volume_set(ta_ctx* c, const void* host_ptr, int itemsize, const in
     c->a_origin = 0;
     c->first_owned = 0;
     c->extracted = c->checked = false;
+    signal_on_new_volume(c);
     return TA_OK;
 }
 
@@ -685,6 +712,7 @@ TA_API int ta_volume_set_device(ta_ctx* c, const void* dev_ptr, int itemsize, co
     c->a_origin = a0_origin;
     c->first_owned = has_low_halo ? 1 : 0;
     c->extracted = c->checked = false;
+    signal_on_new_volume(c);
     return TA_OK;
 }
 
@@ -1755,6 +1783,199 @@ TA_API int ta_memcpy_h2d(ta_ctx* c, void* dev_dst, const void* host_src, uint64_
     if (rc != TA_OK) return rc;
     TA_HIP(hipMemcpyAsync(dev_dst, host_src, bytes, hipMemcpyHostToDevice, c->stream));
     TA_HIP(hipStreamSynchronize(c->stream));
+    return TA_OK;
+}
+
+// ---- signal statistics (include/tissue_scan_signal.h; kernels_signal.hip) -----------------------------------------------------
+
+}  // extern "C"
+
+namespace {
+
+bool signal_current(const ta_ctx* c) { return c->sig_seq != 0 && c->extracted && c->sig_seq == c->extract_seq; }
+
+// byte offsets of the parts of sig_out for R rows and P pairs
+struct SignalLayout {
+    uint64_t flags = 0, n, sum, sumsq, vmin, vmax, side_lo, side_hi, bytes;
+    SignalLayout(uint64_t R, uint64_t P) {
+        n = 16; sum = n + 8 * R; sumsq = sum + 8 * R; vmin = sumsq + 16 * R; vmax = vmin + 4 * R;
+        side_lo = vmax + 4 * R; side_hi = side_lo + 8 * P; bytes = side_hi + 8 * P;
+    }
+};
+
+int signal_adopt(ta_ctx* c, int itemsize) {
+    c->sig_itemsize = itemsize;
+    for (int k = 0; k < 3; ++k) c->sig_mdims[k] = c->mdims[k];
+    c->sig_seq = 0;
+    return TA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+TA_API int ta_signal_set(ta_ctx* c, const void* host_ptr, int itemsize, const int64_t dims[3], const int64_t strides_bytes[3]) {
+    if (!c) return fail(TA_EINVAL, "ctx is NULL");
+    if (!host_ptr || !dims) return fail(TA_EINVAL, "NULL argument");
+    if (itemsize != 1 && itemsize != 2) return fail(TA_EINVAL, "signal itemsize must be 1 (uint8) or 2 (uint16), not %d", itemsize);
+    if (!c->vol) return fail(TA_EINVAL, "no label volume set: the signal takes its dims and layout");
+    int64_t adims[3], el[3];                     // the label volume's dims and element strides, in array-axis order
+    int64_t e = 1;
+    for (int k = 2; k >= 0; --k) { adims[c->perm[k]] = c->mdims[k]; el[c->perm[k]] = e; e *= c->mdims[k]; }
+    for (int d = 0; d < 3; ++d) {
+        if (dims[d] != adims[d])
+            return fail(TA_EINVAL, "signal dims (%lld, %lld, %lld) differ from the label volume's (%lld, %lld, %lld)", (long long)dims[0],
+                        (long long)dims[1], (long long)dims[2], (long long)adims[0], (long long)adims[1], (long long)adims[2]);
+        const int64_t st = strides_bytes ? strides_bytes[d] : (d == 2 ? 1 : (d == 1 ? dims[2] : dims[1] * dims[2])) * itemsize;
+        if (dims[d] != 1 && st != el[d] * itemsize)
+            return fail(TA_EINVAL, "the signal's layout differs from the label volume's (axis %d: stride %lld bytes, expected %lld)", d,
+                        (long long)st, (long long)(el[d] * itemsize));
+    }
+    int rc = use_device(c);
+    if (rc != TA_OK) return rc;
+    const uint64_t bytes = (uint64_t)e * itemsize;
+    TA_HIP(hipStreamSynchronize(c->stream));     // (a pass in flight may still read the old signal)
+    c->sig = nullptr;
+    if ((rc = c->owned_sig.reserve(bytes + 64)) != TA_OK) return rc;
+    TA_HIP(hipMemcpyAsync(c->owned_sig.p, host_ptr, bytes, hipMemcpyHostToDevice, c->stream));
+    TA_HIP(hipStreamSynchronize(c->stream));     // the host buffer may be freed after return
+    c->sig = c->owned_sig.p;
+    return signal_adopt(c, itemsize);
+}
+
+TA_API int ta_signal_set_device(ta_ctx* c, const void* dev_ptr, int itemsize) {
+    if (!c) return fail(TA_EINVAL, "ctx is NULL");
+    if (!dev_ptr) return fail(TA_EINVAL, "NULL argument");
+    if (itemsize != 1 && itemsize != 2) return fail(TA_EINVAL, "signal itemsize must be 1 (uint8) or 2 (uint16), not %d", itemsize);
+    if (!c->vol) return fail(TA_EINVAL, "no label volume set: the signal takes its buffer dims");
+    if (((uintptr_t)dev_ptr % itemsize) != 0) return fail(TA_EINVAL, "device pointer is not aligned to the signal type");
+    int rc = use_device(c);
+    if (rc != TA_OK) return rc;
+    TA_HIP(hipStreamSynchronize(c->stream));
+    c->owned_sig.release();
+    c->sig = dev_ptr;
+    return signal_adopt(c, itemsize);
+}
+
+TA_API int ta_signal_extract(ta_ctx* c, uint32_t what) {
+    if (!c) return fail(TA_EINVAL, "ctx is NULL");
+    if (what == 0 || (what & ~(TA_SIG_LABELS | TA_SIG_WALLS))) return fail(TA_EINVAL, "bad signal mask 0x%x", what);
+    if (!c->sig) return fail(TA_EINVAL, "no signal set");
+    if (!c->vol || c->sig_mdims[0] != c->mdims[0] || c->sig_mdims[1] != c->mdims[1] || c->sig_mdims[2] != c->mdims[2])
+        return fail(TA_EINVAL, "the signal does not match the label volume");
+    int rc = use_device(c);
+    if (rc != TA_OK) return rc;
+    if (!c->extracted) return fail(TA_EINVAL, "the signal pass needs a ta_extract of the current volume first");
+    if ((rc = finish_extract(c)) != TA_OK) return rc;
+    const bool walls = what & TA_SIG_WALLS;
+    if (walls && !(c->feature_mask & TA_F_ADJACENCY)) return fail(TA_EINVAL, "TA_SIG_WALLS needs an extraction with TA_F_ADJACENCY");
+    if (walls && c->exchanged) return fail(TA_EINVAL, "TA_SIG_WALLS needs this context's own pair list (not a merged one)");
+    const uint64_t R = (uint64_t)c->max_label + 1, P = walls ? (uint64_t)c->npairs : 0;
+    const SignalLayout L(R, P);
+    if ((rc = c->sig_out.reserve(L.bytes)) != TA_OK) return rc;
+    for (auto& ev : c->sig_ev) if (!ev) TA_HIP(hipEventCreate(&ev));
+    ta::SignalArgs a;
+    a.hkeys = nullptr; a.hrows = nullptr; a.hmask = 0;
+    if (walls && P) {
+        // pair -> row: an open-addressed table of the sorted pair list (ta_adjacency_get sorts it on the device once per extraction)
+        if ((rc = ta_adjacency_get(c, nullptr, nullptr, nullptr)) != TA_OK) return rc;
+        uint64_t cap = 64;
+        while (cap < 2 * P) cap <<= 1;
+        if (cap > (1ull << 32)) return fail(TA_EINVAL, "too many pairs (%llu)", (unsigned long long)P);
+        if ((rc = c->sig_hash.reserve(cap * 12 + P * 8)) != TA_OK) return rc;
+        uint64_t* hkeys = (uint64_t*)c->sig_hash.p;
+        uint64_t* sorted = hkeys + cap;
+        uint32_t* hrows = (uint32_t*)(sorted + P);
+        TA_HIP(hipMemsetAsync(hkeys, 0xff, cap * 8, c->stream));
+        TA_HIP(hipMemcpyAsync(sorted, c->h_pairs.p, P * 8, hipMemcpyHostToDevice, c->stream));
+        ta::launch_signal_hash(c->stream, sorted, P, hkeys, hrows, (uint32_t)(cap - 1));
+        a.hkeys = hkeys; a.hrows = hrows; a.hmask = (uint32_t)(cap - 1);
+    }
+    char* o = (char*)c->sig_out.p;
+    TA_HIP(hipMemsetAsync(o, 0, L.bytes, c->stream));
+    TA_HIP(hipMemsetAsync(o + L.vmin, 0xff, 4 * R, c->stream));
+    a.vol = sweep_vol(c);
+    a.sig = c->sig;
+    a.n0 = c->mdims[0]; a.n1 = c->mdims[1]; a.n2 = c->mdims[2];
+    a.first_owned = c->first_owned;
+    a.max_label = c->max_label;
+    a.n = (unsigned long long*)(o + L.n);
+    a.sum = (unsigned long long*)(o + L.sum);
+    a.sumsq = (unsigned long long*)(o + L.sumsq);
+    a.vmin = (uint32_t*)(o + L.vmin);
+    a.vmax = (uint32_t*)(o + L.vmax);
+    a.side_lo = (unsigned long long*)(o + L.side_lo);
+    a.side_hi = (unsigned long long*)(o + L.side_hi);
+    a.flags = (uint32_t*)o;
+    a.tiles_per_group = 0;
+    TA_HIP(hipEventRecord(c->sig_ev[0], c->stream));
+    ta::launch_signal(c->stream, a, c->itemsize, c->sig_itemsize, (what & TA_SIG_LABELS ? ta::SIG_LABELS : 0u) | (walls ? ta::SIG_WALLS : 0u));
+    TA_HIP(hipGetLastError());
+    TA_HIP(hipEventRecord(c->sig_ev[1], c->stream));
+    c->sig_seq = c->extract_seq;
+    c->sig_what = what;
+    c->sig_rows = (uint32_t)R;
+    c->sig_npairs = (int64_t)P;
+    return TA_OK;
+}
+
+namespace {
+// drain the stream and look at the pass's flag words
+int signal_finish(ta_ctx* c) {
+    uint32_t flags[ta::SIG_NFLAGS] = {0, 0, 0, 0};
+    TA_HIP(hipMemcpyAsync(flags, c->sig_out.p, sizeof(flags), hipMemcpyDeviceToHost, c->stream));
+    TA_HIP(hipStreamSynchronize(c->stream));
+    if (flags[ta::SIG_FLAG_RANGE]) return fail(TA_ERANGE, "the signal pass met a label above max_label=%u (the volume changed since ta_extract)", c->max_label);
+    if (flags[ta::SIG_FLAG_PAIR_MISS]) return fail(TA_ERANGE, "the signal pass met a pair the extraction does not hold (the volume changed since ta_extract)");
+    return TA_OK;
+}
+}  // namespace
+
+TA_API int ta_signal_get_labels(ta_ctx* c, uint64_t* n, uint64_t* sum, uint64_t* sumsq, uint32_t* vmin, uint32_t* vmax) {
+    if (!c) return fail(TA_EINVAL, "ctx is NULL");
+    if (!signal_current(c) || !(c->sig_what & TA_SIG_LABELS))
+        return fail(TA_EINVAL, "no per-label signal results for the current extraction (run ta_signal_extract with TA_SIG_LABELS)");
+    int rc = use_device(c);
+    if (rc != TA_OK) return rc;
+    if ((rc = signal_finish(c)) != TA_OK) return rc;
+    const uint64_t R = c->sig_rows;
+    const SignalLayout L(R, (uint64_t)c->sig_npairs);
+    const char* o = (const char*)c->sig_out.p;
+    if (n) TA_HIP(hipMemcpyAsync(n, o + L.n, 8 * R, hipMemcpyDeviceToHost, c->stream));
+    if (sum) TA_HIP(hipMemcpyAsync(sum, o + L.sum, 8 * R, hipMemcpyDeviceToHost, c->stream));
+    if (sumsq) TA_HIP(hipMemcpyAsync(sumsq, o + L.sumsq, 16 * R, hipMemcpyDeviceToHost, c->stream));
+    if (vmin) TA_HIP(hipMemcpyAsync(vmin, o + L.vmin, 4 * R, hipMemcpyDeviceToHost, c->stream));
+    if (vmax) TA_HIP(hipMemcpyAsync(vmax, o + L.vmax, 4 * R, hipMemcpyDeviceToHost, c->stream));
+    TA_HIP(hipStreamSynchronize(c->stream));
+    return TA_OK;
+}
+
+TA_API int ta_signal_get_walls(ta_ctx* c, uint64_t* side_lo, uint64_t* side_hi) {
+    if (!c) return fail(TA_EINVAL, "ctx is NULL");
+    if (!signal_current(c) || !(c->sig_what & TA_SIG_WALLS) || c->exchanged)
+        return fail(TA_EINVAL, "no per-wall signal results for the current extraction (run ta_signal_extract with TA_SIG_WALLS)");
+    int rc = use_device(c);
+    if (rc != TA_OK) return rc;
+    if ((rc = signal_finish(c)) != TA_OK) return rc;
+    const uint64_t P = (uint64_t)c->sig_npairs;
+    const SignalLayout L(c->sig_rows, P);
+    const char* o = (const char*)c->sig_out.p;
+    if (side_lo && P) TA_HIP(hipMemcpyAsync(side_lo, o + L.side_lo, 8 * P, hipMemcpyDeviceToHost, c->stream));
+    if (side_hi && P) TA_HIP(hipMemcpyAsync(side_hi, o + L.side_hi, 8 * P, hipMemcpyDeviceToHost, c->stream));
+    TA_HIP(hipStreamSynchronize(c->stream));
+    return TA_OK;
+}
+
+TA_API int ta_signal_timing(ta_ctx* c, double* ms) {
+    if (!c) return fail(TA_EINVAL, "ctx is NULL");
+    if (!ms) return fail(TA_EINVAL, "NULL argument");
+    if (c->sig_seq == 0 || !c->sig_ev[1]) return fail(TA_EINVAL, "no signal pass has been run");
+    int rc = use_device(c);
+    if (rc != TA_OK) return rc;
+    TA_HIP(hipEventSynchronize(c->sig_ev[1]));
+    float t = 0.f;
+    TA_HIP(hipEventElapsedTime(&t, c->sig_ev[0], c->sig_ev[1]));
+    *ms = (double)t;
     return TA_OK;
 }
 

@@ -473,6 +473,7 @@ class ResidentVolume(object):
         self.ctx = _capi.Context(device)
         self.uploads = 0
         self.ms = {}                  # wall-clock milliseconds of the last upload / sweep / fetch (host side)
+        self.last = None              # the Extraction of the last sweep of this context (what signal() lines up with)
         self.upload()
 
     def close(self):
@@ -495,6 +496,7 @@ class ResidentVolume(object):
         self.ctx.set_volume(self.host)
         self.ms["upload"] = (time.perf_counter() - t0) * 1e3
         self.uploads += 1
+        self.last = None
 
     def extract(self, features=_capi.F_ALL, max_label=None, sparse=None):
         """One sweep of the resident volume.  Ids that are sparse (`wants_compaction`) are swept in their ranks: the
@@ -503,7 +505,19 @@ class ResidentVolume(object):
         t0 = time.perf_counter()
         x = extract_resident(self.ctx, self.host.shape, features, max_label, sparse)
         self.ms["extract"] = (time.perf_counter() - t0) * 1e3
+        self.last = x
         return x
+
+    def signal(self, signal, walls=True):
+        """Statistics of an intensity image (uint8 / uint16, the shape of the labels; a 2-D one for a 2-D label image) per
+        label and, with `walls`, per wall: a `SignalStats` whose rows line up with the last extraction (`.ids` when sparse,
+        `.lo` / `.hi` for walls).  One upload of the signal and one pass over labels + signal on the GPU."""
+        import time
+        from .signal_stats import resident_signal
+        t0 = time.perf_counter()
+        st = resident_signal(self, signal, walls)
+        self.ms["signal"] = (time.perf_counter() - t0) * 1e3
+        return st
 
     def wall_table(self):
         if self.host.flags.c_contiguous:       # memory order IS np.where order: the device groups the records by pair

@@ -120,9 +120,11 @@ def _wall_median_columns(graph, analysis, pairs, background):
         graph.set_vertex_column(name, value, valid, _show_point)
 
 
-def tissue_tables(analysis, labels, background, properties, property_as_real=True, min_contact_area=None):
+def tissue_tables(analysis, labels, background, properties, property_as_real=True, min_contact_area=None, signal=None):
     """The vertex / edge tables of the tissue graph from the sweep results held by `analysis`.
-    `labels`: the vertex ids (any order, distinct).  Returns a PropertyGraph whose columns are plain numpy arrays."""
+    `labels`: the vertex ids (any order, distinct).  Returns a PropertyGraph whose columns are plain numpy arrays.
+    With an intensity image `signal`, 'mean_signal' (vertex: cell_signal's mean) and 'wall_signal' (edge: wall_signal's
+    face-weighted mean) can be asked for too."""
     x = analysis.extraction
     ids = np.asarray(labels, dtype=np.int64).reshape(-1)
     pairs = _PairView(analysis, ids, min_contact_area)
@@ -190,11 +192,19 @@ def tissue_tables(analysis, labels, background, properties, property_as_real=Tru
         graph.set_vertex_column('epidermis_surface', value, l1)
     if 'wall_median' in properties:
         _wall_median_columns(graph, analysis, pairs, background)
+    if signal is not None and ('mean_signal' in properties or 'wall_signal' in properties):
+        stats = analysis._signal_stats(signal)
+        if 'mean_signal' in properties:
+            graph.set_vertex_column('mean_signal', stats.of_labels(ids, 'mean'), asked)
+        if 'wall_signal' in properties:
+            rows = stats.wall_rows(pairs.lo[is_edge], pairs.hi[is_edge])
+            found = rows >= 0
+            graph.set_edge_column('wall_signal', np.where(found, stats.wall_mean[np.where(found, rows, 0)], np.nan), found)
     return graph
 
 
 def _graph_from_image(image, labels, background, default_properties, property_as_real, ignore_cells_at_stack_margins,
-                      min_contact_area):
+                      min_contact_area, signal=None):
     """TGI:77-244: which analysis object, which labels are ignored, which become vertices -- then the tables."""
     if isinstance(image, AbstractSpatialImageAnalysis):
         analysis = image
@@ -215,21 +225,22 @@ def _graph_from_image(image, labels, background, default_properties, property_as
             labels.remove(background)                                      # the caller's list, as in the reference
         ids = np.asarray(labels, dtype=np.int64)
         analysis.add2ignoredlabels(np.setdiff1d(np.asarray(analysis.labels(), dtype=np.int64), ids))
-    return tissue_tables(analysis, ids, background, default_properties, property_as_real, min_contact_area)
+    return tissue_tables(analysis, ids, background, default_properties, property_as_real, min_contact_area, signal)
 
 
 def graph_from_image2D(image, labels, background, spatio_temporal_properties, property_as_real,
-                       ignore_cells_at_stack_margins, min_contact_area):
+                       ignore_cells_at_stack_margins, min_contact_area, signal=None):
     return _graph_from_image(image, labels, background, spatio_temporal_properties, property_as_real,
-                             ignore_cells_at_stack_margins, min_contact_area)
+                             ignore_cells_at_stack_margins, min_contact_area, signal)
 
 
 graph_from_image3D = graph_from_image2D        # (the reference's two entry points run the same body, TGI:247-258)
 
 
 def graph_from_image(image, labels=None, background=1, spatio_temporal_properties=None, property_as_real=True,
-                     ignore_cells_at_stack_margins=True, min_contact_area=None):
-    """TGI:260-284.  `image`: a label image or an analysis object of this package."""
+                     ignore_cells_at_stack_margins=True, min_contact_area=None, signal=None):
+    """TGI:260-284.  `image`: a label image or an analysis object of this package.  `signal`: an intensity image (uint8 /
+    uint16) of the same shape, which makes the properties 'mean_signal' (vertex) and 'wall_signal' (edge) available."""
     if isinstance(image, AbstractSpatialImageAnalysis):
         shape = np.shape(image.image)
         if labels is None:
@@ -241,7 +252,7 @@ def graph_from_image(image, labels=None, background=1, spatio_temporal_propertie
         spatio_temporal_properties = spatio_temporal_properties2D if flat else spatio_temporal_properties3D
     build = graph_from_image2D if flat else graph_from_image3D
     return build(image, labels, background, spatio_temporal_properties, property_as_real, ignore_cells_at_stack_margins,
-                 min_contact_area)
+                 min_contact_area, signal)
 
 
 # ----------------------------------------------------------------------------- helpers of TGI:30-60, 309-398, by name

@@ -35,6 +35,7 @@ import numpy as np
 from . import _capi
 from .extraction import Extraction, extract_volume
 from .geometry import _find_wall_median_voxel, find_wall_median_voxel, geometric_median   # module-level in SIA too (SIA:1499-1635)
+from .signal_stats import STATISTICS, WALL_STATISTICS
 from .spatial_image import SpatialImage
 
 NPLIST, LIST, DICT = range(3)  # SIA:204
@@ -201,6 +202,7 @@ class AbstractSpatialImageAnalysis(object):
         self._center_of_mass = {}
         self._walls = None
         self._wall_medians = None
+        self._signal_cache = None
         try:
             self.filepath, self.filename = split(image.info["Filename"])
         except Exception:
@@ -254,6 +256,7 @@ class AbstractSpatialImageAnalysis(object):
         self._center_of_mass = {}
         self._walls = None
         self._wall_medians = None
+        self._signal_cache = None
         self._voxel_layer1 = None
         self._voxel_layer18 = None
 
@@ -535,6 +538,46 @@ class AbstractSpatialImageAnalysis(object):
                     areas[key] = areas.get(key, 0.0) + val
         return areas
 
+    # -- intensity statistics of a signal image over the labels (include/tissue_scan_signal.h; one pass on the GPU)
+    def _signal_stats(self, signal):
+        """SignalStats of `signal` over this image: uploaded and reduced once per array OBJECT (a signal modified in place
+        needs a new array, or refresh()), on the resident label volume."""
+        cache = getattr(self, "_signal_cache", None)
+        if cache is not None and cache[0] is signal:
+            return cache[1]
+        stats = self._resident_rows().signal(np.asarray(signal), walls=True)
+        self._signal_cache = (signal, stats)
+        return stats
+
+    def cell_signal(self, signal, labels=None, statistic='mean'):
+        """Per-label `statistic` of the intensity image `signal` (uint8 / uint16, the image's shape): 'mean', 'std'
+        (population), 'min', 'max' (float64) or 'sum' (integer); returned like volume()."""
+        if statistic not in STATISTICS:
+            raise ValueError("statistic must be one of %s, not %r" % ("|".join(STATISTICS), statistic))
+        labels = self.label_request(labels)
+        values = self._signal_stats(signal).of_labels(labels, statistic)
+        return self.convert_return(values, labels)
+
+    def wall_signal(self, signal, neighbors=None, statistic='mean'):
+        """{(l1, l2): value} for the walls wall_areas(neighbors) returns: 'mean' = the signal averaged over both sides of every
+        face of the wall (face-weighted, like the wall area), 'sides' = (mean on l1's side, mean on l2's side), l1 < l2."""
+        if statistic not in WALL_STATISTICS:
+            raise ValueError("statistic must be one of %s, not %r" % ("|".join(WALL_STATISTICS), statistic))
+        walls = self.wall_areas(neighbors, real=False)
+        if isinstance(walls, tuple):
+            keys = [tuple(k) for k in np.asarray(walls[0]).tolist()]
+        else:
+            keys = list(walls.keys())
+        stats = self._signal_stats(signal)
+        lo = np.array([k[0] for k in keys], dtype=np.int64)
+        hi = np.array([k[1] for k in keys], dtype=np.int64)
+        rows = stats.wall_rows(lo, hi)
+        if statistic == 'mean':
+            col = stats.wall_mean
+            return dict((k, float(col[r]) if r >= 0 else float('nan')) for k, r in zip(keys, rows.tolist()))
+        a, b = stats.wall_side_means
+        return dict((k, (float(a[r]), float(b[r])) if r >= 0 else (float('nan'), float('nan'))) for k, r in zip(keys, rows.tolist()))
+
     def surface_area(self, labels=None, real=True):
         """Per-label total surface area = the sum of the label's wall areas with all its face neighbours
         (SURVEY.md §8 "Semantics": sum_m wall_area(l, m); the reference has no dedicated method, `cell_wall_area`
@@ -776,6 +819,7 @@ class AbstractSpatialImageAnalysis(object):
         self._center_of_mass = {}
         self._walls = None
         self._wall_medians = None
+        self._signal_cache = None
         self._voxel_layer1 = None
         self._voxel_layer18 = None
 
