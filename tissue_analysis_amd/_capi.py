@@ -44,6 +44,10 @@ SIGNAL_SYMBOLS = (
     "ta_signal_timing",
 )
 SIG_LABELS, SIG_WALLS = 1, 2           # TA_SIG_LABELS / TA_SIG_WALLS
+
+# every symbol include/tissue_scan_mesh.h declares (same library)
+MESH_SYMBOLS = ("ta_mesh_extract", "ta_mesh_size", "ta_mesh_get", "ta_mesh_timing")
+MESH_OUTSIDE = 0xFFFFFFFF              # TA_MESH_OUTSIDE
 SIGNAL_DTYPES = (np.uint8, np.uint16)
 
 
@@ -143,8 +147,12 @@ def load():
         "ta_signal_get_labels": (ci, [vp, vp, vp, vp, vp, vp]),
         "ta_signal_get_walls": (ci, [vp, vp, vp]),
         "ta_signal_timing": (ci, [vp, P(ctypes.c_double)]),
+        "ta_mesh_extract": (ci, [vp, ci, vp]),
+        "ta_mesh_size": (ci, [vp, P(u64), P(u64), P(u64)]),
+        "ta_mesh_get": (ci, [vp, vp, vp, vp, vp, vp, vp, vp]),
+        "ta_mesh_timing": (ci, [vp, P(ctypes.c_double)]),
     }
-    for name in SYMBOLS + SIGNAL_SYMBOLS:
+    for name in SYMBOLS + SIGNAL_SYMBOLS + MESH_SYMBOLS:
         fn = getattr(lib, name)      # AttributeError here == the .so does not match the header
         fn.restype, fn.argtypes = sig[name]
     if lib.ta_version() != ABI_VERSION:
@@ -413,6 +421,35 @@ class Context(object):
     def signal_timing(self):
         ms = ctypes.c_double(0.0)
         _check(self._lib.ta_signal_timing(self._h, ctypes.byref(ms)))
+        return ms.value
+
+    # -- cell meshes (include/tissue_scan_mesh.h)
+    def mesh(self, sub_factor=1, wanted_rows=None):
+        """The surface meshes of the rows with wanted_rows[row] != 0 (uint8, one per row of the last extraction; None = every
+        row, background included) on vol[::s, ::s, ::s].  Returns (cells u32[C] (rows), vertex_offsets u64[C+1],
+        triangle_offsets u64[C+1], corners u64[V] (C-order index on the corner grid of dims ceil(n / s) + 1), triangles
+        u32[T, 3], triangle_cell u32[T] (rows), triangle_neighbor u32[T] (rows, MESH_OUTSIDE at the border), device ms)."""
+        keep = None
+        if wanted_rows is not None:
+            keep = np.ascontiguousarray(wanted_rows, dtype=np.uint8)
+            if keep.size != self._max_label + 1:
+                raise ValueError("wanted_rows has %d entries, the extraction %d rows" % (keep.size, self._max_label + 1))
+        _check(self._lib.ta_mesh_extract(self._h, int(sub_factor), None if keep is None else keep.ctypes.data))
+        C, V, T = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+        _check(self._lib.ta_mesh_size(self._h, ctypes.byref(C), ctypes.byref(V), ctypes.byref(T)))
+        C, V, T = C.value, V.value, T.value
+        cells = np.zeros(C, dtype=np.uint32)
+        voff, toff = np.zeros(C + 1, dtype=np.uint64), np.zeros(C + 1, dtype=np.uint64)
+        corners = np.zeros(V, dtype=np.uint64)
+        tri = np.zeros((T, 3), dtype=np.uint32)
+        tcell, tnb = np.zeros(T, dtype=np.uint32), np.zeros(T, dtype=np.uint32)
+        _check(self._lib.ta_mesh_get(self._h, cells.ctypes.data, voff.ctypes.data, toff.ctypes.data, corners.ctypes.data,
+                                     tri.ctypes.data, tcell.ctypes.data, tnb.ctypes.data))
+        return cells, voff, toff, corners, tri, tcell, tnb, self.mesh_timing()
+
+    def mesh_timing(self):
+        ms = ctypes.c_double(0.0)
+        _check(self._lib.ta_mesh_timing(self._h, ctypes.byref(ms)))
         return ms.value
 
     def max_label(self):

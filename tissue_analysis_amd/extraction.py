@@ -519,6 +519,17 @@ class ResidentVolume(object):
         self.ms["signal"] = (time.perf_counter() - t0) * 1e3
         return st
 
+    def meshes(self, labels=None, sub_factor=1, voxelsize=(1.0, 1.0, 1.0)):
+        """The exact voxel-face surface meshes of the cells `labels` (ids; None = every label, background included) of
+        host[::s, ::s, ::s]: a `CellMeshes`.  Count, scan and emit on the GPU, over the current extraction (swept first when
+        there is none)."""
+        import time
+        from .cell_meshes import resident_meshes
+        t0 = time.perf_counter()
+        m = resident_meshes(self, labels, sub_factor, voxelsize)
+        self.ms["meshes"] = (time.perf_counter() - t0) * 1e3
+        return m
+
     def wall_table(self):
         if self.host.flags.c_contiguous:       # memory order IS np.where order: the device groups the records by pair
             lo, hi, coords, ms = self.ctx.wall_voxels(by_pair=True)

@@ -203,6 +203,7 @@ class AbstractSpatialImageAnalysis(object):
         self._walls = None
         self._wall_medians = None
         self._signal_cache = None
+        self._mesh_cache = {}
         try:
             self.filepath, self.filename = split(image.info["Filename"])
         except Exception:
@@ -257,6 +258,7 @@ class AbstractSpatialImageAnalysis(object):
         self._walls = None
         self._wall_medians = None
         self._signal_cache = None
+        self._mesh_cache = {}
         self._voxel_layer1 = None
         self._voxel_layer18 = None
 
@@ -578,6 +580,22 @@ class AbstractSpatialImageAnalysis(object):
         a, b = stats.wall_side_means
         return dict((k, (float(a[r]), float(b[r])) if r >= 0 else (float('nan'), float('nan'))) for k, r in zip(keys, rows.tolist()))
 
+    # -- cell surface meshes (include/tissue_scan_mesh.h; count, scan and emit on the GPU)
+    def cell_meshes(self, labels=None, sub_factor=1):
+        """The exact voxel-face surface meshes of `labels` (default: labels(), so no background and no ignored label) on
+        image[::sub_factor, ::sub_factor, ::sub_factor], in real units (voxel size times sub_factor): a `CellMeshes`,
+        `meshes[label]` = (points, triangles).  Unlike the reference (VTK marching cubes and smoothing on an image subsampled
+        by interpolation), no smoothing and a strided subsampling.  Cached per argument set until the image changes."""
+        wanted = tuple(self.labels()) if labels is None else tuple(self.label_request(labels))
+        key = (wanted, int(sub_factor))
+        cache = getattr(self, "_mesh_cache", None)
+        if cache is None:
+            cache = self._mesh_cache = {}
+        if key not in cache:
+            vs = tuple(float(v) for v in self._voxelsize)
+            cache[key] = self._resident_rows().meshes(list(wanted), int(sub_factor), vs)
+        return cache[key]
+
     def surface_area(self, labels=None, real=True):
         """Per-label total surface area = the sum of the label's wall areas with all its face neighbours
         (SURVEY.md §8 "Semantics": sum_m wall_area(l, m); the reference has no dedicated method, `cell_wall_area`
@@ -820,6 +838,7 @@ class AbstractSpatialImageAnalysis(object):
         self._walls = None
         self._wall_medians = None
         self._signal_cache = None
+        self._mesh_cache = {}
         self._voxel_layer1 = None
         self._voxel_layer18 = None
 
