@@ -50,6 +50,12 @@ MESH_SYMBOLS = ("ta_mesh_extract", "ta_mesh_size", "ta_mesh_get", "ta_mesh_timin
 MESH_OUTSIDE = 0xFFFFFFFF              # TA_MESH_OUTSIDE
 SIGNAL_DTYPES = (np.uint8, np.uint16)
 
+# every symbol include/tissue_scan_overlap.h declares (same library)
+OVERLAP_SYMBOLS = (
+    "ta_overlap_set", "ta_overlap_set_device", "ta_overlap_set_capacity", "ta_overlap_extract", "ta_overlap_size", "ta_overlap_get",
+    "ta_overlap_timing", "ta_overlap_timing_compaction",
+)
+
 
 def exchange_words(capacity_pairs):
     """uint64 words of one exchange block (TA_EXCHANGE_WORDS in include/tissue_scan.h)."""
@@ -151,8 +157,16 @@ def load():
         "ta_mesh_size": (ci, [vp, P(u64), P(u64), P(u64)]),
         "ta_mesh_get": (ci, [vp, vp, vp, vp, vp, vp, vp, vp]),
         "ta_mesh_timing": (ci, [vp, P(ctypes.c_double)]),
+        "ta_overlap_set": (ci, [vp, vp, ci, P(i64), P(i64)]),
+        "ta_overlap_set_device": (ci, [vp, vp, ci]),
+        "ta_overlap_set_capacity": (ci, [vp, ci]),
+        "ta_overlap_extract": (ci, [vp]),
+        "ta_overlap_size": (ci, [vp, P(u64)]),
+        "ta_overlap_get": (ci, [vp, vp, vp, vp]),
+        "ta_overlap_timing": (ci, [vp, P(ctypes.c_double)]),
+        "ta_overlap_timing_compaction": (ci, [vp, P(ctypes.c_double), P(ci)]),
     }
-    for name in SYMBOLS + SIGNAL_SYMBOLS + MESH_SYMBOLS:
+    for name in SYMBOLS + SIGNAL_SYMBOLS + MESH_SYMBOLS + OVERLAP_SYMBOLS:
         fn = getattr(lib, name)      # AttributeError here == the .so does not match the header
         fn.restype, fn.argtypes = sig[name]
     if lib.ta_version() != ABI_VERSION:
@@ -451,6 +465,68 @@ class Context(object):
         ms = ctypes.c_double(0.0)
         _check(self._lib.ta_mesh_timing(self._h, ctypes.byref(ms)))
         return ms.value
+
+    # -- label overlap with a second label volume (include/tissue_scan_overlap.h)
+    def set_overlap(self, array):
+        """Upload the second label volume B (uint16 / uint32, the label volume's shape).  One stored in another axis permutation
+        than the labels is copied into the labels' layout first."""
+        a = np.asarray(array)
+        if a.dtype not in (np.uint16, np.uint32):
+            raise TypeError("label volumes must be uint16 or uint32, not %s" % a.dtype)
+        layout = getattr(self, "_vol_layout", None)
+        if layout is None:
+            raise ValueError("set a label volume before the one it is compared with")
+        shape, el = layout
+        if a.ndim == 2 and len(shape) == 3 and shape[2] == 1:
+            a = a[:, :, None]
+        if tuple(a.shape) != shape:
+            raise ValueError("the second volume's shape %s differs from the label volume's %s" % (tuple(a.shape), shape))
+        same = all(n == 1 or st == e * a.dtype.itemsize for n, st, e in zip(a.shape, a.strides, el))
+        if not same:              # the labels' layout: a flat buffer viewed with their element strides
+            flat = np.empty(int(np.prod(shape)), dtype=a.dtype)
+            view = np.lib.stride_tricks.as_strided(flat, shape=shape, strides=[e * a.dtype.itemsize for e in el])
+            view[...] = a
+            a = view
+        _check(self._lib.ta_overlap_set(self._h, ctypes.c_void_p(a.ctypes.data), a.dtype.itemsize, _i64x3(a.shape), _i64x3(a.strides)))
+        self._keep_overlap = None
+
+    def set_overlap_device(self, dev_ptr, itemsize, keep=None):
+        """Adopt a device-resident B: dense C order with the label volume's buffer dims (halo plane included)."""
+        _check(self._lib.ta_overlap_set_device(self._h, ctypes.c_void_p(int(dev_ptr)), int(itemsize)))
+        self._keep_overlap = keep
+
+    def set_overlap_capacity(self, log2_slots=0):
+        """log2 of the slots the pass's device hash table starts with (0 = automatic); a table that is too small is grown."""
+        _check(self._lib.ta_overlap_set_capacity(self._h, int(log2_slots)))
+
+    def overlap_extract(self):
+        """Enqueue the overlap pass over the label volume and B."""
+        _check(self._lib.ta_overlap_extract(self._h))
+
+    def overlap_size(self):
+        n = ctypes.c_uint64(0)
+        _check(self._lib.ta_overlap_size(self._h, ctypes.byref(n)))
+        return int(n.value)
+
+    def overlap_get(self):
+        """(a u32[P], b u32[P], n u64[P]): the voxels n with label a in the volume and b in B, sorted by (a, b)."""
+        P = self.overlap_size()
+        a, b = np.zeros(P, dtype=np.uint32), np.zeros(P, dtype=np.uint32)
+        n = np.zeros(P, dtype=np.uint64)
+        _check(self._lib.ta_overlap_get(self._h, a.ctypes.data, b.ctypes.data, n.ctypes.data))
+        return a, b, n
+
+    def overlap_timing(self):
+        """Milliseconds of the pass kernel of the last overlap_extract."""
+        ms = ctypes.c_double(0.0)
+        _check(self._lib.ta_overlap_timing(self._h, ctypes.byref(ms)))
+        return ms.value
+
+    def overlap_timing_compaction(self):
+        """(milliseconds of compaction + sort of the settled table, runs of the pass kernel it took)."""
+        ms, passes = ctypes.c_double(0.0), ctypes.c_int(0)
+        _check(self._lib.ta_overlap_timing_compaction(self._h, ctypes.byref(ms), ctypes.byref(passes)))
+        return ms.value, int(passes.value)
 
     def max_label(self):
         v = ctypes.c_uint32(0)

@@ -313,9 +313,9 @@ hipError_t launch_wall_group_keyed(hipStream_t s, uint64_t n, uint64_t* keys0, u
 
 // The same passes on bare 32-bit keys with a u32 value each (kernels_mesh.hip groups its face and corner records by cell with it):
 // every pass writes keys and values, no record is unpacked.  Stable, so records of one key keep their order.
-template <int DB>
-static hipError_t radix_sort_u32_db(hipStream_t s, uint64_t n, uint32_t* keys0, uint32_t* keys1, uint32_t* idx0, uint32_t* idx1,
-                                    void* temp, int key_bits, uint32_t** keys_out, uint32_t** idx_out) {
+template <typename K, int DB>
+static hipError_t radix_sort_keys_db(hipStream_t s, uint64_t n, K* keys0, K* keys1, uint32_t* idx0, uint32_t* idx1,
+                                     void* temp, int key_bits, K** keys_out, uint32_t** idx_out) {
     const uint32_t nb = (uint32_t)rs_blocks(n);
     const uint64_t cells = (uint64_t)(1 << DB) * nb;
     char* p = (char*)temp;
@@ -328,17 +328,17 @@ static hipError_t radix_sort_u32_db(hipStream_t s, uint64_t n, uint32_t* keys0, 
     const size_t pass_words = seg_words + (size_t)RS_COPIES * (1 << DB);
     const hipError_t ez = hipMemsetAsync(totals, 0, (size_t)passes * pass_words * sizeof(uint32_t), s);
     if (ez != hipSuccess) return ez;
-    uint32_t* kin = keys0; uint32_t* kout = keys1;
+    K* kin = keys0; K* kout = keys1;
     uint32_t* vin = idx0; uint32_t* vout = idx1;
     const WallLin none = {0u, 0u, {0, 1, 2}};
     for (int pass = 0; pass < passes; ++pass) {
         const int shift = pass * DB;
         uint32_t* seg_total = totals + (size_t)pass * pass_words;
-        hipLaunchKernelGGL((radix_hist_kernel<uint32_t, DB>), dim3(nb), dim3(256), 0, s, kin, n, shift, hist, seg_total, seg_total + seg_words);
+        hipLaunchKernelGGL((radix_hist_kernel<K, DB>), dim3(nb), dim3(256), 0, s, kin, n, shift, hist, seg_total, seg_total + seg_words);
         hipLaunchKernelGGL((radix_offsets_kernel<DB>), dim3(nseg, ((1 << DB) + 255) / 256), dim3(256), 0, s, hist, nb, seg_total, seg_total + seg_words, offs);
-        hipLaunchKernelGGL((radix_scatter_kernel<uint32_t, DB, false>), dim3(nb), dim3(256), 0, s, kin, vin, n, shift, offs, kout, vout,
+        hipLaunchKernelGGL((radix_scatter_kernel<K, DB, false>), dim3(nb), dim3(256), 0, s, kin, vin, n, shift, offs, kout, vout,
                            (const WallInt3*)nullptr, (uint2*)nullptr, (WallInt3*)nullptr, key_bits, none);
-        uint32_t* tk = kin; kin = kout; kout = tk;
+        K* tk = kin; kin = kout; kout = tk;
         uint32_t* tv = vin; vin = vout; vout = tv;
     }
     *keys_out = kin;
@@ -354,9 +354,24 @@ hipError_t launch_radix_sort_u32(hipStream_t s, uint64_t n, uint32_t* keys0, uin
     if (key_bits < 1) key_bits = 1;
     if (key_bits > 32) key_bits = 32;
     switch (rs_digit_bits(key_bits)) {
-        case 10: return radix_sort_u32_db<10>(s, n, keys0, keys1, idx0, idx1, temp, key_bits, keys_out, idx_out);
-        case 9: return radix_sort_u32_db<9>(s, n, keys0, keys1, idx0, idx1, temp, key_bits, keys_out, idx_out);
-        default: return radix_sort_u32_db<8>(s, n, keys0, keys1, idx0, idx1, temp, key_bits, keys_out, idx_out);
+        case 10: return radix_sort_keys_db<uint32_t, 10>(s, n, keys0, keys1, idx0, idx1, temp, key_bits, keys_out, idx_out);
+        case 9: return radix_sort_keys_db<uint32_t, 9>(s, n, keys0, keys1, idx0, idx1, temp, key_bits, keys_out, idx_out);
+        default: return radix_sort_keys_db<uint32_t, 8>(s, n, keys0, keys1, idx0, idx1, temp, key_bits, keys_out, idx_out);
+    }
+}
+
+// ... and on 64-bit keys (kernels_overlap.hip sorts its pair keys a << bits | b with it, the table slot as value)
+hipError_t launch_radix_sort_u64(hipStream_t s, uint64_t n, uint64_t* keys0, uint64_t* keys1, uint32_t* idx0, uint32_t* idx1,
+                                 void* temp, int key_bits, uint64_t** keys_out, uint32_t** idx_out) {
+    *keys_out = keys0;
+    *idx_out = idx0;
+    if (n == 0) return hipSuccess;
+    if (key_bits < 1) key_bits = 1;
+    if (key_bits > 64) key_bits = 64;
+    switch (rs_digit_bits(key_bits)) {
+        case 10: return radix_sort_keys_db<uint64_t, 10>(s, n, keys0, keys1, idx0, idx1, temp, key_bits, keys_out, idx_out);
+        case 9: return radix_sort_keys_db<uint64_t, 9>(s, n, keys0, keys1, idx0, idx1, temp, key_bits, keys_out, idx_out);
+        default: return radix_sort_keys_db<uint64_t, 8>(s, n, keys0, keys1, idx0, idx1, temp, key_bits, keys_out, idx_out);
     }
 }
 

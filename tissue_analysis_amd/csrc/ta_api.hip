@@ -1,9 +1,11 @@
 // ta_api.hip -- the C ABI of include/tissue_scan.h on top of the gfx950 kernels.
 #include "../../include/tissue_scan_signal.h"
 #include "../../include/tissue_scan_mesh.h"
+#include "../../include/tissue_scan_overlap.h"
 #include "ta_kernels.h"
 #include "ta_signal.h"
 #include "ta_mesh.h"
+#include "ta_overlap.h"
 
 #include <algorithm>
 #include <cmath>
@@ -181,6 +183,24 @@ struct ta_ctx {
     std::vector<uint32_t> mesh_cells;
     std::vector<uint64_t> mesh_voff, mesh_toff;
     hipEvent_t mesh_ev[4] = {nullptr, nullptr, nullptr, nullptr};
+
+    // label overlap with a second label volume B (include/tissue_scan_overlap.h): same buffer dims and layout as the label volume
+    const void* ovb = nullptr;                          // device pointer (owned_ovb.p or adopted), NULL = no B
+    DevBuf owned_ovb;
+    int ovb_itemsize = 0;
+    int64_t ovb_mdims[3] = {0, 0, 0};                   // the label buffer dims it was set for
+    DevBuf ov_table;                                    // the device-global pair table: keys u64[slots] | counts u64[slots]
+    DevBuf ov_small;                                    // flags u32[4] | voxels of the pair (2^32 - 1, 2^32 - 1) u64
+    DevBuf ov_work;                                     // compaction: block counts u32[B] | block offsets u64[B] | scan scratch
+    DevBuf ov_sort;                                     // sort keys u64[P] x 2 | slots u32[P] x 2 | radix temp
+    DevBuf ov_rows;                                     // the sorted table: a u32[P] | b u32[P] | n u64[P]
+    int ov_opt_log2 = 0;                                // ta_overlap_set_capacity: 0 = automatic
+    int ov_grown_log2 = 0;                              // what an automatic table of this volume had to grow to
+    int ov_log2 = 0;                                    // slots of the table of the pass in flight
+    int ov_state = 0;                                   // 0 = no table, 1 = pass enqueued, 2 = settled (ov_rows holds ov_npairs rows)
+    int ov_passes = 0;                                  // runs of the pass kernel for this table
+    uint64_t ov_npairs = 0;
+    hipEvent_t ov_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // pass begin, end | count + scan end | emit begin, rows end
 };
 
 namespace {
@@ -204,6 +224,17 @@ void drop_census(ta_ctx* c) {          // (whenever the voxels change)
     c->tune_launched = 0;
     for (bool& d : c->tune_done) d = false;
     if (c->compact) { c->compact = false; c->extracted = c->checked = false; }
+}
+
+// a new label volume (or new label values in it): the overlap table is stale; a B of other dims is dropped
+void overlap_on_new_volume(ta_ctx* c) {
+    c->ov_state = 0;
+    c->ov_grown_log2 = 0;
+    if (c->ovb && (c->ovb_mdims[0] != c->mdims[0] || c->ovb_mdims[1] != c->mdims[1] || c->ovb_mdims[2] != c->mdims[2])) {
+        c->ovb = nullptr;
+        c->owned_ovb.release();
+        c->ovb_itemsize = 0;
+    }
 }
 
 // a new label volume: the signal results are stale (extracted is false); a signal of other dims is dropped
@@ -558,6 +589,8 @@ TA_API int ta_ctx_destroy(ta_ctx* c) {
     for (auto& e : c->sig_ev) if (e) (void)hipEventDestroy(e);
     c->mesh_small.release(); c->mesh_work.release(); c->mesh_out.release();
     for (auto& e : c->mesh_ev) if (e) (void)hipEventDestroy(e);
+    c->owned_ovb.release(); c->ov_table.release(); c->ov_small.release(); c->ov_work.release(); c->ov_sort.release(); c->ov_rows.release();
+    for (auto& e : c->ov_ev) if (e) (void)hipEventDestroy(e);
     if (c->h_small) (void)hipHostFree(c->h_small);
     for (auto& e : c->ev) if (e) (void)hipEventDestroy(e);
     for (auto& e : c->ring) if (e) (void)hipEventDestroy(e);
@@ -705,6 +738,7 @@ TA_API int ta_volume_set(ta_ctx* c, const void* host_ptr, int itemsize, const in
     c->first_owned = 0;
     c->extracted = c->checked = false;
     signal_on_new_volume(c);
+    overlap_on_new_volume(c);
     return TA_OK;
 }
 
@@ -730,6 +764,7 @@ TA_API int ta_volume_set_device(ta_ctx* c, const void* dev_ptr, int itemsize, co
     c->first_owned = has_low_halo ? 1 : 0;
     c->extracted = c->checked = false;
     signal_on_new_volume(c);
+    overlap_on_new_volume(c);
     return TA_OK;
 }
 
@@ -761,6 +796,7 @@ TA_API int ta_volume_relabel(ta_ctx* c, const uint32_t* lut, uint32_t lut_len) {
     c->wall_median_count = -1;
     c->wall_records = -1;           // the staged wall records carry the OLD labels: a fetch must ask for a fresh count
     c->wall_region = 0; c->wall_not_staged = 0;
+    overlap_on_new_volume(c);
     return TA_OK;
 }
 
@@ -2231,6 +2267,252 @@ TA_API int ta_mesh_timing(ta_ctx* c, double* ms) {
     TA_HIP(hipEventElapsedTime(&t0, c->mesh_ev[0], c->mesh_ev[1]));
     TA_HIP(hipEventElapsedTime(&t1, c->mesh_ev[2], c->mesh_ev[3]));
     *ms = (double)t0 + (double)t1;
+    return TA_OK;
+}
+
+// ---- label overlap with a second label volume (include/tissue_scan_overlap.h; kernels_overlap.hip) ---------------------------
+
+}  // extern "C"
+
+namespace {
+
+constexpr int OV_MIN_LOG2 = 4, OV_MAX_LOG2 = 31;       // (the sort's values are u32 slot numbers)
+
+uint64_t overlap_voxels(const ta_ctx* c) { return (uint64_t)(c->mdims[0] - c->first_owned) * (uint64_t)c->mdims[1] * (uint64_t)c->mdims[2]; }
+
+// the table no pass over this volume can fill: two slots a voxel
+int overlap_top_log2(const ta_ctx* c) {
+    int l = OV_MIN_LOG2;
+    while (l < OV_MAX_LOG2 && (1ull << l) < 2 * overlap_voxels(c)) ++l;
+    return l;
+}
+
+// the automatic table: a slot per 512 voxels (two Voronoi frames hold a pair per ~3000 voxels), 2^16 .. 2^24 slots
+int overlap_auto_log2(const ta_ctx* c) {
+    int l = 16;
+    while (l < 24 && (1ull << l) < overlap_voxels(c) / 512) ++l;
+    return l;
+}
+
+int overlap_adopt(ta_ctx* c, int itemsize) {
+    c->ovb_itemsize = itemsize;
+    for (int k = 0; k < 3; ++k) c->ovb_mdims[k] = c->mdims[k];
+    c->ov_state = 0;
+    return TA_OK;
+}
+
+// clear a table of 2^ov_log2 slots and enqueue the pass, then the count and the scan of its occupied slots
+int overlap_launch(ta_ctx* c) {
+    const uint64_t slots = 1ull << c->ov_log2, blocks = ta::overlap_compact_blocks(slots);
+    int rc;
+    if ((rc = c->ov_table.reserve(slots * 16)) != TA_OK) return rc;
+    if ((rc = c->ov_small.reserve(32)) != TA_OK) return rc;
+    const uint64_t offsets_at = (blocks * 4 + 15) & ~15ull, scratch_at = offsets_at + blocks * 8;
+    if ((rc = c->ov_work.reserve(scratch_at + ta::scan_u32_scratch_bytes(blocks))) != TA_OK) return rc;
+    for (auto& ev : c->ov_ev) if (!ev) TA_HIP(hipEventCreate(&ev));
+    ta::OverlapArgs a;
+    a.a = c->vol;                  // (the ids as the caller stored them: never the rank copy of a compacted context)
+    a.b = c->ovb;
+    a.n0 = c->mdims[0]; a.n1 = c->mdims[1]; a.n2 = c->mdims[2];
+    a.first_owned = c->first_owned;
+    a.keys = (unsigned long long*)c->ov_table.p;
+    a.counts = a.keys + slots;
+    a.mask = (uint32_t)(slots - 1);
+    a.flags = (uint32_t*)c->ov_small.p;
+    a.top = (unsigned long long*)((char*)c->ov_small.p + 16);
+    a.tiles_per_group = 0;
+    TA_HIP(hipMemsetAsync(a.keys, 0xff, slots * 8, c->stream));
+    TA_HIP(hipMemsetAsync(a.counts, 0, slots * 8, c->stream));
+    TA_HIP(hipMemsetAsync(c->ov_small.p, 0, 32, c->stream));
+    TA_HIP(hipEventRecord(c->ov_ev[0], c->stream));
+    ta::launch_overlap(c->stream, a, c->itemsize, c->ovb_itemsize);
+    TA_HIP(hipGetLastError());
+    TA_HIP(hipEventRecord(c->ov_ev[1], c->stream));
+    char* w = (char*)c->ov_work.p;
+    ta::launch_overlap_count(c->stream, a.keys, slots, (uint32_t*)w);
+    ta::launch_scan_u32_exclusive(c->stream, (const uint32_t*)w, blocks, w + scratch_at, (uint64_t*)(w + offsets_at));
+    TA_HIP(hipGetLastError());
+    TA_HIP(hipEventRecord(c->ov_ev[2], c->stream));
+    c->ov_passes += 1;
+    return TA_OK;
+}
+
+// drain the stream; a table that overflowed is grown and the pass repeated; then the occupied slots become the sorted rows
+int overlap_settle(ta_ctx* c) {
+    if (c->ov_state == 2) return TA_OK;
+    if (c->ov_state != 1) return fail(TA_EINVAL, "no overlap table for the current volume and B (run ta_overlap_extract)");
+    int rc;
+    uint64_t occupied = 0, top = 0;
+    for (;;) {
+        const uint64_t slots = 1ull << c->ov_log2, blocks = ta::overlap_compact_blocks(slots);
+        const uint64_t scratch_at = ((blocks * 4 + 15) & ~15ull) + blocks * 8;
+        uint32_t small[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        TA_HIP(hipMemcpyAsync(small, c->ov_small.p, sizeof(small), hipMemcpyDeviceToHost, c->stream));
+        TA_HIP(hipMemcpyAsync(&occupied, ta::scan_u32_total((char*)c->ov_work.p + scratch_at, blocks), 8, hipMemcpyDeviceToHost, c->stream));
+        TA_HIP(hipStreamSynchronize(c->stream));
+        memcpy(&top, &small[4], 8);
+        if (!small[ta::OV_FLAG_OVERFLOW]) break;
+        const int most = overlap_top_log2(c);
+        if (c->ov_log2 >= most) {
+            c->ov_state = 0;
+            return fail(TA_ENOMEM, "the overlap table overflowed at its largest size (2^%d slots)", c->ov_log2);
+        }
+        c->ov_log2 = std::min(c->ov_log2 + 3, most);
+        if (!c->ov_opt_log2) c->ov_grown_log2 = c->ov_log2;
+        if ((rc = overlap_launch(c)) != TA_OK) { c->ov_state = 0; return rc; }
+    }
+    const uint64_t slots = 1ull << c->ov_log2, blocks = ta::overlap_compact_blocks(slots);
+    const uint64_t offsets_at = (blocks * 4 + 15) & ~15ull;
+    const uint64_t P = occupied + (top ? 1 : 0);
+    // sort keys u64[n] x 2 | slots u32[n] x 2 | radix temp
+    const uint64_t n = occupied, keys_bytes = (n * 8 + 15) & ~15ull, idx_bytes = (n * 4 + 15) & ~15ull;
+    if ((rc = c->ov_sort.reserve(2 * keys_bytes + 2 * idx_bytes + ta::wall_sort_temp_bytes(n) + 16)) != TA_OK) return rc;
+    if ((rc = c->ov_rows.reserve(P * 16 + 16)) != TA_OK) return rc;
+    char* q = (char*)c->ov_sort.p;
+    uint64_t* k0 = (uint64_t*)q; uint64_t* k1 = (uint64_t*)(q + keys_bytes);
+    uint32_t* i0 = (uint32_t*)(q + 2 * keys_bytes); uint32_t* i1 = (uint32_t*)(q + 2 * keys_bytes + idx_bytes);
+    void* temp = q + 2 * keys_bytes + 2 * idx_bytes;
+    const unsigned long long* keys = (const unsigned long long*)c->ov_table.p;
+    const int shift_b = 8 * c->ovb_itemsize;
+    TA_HIP(hipEventRecord(c->ov_ev[3], c->stream));
+    ta::launch_overlap_emit(c->stream, keys, slots, (const uint64_t*)((char*)c->ov_work.p + offsets_at), shift_b, k0, i0);
+    uint64_t* ks = k0; uint32_t* is = i0;
+    TA_HIP(ta::launch_radix_sort_u64(c->stream, n, k0, k1, i0, i1, temp, 8 * c->itemsize + shift_b, &ks, &is));
+    uint32_t* ra = (uint32_t*)c->ov_rows.p;
+    ta::launch_overlap_rows(c->stream, ks, is, n, keys + slots, shift_b, top, ra, ra + P, (uint64_t*)(ra + 2 * P));
+    TA_HIP(hipGetLastError());
+    TA_HIP(hipEventRecord(c->ov_ev[4], c->stream));
+    TA_HIP(hipStreamSynchronize(c->stream));
+    c->ov_npairs = P;
+    c->ov_state = 2;
+    return TA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+TA_API int ta_overlap_set(ta_ctx* c, const void* host_ptr, int itemsize, const int64_t dims[3], const int64_t strides_bytes[3]) {
+    if (!c) return fail(TA_EINVAL, "ctx is NULL");
+    if (!host_ptr || !dims) return fail(TA_EINVAL, "NULL argument");
+    if (itemsize != 2 && itemsize != 4) return fail(TA_EINVAL, "B's itemsize must be 2 (uint16) or 4 (uint32), not %d", itemsize);
+    if (!c->vol) return fail(TA_EINVAL, "no label volume set: B takes its dims and layout");
+    int64_t adims[3], el[3];                     // the label volume's dims and element strides, in array-axis order
+    int64_t e = 1;
+    for (int k = 2; k >= 0; --k) { adims[c->perm[k]] = c->mdims[k]; el[c->perm[k]] = e; e *= c->mdims[k]; }
+    for (int d = 0; d < 3; ++d) {
+        if (dims[d] != adims[d])
+            return fail(TA_EINVAL, "B's dims (%lld, %lld, %lld) differ from the label volume's (%lld, %lld, %lld)", (long long)dims[0],
+                        (long long)dims[1], (long long)dims[2], (long long)adims[0], (long long)adims[1], (long long)adims[2]);
+        const int64_t st = strides_bytes ? strides_bytes[d] : (d == 2 ? 1 : (d == 1 ? dims[2] : dims[1] * dims[2])) * itemsize;
+        if (dims[d] != 1 && st != el[d] * itemsize)
+            return fail(TA_EINVAL, "B's layout differs from the label volume's (axis %d: stride %lld bytes, expected %lld)", d,
+                        (long long)st, (long long)(el[d] * itemsize));
+    }
+    int rc = use_device(c);
+    if (rc != TA_OK) return rc;
+    const uint64_t bytes = (uint64_t)e * itemsize;
+    TA_HIP(hipStreamSynchronize(c->stream));     // (a pass in flight may still read the old B)
+    c->ovb = nullptr;
+    c->ov_state = 0;
+    if ((rc = c->owned_ovb.reserve(bytes + 64)) != TA_OK) return rc;
+    TA_HIP(hipMemcpyAsync(c->owned_ovb.p, host_ptr, bytes, hipMemcpyHostToDevice, c->stream));
+    TA_HIP(hipStreamSynchronize(c->stream));     // the host buffer may be freed after return
+    c->ovb = c->owned_ovb.p;
+    return overlap_adopt(c, itemsize);
+}
+
+TA_API int ta_overlap_set_device(ta_ctx* c, const void* dev_ptr, int itemsize) {
+    if (!c) return fail(TA_EINVAL, "ctx is NULL");
+    if (!dev_ptr) return fail(TA_EINVAL, "NULL argument");
+    if (itemsize != 2 && itemsize != 4) return fail(TA_EINVAL, "B's itemsize must be 2 (uint16) or 4 (uint32), not %d", itemsize);
+    if (!c->vol) return fail(TA_EINVAL, "no label volume set: B takes its buffer dims");
+    if (((uintptr_t)dev_ptr % itemsize) != 0) return fail(TA_EINVAL, "device pointer is not aligned to B's label type");
+    int rc = use_device(c);
+    if (rc != TA_OK) return rc;
+    TA_HIP(hipStreamSynchronize(c->stream));
+    c->owned_ovb.release();
+    c->ovb = dev_ptr;
+    return overlap_adopt(c, itemsize);
+}
+
+TA_API int ta_overlap_set_capacity(ta_ctx* c, int log2_slots) {
+    if (!c) return fail(TA_EINVAL, "ctx is NULL");
+    if (log2_slots != 0 && (log2_slots < OV_MIN_LOG2 || log2_slots > OV_MAX_LOG2))
+        return fail(TA_EINVAL, "the overlap table takes 2^%d .. 2^%d slots, or 0 for an automatic size", OV_MIN_LOG2, OV_MAX_LOG2);
+    c->ov_opt_log2 = log2_slots;
+    c->ov_grown_log2 = 0;
+    return TA_OK;
+}
+
+TA_API int ta_overlap_extract(ta_ctx* c) {
+    if (!c) return fail(TA_EINVAL, "ctx is NULL");
+    if (!c->vol) return fail(TA_EINVAL, "no label volume set");
+    if (!c->ovb) return fail(TA_EINVAL, "no second label volume set (ta_overlap_set)");
+    if (c->ovb_mdims[0] != c->mdims[0] || c->ovb_mdims[1] != c->mdims[1] || c->ovb_mdims[2] != c->mdims[2])
+        return fail(TA_EINVAL, "B does not match the label volume");
+    int rc = use_device(c);
+    if (rc != TA_OK) return rc;
+    c->ov_state = 0;
+    c->ov_passes = 0;
+    c->ov_log2 = c->ov_opt_log2 ? c->ov_opt_log2 : std::max(overlap_auto_log2(c), c->ov_grown_log2);
+    if ((rc = overlap_launch(c)) != TA_OK) return rc;
+    c->ov_state = 1;
+    return TA_OK;
+}
+
+TA_API int ta_overlap_size(ta_ctx* c, uint64_t* npairs) {
+    if (!c) return fail(TA_EINVAL, "ctx is NULL");
+    if (!npairs) return fail(TA_EINVAL, "NULL argument");
+    if (c->ov_state == 0) return fail(TA_EINVAL, "no overlap table for the current volume and B (run ta_overlap_extract)");
+    int rc = use_device(c);
+    if (rc != TA_OK) return rc;
+    if ((rc = overlap_settle(c)) != TA_OK) return rc;
+    *npairs = c->ov_npairs;
+    return TA_OK;
+}
+
+TA_API int ta_overlap_get(ta_ctx* c, uint32_t* a, uint32_t* b, uint64_t* n) {
+    if (!c) return fail(TA_EINVAL, "ctx is NULL");
+    if (c->ov_state == 0) return fail(TA_EINVAL, "no overlap table for the current volume and B (run ta_overlap_extract)");
+    int rc = use_device(c);
+    if (rc != TA_OK) return rc;
+    if ((rc = overlap_settle(c)) != TA_OK) return rc;
+    const uint64_t P = c->ov_npairs;
+    if (!P) return TA_OK;
+    const uint32_t* ra = (const uint32_t*)c->ov_rows.p;
+    if (a) TA_HIP(hipMemcpyAsync(a, ra, 4 * P, hipMemcpyDeviceToHost, c->stream));
+    if (b) TA_HIP(hipMemcpyAsync(b, ra + P, 4 * P, hipMemcpyDeviceToHost, c->stream));
+    if (n) TA_HIP(hipMemcpyAsync(n, ra + 2 * P, 8 * P, hipMemcpyDeviceToHost, c->stream));
+    TA_HIP(hipStreamSynchronize(c->stream));
+    return TA_OK;
+}
+
+TA_API int ta_overlap_timing(ta_ctx* c, double* ms) {
+    if (!c) return fail(TA_EINVAL, "ctx is NULL");
+    if (!ms) return fail(TA_EINVAL, "NULL argument");
+    if (c->ov_state == 0 || !c->ov_ev[1]) return fail(TA_EINVAL, "no overlap pass has been run");
+    int rc = use_device(c);
+    if (rc != TA_OK) return rc;
+    TA_HIP(hipEventSynchronize(c->ov_ev[1]));
+    float t = 0.f;
+    TA_HIP(hipEventElapsedTime(&t, c->ov_ev[0], c->ov_ev[1]));
+    *ms = (double)t;
+    return TA_OK;
+}
+
+TA_API int ta_overlap_timing_compaction(ta_ctx* c, double* ms, int* passes) {
+    if (!c) return fail(TA_EINVAL, "ctx is NULL");
+    if (!ms) return fail(TA_EINVAL, "NULL argument");
+    if (c->ov_state != 2) return fail(TA_EINVAL, "no settled overlap table (ask ta_overlap_size first)");
+    int rc = use_device(c);
+    if (rc != TA_OK) return rc;
+    TA_HIP(hipEventSynchronize(c->ov_ev[4]));
+    float t0 = 0.f, t1 = 0.f;
+    TA_HIP(hipEventElapsedTime(&t0, c->ov_ev[1], c->ov_ev[2]));
+    TA_HIP(hipEventElapsedTime(&t1, c->ov_ev[3], c->ov_ev[4]));
+    *ms = (double)t0 + (double)t1;
+    if (passes) *passes = c->ov_passes;
     return TA_OK;
 }
 

@@ -530,6 +530,17 @@ class ResidentVolume(object):
         self.ms["meshes"] = (time.perf_counter() - t0) * 1e3
         return m
 
+    def overlap(self, other):
+        """The overlap table of the resident volume with `other`, a second label image of the same shape (an integer array, or a
+        CUDA tensor of it): a `LabelOverlap` of rows (a, b, n) in the ids of the two images.  One upload of `other` (none for a
+        tensor) and one pass over both volumes on the GPU; no sweep is needed."""
+        import time
+        from .label_overlap import resident_overlap
+        t0 = time.perf_counter()
+        ov = resident_overlap(self, other)
+        self.ms["overlap"] = (time.perf_counter() - t0) * 1e3
+        return ov
+
     def wall_table(self):
         if self.host.flags.c_contiguous:       # memory order IS np.where order: the device groups the records by pair
             lo, hi, coords, ms = self.ctx.wall_voxels(by_pair=True)

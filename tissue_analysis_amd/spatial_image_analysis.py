@@ -596,6 +596,13 @@ class AbstractSpatialImageAnalysis(object):
             cache[key] = self._resident_rows().meshes(list(wanted), int(sub_factor), vs)
         return cache[key]
 
+    # -- overlap with a second label image of the same grid (include/tissue_scan_overlap.h; one pass on the GPU)
+    def overlap(self, other_image):
+        """The overlap table of this image with `other_image` (the next frame resampled onto this grid, or another segmentation
+        of the same image): a `LabelOverlap` of rows (a, b, n) in the ids of the two images.  Nothing is excluded here:
+        `overlap(next).lineage(exclude=(0, analysis.background()))` leaves the background out."""
+        return self._resident().overlap(np.asarray(other_image))
+
     def surface_area(self, labels=None, real=True):
         """Per-label total surface area = the sum of the label's wall areas with all its face neighbours
         (SURVEY.md §8 "Semantics": sum_m wall_area(l, m); the reference has no dedicated method, `cell_wall_area`
