@@ -56,6 +56,11 @@ OVERLAP_SYMBOLS = (
     "ta_overlap_timing", "ta_overlap_timing_compaction",
 )
 
+# every symbol include/tissue_scan_junctions.h declares (same library)
+JUNCTION_SYMBOLS = (
+    "ta_junctions_extract", "ta_junctions_size", "ta_junctions_get_edges", "ta_junctions_get_vertices", "ta_junctions_timing",
+)
+
 
 def exchange_words(capacity_pairs):
     """uint64 words of one exchange block (TA_EXCHANGE_WORDS in include/tissue_scan.h)."""
@@ -165,8 +170,13 @@ def load():
         "ta_overlap_get": (ci, [vp, vp, vp, vp]),
         "ta_overlap_timing": (ci, [vp, P(ctypes.c_double)]),
         "ta_overlap_timing_compaction": (ci, [vp, P(ctypes.c_double), P(ci)]),
+        "ta_junctions_extract": (ci, [vp]),
+        "ta_junctions_size": (ci, [vp, P(u64), P(u64), P(u64)]),
+        "ta_junctions_get_edges": (ci, [vp, vp, vp, vp]),
+        "ta_junctions_get_vertices": (ci, [vp, vp, vp, vp]),
+        "ta_junctions_timing": (ci, [vp, P(ctypes.c_double), P(ctypes.c_double)]),
     }
-    for name in SYMBOLS + SIGNAL_SYMBOLS + MESH_SYMBOLS + OVERLAP_SYMBOLS:
+    for name in SYMBOLS + SIGNAL_SYMBOLS + MESH_SYMBOLS + OVERLAP_SYMBOLS + JUNCTION_SYMBOLS:
         fn = getattr(lib, name)      # AttributeError here == the .so does not match the header
         fn.restype, fn.argtypes = sig[name]
     if lib.ta_version() != ABI_VERSION:
@@ -527,6 +537,33 @@ class Context(object):
         ms, passes = ctypes.c_double(0.0), ctypes.c_int(0)
         _check(self._lib.ta_overlap_timing_compaction(self._h, ctypes.byref(ms), ctypes.byref(passes)))
         return ms.value, int(passes.value)
+
+    # -- cell junctions (include/tissue_scan_junctions.h)
+    def junctions_extract(self):
+        """Enqueue the counting walk over the 2 x 2 x 2 blocks of the label volume."""
+        _check(self._lib.ta_junctions_extract(self._h))
+
+    def junctions_size(self):
+        """(rows of the edge table, rows of the vertex table, blocks of five labels or more); settles the tables."""
+        e, v, d = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+        _check(self._lib.ta_junctions_size(self._h, ctypes.byref(e), ctypes.byref(v), ctypes.byref(d)))
+        return int(e.value), int(v.value), int(d.value)
+
+    def junctions_get(self):
+        """((labels u32[E, 3], n u64[E], sums u64[E, 3]), the same with [V, 4] labels for the vertices, degenerate): rows sorted by
+        their labels, sums of the doubled block centres in array-axis order."""
+        E, V, degenerate = self.junctions_size()
+        el, en, es = np.zeros((E, 3), dtype=np.uint32), np.zeros(E, dtype=np.uint64), np.zeros((E, 3), dtype=np.uint64)
+        vl, vn, vs = np.zeros((V, 4), dtype=np.uint32), np.zeros(V, dtype=np.uint64), np.zeros((V, 3), dtype=np.uint64)
+        _check(self._lib.ta_junctions_get_edges(self._h, el.ctypes.data, en.ctypes.data, es.ctypes.data))
+        _check(self._lib.ta_junctions_get_vertices(self._h, vl.ctypes.data, vn.ctypes.data, vs.ctypes.data))
+        return (el, en, es), (vl, vn, vs), degenerate
+
+    def junctions_timing(self):
+        """(milliseconds of the two walks over the volume, milliseconds of everything after them) of settled tables."""
+        a, b = ctypes.c_double(0.0), ctypes.c_double(0.0)
+        _check(self._lib.ta_junctions_timing(self._h, ctypes.byref(a), ctypes.byref(b)))
+        return a.value, b.value
 
     def max_label(self):
         v = ctypes.c_uint32(0)

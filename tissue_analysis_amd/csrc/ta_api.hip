@@ -2,10 +2,12 @@
 #include "../../include/tissue_scan_signal.h"
 #include "../../include/tissue_scan_mesh.h"
 #include "../../include/tissue_scan_overlap.h"
+#include "../../include/tissue_scan_junctions.h"
 #include "ta_kernels.h"
 #include "ta_signal.h"
 #include "ta_mesh.h"
 #include "ta_overlap.h"
+#include "ta_junctions.h"
 
 #include <algorithm>
 #include <cmath>
@@ -201,6 +203,17 @@ struct ta_ctx {
     int ov_passes = 0;                                  // runs of the pass kernel for this table
     uint64_t ov_npairs = 0;
     hipEvent_t ov_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // pass begin, end | count + scan end | emit begin, rows end
+
+    // cell junctions (include/tissue_scan_junctions.h): index 0 = edges (3 labels), 1 = vertices (4 labels)
+    DevBuf jn_small;                                    // blocks of order >= 5 u64
+    DevBuf jn_work;                                     // per wave: counts u32[W] x 2 | offsets u64[W] x 2 | scan scratch x 2
+    DevBuf jn_rec;                                      // records: origins u64[N3] | origins u64[N4] | labels u32[N3][3] | labels u32[N4][4]
+    DevBuf jn_sort[2];                                  // sort keys u64[N] x 2 | order u32[N] x 2 | radix temp | row counts, offsets, scan scratch
+    DevBuf jn_rows[2];                                  // the table: n u64[R] | sums u64[R][3] | labels u32[R][K]
+    int jn_state = 0;                                   // 0 = no tables, 1 = counting walk enqueued, 2 = settled
+    uint64_t jn_waves = 0;                              // waves (= tasks) of a walk
+    uint64_t jn_nrows[2] = {0, 0}, jn_degenerate = 0;
+    hipEvent_t jn_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // count begin, end | scans end | emit begin, end | tables end
 };
 
 namespace {
@@ -236,6 +249,9 @@ void overlap_on_new_volume(ta_ctx* c) {
         c->ovb_itemsize = 0;
     }
 }
+
+// a new label volume (or new label values in it): the junction tables are stale
+void junctions_on_new_volume(ta_ctx* c) { c->jn_state = 0; }
 
 // a new label volume: the signal results are stale (extracted is false); a signal of other dims is dropped
 void signal_on_new_volume(ta_ctx* c) {
@@ -591,6 +607,9 @@ TA_API int ta_ctx_destroy(ta_ctx* c) {
     for (auto& e : c->mesh_ev) if (e) (void)hipEventDestroy(e);
     c->owned_ovb.release(); c->ov_table.release(); c->ov_small.release(); c->ov_work.release(); c->ov_sort.release(); c->ov_rows.release();
     for (auto& e : c->ov_ev) if (e) (void)hipEventDestroy(e);
+    c->jn_small.release(); c->jn_work.release(); c->jn_rec.release();
+    for (int k = 0; k < 2; ++k) { c->jn_sort[k].release(); c->jn_rows[k].release(); }
+    for (auto& e : c->jn_ev) if (e) (void)hipEventDestroy(e);
     if (c->h_small) (void)hipHostFree(c->h_small);
     for (auto& e : c->ev) if (e) (void)hipEventDestroy(e);
     for (auto& e : c->ring) if (e) (void)hipEventDestroy(e);
@@ -739,6 +758,7 @@ TA_API int ta_volume_set(ta_ctx* c, const void* host_ptr, int itemsize, const in
     c->extracted = c->checked = false;
     signal_on_new_volume(c);
     overlap_on_new_volume(c);
+    junctions_on_new_volume(c);
     return TA_OK;
 }
 
@@ -765,6 +785,7 @@ TA_API int ta_volume_set_device(ta_ctx* c, const void* dev_ptr, int itemsize, co
     c->extracted = c->checked = false;
     signal_on_new_volume(c);
     overlap_on_new_volume(c);
+    junctions_on_new_volume(c);
     return TA_OK;
 }
 
@@ -797,6 +818,7 @@ TA_API int ta_volume_relabel(ta_ctx* c, const uint32_t* lut, uint32_t lut_len) {
     c->wall_records = -1;           // the staged wall records carry the OLD labels: a fetch must ask for a fresh count
     c->wall_region = 0; c->wall_not_staged = 0;
     overlap_on_new_volume(c);
+    junctions_on_new_volume(c);
     return TA_OK;
 }
 
@@ -1349,6 +1371,7 @@ TA_API int ta_volume_rerank(ta_ctx* c) {
     if (e != hipSuccess) return fail(TA_EHIP, "re-rank: %s", hipGetErrorString(e));
     c->rerank_check = true;
     c->vol_max = -1;
+    junctions_on_new_volume(c);     // (the caller edited the labels in place)
     return TA_OK;
 }
 
@@ -2513,6 +2536,218 @@ TA_API int ta_overlap_timing_compaction(ta_ctx* c, double* ms, int* passes) {
     TA_HIP(hipEventElapsedTime(&t1, c->ov_ev[3], c->ov_ev[4]));
     *ms = (double)t0 + (double)t1;
     if (passes) *passes = c->ov_passes;
+    return TA_OK;
+}
+
+}  // extern "C"
+
+// ---- cell junctions (include/tissue_scan_junctions.h; kernels_junctions.hip) ---------------------------------------------------
+
+namespace {
+
+// where the parts of jn_work lie, for W waves
+struct JunctionWork {
+    uint64_t counts[2], offsets[2], scratch[2], bytes;
+    explicit JunctionWork(uint64_t W) {
+        uint64_t at = 0;
+        for (int k = 0; k < 2; ++k) { counts[k] = at; at += align16(W * 4); }
+        for (int k = 0; k < 2; ++k) { offsets[k] = at; at += align16(W * 8); }
+        for (int k = 0; k < 2; ++k) { scratch[k] = at; at += align16(ta::scan_u32_scratch_bytes(W)); }
+        bytes = at + 16;
+    }
+};
+
+// where the parts of jn_sort[k] lie, for N records
+struct JunctionSort {
+    uint64_t keys[2], order[2], temp, counts, offsets, scratch, bytes;
+    explicit JunctionSort(uint64_t N) {
+        const uint64_t B = ta::junction_row_blocks(N);
+        uint64_t at = 0;
+        for (int k = 0; k < 2; ++k) { keys[k] = at; at += align16(N * 8); }
+        for (int k = 0; k < 2; ++k) { order[k] = at; at += align16(N * 4); }
+        temp = at; at += align16(ta::wall_sort_temp_bytes(N));
+        counts = at; at += align16(B * 4);
+        offsets = at; at += align16(B * 8);
+        scratch = at; at += align16(ta::scan_u32_scratch_bytes(B));
+        bytes = at + 16;
+    }
+};
+
+ta::JunctionArgs junction_args(ta_ctx* c) {
+    ta::JunctionArgs a = {};
+    a.vol = c->vol;                // (the ids as the caller stored them: never the rank copy of a compacted context, so that
+                                   //  the rows sort by id and need no translation)
+    a.n0 = c->mdims[0]; a.n1 = c->mdims[1]; a.n2 = c->mdims[2];
+    c->jn_waves = ta::junction_plan(a, c->itemsize);
+    const JunctionWork w(c->jn_waves);
+    char* p = (char*)c->jn_work.p;
+    a.wave_counts3 = (uint32_t*)(p + w.counts[0]); a.wave_counts4 = (uint32_t*)(p + w.counts[1]);
+    a.wave_offsets3 = (const uint64_t*)(p + w.offsets[0]); a.wave_offsets4 = (const uint64_t*)(p + w.offsets[1]);
+    a.degenerate = (unsigned long long*)c->jn_small.p;
+    return a;
+}
+
+// drain the stream, read the record counts, allocate, run the emitting walk, sort and reduce the records into the tables
+int junctions_settle(ta_ctx* c) {
+    if (c->jn_state == 2) return TA_OK;
+    if (c->jn_state != 1) return fail(TA_EINVAL, "no junction tables for the current volume (run ta_junctions_extract)");
+    c->jn_state = 0;                               // (whatever fails below: no tables)
+    int rc;
+    ta::JunctionArgs a = junction_args(c);
+    const JunctionWork w(c->jn_waves);
+    char* wp = (char*)c->jn_work.p;
+    uint64_t N[2] = {0, 0}, degenerate = 0;
+    for (int k = 0; k < 2; ++k)
+        TA_HIP(hipMemcpyAsync(&N[k], ta::scan_u32_total(wp + w.scratch[k], c->jn_waves), 8, hipMemcpyDeviceToHost, c->stream));
+    TA_HIP(hipMemcpyAsync(&degenerate, c->jn_small.p, 8, hipMemcpyDeviceToHost, c->stream));
+    TA_HIP(hipStreamSynchronize(c->stream));
+    for (int k = 0; k < 2; ++k)
+        if (N[k] >= (1ull << 32)) return fail(TA_ENOMEM, "%llu junction records: the sort takes fewer than 2^32", (unsigned long long)N[k]);
+    const int K[2] = {3, 4};
+    const uint64_t lab_at[2] = {align16(N[0] * 8) + align16(N[1] * 8), align16(N[0] * 8) + align16(N[1] * 8) + align16(N[0] * 12)};
+    if ((rc = c->jn_rec.reserve(lab_at[1] + align16(N[1] * 16) + 16)) != TA_OK) return rc;
+    for (int k = 0; k < 2; ++k)
+        if ((rc = c->jn_sort[k].reserve(JunctionSort(N[k]).bytes)) != TA_OK) return rc;
+    char* rp = (char*)c->jn_rec.p;
+    uint64_t* origins[2] = {(uint64_t*)rp, (uint64_t*)(rp + align16(N[0] * 8))};
+    uint32_t* labels[2] = {(uint32_t*)(rp + lab_at[0]), (uint32_t*)(rp + lab_at[1])};
+    a.origin3 = origins[0]; a.origin4 = origins[1];
+    a.labels3 = labels[0]; a.labels4 = labels[1];
+    TA_HIP(hipEventRecord(c->jn_ev[3], c->stream));
+    if (N[0] || N[1]) ta::launch_junction_pass(c->stream, a, c->itemsize, true);
+    TA_HIP(hipGetLastError());
+    TA_HIP(hipEventRecord(c->jn_ev[4], c->stream));
+    // stable sorts over the label columns from last to first, then the rows that start in every block of sorted records
+    const int lb = 8 * c->itemsize;
+    uint32_t* order[2] = {nullptr, nullptr};
+    uint64_t R[2] = {0, 0};
+    for (int k = 0; k < 2; ++k) {
+        const uint64_t n = N[k];
+        if (!n) continue;
+        const JunctionSort q(n);
+        char* sp = (char*)c->jn_sort[k].p;
+        uint64_t* k0 = (uint64_t*)(sp + q.keys[0]); uint64_t* k1 = (uint64_t*)(sp + q.keys[1]);
+        uint32_t* i0 = (uint32_t*)(sp + q.order[0]); uint32_t* i1 = (uint32_t*)(sp + q.order[1]);
+        ta::launch_junction_keys(c->stream, labels[k], K[k], n, nullptr, K[k] - 2, K[k] - 1, lb, k0, i0);
+        uint64_t* ks = k0; uint32_t* is = i0;
+        TA_HIP(ta::launch_radix_sort_u64(c->stream, n, k0, k1, i0, i1, sp + q.temp, 2 * lb, &ks, &is));
+        // the leading columns of the records in that order, into the key buffer the order came out with
+        uint64_t* ko = ks == k0 ? k1 : k0; uint32_t* io = is == i0 ? i1 : i0;
+        ta::launch_junction_keys(c->stream, labels[k], K[k], n, is, K[k] == 4 ? 0 : -1, K[k] == 4 ? 1 : 0, lb, ks, nullptr);
+        uint64_t* ks2 = ks; uint32_t* is2 = is;
+        TA_HIP(ta::launch_radix_sort_u64(c->stream, n, ks, ko, is, io, sp + q.temp, K[k] == 4 ? 2 * lb : lb, &ks2, &is2));
+        order[k] = is2;
+        const uint64_t B = ta::junction_row_blocks(n);
+        ta::launch_junction_heads(c->stream, labels[k], K[k], is2, n, (uint32_t*)(sp + q.counts));
+        ta::launch_scan_u32_exclusive(c->stream, (const uint32_t*)(sp + q.counts), B, sp + q.scratch, (uint64_t*)(sp + q.offsets));
+        TA_HIP(hipGetLastError());
+        TA_HIP(hipMemcpyAsync(&R[k], ta::scan_u32_total(sp + q.scratch, B), 8, hipMemcpyDeviceToHost, c->stream));
+    }
+    TA_HIP(hipStreamSynchronize(c->stream));
+    for (int k = 0; k < 2; ++k)
+        if ((rc = c->jn_rows[k].reserve(R[k] * 32 + R[k] * 4 * K[k] + 16)) != TA_OK) return rc;
+    for (int k = 0; k < 2; ++k) {
+        if (!N[k]) continue;
+        const JunctionSort q(N[k]);
+        char* sp = (char*)c->jn_sort[k].p;
+        char* op = (char*)c->jn_rows[k].p;
+        TA_HIP(hipMemsetAsync(op, 0, R[k] * 32, c->stream));
+        ta::JunctionRows rows;
+        rows.n = (unsigned long long*)op;
+        rows.sums = rows.n + R[k];
+        rows.labels = (uint32_t*)(op + R[k] * 32);
+        rows.n0 = c->mdims[0]; rows.n1 = c->mdims[1]; rows.n2 = c->mdims[2];
+        rows.origin0 = c->a_origin - c->first_owned;
+        for (int d = 0; d < 3; ++d) { rows.flat[d] = c->mdims[d] == 1 ? 1 : 0; rows.axis[d] = c->perm[d]; }
+        ta::launch_junction_reduce(c->stream, labels[k], origins[k], K[k], order[k], N[k], (const uint64_t*)(sp + q.offsets), rows);
+        TA_HIP(hipGetLastError());
+    }
+    TA_HIP(hipEventRecord(c->jn_ev[5], c->stream));
+    TA_HIP(hipStreamSynchronize(c->stream));
+    c->jn_nrows[0] = R[0]; c->jn_nrows[1] = R[1];
+    c->jn_degenerate = degenerate;
+    c->jn_state = 2;
+    return TA_OK;
+}
+
+int junctions_get(ta_ctx* c, int k, uint32_t* labels, uint64_t* n, uint64_t* sums) {
+    if (!c) return fail(TA_EINVAL, "ctx is NULL");
+    if (c->jn_state == 0) return fail(TA_EINVAL, "no junction tables for the current volume (run ta_junctions_extract)");
+    int rc = use_device(c);
+    if (rc != TA_OK) return rc;
+    if ((rc = junctions_settle(c)) != TA_OK) return rc;
+    const uint64_t R = c->jn_nrows[k], K = k ? 4 : 3;
+    if (!R) return TA_OK;
+    const char* op = (const char*)c->jn_rows[k].p;
+    if (n) TA_HIP(hipMemcpyAsync(n, op, R * 8, hipMemcpyDeviceToHost, c->stream));
+    if (sums) TA_HIP(hipMemcpyAsync(sums, op + R * 8, R * 24, hipMemcpyDeviceToHost, c->stream));
+    if (labels) TA_HIP(hipMemcpyAsync(labels, op + R * 32, R * 4 * K, hipMemcpyDeviceToHost, c->stream));
+    TA_HIP(hipStreamSynchronize(c->stream));
+    return TA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+TA_API int ta_junctions_extract(ta_ctx* c) {
+    if (!c) return fail(TA_EINVAL, "ctx is NULL");
+    if (!c->vol) return fail(TA_EINVAL, "no label volume set");
+    int rc = use_device(c);
+    if (rc != TA_OK) return rc;
+    c->jn_state = 0;
+    if ((rc = c->jn_small.reserve(16)) != TA_OK) return rc;
+    {
+        ta::JunctionArgs plan = {};
+        plan.n0 = c->mdims[0]; plan.n1 = c->mdims[1]; plan.n2 = c->mdims[2];
+        if ((rc = c->jn_work.reserve(JunctionWork(ta::junction_plan(plan, c->itemsize)).bytes)) != TA_OK) return rc;
+    }
+    for (auto& ev : c->jn_ev) if (!ev) TA_HIP(hipEventCreate(&ev));
+    const ta::JunctionArgs a = junction_args(c);
+    const JunctionWork w(c->jn_waves);
+    char* wp = (char*)c->jn_work.p;
+    TA_HIP(hipMemsetAsync(c->jn_small.p, 0, 16, c->stream));
+    TA_HIP(hipEventRecord(c->jn_ev[0], c->stream));
+    ta::launch_junction_pass(c->stream, a, c->itemsize, false);
+    TA_HIP(hipGetLastError());
+    TA_HIP(hipEventRecord(c->jn_ev[1], c->stream));
+    for (int k = 0; k < 2; ++k)
+        ta::launch_scan_u32_exclusive(c->stream, (const uint32_t*)(wp + w.counts[k]), c->jn_waves, wp + w.scratch[k], (uint64_t*)(wp + w.offsets[k]));
+    TA_HIP(hipGetLastError());
+    TA_HIP(hipEventRecord(c->jn_ev[2], c->stream));
+    c->jn_state = 1;
+    return TA_OK;
+}
+
+TA_API int ta_junctions_size(ta_ctx* c, uint64_t* nedges, uint64_t* nvertices, uint64_t* degenerate) {
+    if (!c) return fail(TA_EINVAL, "ctx is NULL");
+    if (c->jn_state == 0) return fail(TA_EINVAL, "no junction tables for the current volume (run ta_junctions_extract)");
+    int rc = use_device(c);
+    if (rc != TA_OK) return rc;
+    if ((rc = junctions_settle(c)) != TA_OK) return rc;
+    if (nedges) *nedges = c->jn_nrows[0];
+    if (nvertices) *nvertices = c->jn_nrows[1];
+    if (degenerate) *degenerate = c->jn_degenerate;
+    return TA_OK;
+}
+
+TA_API int ta_junctions_get_edges(ta_ctx* c, uint32_t* labels, uint64_t* n, uint64_t* sums) { return junctions_get(c, 0, labels, n, sums); }
+
+TA_API int ta_junctions_get_vertices(ta_ctx* c, uint32_t* labels, uint64_t* n, uint64_t* sums) { return junctions_get(c, 1, labels, n, sums); }
+
+TA_API int ta_junctions_timing(ta_ctx* c, double* ms_pass, double* ms_after) {
+    if (!c) return fail(TA_EINVAL, "ctx is NULL");
+    if (c->jn_state != 2) return fail(TA_EINVAL, "no settled junction tables (ask ta_junctions_size first)");
+    int rc = use_device(c);
+    if (rc != TA_OK) return rc;
+    TA_HIP(hipEventSynchronize(c->jn_ev[5]));
+    float count = 0.f, scans = 0.f, emit = 0.f, rest = 0.f;
+    TA_HIP(hipEventElapsedTime(&count, c->jn_ev[0], c->jn_ev[1]));
+    TA_HIP(hipEventElapsedTime(&scans, c->jn_ev[1], c->jn_ev[2]));
+    TA_HIP(hipEventElapsedTime(&emit, c->jn_ev[3], c->jn_ev[4]));
+    TA_HIP(hipEventElapsedTime(&rest, c->jn_ev[4], c->jn_ev[5]));
+    if (ms_pass) *ms_pass = (double)count + (double)emit;
+    if (ms_after) *ms_after = (double)scans + (double)rest;
     return TA_OK;
 }
 

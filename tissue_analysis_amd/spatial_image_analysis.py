@@ -204,6 +204,7 @@ class AbstractSpatialImageAnalysis(object):
         self._wall_medians = None
         self._signal_cache = None
         self._mesh_cache = {}
+        self._junctions = None
         try:
             self.filepath, self.filename = split(image.info["Filename"])
         except Exception:
@@ -259,6 +260,7 @@ class AbstractSpatialImageAnalysis(object):
         self._wall_medians = None
         self._signal_cache = None
         self._mesh_cache = {}
+        self._junctions = None
         self._voxel_layer1 = None
         self._voxel_layer18 = None
 
@@ -603,6 +605,19 @@ class AbstractSpatialImageAnalysis(object):
         `overlap(next).lineage(exclude=(0, analysis.background()))` leaves the background out."""
         return self._resident().overlap(np.asarray(other_image))
 
+    # -- cell junctions (include/tissue_scan_junctions.h; two walks over the resident volume on the GPU)
+    def cell_junctions(self):
+        """The lines where three cells meet and the points where four cells meet: a `CellJunctions` in the ids of the image and
+        with this analysis' voxel size.  Nothing is excluded here (the background and the ignored labels have rows): the
+        methods of the result take an `exclude`.  Cached until `refresh()` or an edit of the image."""
+        if getattr(self, "_junctions", None) is None:
+            self._junctions = self._resident().junctions(tuple(float(v) for v in self._voxelsize))
+        return self._junctions
+
+    def cell_vertices(self, real=True):
+        """{(a, b, c, d): xyz} of every point where four labels meet (none excluded)."""
+        return self.cell_junctions().cell_vertices(real=real)
+
     def surface_area(self, labels=None, real=True):
         """Per-label total surface area = the sum of the label's wall areas with all its face neighbours
         (SURVEY.md §8 "Semantics": sum_m wall_area(l, m); the reference has no dedicated method, `cell_wall_area`
@@ -846,6 +861,7 @@ class AbstractSpatialImageAnalysis(object):
         self._wall_medians = None
         self._signal_cache = None
         self._mesh_cache = {}
+        self._junctions = None
         self._voxel_layer1 = None
         self._voxel_layer18 = None
 
