@@ -214,3 +214,193 @@ def test_sia_cell_meshes_and_reference_functions():
     assert len(matching) == len(m.triangles)
     sia.refresh()
     assert sia.cell_meshes() is not m
+
+
+def as_meshes(r):
+    """The reference's dict as a CellMeshes (for comparisons that go through tri_set)."""
+    return CellMeshes(r["labels"], r["points"], r["triangles"], r["triangle_cell"], r["triangle_neighbor"], r["vertex_offsets"],
+                      r["triangle_offsets"])
+
+
+def assert_same_sets(m, r):
+    """Cells, offsets and each cell's vertices identical (the vertex order holds in every layout); the faces as a set."""
+    w = as_meshes(r)
+    assert np.array_equal(m.labels, w.labels)
+    assert np.array_equal(m.vertex_offsets, w.vertex_offsets) and np.array_equal(m.triangle_offsets, w.triangle_offsets)
+    for i in range(w.labels.size):
+        v0, v1 = int(w.vertex_offsets[i]), int(w.vertex_offsets[i + 1])
+        assert sorted(map(tuple, m.points[v0:v1].tolist())) == sorted(map(tuple, w.points[v0:v1].tolist()))
+    assert np.array_equal(m.points, w.points)
+    assert tri_set(m) == tri_set(w)
+
+
+@pytest.mark.parametrize("shape", [(1, 1, 1), (1, 1, 77), (1, 9, 40), (5, 1, 64), (3, 5, 1031), (2, 2, 2100)])
+def test_thin_and_tiny_volumes_and_rows_longer_than_a_wave(shape):
+    """(3, 5, 1031), (2, 2, 2100): a wave's 1024 voxels end inside a row, and the rows of the corner grid (1032, 2101) wrap
+    inside a step of 64 lanes."""
+    rng = np.random.default_rng(sum(shape))
+    for dt in (np.uint16, np.uint32):
+        V = synth.voronoi_labels(shape, max(1, int(np.prod(shape)) // 60), 3, dt, ellipsoid=False)
+        m = check(V)
+        assert len(m.triangles) >= 12
+        check(rng.integers(1, 4, size=shape).astype(dt))
+        check(V, sub_factor=2)
+    if int(np.prod(shape)) > 1:
+        assert np.unique(V).size > 1
+
+
+def test_noise_and_a_uniform_volume():
+    rng = np.random.default_rng(12)
+    V = rng.integers(0, 6, size=(12, 14, 40)).astype(np.uint16)           # nearly every face a boundary, corners with many cells
+    m = check(V)
+    assert len(m.triangles) > 2 * 2.4 * V.size                            # (5/6 of the inner faces, counted from both sides)
+    check(V.astype(np.uint32), labels=[0, 3, 5])
+    V = rng.integers(0, 4000, size=(10, 10, 16)).astype(np.uint16)        # every face a boundary, up to eight cells a corner
+    m = check(V)
+    assert len(m.triangles) >= 2 * 5.99 * V.size and len(m.labels) > 1200
+    check(V.astype(np.uint32))
+    for dt in (np.uint16, np.uint32):
+        V = np.full((9, 6, 70), 5, dtype=dt)                              # one cell: only border faces
+        m = check(V)
+        assert m.labels.tolist() == [5] and (m.triangle_neighbor == -1).all()
+        assert len(m.triangles) == 4 * (9 * 6 + 9 * 70 + 6 * 70)
+
+
+def test_sub_factors_of_the_reference_and_beyond_the_dims():
+    V = synth.voronoi_labels((37, 41, 50), 30, 6, np.uint16)
+    for s in (4, 6):                                                      # what the reference subsamples by
+        check(V, sub_factor=s, voxelsize=(0.7, 1.1, 0.3))
+        check(V.astype(np.uint32), labels=[1, 2, 5, 9], sub_factor=s)
+    for s in (50, 64):                                                    # W is the single voxel V[0, 0, 0]
+        m = check(V, sub_factor=s)
+        assert m.labels.tolist() == [int(V[0, 0, 0])] and len(m.points) == 8 and len(m.triangles) == 12
+    check(V, sub_factor=41)                                               # W = V[::41, 0:1, ::41]: (1, 1, 2)
+    for X in (np.asfortranarray(V), np.transpose(V, (1, 0, 2)), np.transpose(V.astype(np.uint32), (2, 0, 1))):
+        assert not X.flags.c_contiguous
+        for s in (1, 3):
+            assert_same_sets(device_meshes(X, sub_factor=s), ref.mesh(X, sub_factor=s))
+
+
+def _code(code, call, *args):
+    with pytest.raises(_capi.TissueScanError) as e:
+        call(*args)
+    assert e.value.code == code
+
+
+def _einval(call, *args):
+    _code(_capi.TA_EINVAL, call, *args)
+
+
+def context_meshes(ctx, sub_factor=1, wanted_rows=None, ids=None):
+    """Context.mesh as a CellMeshes of unit voxels (rows are ids unless `ids` maps them)."""
+    cells, voff, toff, corners, tri, tcell, tnb, ms = ctx.mesh(sub_factor, wanted_rows)
+    assert ms > 0.0
+    name = (lambda r: r.astype(np.int64)) if ids is None else (lambda r: ids[r.astype(np.int64)].astype(np.int64))
+    nb = np.full(tnb.shape, -1, dtype=np.int64)
+    nb[tnb != _capi.MESH_OUTSIDE] = name(tnb[tnb != _capi.MESH_OUTSIDE])
+    g = tuple(-(-int(n) // sub_factor) + 1 for n in ctx._vol_layout[0])
+    K = np.stack(np.unravel_index(corners.astype(np.int64), g), axis=1).astype(np.float64)
+    return CellMeshes(name(cells), (K - 0.5) * sub_factor, tri, name(tcell), nb, voff, toff, sub_factor=sub_factor, ms=ms)
+
+
+def test_argument_checks_and_invalidation():
+    import torch
+    V = synth.voronoi_labels((10, 12, 40), 30, 3, dtype=np.uint16)
+    top = int(V.max())
+    ctx = _capi.Context(0)
+    try:
+        lib, h = ctx._lib, ctx._h
+        _einval(ctx.mesh)                                           # no volume
+        _einval(ctx.mesh_timing)                                    # no pass has ever run
+        ctx.set_volume(V)
+        _einval(ctx.mesh)                                           # a volume, but no ta_extract yet
+        assert lib.ta_mesh_size(h, None, None, None) == _capi.TA_EINVAL
+        assert lib.ta_mesh_get(h, None, None, None, None, None, None, None) == _capi.TA_EINVAL
+        _einval(ctx.mesh_timing)
+        ctx.extract(_capi.F_ALL, top)
+        _einval(ctx.mesh, 0)                                        # sub_factor 0
+        _einval(ctx.mesh, -2)
+        assert lib.ta_mesh_size(h, None, None, None) == _capi.TA_EINVAL           # an extraction, but no mesh pass yet
+        assert lib.ta_mesh_get(h, None, None, None, None, None, None, None) == _capi.TA_EINVAL
+        _einval(ctx.mesh_timing)
+        with pytest.raises(ValueError):
+            ctx.mesh(1, np.ones(top, dtype=np.uint8))               # wanted_rows: one byte per row, top + 1 of them
+        with pytest.raises(ValueError):
+            ctx.mesh(1, np.ones(top + 2, dtype=np.uint8))
+        assert_identical(context_meshes(ctx), ref.mesh(V))
+        assert lib.ta_mesh_size(h, None, None, None) == _capi.TA_OK               # any pointer may be NULL
+        assert lib.ta_mesh_get(h, None, None, None, None, None, None, None) == _capi.TA_OK
+        assert ctx.mesh_timing() > 0.0
+
+        def getters_refuse():
+            assert lib.ta_mesh_size(h, None, None, None) == _capi.TA_EINVAL
+            assert lib.ta_mesh_get(h, None, None, None, None, None, None, None) == _capi.TA_EINVAL
+
+        ctx.extract(_capi.F_VOLUME, top + 3)                        # a new ta_extract: other rows
+        getters_refuse()
+        wanted = np.zeros(top + 4, dtype=np.uint8)
+        wanted[[1, 4, top, top + 2]] = 1
+        assert_identical(context_meshes(ctx, 1, wanted), ref.mesh(V, [1, 4, top, top + 2]))
+        lut = np.arange(top + 1, dtype=np.uint32)
+        lut[2:] += 100
+        lut[5] = 3                                                  # two cells fused
+        ctx.relabel(lut)                                            # ta_volume_relabel
+        getters_refuse()
+        _einval(ctx.mesh)                                           # ... and the extraction went with the volume
+        ctx.extract(_capi.F_ALL, top + 100)
+        assert_identical(context_meshes(ctx, 2), ref.mesh(lut[V], sub_factor=2))
+        ctx.set_volume(np.ascontiguousarray(V[:, :, :32]))          # a new volume
+        getters_refuse()
+        _einval(ctx.mesh)
+        ctx.extract(_capi.F_ALL, top)
+        assert_identical(context_meshes(ctx), ref.mesh(V[:, :, :32]))
+        ids = ctx.compact_labels()                                  # compaction: rows become ranks
+        getters_refuse()
+        _einval(ctx.mesh)
+        ctx.extract(_capi.F_ALL, ids.size - 1)
+        assert_identical(context_meshes(ctx, ids=ids), ref.mesh(V[:, :, :32]))
+        ctx.uncompact()                                             # ... and its end
+        getters_refuse()
+        _einval(ctx.mesh)
+        ctx.extract(_capi.F_ALL, top)
+        assert_identical(context_meshes(ctx), ref.mesh(V[:, :, :32]))
+        t = torch.from_numpy(V.view(np.int16).copy()).cuda()        # a slab adopted with a halo plane
+        torch.cuda.synchronize()
+        ctx.set_volume_device(t.data_ptr(), 2, t.shape, a0_origin=4, has_low_halo=True, keep=t)
+        ctx.extract(_capi.F_ALL, top)
+        _einval(ctx.mesh)
+        getters_refuse()
+        ctx.set_volume_device(t.data_ptr(), 2, t.shape, keep=t)     # the same planes without one
+        ctx.extract(_capi.F_ALL, top)
+        assert_identical(context_meshes(ctx), ref.mesh(V))
+    finally:
+        ctx.close()
+
+
+def test_a_volume_changed_behind_the_extraction_is_an_error_not_a_fault():
+    """A label above the rows of the extraction: the count kernels see it (they guard the read of the wanted table) and
+    ta_mesh_extract answers TA_ERANGE; the context goes on working."""
+    import torch
+    V = synth.voronoi_labels((12, 20, 70), 30, 5, np.uint32)
+    top = int(V.max())
+    for patch in ((slice(3, 6), slice(4, 9), slice(10, 50)), (slice(11, 12), slice(19, 20), slice(69, 70))):
+        t = torch.from_numpy(V.view(np.int32).copy()).cuda()
+        torch.cuda.synchronize()
+        ctx = _capi.Context(0)
+        try:
+            ctx.set_volume_device(t.data_ptr(), 4, t.shape, keep=t)
+            ctx.extract(_capi.F_ALL, top)
+            assert_identical(context_meshes(ctx), ref.mesh(V))
+            t[patch] = top + 1 + 70000
+            torch.cuda.synchronize()
+            _code(_capi.TA_ERANGE, ctx.mesh)
+            assert ctx._lib.ta_mesh_size(ctx._h, None, None, None) == _capi.TA_EINVAL          # no result is held
+            wanted = np.zeros(top + 1, dtype=np.uint8)
+            wanted[2] = 1
+            _code(_capi.TA_ERANGE, ctx.mesh, 1, wanted)
+            W = V.copy()
+            W[patch] = top + 1 + 70000
+            ctx.extract(_capi.F_ALL, int(W.max()))                  # a new extraction of the volume as it is now
+            assert_identical(context_meshes(ctx), ref.mesh(W))
+        finally:
+            ctx.close()
