@@ -14,9 +14,10 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJDIR = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "libtissue_scan.so")
-SOURCES = ["ta_api.hip", "kernels_basic.hip", "kernels_scan.hip", "kernels_walls.hip", "kernels_wallsort.hip", "kernels_wallmedian.hip", "kernels_census.hip",
+SOURCES = ["ta_api.hip", "ta_api_signal.hip", "ta_api_mesh.hip", "ta_api_overlap.hip", "ta_api_junctions.hip",
+           "kernels_basic.hip", "kernels_scan.hip", "kernels_walls.hip", "kernels_wallsort.hip", "kernels_wallmedian.hip", "kernels_census.hip",
            "kernels_pairsort.hip", "kernels_signal.hip", "kernels_mesh.hip", "kernels_overlap.hip", "kernels_junctions.hip"]
-HEADERS = ["ta_device.h", "ta_kernels.h", "ta_sweep_common.h", "ta_sweep_switches.h", "ta_pin_tables.inc", "ta_signal.h", "ta_mesh.h", "ta_overlap.h", "ta_junctions.h",
+HEADERS = ["ta_ctx.h", "ta_device.h", "ta_kernels.h", "ta_sweep_common.h", "ta_sweep_switches.h", "ta_pin_tables.inc", "ta_signal.h", "ta_mesh.h", "ta_overlap.h", "ta_junctions.h",
            os.path.join("..", "..", "include", "tissue_scan.h"), os.path.join("..", "..", "include", "tissue_scan_signal.h"),
            os.path.join("..", "..", "include", "tissue_scan_mesh.h"), os.path.join("..", "..", "include", "tissue_scan_overlap.h"),
            os.path.join("..", "..", "include", "tissue_scan_junctions.h")]
@@ -156,7 +157,7 @@ def sanitizer_runtime():
 
 
 def build_sanitized(force=False, verbose=False):
-    """HOST side of the same three sources under -fsanitize=address,undefined (the device side cannot be
+    """HOST side of the same SOURCES under -fsanitize=address,undefined (the device side cannot be
     instrumented on this pool and is compiled as usual): the library the CPU suite loads to walk the C ABI's
     argument checks and failure paths.  Never the product build."""
     hipcc = _hipcc()

@@ -1,28 +1,12 @@
-// ta_api.hip -- the C ABI of include/tissue_scan.h on top of the gfx950 kernels.
-#include "../../include/tissue_scan_signal.h"
-#include "../../include/tissue_scan_mesh.h"
-#include "../../include/tissue_scan_overlap.h"
-#include "../../include/tissue_scan_junctions.h"
-#include "ta_kernels.h"
-#include "ta_signal.h"
-#include "ta_mesh.h"
-#include "ta_overlap.h"
-#include "ta_junctions.h"
+// ta_api.hip -- the core C ABI of include/tissue_scan.h on top of the gfx950 kernels (the features: ta_api_<feature>.hip).
+#include "ta_ctx.h"
 
-#include <algorithm>
-#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
-#include <cstring>
 #include <new>
-#include <numeric>
-#include <string>
-#include <vector>
 
-namespace {
-
-thread_local std::string g_err;
+static thread_local std::string g_err;
 
 int fail(int code, const char* fmt, ...) {
     char buf[512];
@@ -34,188 +18,6 @@ int fail(int code, const char* fmt, ...) {
     return code;
 }
 
-#define TA_HIP(expr)                                                                         \
-    do {                                                                                     \
-        hipError_t e_ = (expr);                                                              \
-        if (e_ != hipSuccess)                                                                \
-            return fail(e_ == hipErrorOutOfMemory ? TA_ENOMEM : TA_EHIP, "%s: %s (%s:%d)",  \
-                        #expr, hipGetErrorString(e_), __FILE__, __LINE__);                   \
-    } while (0)
-
-struct DevBuf {
-    void* p = nullptr;
-    uint64_t bytes = 0;
-    int reserve(uint64_t need) {
-        if (need <= bytes) return TA_OK;
-        if (p) { (void)hipFree(p); p = nullptr; bytes = 0; }
-        if (hipMalloc(&p, need ? need : 16) != hipSuccess) {
-            (void)hipGetLastError();
-            p = nullptr;
-            return fail(TA_ENOMEM, "hipMalloc of %llu bytes failed", (unsigned long long)need);
-        }
-        bytes = need;
-        return TA_OK;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
-};
-
-// page-locked host memory (grow-only): device-to-host copies into it run at PCIe speed, into a std::vector they are staged
-struct PinnedBuf {
-    void* p = nullptr;
-    uint64_t bytes = 0;
-    int reserve(uint64_t need) {
-        if (need <= bytes) return TA_OK;
-        if (p) { (void)hipHostFree(p); p = nullptr; bytes = 0; }
-        if (hipHostMalloc(&p, need ? need : 16, hipHostMallocDefault) != hipSuccess) {
-            (void)hipGetLastError();
-            p = nullptr;
-            return fail(TA_ENOMEM, "hipHostMalloc of %llu bytes failed", (unsigned long long)need);
-        }
-        bytes = need;
-        return TA_OK;
-    }
-    void release() { if (p) (void)hipHostFree(p); p = nullptr; bytes = 0; }
-};
-
-}  // namespace
-
-struct ta_ctx {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};   // [0] step begin, [3] step end (TA_OPT_TIMING = 2 only)
-    std::vector<hipEvent_t> ring;                       // 2 events per slot around the sweep kernel of the last `ring.size()/2` extractions
-    int timing = 1;                                     // TA_OPT_TIMING
-    uint64_t extract_seq = 0, ring_since = 0;           // extractions run; the one the ring's oldest valid slot belongs to
-
-    // resident volume
-    const void* vol = nullptr;       // device pointer (owned_vol.p or adopted)
-    DevBuf owned_vol;
-    int itemsize = 0;
-    int64_t mdims[3] = {0, 0, 0};    // buffer dims in memory-axis order
-    int perm[3] = {0, 1, 2};         // perm[k] = array axis of memory axis k
-    int64_t a_origin = 0;
-    int first_owned = 0;
-
-    // sparse label ids: the census of the volume's ids and the copy of the volume in their ranks (what the sweep then reads)
-    DevBuf census, census_ids, compact_vol, census_list;      // (census_list: the label list of the one-pass census, ~n / 256 entries)
-    uint32_t census_max = 0;            // ids 0 .. census_max have a bit
-    int64_t census_n = -1;              // ids present, -1 = no census
-    int64_t vol_max = -1;               // largest label of the resident buffer (halo included), -1 = not known
-    bool compact = false;               // per-label ROWS are ranks 0 .. census_n - 1; every label VALUE handed out is an id
-    bool census_of_volume = false;      // the census on the context was taken from THIS volume (not a caller's id list)
-    bool rerank_check = false;          // ta_volume_rerank's "id not in the list" word has not been looked at yet
-    std::vector<uint32_t> h_ids;        // rank -> id (host copy, compact mode)
-
-    // accumulators
-    DevBuf own_sums, own_boxes;
-    uint64_t* sums = nullptr;
-    int32_t* boxes = nullptr;
-    bool bound = false;
-    uint32_t bound_max_label = 0;
-    uint32_t max_label = 0;
-
-    // adjacency
-    DevBuf pkeys, pfaces, out_keys, out_faces, small;   // small: flags[NFLAGS] | cursor | maxlabel
-    DevBuf hot_rows;                                    // [workgroups][16] private rows of the hot label
-    DevBuf sort_buf;                                    // scratch of ta_adjacency_get's device sort (kept between calls)
-    DevBuf wall_counts;                                 // wall voxels: per-chunk record counts, then offsets
-    DevBuf wall_stage;                                  // wall voxels: the records the count pass staged (kept until the volume changes)
-    int64_t wall_records = -1;                          // result of the last ta_wall_voxels_count, -1 = none
-    uint32_t wall_region = 0, wall_not_staged = 0;      // records per staging region of that call (0 = nothing staged); cells left to the second walk
-    DevBuf wall_medians;                                // ta_wall_medians: pairs u32[E][2] | sizes u32[E] | medians i32[E][3]
-    int64_t wall_median_count = -1;                     // E of the last ta_wall_medians, -1 = none
-    bool wall_wide = false;                             // that call met a label >= 2^31
-    uint32_t wall_label_or = 0;                         // OR of all labels of the volume (that call): the bits a label takes
-    double wall_ms = 0.0;
-    int pair_log2 = 0;                                  // current table log2 capacity
-    int opt_pair_log2 = 0;
-    bool table_clean = false;
-    uint32_t* h_small = nullptr;                        // pinned, device-mapped mirror of `small`
-    uint32_t* h_small_dev = nullptr;                    // its device address: the last kernel of a step writes it
-
-    // options / state
-    int impl = 0;
-    int tile_planes = 0;
-    // the tile shape of the sweep of a uint32 volume with adjacency (kernels_scan.hip): both give the same results; which one
-    // is faster depends on the tissue (background around it: the wide one; cells everywhere: the narrow one), so the first four
-    // sweeps of a volume take turns (wide, narrow, wide, narrow) between two events each, and the faster shape keeps the volume
-    int opt_shape = -1;                                 // TA_OPT_SWEEP_SHAPE: -1 = measure, 0 / 1 = as told
-    int shape_pick = -1;                                // choice for this volume, -1 = not yet
-    double shape_density = -1.0;                        // label changes per voxel in the sampled planes (what decided it), -1 = not measured
-    int last_shape = 0;                                 // TA_OPT_SWEEP_SHAPE_USED: the shape of the last sweep
-    int tune_launched = 0;                              // measuring sweeps launched (0 .. 4)
-    hipEvent_t tune_ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    bool tune_done[4] = {false, false, false, false};
-    float tune_ms[4] = {0.f, 0.f, 0.f, 0.f};
-    int64_t volume_slack = 0;                           // TA_OPT_VOLUME_SLACK: bytes readable behind an adopted volume
-    int auto_tile_shift = 0;                            // automatic tile height halved this many times (table spills seen)
-    uint64_t last_grid = 0;                             // workgroups of the last sweep
-    uint32_t feature_mask = 0;
-    bool extracted = false, checked = false;
-    bool exchanged = false;                             // adjacency rebuilt by ta_adjacency_merge_blocks
-    bool shared_packed = false;                         // ... from ta_adjacency_pack_shared blocks: the list is PARTIAL
-    bool reduced = false;                               // the bound accumulators hold other ranks' contributions too
-    int64_t npairs = 0;
-    PinnedBuf h_pairs;                                  // sorted host copy for ta_adjacency_get: keys u64[n], then faces u64[n][3]
-    bool host_pairs_ready = false;
-
-    // signal image (include/tissue_scan_signal.h): same buffer dims and layout as the label volume
-    const void* sig = nullptr;                          // device pointer (owned_sig.p or adopted), NULL = no signal
-    DevBuf owned_sig;
-    int sig_itemsize = 0;
-    int64_t sig_mdims[3] = {0, 0, 0};                   // the label buffer dims it was set for
-    DevBuf sig_out;                                     // flags u32[4] | n | sum | sumsq[2] | min | max | side_lo | side_hi
-    DevBuf sig_hash;                                    // pair -> row table of the sorted pair list: keys u64[cap] | rows u32[cap]
-    uint64_t sig_seq = 0;                               // extract_seq of the extraction the results belong to, 0 = none
-    uint32_t sig_what = 0;
-    uint32_t sig_rows = 0;                              // max_label + 1 of that extraction
-    int64_t sig_npairs = 0;
-    hipEvent_t sig_ev[2] = {nullptr, nullptr};
-
-    // cell meshes (include/tissue_scan_mesh.h)
-    DevBuf mesh_small;                                  // flags u32[4] | wanted u8[R] | per-wave counts and offsets | scan scratch
-    DevBuf mesh_work;                                   // face records u64[F] | neighbours u32[F] | corners u64[V] | sort keys, values x 2 | sort temp
-    DevBuf mesh_out;                                    // vertex corners u64[V] | vbeg, vend, fbeg, fend u64[R] | triangles u32[2F][3] | cell, neighbour u32[2F]
-    uint64_t mesh_seq = 0;                              // extract_seq of the extraction the mesh belongs to, 0 = none
-    uint64_t mesh_faces = 0, mesh_verts = 0;
-    uint32_t mesh_rows = 0;
-    int64_t mesh_m[3] = {0, 0, 0};                      // dims of the meshed image, memory order
-    bool mesh_host_ready = false;                       // cells and CSR offsets below are read back
-    std::vector<uint32_t> mesh_cells;
-    std::vector<uint64_t> mesh_voff, mesh_toff;
-    hipEvent_t mesh_ev[4] = {nullptr, nullptr, nullptr, nullptr};
-
-    // label overlap with a second label volume B (include/tissue_scan_overlap.h): same buffer dims and layout as the label volume
-    const void* ovb = nullptr;                          // device pointer (owned_ovb.p or adopted), NULL = no B
-    DevBuf owned_ovb;
-    int ovb_itemsize = 0;
-    int64_t ovb_mdims[3] = {0, 0, 0};                   // the label buffer dims it was set for
-    DevBuf ov_table;                                    // the device-global pair table: keys u64[slots] | counts u64[slots]
-    DevBuf ov_small;                                    // flags u32[4] | voxels of the pair (2^32 - 1, 2^32 - 1) u64
-    DevBuf ov_work;                                     // compaction: block counts u32[B] | block offsets u64[B] | scan scratch
-    DevBuf ov_sort;                                     // sort keys u64[P] x 2 | slots u32[P] x 2 | radix temp
-    DevBuf ov_rows;                                     // the sorted table: a u32[P] | b u32[P] | n u64[P]
-    int ov_opt_log2 = 0;                                // ta_overlap_set_capacity: 0 = automatic
-    int ov_grown_log2 = 0;                              // what an automatic table of this volume had to grow to
-    int ov_log2 = 0;                                    // slots of the table of the pass in flight
-    int ov_state = 0;                                   // 0 = no table, 1 = pass enqueued, 2 = settled (ov_rows holds ov_npairs rows)
-    int ov_passes = 0;                                  // runs of the pass kernel for this table
-    uint64_t ov_npairs = 0;
-    hipEvent_t ov_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // pass begin, end | count + scan end | emit begin, rows end
-
-    // cell junctions (include/tissue_scan_junctions.h): index 0 = edges (3 labels), 1 = vertices (4 labels)
-    DevBuf jn_small;                                    // blocks of order >= 5 u64
-    DevBuf jn_work;                                     // per wave: counts u32[W] x 2 | offsets u64[W] x 2 | scan scratch x 2
-    DevBuf jn_rec;                                      // records: origins u64[N3] | origins u64[N4] | labels u32[N3][3] | labels u32[N4][4]
-    DevBuf jn_sort[2];                                  // sort keys u64[N] x 2 | order u32[N] x 2 | radix temp | row counts, offsets, scan scratch
-    DevBuf jn_rows[2];                                  // the table: n u64[R] | sums u64[R][3] | labels u32[R][K]
-    int jn_state = 0;                                   // 0 = no tables, 1 = counting walk enqueued, 2 = settled
-    uint64_t jn_waves = 0;                              // waves (= tasks) of a walk
-    uint64_t jn_nrows[2] = {0, 0}, jn_degenerate = 0;
-    hipEvent_t jn_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // count begin, end | scans end | emit begin, end | tables end
-};
-
 namespace {
 
 constexpr int SMALL_WORDS = ta::SMALL_WORDS_DEV;   // flags, cursor, max label, parked hot-row pointer (2 words), tile queues (8)
@@ -223,9 +25,6 @@ constexpr int SMALL_WORDS = ta::SMALL_WORDS_DEV;   // flags, cursor, max label, 
 uint32_t* flags_dev(ta_ctx* c) { return (uint32_t*)c->small.p; }
 uint32_t* cursor_dev(ta_ctx* c) { return (uint32_t*)c->small.p + ta::NFLAGS; }
 uint32_t* maxlab_dev(ta_ctx* c) { return (uint32_t*)c->small.p + ta::NFLAGS + 1; }
-
-// the volume the sweep reads: the rank copy in compact mode
-const void* sweep_vol(const ta_ctx* c) { return c->compact ? c->compact_vol.p : c->vol; }
 
 void drop_census(ta_ctx* c) {          // (whenever the voxels change)
     c->census_n = -1;
@@ -237,35 +36,6 @@ void drop_census(ta_ctx* c) {          // (whenever the voxels change)
     c->tune_launched = 0;
     for (bool& d : c->tune_done) d = false;
     if (c->compact) { c->compact = false; c->extracted = c->checked = false; }
-}
-
-// a new label volume (or new label values in it): the overlap table is stale; a B of other dims is dropped
-void overlap_on_new_volume(ta_ctx* c) {
-    c->ov_state = 0;
-    c->ov_grown_log2 = 0;
-    if (c->ovb && (c->ovb_mdims[0] != c->mdims[0] || c->ovb_mdims[1] != c->mdims[1] || c->ovb_mdims[2] != c->mdims[2])) {
-        c->ovb = nullptr;
-        c->owned_ovb.release();
-        c->ovb_itemsize = 0;
-    }
-}
-
-// a new label volume (or new label values in it): the junction tables are stale
-void junctions_on_new_volume(ta_ctx* c) { c->jn_state = 0; }
-
-// a new label volume: the signal results are stale (extracted is false); a signal of other dims is dropped
-void signal_on_new_volume(ta_ctx* c) {
-    c->sig_seq = 0;
-    if (c->sig && (c->sig_mdims[0] != c->mdims[0] || c->sig_mdims[1] != c->mdims[1] || c->sig_mdims[2] != c->mdims[2])) {
-        c->sig = nullptr;
-        c->owned_sig.release();
-        c->sig_itemsize = 0;
-    }
-}
-
-int use_device(ta_ctx* c) {
-    TA_HIP(hipSetDevice(c->device));
-    return TA_OK;
 }
 
 int ensure_pair_table(ta_ctx* c, int log2cap) {
@@ -480,6 +250,8 @@ int settle_rerank(ta_ctx* c) {
     return TA_OK;
 }
 
+}  // namespace
+
 // Drain the stream and validate the flags of the last pass; grows the adjacency table and
 // re-runs when it overflowed.
 int finish_extract(ta_ctx* c) {
@@ -531,7 +303,59 @@ int finish_extract(ta_ctx* c) {
     return fail(TA_ECAPACITY, "adjacency table overflow at 2^%d slots", c->pair_log2);
 }
 
-}  // namespace
+// ---- companion volumes (ta_ctx.h) ------------------------------------------------------------------------------------------
+
+static void companion_adopt(const ta_ctx* c, Companion& v, const void* dev_ptr, int itemsize) {
+    v.p = dev_ptr;
+    v.itemsize = itemsize;
+    for (int m = 0; m < 3; ++m) v.mdims[m] = c->mdims[m];
+}
+
+int companion_set_host(ta_ctx* c, Companion& v, const CompanionKind& k, const void* host_ptr, int itemsize, const int64_t dims[3],
+                       const int64_t strides_bytes[3]) {
+    if (!host_ptr || !dims) return fail(TA_EINVAL, "NULL argument");
+    if (itemsize != k.size_a && itemsize != k.size_b) return fail(TA_EINVAL, "%s: itemsize must be %d or %d bytes, not %d", k.noun, k.size_a, k.size_b, itemsize);
+    if (!c->vol) return fail(TA_EINVAL, "no label volume set: %s takes its dims and layout", k.noun);
+    int64_t adims[3], el[3];                     // the label volume's dims and element strides, in array-axis order
+    int64_t e = 1;
+    for (int m = 2; m >= 0; --m) { adims[c->perm[m]] = c->mdims[m]; el[c->perm[m]] = e; e *= c->mdims[m]; }
+    for (int d = 0; d < 3; ++d) {
+        if (dims[d] != adims[d])
+            return fail(TA_EINVAL, "%s: dims (%lld, %lld, %lld) differ from the label volume's (%lld, %lld, %lld)", k.noun, (long long)dims[0],
+                        (long long)dims[1], (long long)dims[2], (long long)adims[0], (long long)adims[1], (long long)adims[2]);
+        const int64_t st = strides_bytes ? strides_bytes[d] : (d == 2 ? 1 : (d == 1 ? dims[2] : dims[1] * dims[2])) * itemsize;
+        if (dims[d] != 1 && st != el[d] * itemsize)
+            return fail(TA_EINVAL, "%s: the layout differs from the label volume's (axis %d: stride %lld bytes, expected %lld)", k.noun, d,
+                        (long long)st, (long long)(el[d] * itemsize));
+    }
+    int rc = use_device(c);
+    if (rc != TA_OK) return rc;
+    const uint64_t bytes = (uint64_t)e * itemsize;
+    TA_HIP(hipStreamSynchronize(c->stream));     // (a pass in flight may still read the old one)
+    v.p = nullptr;
+    if ((rc = v.owned.reserve(bytes + 64)) != TA_OK) return rc;
+    TA_HIP(hipMemcpyAsync(v.owned.p, host_ptr, bytes, hipMemcpyHostToDevice, c->stream));
+    TA_HIP(hipStreamSynchronize(c->stream));     // the host buffer may be freed after return
+    companion_adopt(c, v, v.owned.p, itemsize);
+    return TA_OK;
+}
+
+int companion_set_device(ta_ctx* c, Companion& v, const CompanionKind& k, const void* dev_ptr, int itemsize) {
+    if (!dev_ptr) return fail(TA_EINVAL, "NULL argument");
+    if (itemsize != k.size_a && itemsize != k.size_b) return fail(TA_EINVAL, "%s: itemsize must be %d or %d bytes, not %d", k.noun, k.size_a, k.size_b, itemsize);
+    if (!c->vol) return fail(TA_EINVAL, "no label volume set: %s takes its buffer dims", k.noun);
+    if (((uintptr_t)dev_ptr % itemsize) != 0) return fail(TA_EINVAL, "%s: the device pointer is not aligned to its type", k.noun);
+    int rc = use_device(c);
+    if (rc != TA_OK) return rc;
+    TA_HIP(hipStreamSynchronize(c->stream));
+    v.owned.release();
+    companion_adopt(c, v, dev_ptr, itemsize);
+    return TA_OK;
+}
+
+void companion_on_new_volume(const ta_ctx* c, Companion& v) {
+    if (v.p && !companion_matches(c, v)) { v.p = nullptr; v.owned.release(); v.itemsize = 0; }
+}
 
 extern "C" {
 
@@ -601,19 +425,10 @@ TA_API int ta_ctx_destroy(ta_ctx* c) {
     c->wall_stage.release();
     c->wall_medians.release();
     c->census.release(); c->census_ids.release(); c->compact_vol.release(); c->census_list.release();
-    c->owned_sig.release(); c->sig_out.release(); c->sig_hash.release();
-    for (auto& e : c->sig_ev) if (e) (void)hipEventDestroy(e);
-    c->mesh_small.release(); c->mesh_work.release(); c->mesh_out.release();
-    for (auto& e : c->mesh_ev) if (e) (void)hipEventDestroy(e);
-    c->owned_ovb.release(); c->ov_table.release(); c->ov_small.release(); c->ov_work.release(); c->ov_sort.release(); c->ov_rows.release();
-    for (auto& e : c->ov_ev) if (e) (void)hipEventDestroy(e);
-    c->jn_small.release(); c->jn_work.release(); c->jn_rec.release();
-    for (int k = 0; k < 2; ++k) { c->jn_sort[k].release(); c->jn_rows[k].release(); }
-    for (auto& e : c->jn_ev) if (e) (void)hipEventDestroy(e);
+    c->sig.release(); c->mesh.release(); c->ov.release(); c->jn.release();
     if (c->h_small) (void)hipHostFree(c->h_small);
-    for (auto& e : c->ev) if (e) (void)hipEventDestroy(e);
+    destroy_events(c->ev); destroy_events(c->tune_ev);
     for (auto& e : c->ring) if (e) (void)hipEventDestroy(e);
-    for (auto& e : c->tune_ev) if (e) (void)hipEventDestroy(e);
     if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
     return TA_OK;
@@ -1032,7 +847,7 @@ int wall_records_device(ta_ctx* c, bool by_pair, DevBuf& buf, uint32_t** pairs_d
     const char* env_keyed = getenv("TA_WALL_KEYED");
     const bool keyed = by_pair && nvox < (1ull << 32) && !(env_keyed && env_keyed[0] == '0');
     const uint64_t temp_bytes = by_pair ? ta::wall_sort_temp_bytes(n) : 0;
-    const uint64_t rec = n * 8, co = (n * 12 + 15) & ~15ull, ix = (n * 4 + 15) & ~15ull;
+    const uint64_t rec = n * 8, co = align16(n * 12), ix = align16(n * 4);
     if ((rc = buf.reserve(by_pair ? (keyed ? 0 : rec + co) + rec + co + 2 * rec + 2 * ix + temp_bytes + 64 : rec + co)) != TA_OK) return rc;
     char* p = (char*)buf.p;
     int label_bits = 1;                                             // bits a label of this volume takes
@@ -1859,895 +1674,6 @@ TA_API int ta_memcpy_h2d(ta_ctx* c, void* dev_dst, const void* host_src, uint64_
     if (rc != TA_OK) return rc;
     TA_HIP(hipMemcpyAsync(dev_dst, host_src, bytes, hipMemcpyHostToDevice, c->stream));
     TA_HIP(hipStreamSynchronize(c->stream));
-    return TA_OK;
-}
-
-// ---- signal statistics (include/tissue_scan_signal.h; kernels_signal.hip) -----------------------------------------------------
-
-}  // extern "C"
-
-namespace {
-
-bool signal_current(const ta_ctx* c) { return c->sig_seq != 0 && c->extracted && c->sig_seq == c->extract_seq; }
-
-// byte offsets of the parts of sig_out for R rows and P pairs
-struct SignalLayout {
-    uint64_t flags = 0, n, sum, sumsq, vmin, vmax, side_lo, side_hi, bytes;
-    SignalLayout(uint64_t R, uint64_t P) {
-        n = 16; sum = n + 8 * R; sumsq = sum + 8 * R; vmin = sumsq + 16 * R; vmax = vmin + 4 * R;
-        side_lo = vmax + 4 * R; side_hi = side_lo + 8 * P; bytes = side_hi + 8 * P;
-    }
-};
-
-int signal_adopt(ta_ctx* c, int itemsize) {
-    c->sig_itemsize = itemsize;
-    for (int k = 0; k < 3; ++k) c->sig_mdims[k] = c->mdims[k];
-    c->sig_seq = 0;
-    return TA_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-TA_API int ta_signal_set(ta_ctx* c, const void* host_ptr, int itemsize, const int64_t dims[3], const int64_t strides_bytes[3]) {
-    if (!c) return fail(TA_EINVAL, "ctx is NULL");
-    if (!host_ptr || !dims) return fail(TA_EINVAL, "NULL argument");
-    if (itemsize != 1 && itemsize != 2) return fail(TA_EINVAL, "signal itemsize must be 1 (uint8) or 2 (uint16), not %d", itemsize);
-    if (!c->vol) return fail(TA_EINVAL, "no label volume set: the signal takes its dims and layout");
-    int64_t adims[3], el[3];                     // the label volume's dims and element strides, in array-axis order
-    int64_t e = 1;
-    for (int k = 2; k >= 0; --k) { adims[c->perm[k]] = c->mdims[k]; el[c->perm[k]] = e; e *= c->mdims[k]; }
-    for (int d = 0; d < 3; ++d) {
-        if (dims[d] != adims[d])
-            return fail(TA_EINVAL, "signal dims (%lld, %lld, %lld) differ from the label volume's (%lld, %lld, %lld)", (long long)dims[0],
-                        (long long)dims[1], (long long)dims[2], (long long)adims[0], (long long)adims[1], (long long)adims[2]);
-        const int64_t st = strides_bytes ? strides_bytes[d] : (d == 2 ? 1 : (d == 1 ? dims[2] : dims[1] * dims[2])) * itemsize;
-        if (dims[d] != 1 && st != el[d] * itemsize)
-            return fail(TA_EINVAL, "the signal's layout differs from the label volume's (axis %d: stride %lld bytes, expected %lld)", d,
-                        (long long)st, (long long)(el[d] * itemsize));
-    }
-    int rc = use_device(c);
-    if (rc != TA_OK) return rc;
-    const uint64_t bytes = (uint64_t)e * itemsize;
-    TA_HIP(hipStreamSynchronize(c->stream));     // (a pass in flight may still read the old signal)
-    c->sig = nullptr;
-    if ((rc = c->owned_sig.reserve(bytes + 64)) != TA_OK) return rc;
-    TA_HIP(hipMemcpyAsync(c->owned_sig.p, host_ptr, bytes, hipMemcpyHostToDevice, c->stream));
-    TA_HIP(hipStreamSynchronize(c->stream));     // the host buffer may be freed after return
-    c->sig = c->owned_sig.p;
-    return signal_adopt(c, itemsize);
-}
-
-TA_API int ta_signal_set_device(ta_ctx* c, const void* dev_ptr, int itemsize) {
-    if (!c) return fail(TA_EINVAL, "ctx is NULL");
-    if (!dev_ptr) return fail(TA_EINVAL, "NULL argument");
-    if (itemsize != 1 && itemsize != 2) return fail(TA_EINVAL, "signal itemsize must be 1 (uint8) or 2 (uint16), not %d", itemsize);
-    if (!c->vol) return fail(TA_EINVAL, "no label volume set: the signal takes its buffer dims");
-    if (((uintptr_t)dev_ptr % itemsize) != 0) return fail(TA_EINVAL, "device pointer is not aligned to the signal type");
-    int rc = use_device(c);
-    if (rc != TA_OK) return rc;
-    TA_HIP(hipStreamSynchronize(c->stream));
-    c->owned_sig.release();
-    c->sig = dev_ptr;
-    return signal_adopt(c, itemsize);
-}
-
-TA_API int ta_signal_extract(ta_ctx* c, uint32_t what) {
-    if (!c) return fail(TA_EINVAL, "ctx is NULL");
-    if (what == 0 || (what & ~(TA_SIG_LABELS | TA_SIG_WALLS))) return fail(TA_EINVAL, "bad signal mask 0x%x", what);
-    if (!c->sig) return fail(TA_EINVAL, "no signal set");
-    if (!c->vol || c->sig_mdims[0] != c->mdims[0] || c->sig_mdims[1] != c->mdims[1] || c->sig_mdims[2] != c->mdims[2])
-        return fail(TA_EINVAL, "the signal does not match the label volume");
-    int rc = use_device(c);
-    if (rc != TA_OK) return rc;
-    if (!c->extracted) return fail(TA_EINVAL, "the signal pass needs a ta_extract of the current volume first");
-    if ((rc = finish_extract(c)) != TA_OK) return rc;
-    const bool walls = what & TA_SIG_WALLS;
-    if (walls && !(c->feature_mask & TA_F_ADJACENCY)) return fail(TA_EINVAL, "TA_SIG_WALLS needs an extraction with TA_F_ADJACENCY");
-    if (walls && c->exchanged) return fail(TA_EINVAL, "TA_SIG_WALLS needs this context's own pair list (not a merged one)");
-    const uint64_t R = (uint64_t)c->max_label + 1, P = walls ? (uint64_t)c->npairs : 0;
-    const SignalLayout L(R, P);
-    if ((rc = c->sig_out.reserve(L.bytes)) != TA_OK) return rc;
-    for (auto& ev : c->sig_ev) if (!ev) TA_HIP(hipEventCreate(&ev));
-    ta::SignalArgs a;
-    a.hkeys = nullptr; a.hrows = nullptr; a.hmask = 0;
-    if (walls && P) {
-        // pair -> row: an open-addressed table of the sorted pair list (ta_adjacency_get sorts it on the device once per extraction)
-        if ((rc = ta_adjacency_get(c, nullptr, nullptr, nullptr)) != TA_OK) return rc;
-        uint64_t cap = 64;
-        while (cap < 2 * P) cap <<= 1;
-        if (cap > (1ull << 32)) return fail(TA_EINVAL, "too many pairs (%llu)", (unsigned long long)P);
-        if ((rc = c->sig_hash.reserve(cap * 12 + P * 8)) != TA_OK) return rc;
-        uint64_t* hkeys = (uint64_t*)c->sig_hash.p;
-        uint64_t* sorted = hkeys + cap;
-        uint32_t* hrows = (uint32_t*)(sorted + P);
-        TA_HIP(hipMemsetAsync(hkeys, 0xff, cap * 8, c->stream));
-        TA_HIP(hipMemcpyAsync(sorted, c->h_pairs.p, P * 8, hipMemcpyHostToDevice, c->stream));
-        ta::launch_signal_hash(c->stream, sorted, P, hkeys, hrows, (uint32_t)(cap - 1));
-        a.hkeys = hkeys; a.hrows = hrows; a.hmask = (uint32_t)(cap - 1);
-    }
-    char* o = (char*)c->sig_out.p;
-    TA_HIP(hipMemsetAsync(o, 0, L.bytes, c->stream));
-    TA_HIP(hipMemsetAsync(o + L.vmin, 0xff, 4 * R, c->stream));
-    a.vol = sweep_vol(c);
-    a.sig = c->sig;
-    a.n0 = c->mdims[0]; a.n1 = c->mdims[1]; a.n2 = c->mdims[2];
-    a.first_owned = c->first_owned;
-    a.max_label = c->max_label;
-    a.n = (unsigned long long*)(o + L.n);
-    a.sum = (unsigned long long*)(o + L.sum);
-    a.sumsq = (unsigned long long*)(o + L.sumsq);
-    a.vmin = (uint32_t*)(o + L.vmin);
-    a.vmax = (uint32_t*)(o + L.vmax);
-    a.side_lo = (unsigned long long*)(o + L.side_lo);
-    a.side_hi = (unsigned long long*)(o + L.side_hi);
-    a.flags = (uint32_t*)o;
-    a.tiles_per_group = 0;
-    TA_HIP(hipEventRecord(c->sig_ev[0], c->stream));
-    ta::launch_signal(c->stream, a, c->itemsize, c->sig_itemsize, (what & TA_SIG_LABELS ? ta::SIG_LABELS : 0u) | (walls ? ta::SIG_WALLS : 0u));
-    TA_HIP(hipGetLastError());
-    TA_HIP(hipEventRecord(c->sig_ev[1], c->stream));
-    c->sig_seq = c->extract_seq;
-    c->sig_what = what;
-    c->sig_rows = (uint32_t)R;
-    c->sig_npairs = (int64_t)P;
-    return TA_OK;
-}
-
-namespace {
-// drain the stream and look at the pass's flag words
-int signal_finish(ta_ctx* c) {
-    uint32_t flags[ta::SIG_NFLAGS] = {0, 0, 0, 0};
-    TA_HIP(hipMemcpyAsync(flags, c->sig_out.p, sizeof(flags), hipMemcpyDeviceToHost, c->stream));
-    TA_HIP(hipStreamSynchronize(c->stream));
-    if (flags[ta::SIG_FLAG_RANGE]) return fail(TA_ERANGE, "the signal pass met a label above max_label=%u (the volume changed since ta_extract)", c->max_label);
-    if (flags[ta::SIG_FLAG_PAIR_MISS]) return fail(TA_ERANGE, "the signal pass met a pair the extraction does not hold (the volume changed since ta_extract)");
-    return TA_OK;
-}
-}  // namespace
-
-TA_API int ta_signal_get_labels(ta_ctx* c, uint64_t* n, uint64_t* sum, uint64_t* sumsq, uint32_t* vmin, uint32_t* vmax) {
-    if (!c) return fail(TA_EINVAL, "ctx is NULL");
-    if (!signal_current(c) || !(c->sig_what & TA_SIG_LABELS))
-        return fail(TA_EINVAL, "no per-label signal results for the current extraction (run ta_signal_extract with TA_SIG_LABELS)");
-    int rc = use_device(c);
-    if (rc != TA_OK) return rc;
-    if ((rc = signal_finish(c)) != TA_OK) return rc;
-    const uint64_t R = c->sig_rows;
-    const SignalLayout L(R, (uint64_t)c->sig_npairs);
-    const char* o = (const char*)c->sig_out.p;
-    if (n) TA_HIP(hipMemcpyAsync(n, o + L.n, 8 * R, hipMemcpyDeviceToHost, c->stream));
-    if (sum) TA_HIP(hipMemcpyAsync(sum, o + L.sum, 8 * R, hipMemcpyDeviceToHost, c->stream));
-    if (sumsq) TA_HIP(hipMemcpyAsync(sumsq, o + L.sumsq, 16 * R, hipMemcpyDeviceToHost, c->stream));
-    if (vmin) TA_HIP(hipMemcpyAsync(vmin, o + L.vmin, 4 * R, hipMemcpyDeviceToHost, c->stream));
-    if (vmax) TA_HIP(hipMemcpyAsync(vmax, o + L.vmax, 4 * R, hipMemcpyDeviceToHost, c->stream));
-    TA_HIP(hipStreamSynchronize(c->stream));
-    return TA_OK;
-}
-
-TA_API int ta_signal_get_walls(ta_ctx* c, uint64_t* side_lo, uint64_t* side_hi) {
-    if (!c) return fail(TA_EINVAL, "ctx is NULL");
-    if (!signal_current(c) || !(c->sig_what & TA_SIG_WALLS) || c->exchanged)
-        return fail(TA_EINVAL, "no per-wall signal results for the current extraction (run ta_signal_extract with TA_SIG_WALLS)");
-    int rc = use_device(c);
-    if (rc != TA_OK) return rc;
-    if ((rc = signal_finish(c)) != TA_OK) return rc;
-    const uint64_t P = (uint64_t)c->sig_npairs;
-    const SignalLayout L(c->sig_rows, P);
-    const char* o = (const char*)c->sig_out.p;
-    if (side_lo && P) TA_HIP(hipMemcpyAsync(side_lo, o + L.side_lo, 8 * P, hipMemcpyDeviceToHost, c->stream));
-    if (side_hi && P) TA_HIP(hipMemcpyAsync(side_hi, o + L.side_hi, 8 * P, hipMemcpyDeviceToHost, c->stream));
-    TA_HIP(hipStreamSynchronize(c->stream));
-    return TA_OK;
-}
-
-TA_API int ta_signal_timing(ta_ctx* c, double* ms) {
-    if (!c) return fail(TA_EINVAL, "ctx is NULL");
-    if (!ms) return fail(TA_EINVAL, "NULL argument");
-    if (c->sig_seq == 0 || !c->sig_ev[1]) return fail(TA_EINVAL, "no signal pass has been run");
-    int rc = use_device(c);
-    if (rc != TA_OK) return rc;
-    TA_HIP(hipEventSynchronize(c->sig_ev[1]));
-    float t = 0.f;
-    TA_HIP(hipEventElapsedTime(&t, c->sig_ev[0], c->sig_ev[1]));
-    *ms = (double)t;
-    return TA_OK;
-}
-
-// ---- cell meshes (include/tissue_scan_mesh.h; kernels_mesh.hip) ------------------------------------------------------------
-
-}  // extern "C"
-
-namespace {
-
-bool mesh_current(const ta_ctx* c) { return c->mesh_seq != 0 && c->extracted && c->mesh_seq == c->extract_seq; }
-
-uint64_t align16(uint64_t b) { return (b + 15) & ~15ull; }
-
-// byte offsets of the parts of mesh_small for R rows and wf / wc waves of the face / corner kernels
-struct MeshSmall {
-    uint64_t flags = 0, wanted, fcounts, ccounts, foffs, coffs, fscan, cscan, bytes;
-    MeshSmall(uint64_t R, uint64_t wf, uint64_t wc) {
-        wanted = 16; fcounts = wanted + align16(R); ccounts = fcounts + align16(4 * wf); foffs = ccounts + align16(4 * wc);
-        coffs = foffs + align16(8 * wf); fscan = coffs + align16(8 * wc); cscan = fscan + align16(ta::scan_u32_scratch_bytes(wf));
-        bytes = cscan + align16(ta::scan_u32_scratch_bytes(wc));
-    }
-};
-// ... of mesh_work for F faces and V vertex records
-struct MeshWork {
-    uint64_t frec = 0, fnb, corner, keys0, keys1, idx0, idx1, temp, bytes;
-    MeshWork(uint64_t F, uint64_t V) {
-        const uint64_t N = F > V ? F : V;
-        fnb = align16(8 * F); corner = fnb + align16(4 * F); keys0 = corner + align16(8 * V); keys1 = keys0 + align16(4 * N);
-        idx0 = keys1 + align16(4 * N); idx1 = idx0 + align16(4 * N); temp = idx1 + align16(4 * N);
-        bytes = temp + align16(ta::wall_sort_temp_bytes(N));
-    }
-};
-// ... of mesh_out
-struct MeshOut {
-    uint64_t vcorner = 0, vbeg, vend, fbeg, fend, tri, tcell, tnb, bytes;
-    MeshOut(uint64_t R, uint64_t F, uint64_t V) {
-        vbeg = align16(8 * V); vend = vbeg + 8 * R; fbeg = vend + 8 * R; fend = fbeg + 8 * R; tri = align16(fend + 8 * R);
-        tcell = tri + align16(24 * F); tnb = tcell + align16(8 * F); bytes = tnb + align16(8 * F);
-    }
-};
-
-// drain the stream, look at the flags of the emit / resolve kernels, and read the cells and their CSR offsets back once
-int mesh_finish(ta_ctx* c) {
-    uint32_t flags[ta::MESH_NFLAGS] = {0, 0, 0, 0};
-    TA_HIP(hipMemcpyAsync(flags, c->mesh_small.p, sizeof(flags), hipMemcpyDeviceToHost, c->stream));
-    TA_HIP(hipStreamSynchronize(c->stream));
-    if (flags[ta::MESH_FLAG_RANGE] || flags[ta::MESH_FLAG_MISS] || flags[ta::MESH_FLAG_OVERRUN])
-        return fail(TA_ERANGE, "the mesh pass found the volume changed since ta_extract (flags %u %u %u)", flags[0], flags[1], flags[2]);
-    if (c->mesh_host_ready) return TA_OK;
-    const uint64_t R = c->mesh_rows;
-    const MeshOut O(R, c->mesh_faces, c->mesh_verts);
-    std::vector<uint64_t> t(4 * R);
-    const char* o = (const char*)c->mesh_out.p;
-    if (R) TA_HIP(hipMemcpyAsync(t.data(), o + O.vbeg, 32 * R, hipMemcpyDeviceToHost, c->stream));
-    TA_HIP(hipStreamSynchronize(c->stream));
-    const uint64_t *vbeg = t.data(), *vend = vbeg + R, *fbeg = vend + R, *fend = fbeg + R;
-    c->mesh_cells.clear(); c->mesh_voff.clear(); c->mesh_toff.clear();
-    for (uint64_t r = 0; r < R; ++r) {
-        if (vend[r] <= vbeg[r]) continue;
-        if (fend[r] <= fbeg[r]) return fail(TA_ERANGE, "mesh: row %llu has vertices and no faces", (unsigned long long)r);
-        c->mesh_cells.push_back((uint32_t)r);
-        c->mesh_voff.push_back(vbeg[r]);
-        c->mesh_toff.push_back(2 * fbeg[r]);
-    }
-    c->mesh_voff.push_back(c->mesh_verts);
-    c->mesh_toff.push_back(2 * c->mesh_faces);
-    c->mesh_host_ready = true;
-    return TA_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-TA_API int ta_mesh_extract(ta_ctx* c, int sub_factor, const uint8_t* wanted_rows) {
-    if (!c) return fail(TA_EINVAL, "ctx is NULL");
-    if (sub_factor < 1) return fail(TA_EINVAL, "sub_factor must be >= 1, not %d", sub_factor);
-    if (!c->vol) return fail(TA_EINVAL, "no volume set");
-    if (c->first_owned) return fail(TA_EINVAL, "cell meshes are not available on a slab that carries a halo plane");
-    int rc = use_device(c);
-    if (rc != TA_OK) return rc;
-    if (!c->extracted) return fail(TA_EINVAL, "the mesh pass needs a ta_extract of the current volume first");
-    if ((rc = finish_extract(c)) != TA_OK) return rc;
-    c->mesh_seq = 0;
-    c->mesh_host_ready = false;
-    const uint64_t R = (uint64_t)c->max_label + 1;
-    ta::MeshArgs a;
-    a.vol = sweep_vol(c);
-    a.n0 = c->mdims[0]; a.n1 = c->mdims[1]; a.n2 = c->mdims[2];
-    a.s = sub_factor;
-    a.m0 = (a.n0 + a.s - 1) / a.s; a.m1 = (a.n1 + a.s - 1) / a.s; a.m2 = (a.n2 + a.s - 1) / a.s;
-    for (int k = 0; k < 3; ++k) a.inv[c->perm[k]] = k;
-    a.rows = (uint32_t)R;
-    const uint64_t nvox = (uint64_t)a.m0 * a.m1 * a.m2, ncorner = (uint64_t)(a.m0 + 1) * (a.m1 + 1) * (a.m2 + 1);
-    const uint64_t wf = ta::mesh_waves(nvox), wc = ta::mesh_waves(ncorner);
-    const MeshSmall S(R, wf, wc);
-    if ((rc = c->mesh_small.reserve(S.bytes)) != TA_OK) return rc;
-    char* sm = (char*)c->mesh_small.p;
-    a.flags = (uint32_t*)sm;
-    a.wanted = (const uint8_t*)(sm + S.wanted);
-    for (auto& ev : c->mesh_ev) if (!ev) TA_HIP(hipEventCreate(&ev));
-    TA_HIP(hipMemsetAsync(sm, 0, 16, c->stream));
-    if (wanted_rows) TA_HIP(hipMemcpyAsync(sm + S.wanted, wanted_rows, R, hipMemcpyHostToDevice, c->stream));
-    else TA_HIP(hipMemsetAsync(sm + S.wanted, 1, R, c->stream));
-    // count -> scan: the totals are all the host needs before it sizes the output
-    uint32_t* fcounts = (uint32_t*)(sm + S.fcounts);
-    uint32_t* ccounts = (uint32_t*)(sm + S.ccounts);
-    uint64_t* foffs = (uint64_t*)(sm + S.foffs);
-    uint64_t* coffs = (uint64_t*)(sm + S.coffs);
-    TA_HIP(hipEventRecord(c->mesh_ev[0], c->stream));
-    ta::launch_mesh_face_count(c->stream, a, c->itemsize, fcounts);
-    ta::launch_mesh_corner_count(c->stream, a, c->itemsize, ccounts);
-    ta::launch_scan_u32_exclusive(c->stream, fcounts, wf, sm + S.fscan, foffs);
-    ta::launch_scan_u32_exclusive(c->stream, ccounts, wc, sm + S.cscan, coffs);
-    TA_HIP(hipGetLastError());
-    TA_HIP(hipEventRecord(c->mesh_ev[1], c->stream));
-    uint64_t tot[2] = {0, 0};
-    uint32_t flags[ta::MESH_NFLAGS] = {0, 0, 0, 0};
-    if (wf) TA_HIP(hipMemcpyAsync(&tot[0], ta::scan_u32_total(sm + S.fscan, wf), 8, hipMemcpyDeviceToHost, c->stream));
-    if (wc) TA_HIP(hipMemcpyAsync(&tot[1], ta::scan_u32_total(sm + S.cscan, wc), 8, hipMemcpyDeviceToHost, c->stream));
-    TA_HIP(hipMemcpyAsync(flags, sm, sizeof(flags), hipMemcpyDeviceToHost, c->stream));
-    TA_HIP(hipStreamSynchronize(c->stream));
-    if (flags[ta::MESH_FLAG_RANGE]) return fail(TA_ERANGE, "the mesh pass met a label above max_label=%u (the volume changed since ta_extract)", c->max_label);
-    const uint64_t F = tot[0], V = tot[1];
-    if (V > 0xFFFFFFFFull) return fail(TA_ERANGE, "the meshes have %llu vertices: more than 2^32 - 1", (unsigned long long)V);
-    if (F > 0xFFFFFFFFull) return fail(TA_ERANGE, "the meshes have %llu faces: more than 2^32 - 1", (unsigned long long)F);
-    const MeshWork Wk(F, V);
-    const MeshOut O(R, F, V);
-    if ((rc = c->mesh_work.reserve(Wk.bytes)) != TA_OK) return rc;
-    if ((rc = c->mesh_out.reserve(O.bytes)) != TA_OK) return rc;
-    char* w = (char*)c->mesh_work.p;
-    char* o = (char*)c->mesh_out.p;
-    uint64_t* frec = (uint64_t*)(w + Wk.frec);
-    uint32_t* fnb = (uint32_t*)(w + Wk.fnb);
-    uint64_t* corner = (uint64_t*)(w + Wk.corner);
-    uint32_t *keys0 = (uint32_t*)(w + Wk.keys0), *keys1 = (uint32_t*)(w + Wk.keys1);
-    uint32_t *idx0 = (uint32_t*)(w + Wk.idx0), *idx1 = (uint32_t*)(w + Wk.idx1);
-    void* temp = w + Wk.temp;
-    uint64_t* vcorner = (uint64_t*)(o + O.vcorner);
-    uint64_t *vbeg = (uint64_t*)(o + O.vbeg), *vend = (uint64_t*)(o + O.vend);
-    uint64_t *fbeg = (uint64_t*)(o + O.fbeg), *fend = (uint64_t*)(o + O.fend);
-    const int key_bits = c->max_label ? 32 - __builtin_clz(c->max_label) : 1;
-    uint32_t *skeys = nullptr, *sidx = nullptr;
-    // emit -> group by cell -> resolve
-    TA_HIP(hipEventRecord(c->mesh_ev[2], c->stream));
-    TA_HIP(hipMemsetAsync(vbeg, 0, 32 * R, c->stream));
-    ta::launch_mesh_corner_emit(c->stream, a, c->itemsize, coffs, V, corner, keys0, idx0);
-    TA_HIP(ta::launch_radix_sort_u32(c->stream, V, keys0, keys1, idx0, idx1, temp, key_bits, &skeys, &sidx));
-    ta::launch_mesh_bounds(c->stream, skeys, V, vbeg, vend);
-    ta::launch_mesh_gather(c->stream, corner, sidx, V, vcorner);
-    ta::launch_mesh_face_emit(c->stream, a, c->itemsize, foffs, F, frec, fnb, keys0, idx0);
-    TA_HIP(ta::launch_radix_sort_u32(c->stream, F, keys0, keys1, idx0, idx1, temp, key_bits, &skeys, &sidx));
-    ta::launch_mesh_bounds(c->stream, skeys, F, fbeg, fend);
-    ta::launch_mesh_resolve(c->stream, a, skeys, sidx, frec, fnb, F, vcorner, vbeg, vend, (uint32_t*)(o + O.tri),
-                            (uint32_t*)(o + O.tcell), (uint32_t*)(o + O.tnb));
-    TA_HIP(hipGetLastError());
-    TA_HIP(hipEventRecord(c->mesh_ev[3], c->stream));
-    c->mesh_faces = F;
-    c->mesh_verts = V;
-    c->mesh_rows = (uint32_t)R;
-    c->mesh_m[0] = a.m0; c->mesh_m[1] = a.m1; c->mesh_m[2] = a.m2;
-    c->mesh_seq = c->extract_seq;
-    return TA_OK;
-}
-
-TA_API int ta_mesh_size(ta_ctx* c, uint64_t* n_cells, uint64_t* n_vertices, uint64_t* n_triangles) {
-    if (!c) return fail(TA_EINVAL, "ctx is NULL");
-    if (!mesh_current(c)) return fail(TA_EINVAL, "no mesh of the current extraction (run ta_mesh_extract)");
-    int rc = use_device(c);
-    if (rc != TA_OK) return rc;
-    if ((rc = mesh_finish(c)) != TA_OK) return rc;
-    if (n_cells) *n_cells = (uint64_t)c->mesh_cells.size();
-    if (n_vertices) *n_vertices = c->mesh_verts;
-    if (n_triangles) *n_triangles = 2 * c->mesh_faces;
-    return TA_OK;
-}
-
-TA_API int ta_mesh_get(ta_ctx* c, uint32_t* cells, uint64_t* vertex_offsets, uint64_t* triangle_offsets, uint64_t* corners,
-                       uint32_t* triangles, uint32_t* triangle_cell, uint32_t* triangle_neighbor) {
-    if (!c) return fail(TA_EINVAL, "ctx is NULL");
-    if (!mesh_current(c)) return fail(TA_EINVAL, "no mesh of the current extraction (run ta_mesh_extract)");
-    int rc = use_device(c);
-    if (rc != TA_OK) return rc;
-    if ((rc = mesh_finish(c)) != TA_OK) return rc;
-    const uint64_t F = c->mesh_faces, V = c->mesh_verts;
-    const MeshOut O(c->mesh_rows, F, V);
-    const char* o = (const char*)c->mesh_out.p;
-    if (cells && !c->mesh_cells.empty()) std::memcpy(cells, c->mesh_cells.data(), 4 * c->mesh_cells.size());
-    if (vertex_offsets) std::memcpy(vertex_offsets, c->mesh_voff.data(), 8 * c->mesh_voff.size());
-    if (triangle_offsets) std::memcpy(triangle_offsets, c->mesh_toff.data(), 8 * c->mesh_toff.size());
-    const bool c_order = c->perm[0] == 0 && c->perm[1] == 1 && c->perm[2] == 2;
-    std::vector<uint64_t> k;                     // (another layout: the corners, converted to array-axis indices, then re-sorted)
-    if (!c_order && V) {
-        k.resize(V);
-        TA_HIP(hipMemcpyAsync(k.data(), o + O.vcorner, 8 * V, hipMemcpyDeviceToHost, c->stream));
-    } else if (corners && V) {
-        TA_HIP(hipMemcpyAsync(corners, o + O.vcorner, 8 * V, hipMemcpyDeviceToHost, c->stream));
-    }
-    if (triangles && F) TA_HIP(hipMemcpyAsync(triangles, o + O.tri, 24 * F, hipMemcpyDeviceToHost, c->stream));
-    if (triangle_cell && F) TA_HIP(hipMemcpyAsync(triangle_cell, o + O.tcell, 8 * F, hipMemcpyDeviceToHost, c->stream));
-    if (triangle_neighbor && F) TA_HIP(hipMemcpyAsync(triangle_neighbor, o + O.tnb, 8 * F, hipMemcpyDeviceToHost, c->stream));
-    TA_HIP(hipStreamSynchronize(c->stream));
-    if (!c_order && V) {
-        // the device sorted each cell's corners by their index in MEMORY order: convert them to C-order indices of the array
-        // axes and sort each cell's vertices by those (a 2-D image, stored (n0, n1, 1), is such a layout too)
-        int64_t g[3], ga[3];
-        for (int a = 0; a < 3; ++a) { g[a] = c->mesh_m[a] + 1; ga[c->perm[a]] = g[a]; }
-        for (uint64_t i = 0; i < V; ++i) {
-            const uint64_t x = k[i];
-            const int64_t k2 = (int64_t)(x % (uint64_t)g[2]), r = (int64_t)(x / (uint64_t)g[2]);
-            int64_t ka[3];
-            ka[c->perm[0]] = r / g[1]; ka[c->perm[1]] = r % g[1]; ka[c->perm[2]] = k2;
-            k[i] = (uint64_t)((ka[0] * ga[1] + ka[1]) * ga[2] + ka[2]);
-        }
-        std::vector<uint32_t> ord(V), newpos(V);
-        for (size_t ci = 0; ci + 1 < c->mesh_voff.size(); ++ci) {
-            const uint64_t v0 = c->mesh_voff[ci], v1 = c->mesh_voff[ci + 1];
-            for (uint64_t i = v0; i < v1; ++i) ord[i] = (uint32_t)i;
-            std::sort(ord.begin() + v0, ord.begin() + v1, [&](uint32_t x, uint32_t y) { return k[x] < k[y]; });
-            for (uint64_t i = v0; i < v1; ++i) newpos[ord[i]] = (uint32_t)i;
-        }
-        if (corners) for (uint64_t i = 0; i < V; ++i) corners[i] = k[ord[i]];
-        if (triangles) for (uint64_t i = 0; i < 6 * F; ++i) triangles[i] = newpos[triangles[i]];
-    }
-    return TA_OK;
-}
-
-TA_API int ta_mesh_timing(ta_ctx* c, double* ms) {
-    if (!c) return fail(TA_EINVAL, "ctx is NULL");
-    if (!ms) return fail(TA_EINVAL, "NULL argument");
-    if (c->mesh_seq == 0 || !c->mesh_ev[3]) return fail(TA_EINVAL, "no mesh pass has been run");
-    int rc = use_device(c);
-    if (rc != TA_OK) return rc;
-    TA_HIP(hipEventSynchronize(c->mesh_ev[3]));
-    float t0 = 0.f, t1 = 0.f;
-    TA_HIP(hipEventElapsedTime(&t0, c->mesh_ev[0], c->mesh_ev[1]));
-    TA_HIP(hipEventElapsedTime(&t1, c->mesh_ev[2], c->mesh_ev[3]));
-    *ms = (double)t0 + (double)t1;
-    return TA_OK;
-}
-
-// ---- label overlap with a second label volume (include/tissue_scan_overlap.h; kernels_overlap.hip) ---------------------------
-
-}  // extern "C"
-
-namespace {
-
-constexpr int OV_MIN_LOG2 = 4, OV_MAX_LOG2 = 31;       // (the sort's values are u32 slot numbers)
-
-uint64_t overlap_voxels(const ta_ctx* c) { return (uint64_t)(c->mdims[0] - c->first_owned) * (uint64_t)c->mdims[1] * (uint64_t)c->mdims[2]; }
-
-// the table no pass over this volume can fill: two slots a voxel
-int overlap_top_log2(const ta_ctx* c) {
-    int l = OV_MIN_LOG2;
-    while (l < OV_MAX_LOG2 && (1ull << l) < 2 * overlap_voxels(c)) ++l;
-    return l;
-}
-
-// the automatic table: a slot per 512 voxels (two Voronoi frames hold a pair per ~3000 voxels), 2^16 .. 2^24 slots
-int overlap_auto_log2(const ta_ctx* c) {
-    int l = 16;
-    while (l < 24 && (1ull << l) < overlap_voxels(c) / 512) ++l;
-    return l;
-}
-
-int overlap_adopt(ta_ctx* c, int itemsize) {
-    c->ovb_itemsize = itemsize;
-    for (int k = 0; k < 3; ++k) c->ovb_mdims[k] = c->mdims[k];
-    c->ov_state = 0;
-    return TA_OK;
-}
-
-// clear a table of 2^ov_log2 slots and enqueue the pass, then the count and the scan of its occupied slots
-int overlap_launch(ta_ctx* c) {
-    const uint64_t slots = 1ull << c->ov_log2, blocks = ta::overlap_compact_blocks(slots);
-    int rc;
-    if ((rc = c->ov_table.reserve(slots * 16)) != TA_OK) return rc;
-    if ((rc = c->ov_small.reserve(32)) != TA_OK) return rc;
-    const uint64_t offsets_at = (blocks * 4 + 15) & ~15ull, scratch_at = offsets_at + blocks * 8;
-    if ((rc = c->ov_work.reserve(scratch_at + ta::scan_u32_scratch_bytes(blocks))) != TA_OK) return rc;
-    for (auto& ev : c->ov_ev) if (!ev) TA_HIP(hipEventCreate(&ev));
-    ta::OverlapArgs a;
-    a.a = c->vol;                  // (the ids as the caller stored them: never the rank copy of a compacted context)
-    a.b = c->ovb;
-    a.n0 = c->mdims[0]; a.n1 = c->mdims[1]; a.n2 = c->mdims[2];
-    a.first_owned = c->first_owned;
-    a.keys = (unsigned long long*)c->ov_table.p;
-    a.counts = a.keys + slots;
-    a.mask = (uint32_t)(slots - 1);
-    a.flags = (uint32_t*)c->ov_small.p;
-    a.top = (unsigned long long*)((char*)c->ov_small.p + 16);
-    a.tiles_per_group = 0;
-    TA_HIP(hipMemsetAsync(a.keys, 0xff, slots * 8, c->stream));
-    TA_HIP(hipMemsetAsync(a.counts, 0, slots * 8, c->stream));
-    TA_HIP(hipMemsetAsync(c->ov_small.p, 0, 32, c->stream));
-    TA_HIP(hipEventRecord(c->ov_ev[0], c->stream));
-    ta::launch_overlap(c->stream, a, c->itemsize, c->ovb_itemsize);
-    TA_HIP(hipGetLastError());
-    TA_HIP(hipEventRecord(c->ov_ev[1], c->stream));
-    char* w = (char*)c->ov_work.p;
-    ta::launch_overlap_count(c->stream, a.keys, slots, (uint32_t*)w);
-    ta::launch_scan_u32_exclusive(c->stream, (const uint32_t*)w, blocks, w + scratch_at, (uint64_t*)(w + offsets_at));
-    TA_HIP(hipGetLastError());
-    TA_HIP(hipEventRecord(c->ov_ev[2], c->stream));
-    c->ov_passes += 1;
-    return TA_OK;
-}
-
-// drain the stream; a table that overflowed is grown and the pass repeated; then the occupied slots become the sorted rows
-int overlap_settle(ta_ctx* c) {
-    if (c->ov_state == 2) return TA_OK;
-    if (c->ov_state != 1) return fail(TA_EINVAL, "no overlap table for the current volume and B (run ta_overlap_extract)");
-    int rc;
-    uint64_t occupied = 0, top = 0;
-    for (;;) {
-        const uint64_t slots = 1ull << c->ov_log2, blocks = ta::overlap_compact_blocks(slots);
-        const uint64_t scratch_at = ((blocks * 4 + 15) & ~15ull) + blocks * 8;
-        uint32_t small[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        TA_HIP(hipMemcpyAsync(small, c->ov_small.p, sizeof(small), hipMemcpyDeviceToHost, c->stream));
-        TA_HIP(hipMemcpyAsync(&occupied, ta::scan_u32_total((char*)c->ov_work.p + scratch_at, blocks), 8, hipMemcpyDeviceToHost, c->stream));
-        TA_HIP(hipStreamSynchronize(c->stream));
-        memcpy(&top, &small[4], 8);
-        if (!small[ta::OV_FLAG_OVERFLOW]) break;
-        const int most = overlap_top_log2(c);
-        if (c->ov_log2 >= most) {
-            c->ov_state = 0;
-            return fail(TA_ENOMEM, "the overlap table overflowed at its largest size (2^%d slots)", c->ov_log2);
-        }
-        c->ov_log2 = std::min(c->ov_log2 + 3, most);
-        if (!c->ov_opt_log2) c->ov_grown_log2 = c->ov_log2;
-        if ((rc = overlap_launch(c)) != TA_OK) { c->ov_state = 0; return rc; }
-    }
-    const uint64_t slots = 1ull << c->ov_log2, blocks = ta::overlap_compact_blocks(slots);
-    const uint64_t offsets_at = (blocks * 4 + 15) & ~15ull;
-    const uint64_t P = occupied + (top ? 1 : 0);
-    // sort keys u64[n] x 2 | slots u32[n] x 2 | radix temp
-    const uint64_t n = occupied, keys_bytes = (n * 8 + 15) & ~15ull, idx_bytes = (n * 4 + 15) & ~15ull;
-    if ((rc = c->ov_sort.reserve(2 * keys_bytes + 2 * idx_bytes + ta::wall_sort_temp_bytes(n) + 16)) != TA_OK) return rc;
-    if ((rc = c->ov_rows.reserve(P * 16 + 16)) != TA_OK) return rc;
-    char* q = (char*)c->ov_sort.p;
-    uint64_t* k0 = (uint64_t*)q; uint64_t* k1 = (uint64_t*)(q + keys_bytes);
-    uint32_t* i0 = (uint32_t*)(q + 2 * keys_bytes); uint32_t* i1 = (uint32_t*)(q + 2 * keys_bytes + idx_bytes);
-    void* temp = q + 2 * keys_bytes + 2 * idx_bytes;
-    const unsigned long long* keys = (const unsigned long long*)c->ov_table.p;
-    const int shift_b = 8 * c->ovb_itemsize;
-    TA_HIP(hipEventRecord(c->ov_ev[3], c->stream));
-    ta::launch_overlap_emit(c->stream, keys, slots, (const uint64_t*)((char*)c->ov_work.p + offsets_at), shift_b, k0, i0);
-    uint64_t* ks = k0; uint32_t* is = i0;
-    TA_HIP(ta::launch_radix_sort_u64(c->stream, n, k0, k1, i0, i1, temp, 8 * c->itemsize + shift_b, &ks, &is));
-    uint32_t* ra = (uint32_t*)c->ov_rows.p;
-    ta::launch_overlap_rows(c->stream, ks, is, n, keys + slots, shift_b, top, ra, ra + P, (uint64_t*)(ra + 2 * P));
-    TA_HIP(hipGetLastError());
-    TA_HIP(hipEventRecord(c->ov_ev[4], c->stream));
-    TA_HIP(hipStreamSynchronize(c->stream));
-    c->ov_npairs = P;
-    c->ov_state = 2;
-    return TA_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-TA_API int ta_overlap_set(ta_ctx* c, const void* host_ptr, int itemsize, const int64_t dims[3], const int64_t strides_bytes[3]) {
-    if (!c) return fail(TA_EINVAL, "ctx is NULL");
-    if (!host_ptr || !dims) return fail(TA_EINVAL, "NULL argument");
-    if (itemsize != 2 && itemsize != 4) return fail(TA_EINVAL, "B's itemsize must be 2 (uint16) or 4 (uint32), not %d", itemsize);
-    if (!c->vol) return fail(TA_EINVAL, "no label volume set: B takes its dims and layout");
-    int64_t adims[3], el[3];                     // the label volume's dims and element strides, in array-axis order
-    int64_t e = 1;
-    for (int k = 2; k >= 0; --k) { adims[c->perm[k]] = c->mdims[k]; el[c->perm[k]] = e; e *= c->mdims[k]; }
-    for (int d = 0; d < 3; ++d) {
-        if (dims[d] != adims[d])
-            return fail(TA_EINVAL, "B's dims (%lld, %lld, %lld) differ from the label volume's (%lld, %lld, %lld)", (long long)dims[0],
-                        (long long)dims[1], (long long)dims[2], (long long)adims[0], (long long)adims[1], (long long)adims[2]);
-        const int64_t st = strides_bytes ? strides_bytes[d] : (d == 2 ? 1 : (d == 1 ? dims[2] : dims[1] * dims[2])) * itemsize;
-        if (dims[d] != 1 && st != el[d] * itemsize)
-            return fail(TA_EINVAL, "B's layout differs from the label volume's (axis %d: stride %lld bytes, expected %lld)", d,
-                        (long long)st, (long long)(el[d] * itemsize));
-    }
-    int rc = use_device(c);
-    if (rc != TA_OK) return rc;
-    const uint64_t bytes = (uint64_t)e * itemsize;
-    TA_HIP(hipStreamSynchronize(c->stream));     // (a pass in flight may still read the old B)
-    c->ovb = nullptr;
-    c->ov_state = 0;
-    if ((rc = c->owned_ovb.reserve(bytes + 64)) != TA_OK) return rc;
-    TA_HIP(hipMemcpyAsync(c->owned_ovb.p, host_ptr, bytes, hipMemcpyHostToDevice, c->stream));
-    TA_HIP(hipStreamSynchronize(c->stream));     // the host buffer may be freed after return
-    c->ovb = c->owned_ovb.p;
-    return overlap_adopt(c, itemsize);
-}
-
-TA_API int ta_overlap_set_device(ta_ctx* c, const void* dev_ptr, int itemsize) {
-    if (!c) return fail(TA_EINVAL, "ctx is NULL");
-    if (!dev_ptr) return fail(TA_EINVAL, "NULL argument");
-    if (itemsize != 2 && itemsize != 4) return fail(TA_EINVAL, "B's itemsize must be 2 (uint16) or 4 (uint32), not %d", itemsize);
-    if (!c->vol) return fail(TA_EINVAL, "no label volume set: B takes its buffer dims");
-    if (((uintptr_t)dev_ptr % itemsize) != 0) return fail(TA_EINVAL, "device pointer is not aligned to B's label type");
-    int rc = use_device(c);
-    if (rc != TA_OK) return rc;
-    TA_HIP(hipStreamSynchronize(c->stream));
-    c->owned_ovb.release();
-    c->ovb = dev_ptr;
-    return overlap_adopt(c, itemsize);
-}
-
-TA_API int ta_overlap_set_capacity(ta_ctx* c, int log2_slots) {
-    if (!c) return fail(TA_EINVAL, "ctx is NULL");
-    if (log2_slots != 0 && (log2_slots < OV_MIN_LOG2 || log2_slots > OV_MAX_LOG2))
-        return fail(TA_EINVAL, "the overlap table takes 2^%d .. 2^%d slots, or 0 for an automatic size", OV_MIN_LOG2, OV_MAX_LOG2);
-    c->ov_opt_log2 = log2_slots;
-    c->ov_grown_log2 = 0;
-    return TA_OK;
-}
-
-TA_API int ta_overlap_extract(ta_ctx* c) {
-    if (!c) return fail(TA_EINVAL, "ctx is NULL");
-    if (!c->vol) return fail(TA_EINVAL, "no label volume set");
-    if (!c->ovb) return fail(TA_EINVAL, "no second label volume set (ta_overlap_set)");
-    if (c->ovb_mdims[0] != c->mdims[0] || c->ovb_mdims[1] != c->mdims[1] || c->ovb_mdims[2] != c->mdims[2])
-        return fail(TA_EINVAL, "B does not match the label volume");
-    int rc = use_device(c);
-    if (rc != TA_OK) return rc;
-    c->ov_state = 0;
-    c->ov_passes = 0;
-    c->ov_log2 = c->ov_opt_log2 ? c->ov_opt_log2 : std::max(overlap_auto_log2(c), c->ov_grown_log2);
-    if ((rc = overlap_launch(c)) != TA_OK) return rc;
-    c->ov_state = 1;
-    return TA_OK;
-}
-
-TA_API int ta_overlap_size(ta_ctx* c, uint64_t* npairs) {
-    if (!c) return fail(TA_EINVAL, "ctx is NULL");
-    if (!npairs) return fail(TA_EINVAL, "NULL argument");
-    if (c->ov_state == 0) return fail(TA_EINVAL, "no overlap table for the current volume and B (run ta_overlap_extract)");
-    int rc = use_device(c);
-    if (rc != TA_OK) return rc;
-    if ((rc = overlap_settle(c)) != TA_OK) return rc;
-    *npairs = c->ov_npairs;
-    return TA_OK;
-}
-
-TA_API int ta_overlap_get(ta_ctx* c, uint32_t* a, uint32_t* b, uint64_t* n) {
-    if (!c) return fail(TA_EINVAL, "ctx is NULL");
-    if (c->ov_state == 0) return fail(TA_EINVAL, "no overlap table for the current volume and B (run ta_overlap_extract)");
-    int rc = use_device(c);
-    if (rc != TA_OK) return rc;
-    if ((rc = overlap_settle(c)) != TA_OK) return rc;
-    const uint64_t P = c->ov_npairs;
-    if (!P) return TA_OK;
-    const uint32_t* ra = (const uint32_t*)c->ov_rows.p;
-    if (a) TA_HIP(hipMemcpyAsync(a, ra, 4 * P, hipMemcpyDeviceToHost, c->stream));
-    if (b) TA_HIP(hipMemcpyAsync(b, ra + P, 4 * P, hipMemcpyDeviceToHost, c->stream));
-    if (n) TA_HIP(hipMemcpyAsync(n, ra + 2 * P, 8 * P, hipMemcpyDeviceToHost, c->stream));
-    TA_HIP(hipStreamSynchronize(c->stream));
-    return TA_OK;
-}
-
-TA_API int ta_overlap_timing(ta_ctx* c, double* ms) {
-    if (!c) return fail(TA_EINVAL, "ctx is NULL");
-    if (!ms) return fail(TA_EINVAL, "NULL argument");
-    if (c->ov_state == 0 || !c->ov_ev[1]) return fail(TA_EINVAL, "no overlap pass has been run");
-    int rc = use_device(c);
-    if (rc != TA_OK) return rc;
-    TA_HIP(hipEventSynchronize(c->ov_ev[1]));
-    float t = 0.f;
-    TA_HIP(hipEventElapsedTime(&t, c->ov_ev[0], c->ov_ev[1]));
-    *ms = (double)t;
-    return TA_OK;
-}
-
-TA_API int ta_overlap_timing_compaction(ta_ctx* c, double* ms, int* passes) {
-    if (!c) return fail(TA_EINVAL, "ctx is NULL");
-    if (!ms) return fail(TA_EINVAL, "NULL argument");
-    if (c->ov_state != 2) return fail(TA_EINVAL, "no settled overlap table (ask ta_overlap_size first)");
-    int rc = use_device(c);
-    if (rc != TA_OK) return rc;
-    TA_HIP(hipEventSynchronize(c->ov_ev[4]));
-    float t0 = 0.f, t1 = 0.f;
-    TA_HIP(hipEventElapsedTime(&t0, c->ov_ev[1], c->ov_ev[2]));
-    TA_HIP(hipEventElapsedTime(&t1, c->ov_ev[3], c->ov_ev[4]));
-    *ms = (double)t0 + (double)t1;
-    if (passes) *passes = c->ov_passes;
-    return TA_OK;
-}
-
-}  // extern "C"
-
-// ---- cell junctions (include/tissue_scan_junctions.h; kernels_junctions.hip) ---------------------------------------------------
-
-namespace {
-
-// where the parts of jn_work lie, for W waves
-struct JunctionWork {
-    uint64_t counts[2], offsets[2], scratch[2], bytes;
-    explicit JunctionWork(uint64_t W) {
-        uint64_t at = 0;
-        for (int k = 0; k < 2; ++k) { counts[k] = at; at += align16(W * 4); }
-        for (int k = 0; k < 2; ++k) { offsets[k] = at; at += align16(W * 8); }
-        for (int k = 0; k < 2; ++k) { scratch[k] = at; at += align16(ta::scan_u32_scratch_bytes(W)); }
-        bytes = at + 16;
-    }
-};
-
-// where the parts of jn_sort[k] lie, for N records
-struct JunctionSort {
-    uint64_t keys[2], order[2], temp, counts, offsets, scratch, bytes;
-    explicit JunctionSort(uint64_t N) {
-        const uint64_t B = ta::junction_row_blocks(N);
-        uint64_t at = 0;
-        for (int k = 0; k < 2; ++k) { keys[k] = at; at += align16(N * 8); }
-        for (int k = 0; k < 2; ++k) { order[k] = at; at += align16(N * 4); }
-        temp = at; at += align16(ta::wall_sort_temp_bytes(N));
-        counts = at; at += align16(B * 4);
-        offsets = at; at += align16(B * 8);
-        scratch = at; at += align16(ta::scan_u32_scratch_bytes(B));
-        bytes = at + 16;
-    }
-};
-
-ta::JunctionArgs junction_args(ta_ctx* c) {
-    ta::JunctionArgs a = {};
-    a.vol = c->vol;                // (the ids as the caller stored them: never the rank copy of a compacted context, so that
-                                   //  the rows sort by id and need no translation)
-    a.n0 = c->mdims[0]; a.n1 = c->mdims[1]; a.n2 = c->mdims[2];
-    c->jn_waves = ta::junction_plan(a, c->itemsize);
-    const JunctionWork w(c->jn_waves);
-    char* p = (char*)c->jn_work.p;
-    a.wave_counts3 = (uint32_t*)(p + w.counts[0]); a.wave_counts4 = (uint32_t*)(p + w.counts[1]);
-    a.wave_offsets3 = (const uint64_t*)(p + w.offsets[0]); a.wave_offsets4 = (const uint64_t*)(p + w.offsets[1]);
-    a.degenerate = (unsigned long long*)c->jn_small.p;
-    return a;
-}
-
-// drain the stream, read the record counts, allocate, run the emitting walk, sort and reduce the records into the tables
-int junctions_settle(ta_ctx* c) {
-    if (c->jn_state == 2) return TA_OK;
-    if (c->jn_state != 1) return fail(TA_EINVAL, "no junction tables for the current volume (run ta_junctions_extract)");
-    c->jn_state = 0;                               // (whatever fails below: no tables)
-    int rc;
-    ta::JunctionArgs a = junction_args(c);
-    const JunctionWork w(c->jn_waves);
-    char* wp = (char*)c->jn_work.p;
-    uint64_t N[2] = {0, 0}, degenerate = 0;
-    for (int k = 0; k < 2; ++k)
-        TA_HIP(hipMemcpyAsync(&N[k], ta::scan_u32_total(wp + w.scratch[k], c->jn_waves), 8, hipMemcpyDeviceToHost, c->stream));
-    TA_HIP(hipMemcpyAsync(&degenerate, c->jn_small.p, 8, hipMemcpyDeviceToHost, c->stream));
-    TA_HIP(hipStreamSynchronize(c->stream));
-    for (int k = 0; k < 2; ++k)
-        if (N[k] >= (1ull << 32)) return fail(TA_ENOMEM, "%llu junction records: the sort takes fewer than 2^32", (unsigned long long)N[k]);
-    const int K[2] = {3, 4};
-    const uint64_t lab_at[2] = {align16(N[0] * 8) + align16(N[1] * 8), align16(N[0] * 8) + align16(N[1] * 8) + align16(N[0] * 12)};
-    if ((rc = c->jn_rec.reserve(lab_at[1] + align16(N[1] * 16) + 16)) != TA_OK) return rc;
-    for (int k = 0; k < 2; ++k)
-        if ((rc = c->jn_sort[k].reserve(JunctionSort(N[k]).bytes)) != TA_OK) return rc;
-    char* rp = (char*)c->jn_rec.p;
-    uint64_t* origins[2] = {(uint64_t*)rp, (uint64_t*)(rp + align16(N[0] * 8))};
-    uint32_t* labels[2] = {(uint32_t*)(rp + lab_at[0]), (uint32_t*)(rp + lab_at[1])};
-    a.origin3 = origins[0]; a.origin4 = origins[1];
-    a.labels3 = labels[0]; a.labels4 = labels[1];
-    TA_HIP(hipEventRecord(c->jn_ev[3], c->stream));
-    if (N[0] || N[1]) ta::launch_junction_pass(c->stream, a, c->itemsize, true);
-    TA_HIP(hipGetLastError());
-    TA_HIP(hipEventRecord(c->jn_ev[4], c->stream));
-    // stable sorts over the label columns from last to first, then the rows that start in every block of sorted records
-    const int lb = 8 * c->itemsize;
-    uint32_t* order[2] = {nullptr, nullptr};
-    uint64_t R[2] = {0, 0};
-    for (int k = 0; k < 2; ++k) {
-        const uint64_t n = N[k];
-        if (!n) continue;
-        const JunctionSort q(n);
-        char* sp = (char*)c->jn_sort[k].p;
-        uint64_t* k0 = (uint64_t*)(sp + q.keys[0]); uint64_t* k1 = (uint64_t*)(sp + q.keys[1]);
-        uint32_t* i0 = (uint32_t*)(sp + q.order[0]); uint32_t* i1 = (uint32_t*)(sp + q.order[1]);
-        ta::launch_junction_keys(c->stream, labels[k], K[k], n, nullptr, K[k] - 2, K[k] - 1, lb, k0, i0);
-        uint64_t* ks = k0; uint32_t* is = i0;
-        TA_HIP(ta::launch_radix_sort_u64(c->stream, n, k0, k1, i0, i1, sp + q.temp, 2 * lb, &ks, &is));
-        // the leading columns of the records in that order, into the key buffer the order came out with
-        uint64_t* ko = ks == k0 ? k1 : k0; uint32_t* io = is == i0 ? i1 : i0;
-        ta::launch_junction_keys(c->stream, labels[k], K[k], n, is, K[k] == 4 ? 0 : -1, K[k] == 4 ? 1 : 0, lb, ks, nullptr);
-        uint64_t* ks2 = ks; uint32_t* is2 = is;
-        TA_HIP(ta::launch_radix_sort_u64(c->stream, n, ks, ko, is, io, sp + q.temp, K[k] == 4 ? 2 * lb : lb, &ks2, &is2));
-        order[k] = is2;
-        const uint64_t B = ta::junction_row_blocks(n);
-        ta::launch_junction_heads(c->stream, labels[k], K[k], is2, n, (uint32_t*)(sp + q.counts));
-        ta::launch_scan_u32_exclusive(c->stream, (const uint32_t*)(sp + q.counts), B, sp + q.scratch, (uint64_t*)(sp + q.offsets));
-        TA_HIP(hipGetLastError());
-        TA_HIP(hipMemcpyAsync(&R[k], ta::scan_u32_total(sp + q.scratch, B), 8, hipMemcpyDeviceToHost, c->stream));
-    }
-    TA_HIP(hipStreamSynchronize(c->stream));
-    for (int k = 0; k < 2; ++k)
-        if ((rc = c->jn_rows[k].reserve(R[k] * 32 + R[k] * 4 * K[k] + 16)) != TA_OK) return rc;
-    for (int k = 0; k < 2; ++k) {
-        if (!N[k]) continue;
-        const JunctionSort q(N[k]);
-        char* sp = (char*)c->jn_sort[k].p;
-        char* op = (char*)c->jn_rows[k].p;
-        TA_HIP(hipMemsetAsync(op, 0, R[k] * 32, c->stream));
-        ta::JunctionRows rows;
-        rows.n = (unsigned long long*)op;
-        rows.sums = rows.n + R[k];
-        rows.labels = (uint32_t*)(op + R[k] * 32);
-        rows.n0 = c->mdims[0]; rows.n1 = c->mdims[1]; rows.n2 = c->mdims[2];
-        rows.origin0 = c->a_origin - c->first_owned;
-        for (int d = 0; d < 3; ++d) { rows.flat[d] = c->mdims[d] == 1 ? 1 : 0; rows.axis[d] = c->perm[d]; }
-        ta::launch_junction_reduce(c->stream, labels[k], origins[k], K[k], order[k], N[k], (const uint64_t*)(sp + q.offsets), rows);
-        TA_HIP(hipGetLastError());
-    }
-    TA_HIP(hipEventRecord(c->jn_ev[5], c->stream));
-    TA_HIP(hipStreamSynchronize(c->stream));
-    c->jn_nrows[0] = R[0]; c->jn_nrows[1] = R[1];
-    c->jn_degenerate = degenerate;
-    c->jn_state = 2;
-    return TA_OK;
-}
-
-int junctions_get(ta_ctx* c, int k, uint32_t* labels, uint64_t* n, uint64_t* sums) {
-    if (!c) return fail(TA_EINVAL, "ctx is NULL");
-    if (c->jn_state == 0) return fail(TA_EINVAL, "no junction tables for the current volume (run ta_junctions_extract)");
-    int rc = use_device(c);
-    if (rc != TA_OK) return rc;
-    if ((rc = junctions_settle(c)) != TA_OK) return rc;
-    const uint64_t R = c->jn_nrows[k], K = k ? 4 : 3;
-    if (!R) return TA_OK;
-    const char* op = (const char*)c->jn_rows[k].p;
-    if (n) TA_HIP(hipMemcpyAsync(n, op, R * 8, hipMemcpyDeviceToHost, c->stream));
-    if (sums) TA_HIP(hipMemcpyAsync(sums, op + R * 8, R * 24, hipMemcpyDeviceToHost, c->stream));
-    if (labels) TA_HIP(hipMemcpyAsync(labels, op + R * 32, R * 4 * K, hipMemcpyDeviceToHost, c->stream));
-    TA_HIP(hipStreamSynchronize(c->stream));
-    return TA_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-TA_API int ta_junctions_extract(ta_ctx* c) {
-    if (!c) return fail(TA_EINVAL, "ctx is NULL");
-    if (!c->vol) return fail(TA_EINVAL, "no label volume set");
-    int rc = use_device(c);
-    if (rc != TA_OK) return rc;
-    c->jn_state = 0;
-    if ((rc = c->jn_small.reserve(16)) != TA_OK) return rc;
-    {
-        ta::JunctionArgs plan = {};
-        plan.n0 = c->mdims[0]; plan.n1 = c->mdims[1]; plan.n2 = c->mdims[2];
-        if ((rc = c->jn_work.reserve(JunctionWork(ta::junction_plan(plan, c->itemsize)).bytes)) != TA_OK) return rc;
-    }
-    for (auto& ev : c->jn_ev) if (!ev) TA_HIP(hipEventCreate(&ev));
-    const ta::JunctionArgs a = junction_args(c);
-    const JunctionWork w(c->jn_waves);
-    char* wp = (char*)c->jn_work.p;
-    TA_HIP(hipMemsetAsync(c->jn_small.p, 0, 16, c->stream));
-    TA_HIP(hipEventRecord(c->jn_ev[0], c->stream));
-    ta::launch_junction_pass(c->stream, a, c->itemsize, false);
-    TA_HIP(hipGetLastError());
-    TA_HIP(hipEventRecord(c->jn_ev[1], c->stream));
-    for (int k = 0; k < 2; ++k)
-        ta::launch_scan_u32_exclusive(c->stream, (const uint32_t*)(wp + w.counts[k]), c->jn_waves, wp + w.scratch[k], (uint64_t*)(wp + w.offsets[k]));
-    TA_HIP(hipGetLastError());
-    TA_HIP(hipEventRecord(c->jn_ev[2], c->stream));
-    c->jn_state = 1;
-    return TA_OK;
-}
-
-TA_API int ta_junctions_size(ta_ctx* c, uint64_t* nedges, uint64_t* nvertices, uint64_t* degenerate) {
-    if (!c) return fail(TA_EINVAL, "ctx is NULL");
-    if (c->jn_state == 0) return fail(TA_EINVAL, "no junction tables for the current volume (run ta_junctions_extract)");
-    int rc = use_device(c);
-    if (rc != TA_OK) return rc;
-    if ((rc = junctions_settle(c)) != TA_OK) return rc;
-    if (nedges) *nedges = c->jn_nrows[0];
-    if (nvertices) *nvertices = c->jn_nrows[1];
-    if (degenerate) *degenerate = c->jn_degenerate;
-    return TA_OK;
-}
-
-TA_API int ta_junctions_get_edges(ta_ctx* c, uint32_t* labels, uint64_t* n, uint64_t* sums) { return junctions_get(c, 0, labels, n, sums); }
-
-TA_API int ta_junctions_get_vertices(ta_ctx* c, uint32_t* labels, uint64_t* n, uint64_t* sums) { return junctions_get(c, 1, labels, n, sums); }
-
-TA_API int ta_junctions_timing(ta_ctx* c, double* ms_pass, double* ms_after) {
-    if (!c) return fail(TA_EINVAL, "ctx is NULL");
-    if (c->jn_state != 2) return fail(TA_EINVAL, "no settled junction tables (ask ta_junctions_size first)");
-    int rc = use_device(c);
-    if (rc != TA_OK) return rc;
-    TA_HIP(hipEventSynchronize(c->jn_ev[5]));
-    float count = 0.f, scans = 0.f, emit = 0.f, rest = 0.f;
-    TA_HIP(hipEventElapsedTime(&count, c->jn_ev[0], c->jn_ev[1]));
-    TA_HIP(hipEventElapsedTime(&scans, c->jn_ev[1], c->jn_ev[2]));
-    TA_HIP(hipEventElapsedTime(&emit, c->jn_ev[3], c->jn_ev[4]));
-    TA_HIP(hipEventElapsedTime(&rest, c->jn_ev[4], c->jn_ev[5]));
-    if (ms_pass) *ms_pass = (double)count + (double)emit;
-    if (ms_after) *ms_after = (double)scans + (double)rest;
     return TA_OK;
 }
 

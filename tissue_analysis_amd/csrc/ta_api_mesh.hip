@@ -1,0 +1,234 @@
+// ta_api_mesh.hip -- the C ABI of include/tissue_scan_mesh.h: the triangle surface mesh of every requested cell (kernels_mesh.hip).
+#include "../../include/tissue_scan_mesh.h"
+#include "ta_ctx.h"
+#include "ta_mesh.h"
+
+namespace {
+
+bool mesh_current(const ta_ctx* c) { return c->mesh.seq != 0 && c->extracted && c->mesh.seq == c->extract_seq; }
+
+// byte offsets of the parts of MeshState::small for R rows and wf / wc waves of the face / corner kernels
+struct MeshSmall {
+    uint64_t flags = 0, wanted, fcounts, ccounts, foffs, coffs, fscan, cscan, bytes;
+    MeshSmall(uint64_t R, uint64_t wf, uint64_t wc) {
+        wanted = 16; fcounts = wanted + align16(R); ccounts = fcounts + align16(4 * wf); foffs = ccounts + align16(4 * wc);
+        coffs = foffs + align16(8 * wf); fscan = coffs + align16(8 * wc); cscan = fscan + align16(ta::scan_u32_scratch_bytes(wf));
+        bytes = cscan + align16(ta::scan_u32_scratch_bytes(wc));
+    }
+};
+// ... of MeshState::work for F faces and V vertex records
+struct MeshWork {
+    uint64_t frec = 0, fnb, corner;
+    SortLayout sort;                             // (one workspace for both sorts: the faces', then the vertex records')
+    MeshWork(uint64_t F, uint64_t V)
+        : fnb(align16(8 * F)), corner(fnb + align16(4 * F)), sort(F > V ? F : V, 4, corner + align16(8 * V)) {}
+};
+// ... of MeshState::out
+struct MeshOut {
+    uint64_t vcorner = 0, vbeg, vend, fbeg, fend, tri, tcell, tnb, bytes;
+    MeshOut(uint64_t R, uint64_t F, uint64_t V) {
+        vbeg = align16(8 * V); vend = vbeg + 8 * R; fbeg = vend + 8 * R; fend = fbeg + 8 * R; tri = align16(fend + 8 * R);
+        tcell = tri + align16(24 * F); tnb = tcell + align16(8 * F); bytes = tnb + align16(8 * F);
+    }
+};
+
+// drain the stream, look at the flags of the emit / resolve kernels, and read the cells and their CSR offsets back once
+int mesh_finish(ta_ctx* c) {
+    uint32_t flags[ta::MESH_NFLAGS] = {0, 0, 0, 0};
+    TA_HIP(hipMemcpyAsync(flags, c->mesh.small.p, sizeof(flags), hipMemcpyDeviceToHost, c->stream));
+    TA_HIP(hipStreamSynchronize(c->stream));
+    if (flags[ta::MESH_FLAG_RANGE] || flags[ta::MESH_FLAG_MISS] || flags[ta::MESH_FLAG_OVERRUN])
+        return fail(TA_ERANGE, "the mesh pass found the volume changed since ta_extract (flags %u %u %u)", flags[0], flags[1], flags[2]);
+    if (c->mesh.host_ready) return TA_OK;
+    const uint64_t R = c->mesh.rows;
+    const MeshOut O(R, c->mesh.faces, c->mesh.verts);
+    std::vector<uint64_t> t(4 * R);
+    const char* o = (const char*)c->mesh.out.p;
+    if (R) TA_HIP(hipMemcpyAsync(t.data(), o + O.vbeg, 32 * R, hipMemcpyDeviceToHost, c->stream));
+    TA_HIP(hipStreamSynchronize(c->stream));
+    const uint64_t *vbeg = t.data(), *vend = vbeg + R, *fbeg = vend + R, *fend = fbeg + R;
+    c->mesh.cells.clear(); c->mesh.voff.clear(); c->mesh.toff.clear();
+    for (uint64_t r = 0; r < R; ++r) {
+        if (vend[r] <= vbeg[r]) continue;
+        if (fend[r] <= fbeg[r]) return fail(TA_ERANGE, "mesh: row %llu has vertices and no faces", (unsigned long long)r);
+        c->mesh.cells.push_back((uint32_t)r);
+        c->mesh.voff.push_back(vbeg[r]);
+        c->mesh.toff.push_back(2 * fbeg[r]);
+    }
+    c->mesh.voff.push_back(c->mesh.verts);
+    c->mesh.toff.push_back(2 * c->mesh.faces);
+    c->mesh.host_ready = true;
+    return TA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+TA_API int ta_mesh_extract(ta_ctx* c, int sub_factor, const uint8_t* wanted_rows) {
+    if (!c) return fail(TA_EINVAL, "ctx is NULL");
+    if (sub_factor < 1) return fail(TA_EINVAL, "sub_factor must be >= 1, not %d", sub_factor);
+    if (!c->vol) return fail(TA_EINVAL, "no volume set");
+    if (c->first_owned) return fail(TA_EINVAL, "cell meshes are not available on a slab that carries a halo plane");
+    int rc = use_device(c);
+    if (rc != TA_OK) return rc;
+    if (!c->extracted) return fail(TA_EINVAL, "the mesh pass needs a ta_extract of the current volume first");
+    if ((rc = finish_extract(c)) != TA_OK) return rc;
+    c->mesh.seq = 0;
+    c->mesh.host_ready = false;
+    const uint64_t R = (uint64_t)c->max_label + 1;
+    ta::MeshArgs a;
+    a.vol = sweep_vol(c);
+    a.n0 = c->mdims[0]; a.n1 = c->mdims[1]; a.n2 = c->mdims[2];
+    a.s = sub_factor;
+    a.m0 = (a.n0 + a.s - 1) / a.s; a.m1 = (a.n1 + a.s - 1) / a.s; a.m2 = (a.n2 + a.s - 1) / a.s;
+    for (int k = 0; k < 3; ++k) a.inv[c->perm[k]] = k;
+    a.rows = (uint32_t)R;
+    const uint64_t nvox = (uint64_t)a.m0 * a.m1 * a.m2, ncorner = (uint64_t)(a.m0 + 1) * (a.m1 + 1) * (a.m2 + 1);
+    const uint64_t wf = ta::mesh_waves(nvox), wc = ta::mesh_waves(ncorner);
+    const MeshSmall S(R, wf, wc);
+    if ((rc = c->mesh.small.reserve(S.bytes)) != TA_OK) return rc;
+    char* sm = (char*)c->mesh.small.p;
+    a.flags = (uint32_t*)sm;
+    a.wanted = (const uint8_t*)(sm + S.wanted);
+    if ((rc = ensure_events(c->mesh.ev)) != TA_OK) return rc;
+    TA_HIP(hipMemsetAsync(sm, 0, 16, c->stream));
+    if (wanted_rows) TA_HIP(hipMemcpyAsync(sm + S.wanted, wanted_rows, R, hipMemcpyHostToDevice, c->stream));
+    else TA_HIP(hipMemsetAsync(sm + S.wanted, 1, R, c->stream));
+    // count -> scan: the totals are all the host needs before it sizes the output
+    uint32_t* fcounts = (uint32_t*)(sm + S.fcounts);
+    uint32_t* ccounts = (uint32_t*)(sm + S.ccounts);
+    uint64_t* foffs = (uint64_t*)(sm + S.foffs);
+    uint64_t* coffs = (uint64_t*)(sm + S.coffs);
+    TA_HIP(hipEventRecord(c->mesh.ev[0], c->stream));
+    ta::launch_mesh_face_count(c->stream, a, c->itemsize, fcounts);
+    ta::launch_mesh_corner_count(c->stream, a, c->itemsize, ccounts);
+    ta::launch_scan_u32_exclusive(c->stream, fcounts, wf, sm + S.fscan, foffs);
+    ta::launch_scan_u32_exclusive(c->stream, ccounts, wc, sm + S.cscan, coffs);
+    TA_HIP(hipGetLastError());
+    TA_HIP(hipEventRecord(c->mesh.ev[1], c->stream));
+    uint64_t tot[2] = {0, 0};
+    uint32_t flags[ta::MESH_NFLAGS] = {0, 0, 0, 0};
+    if (wf) TA_HIP(hipMemcpyAsync(&tot[0], ta::scan_u32_total(sm + S.fscan, wf), 8, hipMemcpyDeviceToHost, c->stream));
+    if (wc) TA_HIP(hipMemcpyAsync(&tot[1], ta::scan_u32_total(sm + S.cscan, wc), 8, hipMemcpyDeviceToHost, c->stream));
+    TA_HIP(hipMemcpyAsync(flags, sm, sizeof(flags), hipMemcpyDeviceToHost, c->stream));
+    TA_HIP(hipStreamSynchronize(c->stream));
+    if (flags[ta::MESH_FLAG_RANGE]) return fail(TA_ERANGE, "the mesh pass met a label above max_label=%u (the volume changed since ta_extract)", c->max_label);
+    const uint64_t F = tot[0], V = tot[1];
+    if (V > 0xFFFFFFFFull) return fail(TA_ERANGE, "the meshes have %llu vertices: more than 2^32 - 1", (unsigned long long)V);
+    if (F > 0xFFFFFFFFull) return fail(TA_ERANGE, "the meshes have %llu faces: more than 2^32 - 1", (unsigned long long)F);
+    const MeshWork Wk(F, V);
+    const MeshOut O(R, F, V);
+    if ((rc = c->mesh.work.reserve(Wk.sort.end)) != TA_OK) return rc;
+    if ((rc = c->mesh.out.reserve(O.bytes)) != TA_OK) return rc;
+    char* w = (char*)c->mesh.work.p;
+    char* o = (char*)c->mesh.out.p;
+    uint64_t* frec = (uint64_t*)(w + Wk.frec);
+    uint32_t* fnb = (uint32_t*)(w + Wk.fnb);
+    uint64_t* corner = (uint64_t*)(w + Wk.corner);
+    uint32_t *keys0 = (uint32_t*)(w + Wk.sort.keys[0]), *keys1 = (uint32_t*)(w + Wk.sort.keys[1]);
+    uint32_t *idx0 = (uint32_t*)(w + Wk.sort.idx[0]), *idx1 = (uint32_t*)(w + Wk.sort.idx[1]);
+    void* temp = w + Wk.sort.temp;
+    uint64_t* vcorner = (uint64_t*)(o + O.vcorner);
+    uint64_t *vbeg = (uint64_t*)(o + O.vbeg), *vend = (uint64_t*)(o + O.vend);
+    uint64_t *fbeg = (uint64_t*)(o + O.fbeg), *fend = (uint64_t*)(o + O.fend);
+    const int key_bits = c->max_label ? 32 - __builtin_clz(c->max_label) : 1;
+    uint32_t *skeys = nullptr, *sidx = nullptr;
+    // emit -> group by cell -> resolve
+    TA_HIP(hipEventRecord(c->mesh.ev[2], c->stream));
+    TA_HIP(hipMemsetAsync(vbeg, 0, 32 * R, c->stream));
+    ta::launch_mesh_corner_emit(c->stream, a, c->itemsize, coffs, V, corner, keys0, idx0);
+    TA_HIP(ta::launch_radix_sort_u32(c->stream, V, keys0, keys1, idx0, idx1, temp, key_bits, &skeys, &sidx));
+    ta::launch_mesh_bounds(c->stream, skeys, V, vbeg, vend);
+    ta::launch_mesh_gather(c->stream, corner, sidx, V, vcorner);
+    ta::launch_mesh_face_emit(c->stream, a, c->itemsize, foffs, F, frec, fnb, keys0, idx0);
+    TA_HIP(ta::launch_radix_sort_u32(c->stream, F, keys0, keys1, idx0, idx1, temp, key_bits, &skeys, &sidx));
+    ta::launch_mesh_bounds(c->stream, skeys, F, fbeg, fend);
+    ta::launch_mesh_resolve(c->stream, a, skeys, sidx, frec, fnb, F, vcorner, vbeg, vend, (uint32_t*)(o + O.tri),
+                            (uint32_t*)(o + O.tcell), (uint32_t*)(o + O.tnb));
+    TA_HIP(hipGetLastError());
+    TA_HIP(hipEventRecord(c->mesh.ev[3], c->stream));
+    c->mesh.faces = F;
+    c->mesh.verts = V;
+    c->mesh.rows = (uint32_t)R;
+    c->mesh.m[0] = a.m0; c->mesh.m[1] = a.m1; c->mesh.m[2] = a.m2;
+    c->mesh.seq = c->extract_seq;
+    return TA_OK;
+}
+
+TA_API int ta_mesh_size(ta_ctx* c, uint64_t* n_cells, uint64_t* n_vertices, uint64_t* n_triangles) {
+    if (!c) return fail(TA_EINVAL, "ctx is NULL");
+    if (!mesh_current(c)) return fail(TA_EINVAL, "no mesh of the current extraction (run ta_mesh_extract)");
+    int rc = use_device(c);
+    if (rc != TA_OK) return rc;
+    if ((rc = mesh_finish(c)) != TA_OK) return rc;
+    if (n_cells) *n_cells = (uint64_t)c->mesh.cells.size();
+    if (n_vertices) *n_vertices = c->mesh.verts;
+    if (n_triangles) *n_triangles = 2 * c->mesh.faces;
+    return TA_OK;
+}
+
+TA_API int ta_mesh_get(ta_ctx* c, uint32_t* cells, uint64_t* vertex_offsets, uint64_t* triangle_offsets, uint64_t* corners,
+                       uint32_t* triangles, uint32_t* triangle_cell, uint32_t* triangle_neighbor) {
+    if (!c) return fail(TA_EINVAL, "ctx is NULL");
+    if (!mesh_current(c)) return fail(TA_EINVAL, "no mesh of the current extraction (run ta_mesh_extract)");
+    int rc = use_device(c);
+    if (rc != TA_OK) return rc;
+    if ((rc = mesh_finish(c)) != TA_OK) return rc;
+    const uint64_t F = c->mesh.faces, V = c->mesh.verts;
+    const MeshOut O(c->mesh.rows, F, V);
+    const char* o = (const char*)c->mesh.out.p;
+    if (cells && !c->mesh.cells.empty()) std::memcpy(cells, c->mesh.cells.data(), 4 * c->mesh.cells.size());
+    if (vertex_offsets) std::memcpy(vertex_offsets, c->mesh.voff.data(), 8 * c->mesh.voff.size());
+    if (triangle_offsets) std::memcpy(triangle_offsets, c->mesh.toff.data(), 8 * c->mesh.toff.size());
+    const bool c_order = c->perm[0] == 0 && c->perm[1] == 1 && c->perm[2] == 2;
+    std::vector<uint64_t> k;                     // (another layout: the corners, converted to array-axis indices, then re-sorted)
+    if (!c_order && V) {
+        k.resize(V);
+        TA_HIP(hipMemcpyAsync(k.data(), o + O.vcorner, 8 * V, hipMemcpyDeviceToHost, c->stream));
+    } else if (corners && V) {
+        TA_HIP(hipMemcpyAsync(corners, o + O.vcorner, 8 * V, hipMemcpyDeviceToHost, c->stream));
+    }
+    if (triangles && F) TA_HIP(hipMemcpyAsync(triangles, o + O.tri, 24 * F, hipMemcpyDeviceToHost, c->stream));
+    if (triangle_cell && F) TA_HIP(hipMemcpyAsync(triangle_cell, o + O.tcell, 8 * F, hipMemcpyDeviceToHost, c->stream));
+    if (triangle_neighbor && F) TA_HIP(hipMemcpyAsync(triangle_neighbor, o + O.tnb, 8 * F, hipMemcpyDeviceToHost, c->stream));
+    TA_HIP(hipStreamSynchronize(c->stream));
+    if (!c_order && V) {
+        // the device sorted each cell's corners by their index in MEMORY order: convert them to C-order indices of the array
+        // axes and sort each cell's vertices by those (a 2-D image, stored (n0, n1, 1), is such a layout too)
+        int64_t g[3], ga[3];
+        for (int a = 0; a < 3; ++a) { g[a] = c->mesh.m[a] + 1; ga[c->perm[a]] = g[a]; }
+        for (uint64_t i = 0; i < V; ++i) {
+            const uint64_t x = k[i];
+            const int64_t k2 = (int64_t)(x % (uint64_t)g[2]), r = (int64_t)(x / (uint64_t)g[2]);
+            int64_t ka[3];
+            ka[c->perm[0]] = r / g[1]; ka[c->perm[1]] = r % g[1]; ka[c->perm[2]] = k2;
+            k[i] = (uint64_t)((ka[0] * ga[1] + ka[1]) * ga[2] + ka[2]);
+        }
+        std::vector<uint32_t> ord(V), newpos(V);
+        for (size_t ci = 0; ci + 1 < c->mesh.voff.size(); ++ci) {
+            const uint64_t v0 = c->mesh.voff[ci], v1 = c->mesh.voff[ci + 1];
+            for (uint64_t i = v0; i < v1; ++i) ord[i] = (uint32_t)i;
+            std::sort(ord.begin() + v0, ord.begin() + v1, [&](uint32_t x, uint32_t y) { return k[x] < k[y]; });
+            for (uint64_t i = v0; i < v1; ++i) newpos[ord[i]] = (uint32_t)i;
+        }
+        if (corners) for (uint64_t i = 0; i < V; ++i) corners[i] = k[ord[i]];
+        if (triangles) for (uint64_t i = 0; i < 6 * F; ++i) triangles[i] = newpos[triangles[i]];
+    }
+    return TA_OK;
+}
+
+TA_API int ta_mesh_timing(ta_ctx* c, double* ms) {
+    if (!c) return fail(TA_EINVAL, "ctx is NULL");
+    if (!ms) return fail(TA_EINVAL, "NULL argument");
+    if (c->mesh.seq == 0 || !c->mesh.ev[3]) return fail(TA_EINVAL, "no mesh pass has been run");
+    int rc = use_device(c);
+    if (rc != TA_OK) return rc;
+    TA_HIP(hipEventSynchronize(c->mesh.ev[3]));
+    double t0 = 0.0, t1 = 0.0;
+    if ((rc = elapsed_ms(c->mesh.ev[0], c->mesh.ev[1], &t0)) != TA_OK || (rc = elapsed_ms(c->mesh.ev[2], c->mesh.ev[3], &t1)) != TA_OK) return rc;
+    *ms = t0 + t1;
+    return TA_OK;
+}
+
+}  // extern "C"

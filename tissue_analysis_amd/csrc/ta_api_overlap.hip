@@ -1,0 +1,214 @@
+// ta_api_overlap.hip -- the C ABI of include/tissue_scan_overlap.h on top of kernels_overlap.hip.
+#include "../../include/tissue_scan_overlap.h"
+#include "ta_ctx.h"
+#include "ta_overlap.h"
+
+namespace {
+
+constexpr CompanionKind B_VOLUME = {"B", 2, 4};        // uint16 or uint32
+constexpr int OV_MIN_LOG2 = 4, OV_MAX_LOG2 = 31;       // (the sort's values are u32 slot numbers)
+
+uint64_t overlap_voxels(const ta_ctx* c) { return (uint64_t)(c->mdims[0] - c->first_owned) * (uint64_t)c->mdims[1] * (uint64_t)c->mdims[2]; }
+
+// the table no pass over this volume can fill: two slots a voxel
+int overlap_top_log2(const ta_ctx* c) {
+    int l = OV_MIN_LOG2;
+    while (l < OV_MAX_LOG2 && (1ull << l) < 2 * overlap_voxels(c)) ++l;
+    return l;
+}
+
+// the automatic table: a slot per 512 voxels (two Voronoi frames hold a pair per ~3000 voxels), 2^16 .. 2^24 slots
+int overlap_auto_log2(const ta_ctx* c) {
+    int l = 16;
+    while (l < 24 && (1ull << l) < overlap_voxels(c) / 512) ++l;
+    return l;
+}
+
+// clear a table of 2^ov_log2 slots and enqueue the pass, then the count and the scan of its occupied slots
+int overlap_launch(ta_ctx* c) {
+    const uint64_t slots = 1ull << c->ov.log2, blocks = ta::overlap_compact_blocks(slots);
+    int rc;
+    if ((rc = c->ov.table.reserve(slots * 16)) != TA_OK) return rc;
+    if ((rc = c->ov.small.reserve(32)) != TA_OK) return rc;
+    const uint64_t offsets_at = align16(blocks * 4), scratch_at = offsets_at + blocks * 8;
+    if ((rc = c->ov.work.reserve(scratch_at + ta::scan_u32_scratch_bytes(blocks))) != TA_OK) return rc;
+    if ((rc = ensure_events(c->ov.ev)) != TA_OK) return rc;
+    ta::OverlapArgs a;
+    a.a = c->vol;                  // (the ids as the caller stored them: never the rank copy of a compacted context)
+    a.b = c->ov.b.p;
+    a.n0 = c->mdims[0]; a.n1 = c->mdims[1]; a.n2 = c->mdims[2];
+    a.first_owned = c->first_owned;
+    a.keys = (unsigned long long*)c->ov.table.p;
+    a.counts = a.keys + slots;
+    a.mask = (uint32_t)(slots - 1);
+    a.flags = (uint32_t*)c->ov.small.p;
+    a.top = (unsigned long long*)((char*)c->ov.small.p + 16);
+    a.tiles_per_group = 0;
+    TA_HIP(hipMemsetAsync(a.keys, 0xff, slots * 8, c->stream));
+    TA_HIP(hipMemsetAsync(a.counts, 0, slots * 8, c->stream));
+    TA_HIP(hipMemsetAsync(c->ov.small.p, 0, 32, c->stream));
+    TA_HIP(hipEventRecord(c->ov.ev[0], c->stream));
+    ta::launch_overlap(c->stream, a, c->itemsize, c->ov.b.itemsize);
+    TA_HIP(hipGetLastError());
+    TA_HIP(hipEventRecord(c->ov.ev[1], c->stream));
+    char* w = (char*)c->ov.work.p;
+    ta::launch_overlap_count(c->stream, a.keys, slots, (uint32_t*)w);
+    ta::launch_scan_u32_exclusive(c->stream, (const uint32_t*)w, blocks, w + scratch_at, (uint64_t*)(w + offsets_at));
+    TA_HIP(hipGetLastError());
+    TA_HIP(hipEventRecord(c->ov.ev[2], c->stream));
+    c->ov.passes += 1;
+    return TA_OK;
+}
+
+// drain the stream; a table that overflowed is grown and the pass repeated; then the occupied slots become the sorted rows
+int overlap_settle(ta_ctx* c) {
+    if (c->ov.state == 2) return TA_OK;
+    if (c->ov.state != 1) return fail(TA_EINVAL, "no overlap table for the current volume and B (run ta_overlap_extract)");
+    int rc;
+    uint64_t occupied = 0, top = 0;
+    for (;;) {
+        const uint64_t slots = 1ull << c->ov.log2, blocks = ta::overlap_compact_blocks(slots);
+        const uint64_t scratch_at = align16(blocks * 4) + blocks * 8;
+        uint32_t small[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        TA_HIP(hipMemcpyAsync(small, c->ov.small.p, sizeof(small), hipMemcpyDeviceToHost, c->stream));
+        TA_HIP(hipMemcpyAsync(&occupied, ta::scan_u32_total((char*)c->ov.work.p + scratch_at, blocks), 8, hipMemcpyDeviceToHost, c->stream));
+        TA_HIP(hipStreamSynchronize(c->stream));
+        memcpy(&top, &small[4], 8);
+        if (!small[ta::OV_FLAG_OVERFLOW]) break;
+        const int most = overlap_top_log2(c);
+        if (c->ov.log2 >= most) {
+            c->ov.state = 0;
+            return fail(TA_ENOMEM, "the overlap table overflowed at its largest size (2^%d slots)", c->ov.log2);
+        }
+        c->ov.log2 = std::min(c->ov.log2 + 3, most);
+        if (!c->ov.opt_log2) c->ov.grown_log2 = c->ov.log2;
+        if ((rc = overlap_launch(c)) != TA_OK) { c->ov.state = 0; return rc; }
+    }
+    const uint64_t slots = 1ull << c->ov.log2, blocks = ta::overlap_compact_blocks(slots);
+    const uint64_t offsets_at = align16(blocks * 4);
+    const uint64_t P = occupied + (top ? 1 : 0);
+    const uint64_t n = occupied;
+    const SortLayout S(n, 8);
+    if ((rc = c->ov.sort.reserve(S.end + 16)) != TA_OK) return rc;
+    if ((rc = c->ov.rows.reserve(P * 16 + 16)) != TA_OK) return rc;
+    char* q = (char*)c->ov.sort.p;
+    uint64_t* k0 = (uint64_t*)(q + S.keys[0]); uint64_t* k1 = (uint64_t*)(q + S.keys[1]);
+    uint32_t* i0 = (uint32_t*)(q + S.idx[0]); uint32_t* i1 = (uint32_t*)(q + S.idx[1]);
+    void* temp = q + S.temp;
+    const unsigned long long* keys = (const unsigned long long*)c->ov.table.p;
+    const int shift_b = 8 * c->ov.b.itemsize;
+    TA_HIP(hipEventRecord(c->ov.ev[3], c->stream));
+    ta::launch_overlap_emit(c->stream, keys, slots, (const uint64_t*)((char*)c->ov.work.p + offsets_at), shift_b, k0, i0);
+    uint64_t* ks = k0; uint32_t* is = i0;
+    TA_HIP(ta::launch_radix_sort_u64(c->stream, n, k0, k1, i0, i1, temp, 8 * c->itemsize + shift_b, &ks, &is));
+    uint32_t* ra = (uint32_t*)c->ov.rows.p;
+    ta::launch_overlap_rows(c->stream, ks, is, n, keys + slots, shift_b, top, ra, ra + P, (uint64_t*)(ra + 2 * P));
+    TA_HIP(hipGetLastError());
+    TA_HIP(hipEventRecord(c->ov.ev[4], c->stream));
+    TA_HIP(hipStreamSynchronize(c->stream));
+    c->ov.npairs = P;
+    c->ov.state = 2;
+    return TA_OK;
+}
+
+}  // namespace
+
+// a new label volume (or new label values in it): the overlap table is stale; a B of other dims is dropped
+void overlap_on_new_volume(ta_ctx* c) {
+    c->ov.state = 0;
+    c->ov.grown_log2 = 0;
+    companion_on_new_volume(c, c->ov.b);
+}
+
+extern "C" {
+
+TA_API int ta_overlap_set(ta_ctx* c, const void* host_ptr, int itemsize, const int64_t dims[3], const int64_t strides_bytes[3]) {
+    if (!c) return fail(TA_EINVAL, "ctx is NULL");
+    const int rc = companion_set_host(c, c->ov.b, B_VOLUME, host_ptr, itemsize, dims, strides_bytes);
+    if (rc == TA_OK || !c->ov.b.p) c->ov.state = 0;      // (also when the upload failed and left no B -- a table implies a B: deliberate, as inherited)
+    return rc;
+}
+
+TA_API int ta_overlap_set_device(ta_ctx* c, const void* dev_ptr, int itemsize) {
+    if (!c) return fail(TA_EINVAL, "ctx is NULL");
+    const int rc = companion_set_device(c, c->ov.b, B_VOLUME, dev_ptr, itemsize);
+    if (rc == TA_OK) c->ov.state = 0;
+    return rc;
+}
+
+TA_API int ta_overlap_set_capacity(ta_ctx* c, int log2_slots) {
+    if (!c) return fail(TA_EINVAL, "ctx is NULL");
+    if (log2_slots != 0 && (log2_slots < OV_MIN_LOG2 || log2_slots > OV_MAX_LOG2))
+        return fail(TA_EINVAL, "the overlap table takes 2^%d .. 2^%d slots, or 0 for an automatic size", OV_MIN_LOG2, OV_MAX_LOG2);
+    c->ov.opt_log2 = log2_slots;
+    c->ov.grown_log2 = 0;
+    return TA_OK;
+}
+
+TA_API int ta_overlap_extract(ta_ctx* c) {
+    if (!c) return fail(TA_EINVAL, "ctx is NULL");
+    if (!c->vol) return fail(TA_EINVAL, "no label volume set");
+    if (!c->ov.b.p) return fail(TA_EINVAL, "no second label volume set (ta_overlap_set)");
+    if (!companion_matches(c, c->ov.b)) return fail(TA_EINVAL, "B does not match the label volume");
+    int rc = use_device(c);
+    if (rc != TA_OK) return rc;
+    c->ov.state = 0;
+    c->ov.passes = 0;
+    c->ov.log2 = c->ov.opt_log2 ? c->ov.opt_log2 : std::max(overlap_auto_log2(c), c->ov.grown_log2);
+    if ((rc = overlap_launch(c)) != TA_OK) return rc;
+    c->ov.state = 1;
+    return TA_OK;
+}
+
+TA_API int ta_overlap_size(ta_ctx* c, uint64_t* npairs) {
+    if (!c) return fail(TA_EINVAL, "ctx is NULL");
+    if (!npairs) return fail(TA_EINVAL, "NULL argument");
+    if (c->ov.state == 0) return fail(TA_EINVAL, "no overlap table for the current volume and B (run ta_overlap_extract)");
+    int rc = use_device(c);
+    if (rc != TA_OK) return rc;
+    if ((rc = overlap_settle(c)) != TA_OK) return rc;
+    *npairs = c->ov.npairs;
+    return TA_OK;
+}
+
+TA_API int ta_overlap_get(ta_ctx* c, uint32_t* a, uint32_t* b, uint64_t* n) {
+    if (!c) return fail(TA_EINVAL, "ctx is NULL");
+    if (c->ov.state == 0) return fail(TA_EINVAL, "no overlap table for the current volume and B (run ta_overlap_extract)");
+    int rc = use_device(c);
+    if (rc != TA_OK) return rc;
+    if ((rc = overlap_settle(c)) != TA_OK) return rc;
+    const uint64_t P = c->ov.npairs;
+    if (!P) return TA_OK;
+    const uint32_t* ra = (const uint32_t*)c->ov.rows.p;
+    if (a) TA_HIP(hipMemcpyAsync(a, ra, 4 * P, hipMemcpyDeviceToHost, c->stream));
+    if (b) TA_HIP(hipMemcpyAsync(b, ra + P, 4 * P, hipMemcpyDeviceToHost, c->stream));
+    if (n) TA_HIP(hipMemcpyAsync(n, ra + 2 * P, 8 * P, hipMemcpyDeviceToHost, c->stream));
+    TA_HIP(hipStreamSynchronize(c->stream));
+    return TA_OK;
+}
+
+TA_API int ta_overlap_timing(ta_ctx* c, double* ms) {
+    if (!c) return fail(TA_EINVAL, "ctx is NULL");
+    if (!ms) return fail(TA_EINVAL, "NULL argument");
+    if (c->ov.state == 0 || !c->ov.ev[1]) return fail(TA_EINVAL, "no overlap pass has been run");
+    int rc = use_device(c);
+    if (rc != TA_OK) return rc;
+    TA_HIP(hipEventSynchronize(c->ov.ev[1]));
+    return elapsed_ms(c->ov.ev[0], c->ov.ev[1], ms);
+}
+
+TA_API int ta_overlap_timing_compaction(ta_ctx* c, double* ms, int* passes) {
+    if (!c) return fail(TA_EINVAL, "ctx is NULL");
+    if (!ms) return fail(TA_EINVAL, "NULL argument");
+    if (c->ov.state != 2) return fail(TA_EINVAL, "no settled overlap table (ask ta_overlap_size first)");
+    int rc = use_device(c);
+    if (rc != TA_OK) return rc;
+    TA_HIP(hipEventSynchronize(c->ov.ev[4]));
+    double t0 = 0.0, t1 = 0.0;
+    if ((rc = elapsed_ms(c->ov.ev[1], c->ov.ev[2], &t0)) != TA_OK || (rc = elapsed_ms(c->ov.ev[3], c->ov.ev[4], &t1)) != TA_OK) return rc;
+    *ms = t0 + t1;
+    if (passes) *passes = c->ov.passes;
+    return TA_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,161 @@
+// ta_api_signal.hip -- the C ABI of include/tissue_scan_signal.h on top of kernels_signal.hip.
+#include "../../include/tissue_scan_signal.h"
+#include "ta_ctx.h"
+#include "ta_signal.h"
+
+namespace {
+
+constexpr CompanionKind SIGNAL = {"the signal", 1, 2};      // uint8 or uint16
+
+bool signal_current(const ta_ctx* c) { return c->sig.seq != 0 && c->extracted && c->sig.seq == c->extract_seq; }
+
+// byte offsets of the parts of SignalState::out for R rows and P pairs
+struct SignalLayout {
+    uint64_t flags = 0, n, sum, sumsq, vmin, vmax, side_lo, side_hi, bytes;
+    SignalLayout(uint64_t R, uint64_t P) {
+        n = 16; sum = n + 8 * R; sumsq = sum + 8 * R; vmin = sumsq + 16 * R; vmax = vmin + 4 * R;
+        side_lo = vmax + 4 * R; side_hi = side_lo + 8 * P; bytes = side_hi + 8 * P;
+    }
+};
+
+// drain the stream and look at the pass's flag words
+int signal_finish(ta_ctx* c) {
+    uint32_t flags[ta::SIG_NFLAGS] = {0, 0, 0, 0};
+    TA_HIP(hipMemcpyAsync(flags, c->sig.out.p, sizeof(flags), hipMemcpyDeviceToHost, c->stream));
+    TA_HIP(hipStreamSynchronize(c->stream));
+    if (flags[ta::SIG_FLAG_RANGE]) return fail(TA_ERANGE, "the signal pass met a label above max_label=%u (the volume changed since ta_extract)", c->max_label);
+    if (flags[ta::SIG_FLAG_PAIR_MISS]) return fail(TA_ERANGE, "the signal pass met a pair the extraction does not hold (the volume changed since ta_extract)");
+    return TA_OK;
+}
+
+}  // namespace
+
+// a new label volume: the signal results are stale (extracted is false); a signal of other dims is dropped
+void signal_on_new_volume(ta_ctx* c) {
+    c->sig.seq = 0;
+    companion_on_new_volume(c, c->sig.img);
+}
+
+extern "C" {
+
+TA_API int ta_signal_set(ta_ctx* c, const void* host_ptr, int itemsize, const int64_t dims[3], const int64_t strides_bytes[3]) {
+    if (!c) return fail(TA_EINVAL, "ctx is NULL");
+    const int rc = companion_set_host(c, c->sig.img, SIGNAL, host_ptr, itemsize, dims, strides_bytes);
+    if (rc == TA_OK) c->sig.seq = 0;             // (the results are stale only once a new signal is in place: deliberate, as inherited)
+    return rc;
+}
+
+TA_API int ta_signal_set_device(ta_ctx* c, const void* dev_ptr, int itemsize) {
+    if (!c) return fail(TA_EINVAL, "ctx is NULL");
+    const int rc = companion_set_device(c, c->sig.img, SIGNAL, dev_ptr, itemsize);
+    if (rc == TA_OK) c->sig.seq = 0;
+    return rc;
+}
+
+TA_API int ta_signal_extract(ta_ctx* c, uint32_t what) {
+    if (!c) return fail(TA_EINVAL, "ctx is NULL");
+    if (what == 0 || (what & ~(TA_SIG_LABELS | TA_SIG_WALLS))) return fail(TA_EINVAL, "bad signal mask 0x%x", what);
+    if (!c->sig.img.p) return fail(TA_EINVAL, "no signal set");
+    if (!c->vol || !companion_matches(c, c->sig.img)) return fail(TA_EINVAL, "the signal does not match the label volume");
+    int rc = use_device(c);
+    if (rc != TA_OK) return rc;
+    if (!c->extracted) return fail(TA_EINVAL, "the signal pass needs a ta_extract of the current volume first");
+    if ((rc = finish_extract(c)) != TA_OK) return rc;
+    const bool walls = what & TA_SIG_WALLS;
+    if (walls && !(c->feature_mask & TA_F_ADJACENCY)) return fail(TA_EINVAL, "TA_SIG_WALLS needs an extraction with TA_F_ADJACENCY");
+    if (walls && c->exchanged) return fail(TA_EINVAL, "TA_SIG_WALLS needs this context's own pair list (not a merged one)");
+    const uint64_t R = (uint64_t)c->max_label + 1, P = walls ? (uint64_t)c->npairs : 0;
+    const SignalLayout L(R, P);
+    if ((rc = c->sig.out.reserve(L.bytes)) != TA_OK) return rc;
+    if ((rc = ensure_events(c->sig.ev)) != TA_OK) return rc;
+    ta::SignalArgs a;
+    a.hkeys = nullptr; a.hrows = nullptr; a.hmask = 0;
+    if (walls && P) {
+        // pair -> row: an open-addressed table of the sorted pair list (ta_adjacency_get sorts it on the device once per extraction)
+        if ((rc = ta_adjacency_get(c, nullptr, nullptr, nullptr)) != TA_OK) return rc;
+        uint64_t cap = 64;
+        while (cap < 2 * P) cap <<= 1;
+        if (cap > (1ull << 32)) return fail(TA_EINVAL, "too many pairs (%llu)", (unsigned long long)P);
+        if ((rc = c->sig.hash.reserve(cap * 12 + P * 8)) != TA_OK) return rc;
+        uint64_t* hkeys = (uint64_t*)c->sig.hash.p;
+        uint64_t* sorted = hkeys + cap;
+        uint32_t* hrows = (uint32_t*)(sorted + P);
+        TA_HIP(hipMemsetAsync(hkeys, 0xff, cap * 8, c->stream));
+        TA_HIP(hipMemcpyAsync(sorted, c->h_pairs.p, P * 8, hipMemcpyHostToDevice, c->stream));
+        ta::launch_signal_hash(c->stream, sorted, P, hkeys, hrows, (uint32_t)(cap - 1));
+        a.hkeys = hkeys; a.hrows = hrows; a.hmask = (uint32_t)(cap - 1);
+    }
+    char* o = (char*)c->sig.out.p;
+    TA_HIP(hipMemsetAsync(o, 0, L.bytes, c->stream));
+    TA_HIP(hipMemsetAsync(o + L.vmin, 0xff, 4 * R, c->stream));
+    a.vol = sweep_vol(c);
+    a.sig = c->sig.img.p;
+    a.n0 = c->mdims[0]; a.n1 = c->mdims[1]; a.n2 = c->mdims[2];
+    a.first_owned = c->first_owned;
+    a.max_label = c->max_label;
+    a.n = (unsigned long long*)(o + L.n);
+    a.sum = (unsigned long long*)(o + L.sum);
+    a.sumsq = (unsigned long long*)(o + L.sumsq);
+    a.vmin = (uint32_t*)(o + L.vmin);
+    a.vmax = (uint32_t*)(o + L.vmax);
+    a.side_lo = (unsigned long long*)(o + L.side_lo);
+    a.side_hi = (unsigned long long*)(o + L.side_hi);
+    a.flags = (uint32_t*)o;
+    a.tiles_per_group = 0;
+    TA_HIP(hipEventRecord(c->sig.ev[0], c->stream));
+    ta::launch_signal(c->stream, a, c->itemsize, c->sig.img.itemsize, (what & TA_SIG_LABELS ? ta::SIG_LABELS : 0u) | (walls ? ta::SIG_WALLS : 0u));
+    TA_HIP(hipGetLastError());
+    TA_HIP(hipEventRecord(c->sig.ev[1], c->stream));
+    c->sig.seq = c->extract_seq;
+    c->sig.what = what;
+    c->sig.rows = (uint32_t)R;
+    c->sig.npairs = (int64_t)P;
+    return TA_OK;
+}
+
+TA_API int ta_signal_get_labels(ta_ctx* c, uint64_t* n, uint64_t* sum, uint64_t* sumsq, uint32_t* vmin, uint32_t* vmax) {
+    if (!c) return fail(TA_EINVAL, "ctx is NULL");
+    if (!signal_current(c) || !(c->sig.what & TA_SIG_LABELS))
+        return fail(TA_EINVAL, "no per-label signal results for the current extraction (run ta_signal_extract with TA_SIG_LABELS)");
+    int rc = use_device(c);
+    if (rc != TA_OK) return rc;
+    if ((rc = signal_finish(c)) != TA_OK) return rc;
+    const uint64_t R = c->sig.rows;
+    const SignalLayout L(R, (uint64_t)c->sig.npairs);
+    const char* o = (const char*)c->sig.out.p;
+    if (n) TA_HIP(hipMemcpyAsync(n, o + L.n, 8 * R, hipMemcpyDeviceToHost, c->stream));
+    if (sum) TA_HIP(hipMemcpyAsync(sum, o + L.sum, 8 * R, hipMemcpyDeviceToHost, c->stream));
+    if (sumsq) TA_HIP(hipMemcpyAsync(sumsq, o + L.sumsq, 16 * R, hipMemcpyDeviceToHost, c->stream));
+    if (vmin) TA_HIP(hipMemcpyAsync(vmin, o + L.vmin, 4 * R, hipMemcpyDeviceToHost, c->stream));
+    if (vmax) TA_HIP(hipMemcpyAsync(vmax, o + L.vmax, 4 * R, hipMemcpyDeviceToHost, c->stream));
+    TA_HIP(hipStreamSynchronize(c->stream));
+    return TA_OK;
+}
+
+TA_API int ta_signal_get_walls(ta_ctx* c, uint64_t* side_lo, uint64_t* side_hi) {
+    if (!c) return fail(TA_EINVAL, "ctx is NULL");
+    if (!signal_current(c) || !(c->sig.what & TA_SIG_WALLS) || c->exchanged)
+        return fail(TA_EINVAL, "no per-wall signal results for the current extraction (run ta_signal_extract with TA_SIG_WALLS)");
+    int rc = use_device(c);
+    if (rc != TA_OK) return rc;
+    if ((rc = signal_finish(c)) != TA_OK) return rc;
+    const uint64_t P = (uint64_t)c->sig.npairs;
+    const SignalLayout L(c->sig.rows, P);
+    const char* o = (const char*)c->sig.out.p;
+    if (side_lo && P) TA_HIP(hipMemcpyAsync(side_lo, o + L.side_lo, 8 * P, hipMemcpyDeviceToHost, c->stream));
+    if (side_hi && P) TA_HIP(hipMemcpyAsync(side_hi, o + L.side_hi, 8 * P, hipMemcpyDeviceToHost, c->stream));
+    TA_HIP(hipStreamSynchronize(c->stream));
+    return TA_OK;
+}
+
+TA_API int ta_signal_timing(ta_ctx* c, double* ms) {
+    if (!c) return fail(TA_EINVAL, "ctx is NULL");
+    if (!ms) return fail(TA_EINVAL, "NULL argument");
+    if (c->sig.seq == 0 || !c->sig.ev[1]) return fail(TA_EINVAL, "no signal pass has been run");
+    int rc = use_device(c);
+    if (rc != TA_OK) return rc;
+    TA_HIP(hipEventSynchronize(c->sig.ev[1]));
+    return elapsed_ms(c->sig.ev[0], c->sig.ev[1], ms);
+}
+
+}  // extern "C"

@@ -1,0 +1,249 @@
+// ta_ctx.h -- the context behind the C ABI and what the ta_api*.hip files share (host only, private to csrc/).  ta_api.hip holds
+// the core and defines what is declared here; a feature has one struct of state below and its entry points in ta_api_<feature>.hip.
+#pragma once
+#include "../../include/tissue_scan.h"
+#include "ta_kernels.h"
+
+#include <algorithm>
+#include <cstring>
+#include <string>
+#include <vector>
+
+// sets the calling thread's ta_last_error and returns `code`
+int fail(int code, const char* fmt, ...);
+
+#define TA_HIP(expr)                                                                         \
+    do {                                                                                     \
+        hipError_t e_ = (expr);                                                              \
+        if (e_ != hipSuccess)                                                                \
+            return fail(e_ == hipErrorOutOfMemory ? TA_ENOMEM : TA_EHIP, "%s: %s (%s:%d)",  \
+                        #expr, hipGetErrorString(e_), __FILE__, __LINE__);                   \
+    } while (0)
+
+// grow-only device memory (DevBuf), or page-locked host memory (PinnedBuf): device-to-host copies into it run at PCIe speed, into a
+// std::vector they are staged
+template <bool PINNED> struct Buf {
+    void* p = nullptr;
+    uint64_t bytes = 0;
+    int reserve(uint64_t need) {
+        if (need <= bytes) return TA_OK;
+        release();
+        if ((PINNED ? hipHostMalloc(&p, need ? need : 16, hipHostMallocDefault) : hipMalloc(&p, need ? need : 16)) != hipSuccess) {
+            (void)hipGetLastError();
+            p = nullptr;
+            return fail(TA_ENOMEM, "%s of %llu bytes failed", PINNED ? "hipHostMalloc" : "hipMalloc", (unsigned long long)need);
+        }
+        bytes = need;
+        return TA_OK;
+    }
+    void release() { if (p) (void)(PINNED ? hipHostFree(p) : hipFree(p)); p = nullptr; bytes = 0; }
+};
+using DevBuf = Buf<false>;
+using PinnedBuf = Buf<true>;
+
+inline uint64_t align16(uint64_t b) { return (b + 15) & ~15ull; }
+
+// the events of a feature: created at its first pass, destroyed by its release()
+template <size_t N> int ensure_events(hipEvent_t (&ev)[N]) {
+    for (auto& e : ev) if (!e) TA_HIP(hipEventCreate(&e));
+    return TA_OK;
+}
+template <size_t N> void destroy_events(hipEvent_t (&ev)[N]) { for (auto& e : ev) if (e) (void)hipEventDestroy(e); }
+inline int elapsed_ms(hipEvent_t a, hipEvent_t b, double* ms) {       // (both recorded and complete)
+    float t = 0.f;
+    TA_HIP(hipEventElapsedTime(&t, a, b));
+    *ms = (double)t;
+    return TA_OK;
+}
+
+// the workspace of launch_radix_sort_u32 / _u64 for n records, as byte offsets from `at`: keys (of key_bytes) x 2 | index u32 x 2 | temp
+struct SortLayout {
+    uint64_t keys[2], idx[2], temp, end;
+    SortLayout(uint64_t n, int key_bytes, uint64_t at = 0) {
+        for (auto& k : keys) { k = at; at += align16(n * key_bytes); }
+        for (auto& i : idx) { i = at; at += align16(n * 4); }
+        temp = at; end = at + align16(ta::wall_sort_temp_bytes(n));
+    }
+};
+
+// A companion volume: a second volume with the buffer dims and layout of the label volume (the signal image, the overlap's B).
+struct Companion {
+    const void* p = nullptr;                            // device pointer (owned.p or adopted), NULL = none
+    DevBuf owned;
+    int itemsize = 0;
+    int64_t mdims[3] = {0, 0, 0};                       // the label buffer dims it was set for
+};
+struct CompanionKind { const char* noun; int size_a, size_b; };      // what the messages call it; the item sizes it takes
+
+// signal image (include/tissue_scan_signal.h)
+struct SignalState {
+    Companion img;
+    DevBuf out;                                         // flags u32[4] | n | sum | sumsq[2] | min | max | side_lo | side_hi
+    DevBuf hash;                                        // pair -> row table of the sorted pair list: keys u64[cap] | rows u32[cap]
+    uint64_t seq = 0;                                   // extract_seq of the extraction the results belong to, 0 = none
+    uint32_t what = 0;
+    uint32_t rows = 0;                                  // max_label + 1 of that extraction
+    int64_t npairs = 0;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    void release() { img.owned.release(); out.release(); hash.release(); destroy_events(ev); }
+};
+
+// cell meshes (include/tissue_scan_mesh.h)
+struct MeshState {
+    DevBuf small;                                       // flags u32[4] | wanted u8[R] | per-wave counts and offsets | scan scratch
+    DevBuf work;                                        // face records u64[F] | neighbours u32[F] | corners u64[V] | sort keys, values x 2 | sort temp
+    DevBuf out;                                         // vertex corners u64[V] | vbeg, vend, fbeg, fend u64[R] | triangles u32[2F][3] | cell, neighbour u32[2F]
+    uint64_t seq = 0;                                   // extract_seq of the extraction the mesh belongs to, 0 = none
+    uint64_t faces = 0, verts = 0;
+    uint32_t rows = 0;
+    int64_t m[3] = {0, 0, 0};                           // dims of the meshed image, memory order
+    bool host_ready = false;                            // cells and CSR offsets below are read back
+    std::vector<uint32_t> cells;
+    std::vector<uint64_t> voff, toff;
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    void release() { small.release(); work.release(); out.release(); destroy_events(ev); }
+};
+
+// label overlap with a second label volume B (include/tissue_scan_overlap.h)
+struct OverlapState {
+    Companion b;
+    DevBuf table;                                       // the device-global pair table: keys u64[slots] | counts u64[slots]
+    DevBuf small;                                       // flags u32[4] | voxels of the pair (2^32 - 1, 2^32 - 1) u64
+    DevBuf work;                                        // compaction: block counts u32[B] | block offsets u64[B] | scan scratch
+    DevBuf sort;                                        // sort keys u64[P] x 2 | slots u32[P] x 2 | radix temp
+    DevBuf rows;                                        // the sorted table: a u32[P] | b u32[P] | n u64[P]
+    int opt_log2 = 0;                                   // ta_overlap_set_capacity: 0 = automatic
+    int grown_log2 = 0;                                 // what an automatic table of this volume had to grow to
+    int log2 = 0;                                       // slots of the table of the pass in flight
+    int state = 0;                                      // 0 = no table, 1 = pass enqueued, 2 = settled (rows holds npairs rows)
+    int passes = 0;                                     // runs of the pass kernel for this table
+    uint64_t npairs = 0;
+    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // pass begin, end | count + scan end | emit begin, rows end
+    void release() { b.owned.release(); table.release(); small.release(); work.release(); sort.release(); rows.release(); destroy_events(ev); }
+};
+
+// cell junctions (include/tissue_scan_junctions.h): index 0 = edges (3 labels), 1 = vertices (4 labels)
+struct JunctionState {
+    DevBuf small;                                       // blocks of order >= 5 u64
+    DevBuf work;                                        // per wave: counts u32[W] x 2 | offsets u64[W] x 2 | scan scratch x 2
+    DevBuf rec;                                         // records: origins u64[N3] | origins u64[N4] | labels u32[N3][3] | labels u32[N4][4]
+    DevBuf sort[2];                                     // sort keys u64[N] x 2 | order u32[N] x 2 | radix temp | row counts, offsets, scan scratch
+    DevBuf rows[2];                                     // the table: n u64[R] | sums u64[R][3] | labels u32[R][K]
+    int state = 0;                                      // 0 = no tables, 1 = counting walk enqueued, 2 = settled
+    uint64_t waves = 0;                                 // waves (= tasks) of a walk
+    uint64_t nrows[2] = {0, 0}, degenerate = 0;
+    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // count begin, end | scans end | emit begin, end | tables end
+    void release() { small.release(); work.release(); rec.release(); for (int k = 0; k < 2; ++k) { sort[k].release(); rows[k].release(); } destroy_events(ev); }
+};
+
+struct ta_ctx {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    bool own_stream = false;
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};   // [0] step begin, [3] step end (TA_OPT_TIMING = 2 only)
+    std::vector<hipEvent_t> ring;                       // 2 events per slot around the sweep kernel of the last `ring.size()/2` extractions
+    int timing = 1;                                     // TA_OPT_TIMING
+    uint64_t extract_seq = 0, ring_since = 0;           // extractions run; the one the ring's oldest valid slot belongs to
+
+    // resident volume
+    const void* vol = nullptr;       // device pointer (owned_vol.p or adopted)
+    DevBuf owned_vol;
+    int itemsize = 0;
+    int64_t mdims[3] = {0, 0, 0};    // buffer dims in memory-axis order
+    int perm[3] = {0, 1, 2};         // perm[k] = array axis of memory axis k
+    int64_t a_origin = 0;
+    int first_owned = 0;
+
+    // sparse label ids: the census of the volume's ids and the copy of the volume in their ranks (what the sweep then reads)
+    DevBuf census, census_ids, compact_vol, census_list;      // (census_list: the label list of the one-pass census, ~n / 256 entries)
+    uint32_t census_max = 0;            // ids 0 .. census_max have a bit
+    int64_t census_n = -1;              // ids present, -1 = no census
+    int64_t vol_max = -1;               // largest label of the resident buffer (halo included), -1 = not known
+    bool compact = false;               // per-label ROWS are ranks 0 .. census_n - 1; every label VALUE handed out is an id
+    bool census_of_volume = false;      // the census on the context was taken from THIS volume (not a caller's id list)
+    bool rerank_check = false;          // ta_volume_rerank's "id not in the list" word has not been looked at yet
+    std::vector<uint32_t> h_ids;        // rank -> id (host copy, compact mode)
+
+    // accumulators
+    DevBuf own_sums, own_boxes;
+    uint64_t* sums = nullptr;
+    int32_t* boxes = nullptr;
+    bool bound = false;
+    uint32_t bound_max_label = 0;
+    uint32_t max_label = 0;
+
+    // adjacency
+    DevBuf pkeys, pfaces, out_keys, out_faces, small;   // small: flags[NFLAGS] | cursor | maxlabel
+    DevBuf hot_rows;                                    // [workgroups][16] private rows of the hot label
+    DevBuf sort_buf;                                    // scratch of ta_adjacency_get's device sort (kept between calls)
+    DevBuf wall_counts;                                 // wall voxels: per-chunk record counts, then offsets
+    DevBuf wall_stage;                                  // wall voxels: the records the count pass staged (kept until the volume changes)
+    int64_t wall_records = -1;                          // result of the last ta_wall_voxels_count, -1 = none
+    uint32_t wall_region = 0, wall_not_staged = 0;      // records per staging region of that call (0 = nothing staged); cells left to the second walk
+    DevBuf wall_medians;                                // ta_wall_medians: pairs u32[E][2] | sizes u32[E] | medians i32[E][3]
+    int64_t wall_median_count = -1;                     // E of the last ta_wall_medians, -1 = none
+    bool wall_wide = false;                             // that call met a label >= 2^31
+    uint32_t wall_label_or = 0;                         // OR of all labels of the volume (that call): the bits a label takes
+    double wall_ms = 0.0;
+    int pair_log2 = 0;                                  // current table log2 capacity
+    int opt_pair_log2 = 0;
+    bool table_clean = false;
+    uint32_t* h_small = nullptr;                        // pinned, device-mapped mirror of `small`
+    uint32_t* h_small_dev = nullptr;                    // its device address: the last kernel of a step writes it
+
+    // options / state
+    int impl = 0;
+    int tile_planes = 0;
+    // the tile shape of the sweep of a uint32 volume with adjacency (kernels_scan.hip): both give the same results; which one
+    // is faster depends on the tissue (background around it: the wide one; cells everywhere: the narrow one), so the first four
+    // sweeps of a volume take turns (wide, narrow, wide, narrow) between two events each, and the faster shape keeps the volume
+    int opt_shape = -1;                                 // TA_OPT_SWEEP_SHAPE: -1 = measure, 0 / 1 = as told
+    int shape_pick = -1;                                // choice for this volume, -1 = not yet
+    double shape_density = -1.0;                        // label changes per voxel in the sampled planes (what decided it), -1 = not measured
+    int last_shape = 0;                                 // TA_OPT_SWEEP_SHAPE_USED: the shape of the last sweep
+    int tune_launched = 0;                              // measuring sweeps launched (0 .. 4)
+    hipEvent_t tune_ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    bool tune_done[4] = {false, false, false, false};
+    float tune_ms[4] = {0.f, 0.f, 0.f, 0.f};
+    int64_t volume_slack = 0;                           // TA_OPT_VOLUME_SLACK: bytes readable behind an adopted volume
+    int auto_tile_shift = 0;                            // automatic tile height halved this many times (table spills seen)
+    uint64_t last_grid = 0;                             // workgroups of the last sweep
+    uint32_t feature_mask = 0;
+    bool extracted = false, checked = false;
+    bool exchanged = false;                             // adjacency rebuilt by ta_adjacency_merge_blocks
+    bool shared_packed = false;                         // ... from ta_adjacency_pack_shared blocks: the list is PARTIAL
+    bool reduced = false;                               // the bound accumulators hold other ranks' contributions too
+    int64_t npairs = 0;
+    PinnedBuf h_pairs;                                  // sorted host copy for ta_adjacency_get: keys u64[n], then faces u64[n][3]
+    bool host_pairs_ready = false;
+
+    // the features: each one's state is read and written by its own ta_api_<feature>.hip only
+    SignalState sig;
+    MeshState mesh;
+    OverlapState ov;
+    JunctionState jn;
+};
+
+inline int use_device(ta_ctx* c) {
+    TA_HIP(hipSetDevice(c->device));
+    return TA_OK;
+}
+
+// the volume the sweep reads: the rank copy in compact mode
+inline const void* sweep_vol(const ta_ctx* c) { return c->compact ? c->compact_vol.p : c->vol; }
+
+// Drain the stream and validate the flags of the last pass; grows the adjacency table and re-runs when it overflowed.
+int finish_extract(ta_ctx* c);
+
+// A new label volume (for the overlap and the junctions also: new label values in it).  Defined by the features, called by the core.
+void signal_on_new_volume(ta_ctx* c);
+void overlap_on_new_volume(ta_ctx* c);
+void junctions_on_new_volume(ta_ctx* c);
+
+// Companions: these touch the companion's own fields only.  The setters check the arguments against the label volume and drain the
+// stream (a pass in flight may still read the old companion) before they change anything; a failure later leaves no companion set.
+int companion_set_host(ta_ctx* c, Companion& v, const CompanionKind& kind, const void* host_ptr, int itemsize, const int64_t dims[3],
+                       const int64_t strides_bytes[3]);
+int companion_set_device(ta_ctx* c, Companion& v, const CompanionKind& kind, const void* dev_ptr, int itemsize);
+inline bool companion_matches(const ta_ctx* c, const Companion& v) { return std::equal(v.mdims, v.mdims + 3, c->mdims); }   // set for these dims
+void companion_on_new_volume(const ta_ctx* c, Companion& v);      // ... or dropped

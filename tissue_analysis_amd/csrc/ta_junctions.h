@@ -52,8 +52,4 @@ struct JunctionRows {
 void launch_junction_reduce(hipStream_t s, const uint32_t* labels, const uint64_t* origins, int K, const uint32_t* order, uint64_t n,
                             const uint64_t* block_offsets, const JunctionRows& rows);
 
-// kernels_wallsort.hip: the stable LSD radix sort on 64-bit keys of key_bits bits with a u32 value each (n < 2^32)
-hipError_t launch_radix_sort_u64(hipStream_t s, uint64_t n, uint64_t* keys0, uint64_t* keys1, uint32_t* idx0, uint32_t* idx1,
-                                 void* temp, int key_bits, uint64_t** keys_out, uint32_t** idx_out);
-
 }  // namespace ta

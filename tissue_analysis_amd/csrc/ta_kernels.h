@@ -73,6 +73,13 @@ hipError_t launch_wall_group_by_pair(hipStream_t s, const uint32_t* pairs, const
 hipError_t launch_wall_group_keyed(hipStream_t s, uint64_t n, uint64_t* keys0, uint64_t* keys1, uint32_t* index0, uint32_t* index1,
                                    void* temp, int label_bits, const int64_t mdims[3], const int perm[3], uint32_t* pairs_out,
                                    int32_t* coords_out);
+// ... and the sort by itself, for the features: stable, LSD, on keys of key_bits bits (32-bit or 64-bit words) with a u32 value each
+// (n < 2^32).  keys0 / idx0 hold the input; *keys_out / *idx_out receive whichever of the two buffers holds the sorted keys and
+// values.  Temp: wall_sort_temp_bytes(n).
+hipError_t launch_radix_sort_u32(hipStream_t s, uint64_t n, uint32_t* keys0, uint32_t* keys1, uint32_t* idx0, uint32_t* idx1,
+                                 void* temp, int key_bits, uint32_t** keys_out, uint32_t** idx_out);
+hipError_t launch_radix_sort_u64(hipStream_t s, uint64_t n, uint64_t* keys0, uint64_t* keys1, uint32_t* idx0, uint32_t* idx1,
+                                 void* temp, int key_bits, uint64_t** keys_out, uint32_t** idx_out);
 
 // kernels_walls.hip (continued): exclusive scan of uint32 counts into uint64 offsets (three small kernels)
 uint64_t scan_u32_scratch_bytes(uint64_t n);

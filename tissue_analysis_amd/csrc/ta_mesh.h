@@ -45,9 +45,4 @@ void launch_mesh_resolve(hipStream_t s, const MeshArgs& a, const uint32_t* fkey,
                          const uint32_t* nb, uint64_t nfaces, const uint64_t* vcorner, const uint64_t* vbeg, const uint64_t* vend,
                          uint32_t* tri, uint32_t* tri_cell, uint32_t* tri_nb);
 
-// kernels_wallsort.hip: the stable LSD radix sort of the wall voxels, on 32-bit keys of key_bits bits with a u32 value each (n < 2^32).
-// keys0 / idx0 hold the input; *keys_out / *idx_out receive whichever of the two buffers holds the result.  Temp: wall_sort_temp_bytes.
-hipError_t launch_radix_sort_u32(hipStream_t s, uint64_t n, uint32_t* keys0, uint32_t* keys1, uint32_t* idx0, uint32_t* idx1,
-                                 void* temp, int key_bits, uint32_t** keys_out, uint32_t** idx_out);
-
 }  // namespace ta

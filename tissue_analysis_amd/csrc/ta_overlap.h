@@ -35,9 +35,4 @@ void launch_overlap_emit(hipStream_t s, const unsigned long long* keys, uint64_t
 void launch_overlap_rows(hipStream_t s, const uint64_t* sorted_keys, const uint32_t* slot_of, uint64_t n, const unsigned long long* counts,
                          int shift_b, uint64_t top, uint32_t* a_out, uint32_t* b_out, uint64_t* n_out);
 
-// kernels_wallsort.hip: the stable LSD radix sort of the wall voxels on 64-bit keys of key_bits bits with a u32 value each
-// (n < 2^32; temp: wall_sort_temp_bytes(n)).  *keys_out / *idx_out: which of the two buffers hold the sorted keys and values.
-hipError_t launch_radix_sort_u64(hipStream_t s, uint64_t n, uint64_t* keys0, uint64_t* keys1, uint32_t* idx0, uint32_t* idx1,
-                                 void* temp, int key_bits, uint64_t** keys_out, uint32_t** idx_out);
-
 }  // namespace ta
