@@ -61,6 +61,9 @@ JUNCTION_SYMBOLS = (
     "ta_junctions_extract", "ta_junctions_size", "ta_junctions_get_edges", "ta_junctions_get_vertices", "ta_junctions_timing",
 )
 
+# every symbol include/tissue_scan_wallgeo.h declares (same library)
+WALLGEO_SYMBOLS = ("ta_wallgeo_extract", "ta_wallgeo_get", "ta_wallgeo_spills", "ta_wallgeo_timing")
+
 
 def exchange_words(capacity_pairs):
     """uint64 words of one exchange block (TA_EXCHANGE_WORDS in include/tissue_scan.h)."""
@@ -175,8 +178,12 @@ def load():
         "ta_junctions_get_edges": (ci, [vp, vp, vp, vp]),
         "ta_junctions_get_vertices": (ci, [vp, vp, vp, vp]),
         "ta_junctions_timing": (ci, [vp, P(ctypes.c_double), P(ctypes.c_double)]),
+        "ta_wallgeo_extract": (ci, [vp]),
+        "ta_wallgeo_get": (ci, [vp, vp, vp, vp, vp]),
+        "ta_wallgeo_spills": (ci, [vp, P(u32)]),
+        "ta_wallgeo_timing": (ci, [vp, P(ctypes.c_double)]),
     }
-    for name in SYMBOLS + SIGNAL_SYMBOLS + MESH_SYMBOLS + OVERLAP_SYMBOLS + JUNCTION_SYMBOLS:
+    for name in SYMBOLS + SIGNAL_SYMBOLS + MESH_SYMBOLS + OVERLAP_SYMBOLS + JUNCTION_SYMBOLS + WALLGEO_SYMBOLS:
         fn = getattr(lib, name)      # AttributeError here == the .so does not match the header
         fn.restype, fn.argtypes = sig[name]
     if lib.ta_version() != ABI_VERSION:
@@ -564,6 +571,30 @@ class Context(object):
         a, b = ctypes.c_double(0.0), ctypes.c_double(0.0)
         _check(self._lib.ta_junctions_timing(self._h, ctypes.byref(a), ctypes.byref(b)))
         return a.value, b.value
+
+    # -- wall geometry (include/tissue_scan_wallgeo.h)
+    def wallgeo_extract(self):
+        """Enqueue the wall-geometry pass over the current extraction (which needs its adjacency)."""
+        _check(self._lib.ta_wallgeo_extract(self._h))
+
+    def wallgeo_get(self):
+        """(fwd u64[P, 3], rev u64[P, 3], sum1 u64[P, 3], sum2 u64[P, 6]), rows as adjacency(), array axes."""
+        P = self.adjacency_size()
+        fwd, rev, s1 = np.zeros((P, 3), dtype=np.uint64), np.zeros((P, 3), dtype=np.uint64), np.zeros((P, 3), dtype=np.uint64)
+        s2 = np.zeros((P, 6), dtype=np.uint64)
+        _check(self._lib.ta_wallgeo_get(self._h, fwd.ctypes.data, rev.ctypes.data, s1.ctypes.data, s2.ctypes.data))
+        return fwd, rev, s1, s2
+
+    def wallgeo_spills(self):
+        """Records of the last pass that missed a workgroup's LDS table and went to the global rows directly."""
+        n = ctypes.c_uint32(0)
+        _check(self._lib.ta_wallgeo_spills(self._h, ctypes.byref(n)))
+        return int(n.value)
+
+    def wallgeo_timing(self):
+        ms = ctypes.c_double(0.0)
+        _check(self._lib.ta_wallgeo_timing(self._h, ctypes.byref(ms)))
+        return ms.value
 
     def max_label(self):
         v = ctypes.c_uint32(0)

@@ -425,7 +425,7 @@ TA_API int ta_ctx_destroy(ta_ctx* c) {
     c->wall_stage.release();
     c->wall_medians.release();
     c->census.release(); c->census_ids.release(); c->compact_vol.release(); c->census_list.release();
-    c->sig.release(); c->mesh.release(); c->ov.release(); c->jn.release();
+    c->sig.release(); c->mesh.release(); c->ov.release(); c->jn.release(); c->wg.release();
     if (c->h_small) (void)hipHostFree(c->h_small);
     destroy_events(c->ev); destroy_events(c->tune_ev);
     for (auto& e : c->ring) if (e) (void)hipEventDestroy(e);
@@ -572,6 +572,7 @@ TA_API int ta_volume_set(ta_ctx* c, const void* host_ptr, int itemsize, const in
     c->first_owned = 0;
     c->extracted = c->checked = false;
     signal_on_new_volume(c);
+    wallgeo_on_new_volume(c);
     overlap_on_new_volume(c);
     junctions_on_new_volume(c);
     return TA_OK;
@@ -599,6 +600,7 @@ TA_API int ta_volume_set_device(ta_ctx* c, const void* dev_ptr, int itemsize, co
     c->first_owned = has_low_halo ? 1 : 0;
     c->extracted = c->checked = false;
     signal_on_new_volume(c);
+    wallgeo_on_new_volume(c);
     overlap_on_new_volume(c);
     junctions_on_new_volume(c);
     return TA_OK;

@@ -136,6 +136,16 @@ struct JunctionState {
     void release() { small.release(); work.release(); rec.release(); for (int k = 0; k < 2; ++k) { sort[k].release(); rows[k].release(); } destroy_events(ev); }
 };
 
+// wall geometry (include/tissue_scan_wallgeo.h)
+struct WallGeoState {
+    DevBuf out;                                         // flags u32[4] | rows u64[P][15]: fwd | rev | sum1 | sum2, memory-axis order
+    DevBuf hash;                                        // pair -> row table of the sorted pair list: keys u64[cap] | sorted keys | rows u32[cap]
+    uint64_t seq = 0;                                   // extract_seq of the extraction the rows belong to, 0 = none
+    int64_t npairs = 0;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    void release() { out.release(); hash.release(); destroy_events(ev); }
+};
+
 struct ta_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -222,6 +232,7 @@ struct ta_ctx {
     MeshState mesh;
     OverlapState ov;
     JunctionState jn;
+    WallGeoState wg;
 };
 
 inline int use_device(ta_ctx* c) {
@@ -239,6 +250,7 @@ int finish_extract(ta_ctx* c);
 void signal_on_new_volume(ta_ctx* c);
 void overlap_on_new_volume(ta_ctx* c);
 void junctions_on_new_volume(ta_ctx* c);
+void wallgeo_on_new_volume(ta_ctx* c);
 
 // Companions: these touch the companion's own fields only.  The setters check the arguments against the label volume and drain the
 // stream (a pass in flight may still read the old companion) before they change anything; a failure later leaves no companion set.

@@ -552,6 +552,17 @@ class ResidentVolume(object):
         self.ms["junctions"] = (time.perf_counter() - t0) * 1e3
         return j
 
+    def wall_geometry(self, voxelsize=(1.0, 1.0, 1.0)):
+        """The geometry of every wall of the resident volume: a `WallGeometry` (signed face counts, first and second sums of the
+        face centres) whose rows are the pairs of the current extraction (swept first when there is none), in the ids of the
+        image.  One pass over the labels on the GPU."""
+        import time
+        from .wall_geometry import resident_wall_geometry
+        t0 = time.perf_counter()
+        g = resident_wall_geometry(self, voxelsize)
+        self.ms["wall_geometry"] = (time.perf_counter() - t0) * 1e3
+        return g
+
     def wall_table(self):
         if self.host.flags.c_contiguous:       # memory order IS np.where order: the device groups the records by pair
             lo, hi, coords, ms = self.ctx.wall_voxels(by_pair=True)

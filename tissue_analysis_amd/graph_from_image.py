@@ -69,6 +69,10 @@ def _show_point(row):
     return (int(row[0]), int(row[1]), int(row[2]))
 
 
+def _show_vector(row):
+    return (float(row[0]), float(row[1]), float(row[2]))
+
+
 # ----------------------------------------------------------------------------- the assembly
 class _PairView(object):
     """The sweep's pair list with the per-call quantities every property needs."""
@@ -124,7 +128,8 @@ def tissue_tables(analysis, labels, background, properties, property_as_real=Tru
     """The vertex / edge tables of the tissue graph from the sweep results held by `analysis`.
     `labels`: the vertex ids (any order, distinct).  Returns a PropertyGraph whose columns are plain numpy arrays.
     With an intensity image `signal`, 'mean_signal' (vertex: cell_signal's mean) and 'wall_signal' (edge: wall_signal's
-    face-weighted mean) can be asked for too."""
+    face-weighted mean) can be asked for too.  'wall_centroid', 'wall_normal' and 'wall_projected_area' (edge: the columns of
+    `analysis.wall_geometry()`) run the wall-geometry pass; a property list without them does not."""
     x = analysis.extraction
     ids = np.asarray(labels, dtype=np.int64).reshape(-1)
     pairs = _PairView(analysis, ids, min_contact_area)
@@ -200,6 +205,18 @@ def tissue_tables(analysis, labels, background, properties, property_as_real=Tru
             rows = stats.wall_rows(pairs.lo[is_edge], pairs.hi[is_edge])
             found = rows >= 0
             graph.set_edge_column('wall_signal', np.where(found, stats.wall_mean[np.where(found, rows, 0)], np.nan), found)
+    wall_geometry_columns = [p for p in ('wall_centroid', 'wall_normal', 'wall_projected_area') if p in properties]
+    if wall_geometry_columns:
+        geo = analysis.wall_geometry()
+        rows = geo.wall_rows(pairs.lo[is_edge], pairs.hi[is_edge])
+        found = rows >= 0
+        at = np.where(found, rows, 0)
+        if 'wall_centroid' in properties:
+            graph.set_edge_column('wall_centroid', np.where(found[:, None], geo.centroid(real)[at], np.nan), found, _show_vector)
+        if 'wall_normal' in properties:
+            graph.set_edge_column('wall_normal', np.where(found[:, None], geo.normal()[at], np.nan), found, _show_vector)
+        if 'wall_projected_area' in properties:
+            graph.set_edge_column('wall_projected_area', np.where(found, geo.projected_area(real)[at], np.nan), found)
     return graph
 
 

@@ -205,6 +205,7 @@ class AbstractSpatialImageAnalysis(object):
         self._signal_cache = None
         self._mesh_cache = {}
         self._junctions = None
+        self._wall_geometry = None
         try:
             self.filepath, self.filename = split(image.info["Filename"])
         except Exception:
@@ -261,6 +262,7 @@ class AbstractSpatialImageAnalysis(object):
         self._signal_cache = None
         self._mesh_cache = {}
         self._junctions = None
+        self._wall_geometry = None
         self._voxel_layer1 = None
         self._voxel_layer18 = None
 
@@ -618,6 +620,39 @@ class AbstractSpatialImageAnalysis(object):
         """{(a, b, c, d): xyz} of every point where four labels meet (none excluded)."""
         return self.cell_junctions().cell_vertices(real=real)
 
+    # -- wall geometry (include/tissue_scan_wallgeo.h; one pass over the resident volume on the GPU)
+    def wall_geometry(self):
+        """Signed face counts, centroid sums and second moments of every wall: a `WallGeometry` in the ids of the image and with
+        this analysis' voxel size.  Nothing is excluded here (background walls have rows).  Cached until `refresh()` or an edit
+        of the image."""
+        if getattr(self, "_wall_geometry", None) is None:
+            self._wall_geometry = self._resident_rows().wall_geometry(tuple(float(v) for v in self._voxelsize))
+        return self._wall_geometry
+
+    def _wall_geometry_column(self, neighbors, values):
+        """`values` (one entry per row of wall_geometry()) for the walls wall_areas(neighbors) returns, in its forms."""
+        walls = self.wall_areas(neighbors, real=False)
+        geo = self.wall_geometry()
+        if isinstance(walls, tuple):
+            pairs = np.asarray(walls[0]).reshape(-1, 2)
+            rows = geo.wall_rows(pairs[:, 0], pairs[:, 1])
+            out = np.where((rows >= 0).reshape((-1,) + (1,) * (values.ndim - 1)), values[np.maximum(rows, 0)], np.nan)
+            return walls[0], out
+        keys = list(walls.keys())
+        rows = geo.wall_rows([k[0] for k in keys], [k[1] for k in keys])
+        nan = np.full(values.shape[1:], np.nan) if values.ndim > 1 else float('nan')
+        return dict((k, (values[r] if values.ndim > 1 else float(values[r])) if r >= 0 else nan) for k, r in zip(keys, rows.tolist()))
+
+    def wall_normals(self, neighbors=None):
+        """{(l1, l2): unit normal} for the walls wall_areas(neighbors) returns: along the wall's vector area in real units, from
+        l1 to l2 (l1 < l2); NaN for a closed wall."""
+        return self._wall_geometry_column(neighbors, self.wall_geometry().normal())
+
+    def wall_projected_areas(self, neighbors=None, real=True):
+        """{(l1, l2): area} for the walls wall_areas(neighbors) returns: the norm of the wall's vector area, never more than
+        its voxel-face area of wall_areas()."""
+        return self._wall_geometry_column(neighbors, self.wall_geometry().projected_area(real))
+
     def surface_area(self, labels=None, real=True):
         """Per-label total surface area = the sum of the label's wall areas with all its face neighbours
         (SURVEY.md §8 "Semantics": sum_m wall_area(l, m); the reference has no dedicated method, `cell_wall_area`
@@ -862,6 +897,7 @@ class AbstractSpatialImageAnalysis(object):
         self._signal_cache = None
         self._mesh_cache = {}
         self._junctions = None
+        self._wall_geometry = None
         self._voxel_layer1 = None
         self._voxel_layer18 = None
 
