@@ -187,6 +187,20 @@ def test_repeated_sweeps_of_a_spilling_volume_adapt_the_tile_height(gpu_ctx):
     assert min(ms[2:]) < 1.5 * ms[0], ms
 
 
+def test_flags_words_after_sweep(gpu_ctx):
+    """The words behind the sixteen flag words of the small device buffer -- pair cursor, max label, the parked hot-row
+    pointer -- are where the sweep, the pair collect and the host expect them: a sweep with the full feature mask gives the
+    NumPy restatement's integers, raises neither the range nor the pair-overflow flag, and counts the reference's pairs."""
+    vol16 = random_blocks((8, 16, 512), 300, 41, np.uint16)
+    for vol in (vol16.astype(np.uint32), vol16):
+        want = onepass.extract(vol)
+        got = run(gpu_ctx, vol, 0)
+        assert_same_accumulators(got, want, "flags words %s" % vol.dtype.name)
+        d = gpu_ctx.debug_counters()
+        assert d["range_flag"] == 0 and d["pair_overflow"] == 0, d
+        assert gpu_ctx.adjacency_size() == want["pair_lo"].size
+
+
 @pytest.mark.parametrize("shape,dtype", [((1, 1, 68), np.uint32), ((3, 1, 64), np.uint16), ((2, 5, 260), np.uint32), ((4, 17, 1000), np.uint32),
                                          ((2, 3, 8), np.uint16), ((5, 18, 520), np.uint16), ((1, 68, 1), np.uint32)])
 def test_partial_tiles_of_volumes_with_aligned_rows(gpu_ctx, shape, dtype):

@@ -89,7 +89,7 @@ def _check_pinned(hipcc, verbose=False):
             elif "scan_noadj_kernel" in func:
                 ranges = [bases["MOM"]]
             elif "scan_two_rows_kernel" in func:
-                ranges = [bases["ADJ2"], bases["ADJ2"] + 6]    # (+6: the second landing zone of TA_PLANES_IN_FLIGHT=2, v[96:108])
+                ranges = [bases["ADJ2"]]
             elif "scan_kernel" in func:
                 ranges = [bases["ADJ"]]
             else:

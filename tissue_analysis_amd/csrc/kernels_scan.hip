@@ -49,38 +49,25 @@ struct __attribute__((aligned(16))) ScanWaveLds {
     uint32_t cql[RCAP + 2], cqc[RCAP + 2];              // runs; record i lives in slot i + 1, slot 0 = sentinel / carry, slot RCAP + 1 = trash
 };
 
-// NW packed words of sums per label slot and replica (SumPack); REP_ replicas of every slot: the runs of one label in a group of
-// 64 records come from consecutive rows, and rows of different parity add into different replicas (drain_run_group)
-template <int NW, bool ADJ, int REP_, typename PACK>
+// NW packed words of sums per label slot (SumPack)
+template <int NW, bool ADJ, typename PACK>
 struct __attribute__((aligned(16))) ScanLds {
-    static constexpr int REP = REP_;
     using Pack = PACK;
     ScanWaveLds<ADJ> wave[WAVES];
-    uint64_t lsum[LSLOTS * NW * REP_];
+    uint64_t lsum[LSLOTS * NW];
     uint64_t pkeys[ADJ ? PSLOTS : 2];
-#if TA_PCNT64
-    uint64_t pcnt[ADJ ? PSLOTS : 1];  // three 21-bit face counts per pair (PCNT_BITS)
-#else
     uint32_t pcnt[ADJ ? PSLOTS * 3 : 1];
-#endif
     uint32_t lbox[LSLOTS * 8];
     uint32_t lkeys[LSLOTS];
     uint32_t frame[4];                // origin (axes 0, 1, 2) of the tile-local coordinates: only the spill paths need it
     uint32_t fcnt[2];                 // the flush: occupied label / pair slots (flush_tables gathers them first)
-#ifdef TA_LDS_PAD
-    uint32_t pad_[TA_LDS_PAD];        // experiments only: fewer workgroups per CU
-#endif
 };
 
 // one face of `axis` for the pair in `slot`.  (Three u32 counters: an LDS atomic on 64 bits costs the CU's LDS twice the
 // cycles per lane that shares its address -- profiles/r04_lds_atomics_microbench.txt -- and a pass of 64 faces holds few pairs.)
 template <typename LDS>
 __device__ __forceinline__ void pcnt_add(LDS& S, const uint32_t slot, const uint32_t axis) {
-#if TA_PCNT64
-    atomicAdd((unsigned long long*)&S.pcnt[slot], 1ull << (PCNT_BITS * axis));
-#else
     atomicAdd(&S.pcnt[slot * 3u + axis], 1u);
-#endif
 }
 
 // inclusive add-scan over the 64 lanes: row_shr 1,2,4,8 then the two row broadcasts
@@ -260,7 +247,7 @@ __device__ __forceinline__ void scan_label_add(const SweepArgs* kp, LDS& S,
         k = S.lkeys[h];
     }
     if (slot >= 0) {
-        unsigned long long* row = (unsigned long long*)&S.lsum[slot * NW * LDS::REP];      // (replica 0)
+        unsigned long long* row = (unsigned long long*)&S.lsum[slot * NW];
         uint64_t w[4];
         LDS::Pack::template pack<MOM2>(L, w);
 #ifndef TA_ABL_NOSUMS          // (ablations: results wrong by construction, only the time matters)
@@ -644,13 +631,10 @@ __device__ __forceinline__ void drain_run_group(const SweepArgs* kp, LDS& S, WLD
     const RunSums L = run_sums<MOM2>(c0, kk - c0, al, bl);
     if (TA_ABL_HOT >= 1) asm volatile("" :: "v"(L.n), "v"(L.sa), "v"(L.sb), "v"(L.sc), "v"(L.saa), "v"(L.sab), "v"(L.sac), "v"(L.sbb), "v"(L.sbc), "v"(L.scc), "v"(lslot), "s"(__builtin_amdgcn_ballot_w64(llive && !lpend)));
     if (TA_ABL_HOT < 1 && llive && !lpend) {
-        // (records of one label in a group come from consecutive rows: rows of different parity take different replicas, which
-        //  halves the lanes that share an address in each of these adds)
-        const uint32_t rep = LDS::REP > 1 ? (bl & (uint32_t)(LDS::REP - 1)) : 0u;
 #ifdef TA_ABL_SHARE1       // (ablation: every lane its own row -- no two lanes of an atomic share an address)
-        unsigned long long* row = (unsigned long long*)&S.lsum[((lslot + (uint32_t)lane) & (LSLOTS - 1)) * NW * LDS::REP];
+        unsigned long long* row = (unsigned long long*)&S.lsum[((lslot + (uint32_t)lane) & (LSLOTS - 1)) * NW];
 #else
-        unsigned long long* row = (unsigned long long*)&S.lsum[(lslot * LDS::REP + rep) * NW];
+        unsigned long long* row = (unsigned long long*)&S.lsum[lslot * NW];
 #endif
         uint64_t w[4];
         LDS::Pack::template pack<MOM2>(L, w);
@@ -738,8 +722,6 @@ typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 // VGPRs + 13 pinned (two rows, the row above, the voxel to the left) = 95: FIVE waves per SIMD
 #define TA_PIN_ADJ2 82
 #define TA_CAP_ADJ2 78
-// TA_PLANES_IN_FLIGHT = 2 (experiment): a second landing zone behind the first, 82 + 27 = 109 registers, FOUR waves per SIMD
-#define TA_PIN_ADJ2B 96
 #define TA_CAP_MOM 72
 // the PADDED kernels (partial tiles of a volume whose rows are 16-byte aligned: interior-style loads, edge-style
 // semantics) carry more state: with adjacency 116 + 21 = 137 (three waves per SIMD), without 80 + 16 = 96 (five, like the
@@ -776,9 +758,7 @@ __device__ __forceinline__ void unpack_strip(const u32x4& x, uint32_t (&dst)[VPL
 // column to the left.  PINB: 0 = plain guarded loads (volumes whose rows are not 16-byte aligned), else the first of the
 // hand-pinned registers the plane in flight lands in.  EDGE with PINB != 0 is the PADDED variant: interior-style loads from
 // clamped addresses, the positions outside the volume overwritten with the filler when the plane lands.
-// PINB2 != 0 (experiment, TA_PLANES_IN_FLIGHT = 2): a SECOND landing zone -- two planes in flight per wave, the plane loop
-// unrolled by two, `s_waitcnt vmcnt(4)` where the next plane's four loads stay in flight.
-template <typename T, int VPL, int RB, bool ADJ, bool MOM2, bool EDGE, int PINB, int PINB2, typename LDS>
+template <typename T, int VPL, int RB, bool ADJ, bool MOM2, bool EDGE, int PINB, typename LDS>
 __device__ __forceinline__ void wave_scan(const SweepArgs& A, const SweepArgs* kp, LDS& S, const int lane, const int w,
                                           const uint32_t c_tile0, const uint32_t b_tile0,
                                           const int32_t p_lo, const int32_t p_hi) {
@@ -860,50 +840,49 @@ __device__ __forceinline__ void wave_scan(const SweepArgs& A, const SweepArgs* k
     const uint32_t left_off = (uint32_t)(PAD && b_wave0 + (lane & (RB - 1)) >= n1 ? 0 : (lane & (RB - 1))) * rowbytes;    // (the VGPR offset of a load is unsigned)
     const int64_t plane_bytes = plane * (int64_t)sizeof(T);
     const char* next_row0 = reinterpret_cast<const char*>(vol + (int64_t)(has_prev ? p_lo - 1 : p_lo) * plane + b_base * n2 + c_tile0);
-    auto issue_plane_to = [&](auto zone) {                // issues the plane at `next_row0` into a landing zone and steps it
+    using Zone = Pin<(PINB ? PINB : TA_PIN_ADJ)>;          // the landing zone of the plane in flight
+    auto issue_plane = [&]() {                            // issues the plane at `next_row0` into the landing zone and steps it
         const char* row0 = next_row0;
 #ifndef TA_ABL_L2
         next_row0 += plane_bytes;
 #endif
-        using P = Pin<decltype(zone)::value>;
         if constexpr (sizeof(T) == 4 && VPL == 8) {      // 32-byte strips: two quads a row, two rows, two quads the row above
             static_assert(RB == 2 && ADJ, "eight uint32 voxels a lane: two rows a wave, the 25-register landing zone");
             const char* row1 = row_in[1] ? row0 + rowbytes : row0;
-            P::template issue_strip<0>(lane_off, row0);
-            P::template issue_strip<1>(lane_off, row0 + 16);
-            P::template issue_strip<2>(lane_off, row1);
-            P::template issue_strip<3>(lane_off, row1 + 16);
+            Zone::template issue_strip<0>(lane_off, row0);
+            Zone::template issue_strip<1>(lane_off, row0 + 16);
+            Zone::template issue_strip<2>(lane_off, row1);
+            Zone::template issue_strip<3>(lane_off, row1 + 16);
             const bool up_there = has_up && (!PAD || b_wave0 < n1);
             const char* upr = up_there ? row0 - rowbytes : row0;
-            P::template issue_strip<4>(lane_off, upr);
-            P::template issue_strip<5>(lane_off, upr + 16);
-            P::template issue_voxel<T, RB>(left_off, has_left ? row0 - sizeof(T) : row0);
+            Zone::template issue_strip<4>(lane_off, upr);
+            Zone::template issue_strip<5>(lane_off, upr + 16);
+            Zone::template issue_voxel<T, RB>(left_off, has_left ? row0 - sizeof(T) : row0);
         } else if constexpr (sizeof(T) == 2 && VPL == 4) {      // 8-byte strips: the first half of each landing quad
             static_assert(RB == 2, "four uint16 voxels a lane: the two-row tiles");
-            P::template issue_half<0>(lane_off, row0);
-            P::template issue_half<1>(lane_off, row_in[1] ? row0 + rowbytes : row0);
+            Zone::template issue_half<0>(lane_off, row0);
+            Zone::template issue_half<1>(lane_off, row_in[1] ? row0 + rowbytes : row0);
             if (ADJ) {
                 const bool up_there = has_up && (!PAD || b_wave0 < n1);
-                P::template issue_half<2>(lane_off, up_there ? row0 - rowbytes : row0);
-                P::template issue_voxel<T, RB>(left_off, has_left ? row0 - sizeof(T) : row0);
+                Zone::template issue_half<2>(lane_off, up_there ? row0 - rowbytes : row0);
+                Zone::template issue_voxel<T, RB>(left_off, has_left ? row0 - sizeof(T) : row0);
             }
         } else {
-        P::template issue_strip<0>(lane_off, row0);
-        P::template issue_strip<1>(lane_off, row_in[1] ? row0 + rowbytes : row0);
+        Zone::template issue_strip<0>(lane_off, row0);
+        Zone::template issue_strip<1>(lane_off, row_in[1] ? row0 + rowbytes : row0);
         if (RB > 2) {
-            P::template issue_strip<2>(lane_off, row_in[RB > 2 ? 2 : 0] ? row0 + 2 * (int64_t)rowbytes : row0);
-            P::template issue_strip<3>(lane_off, row_in[RB > 3 ? 3 : 0] ? row0 + 3 * (int64_t)rowbytes : row0);
+            Zone::template issue_strip<2>(lane_off, row_in[RB > 2 ? 2 : 0] ? row0 + 2 * (int64_t)rowbytes : row0);
+            Zone::template issue_strip<3>(lane_off, row_in[RB > 3 ? 3 : 0] ? row0 + 3 * (int64_t)rowbytes : row0);
         }
         if (ADJ) {       // (without adjacency nobody looks at the row above or the voxel to the left)
             // (PADDED, the whole wave past the last row: row0 is the last row of the volume; the row "above" it is not asked for)
             const bool up_there = has_up && (!PAD || b_wave0 < n1);
-            if (RB > 2) P::template issue_strip<4>(lane_off, up_there ? row0 - rowbytes : row0);
-            else        P::template issue_strip<2>(lane_off, up_there ? row0 - rowbytes : row0);
-            P::template issue_voxel<T, RB>(left_off, has_left ? row0 - sizeof(T) : row0);
+            if (RB > 2) Zone::template issue_strip<4>(lane_off, up_there ? row0 - rowbytes : row0);
+            else        Zone::template issue_strip<2>(lane_off, up_there ? row0 - rowbytes : row0);
+            Zone::template issue_voxel<T, RB>(left_off, has_left ? row0 - sizeof(T) : row0);
         }
         }
     };
-    auto issue_plane = [&]() { issue_plane_to(std::integral_constant<int, (PINB ? PINB : TA_PIN_ADJ)>{}); };
 
     // PADDED: what landed for positions outside the volume is overwritten with the filler; a REAL voxel equal to the
     // filler (0xFFFFFFFF in a uint32 volume: above any max_label) is reported like the plain edge loads report it
@@ -1049,16 +1028,15 @@ __device__ __forceinline__ void wave_scan(const SweepArgs& A, const SweepArgs* k
     u32x4 nraw[RB], nup_raw;                                                  // interior tiles: the plane just read back
     u32x4 nraw_hi[RB], nup_hi;                                                // (eight uint32 voxels a lane: their second halves)
     constexpr bool WIDE8 = sizeof(T) == 4 && VPL == 8;
-    auto land = [&](auto zone, auto keep4) {               // the plane in flight -> nraw / nup_raw / nxt_leftv
-        using P = Pin<decltype(zone)::value>;
-        if constexpr (WIDE8) {
+    auto land = [&]() {                                    // the plane in flight -> nraw / nup_raw / nxt_leftv
+        if constexpr (PINB == 0) {
+            // (edge tiles load with bounds: nothing lands)
+        } else if constexpr (WIDE8) {
             u32x4 t[6];
-            P::landed_wide(t, nxt_leftv);
+            Zone::landed_wide(t, nxt_leftv);
             nraw[0] = t[0]; nraw_hi[0] = t[1]; nraw[RB - 1] = t[2]; nraw_hi[RB - 1] = t[3]; nup_raw = t[4]; nup_hi = t[5];
-        } else if constexpr (decltype(keep4)::value) {
-            P::template landed_keep4<RB>(nraw, nup_raw, nxt_leftv);
         } else {
-            P::template landed<RB>(nraw, nup_raw, nxt_leftv);
+            Zone::template landed<RB>(nraw, nup_raw, nxt_leftv);
         }
     };
     auto unpack_row = [&](const int r, uint32_t (&dst)[VPL]) {
@@ -1077,7 +1055,6 @@ __device__ __forceinline__ void wave_scan(const SweepArgs& A, const SweepArgs* k
             unpack_strip<T, VPL>(nup_raw, dst);
         }
     };
-    using ZoneA = std::integral_constant<int, (PINB ? PINB : TA_PIN_ADJ)>;
 #pragma unroll
     for (int j = 0; j < VPL; ++j) { up[j] = INVALID_LABEL; nxt_up[j] = INVALID_LABEL; }
     if constexpr (PINB == 0) {
@@ -1121,7 +1098,7 @@ __device__ __forceinline__ void wave_scan(const SweepArgs& A, const SweepArgs* k
             }
         } else if (has_prev) {
             issue_plane();
-            land(ZoneA{}, std::false_type{});
+            land();
 #pragma unroll
             for (int r = 0; r < RB; ++r) unpack_row(r, cur[r]);
             if constexpr (PAD) {
@@ -1232,19 +1209,7 @@ __device__ __forceinline__ void wave_scan(const SweepArgs& A, const SweepArgs* k
                 //  and the restore becomes `s_mov_b64 exec, exec`)
                 uint64_t live = FULL ? ~0ull : __builtin_amdgcn_ballot_w64(true);
                 if (!FULL) asm volatile("" : "+s"(live));
-#ifdef TA_DBG_EMIT
-                const uint32_t dbg_off0 = offf;
-#endif
                 if (ADJ && r == 0) { if (with_plane_faces) emit_plane_faces(offf, live, full); }
-#ifdef TA_DBG_EMIT
-                if (ADJ && r == 0 && with_plane_faces) {
-                    const uint32_t wrote = (offf - dbg_off0) >> 3, want = count_plane_faces();
-                    if (wrote != want || (wrote != 0u && (offf > fbase + 8u * (uint32_t)FCAP || dbg_off0 < fbase))) {
-                        uint32_t* fl = cold_args(kp)->flags;
-                        if (atomicAdd(&fl[15], 1u) == 0u) { fl[8] = wrote; fl[9] = want; fl[10] = (uint32_t)lane; fl[11] = (dbg_off0 - fbase) >> 3; fl[12] = fcount; fl[13] = FULL ? 1u : 0u; fl[14] = (uint32_t)__builtin_amdgcn_ballot_w64(true); }
-                    }
-                }
-#endif
                 const uint32_t code0 = lane_c | rowcode;
 #pragma unroll
                 for (int j = 0; j < VPL; ++j) {
@@ -1313,58 +1278,29 @@ __device__ __forceinline__ void wave_scan(const SweepArgs& A, const SweepArgs* k
     //      issued into the registers it leaves, the landed one is processed.  (Measured and dropped: TWO planes in flight for
     //      the two-row tiles of uint16 volumes, in the two halves of the sixteen pinned registers -- C2 stayed at 0.070 ms:
     //      that kernel is bound by its instructions per voxel, not by the bytes it has in flight.)
-    auto top_drains = [&]() {
+    for (int32_t p = p_lo; p < p_hi; ++p) {
         if constexpr (DRAIN_ALL) {
+            // the hot drains: between two planes a wave holds nothing but the plane before (and the next one is in flight)
+#ifdef TA_RECCOUNT
+            if (lane == 0 && fcount >= (uint32_t)TA_FDRAIN) atomicAdd(&cold_args(kp)->flags[11], 128u);
+            else if (lane == 0 && TA_FDRAIN1 && VPL == 8 && fcount >= 64u) atomicAdd(&cold_args(kp)->flags[11], 64u);
+            if (lane == 0 && rcount > 64u) atomicAdd(&cold_args(kp)->flags[12], 64u);
+#endif
             if (fcount >= (uint32_t)TA_FDRAIN) drain_face_groups<2, LDS>(kp, S, W, lane, fcount);
-            else if (TA_FDRAIN1 && VPL == 8 && fcount >= 64u) drain_face_groups<1, LDS>(kp, S, W, lane, fcount);   // (the wide tiles: see TA_FDRAIN1)
+            else if (TA_FDRAIN1 && VPL == 8 && fcount >= 64u) drain_face_groups<1, LDS>(kp, S, W, lane, fcount);
             if (rcount > 64u) drain_run_group<MOM2, LDS>(kp, S, W, EDGE, lane, rcount, first_label);
         }
-    };
-    if constexpr (PINB != 0 && PINB2 != 0) {
-        // two planes in flight: plane p lands from zone A (PINB) for even p - p_lo, from zone B (PINB2) for odd; each landing
-        // leaves the other zone's four loads in flight and re-issues its own zone two planes ahead
-        using ZA = std::integral_constant<int, PINB>;
-        using ZB = std::integral_constant<int, PINB2>;
-        if (p_lo + 1 < p_hi) issue_plane_to(ZB{});
-        for (int32_t p = p_lo; p < p_hi; p += 2) {
-            top_drains();
-            if (p + 1 < p_hi) land(ZA{}, std::true_type{});
-            else land(ZA{}, std::false_type{});
-            if (p + 2 < p_hi) issue_plane_to(ZA{});
-            process_plane(p);
-            if (p + 1 < p_hi) {
-                top_drains();
-                if (p + 2 < p_hi) land(ZB{}, std::true_type{});
-                else land(ZB{}, std::false_type{});
-                if (p + 3 < p_hi) issue_plane_to(ZB{});
-                process_plane(p + 1);
-            }
-        }
-    } else {
-        for (int32_t p = p_lo; p < p_hi; ++p) {
-            if constexpr (DRAIN_ALL) {
-                // the hot drains: between two planes a wave holds nothing but the plane before (and the next one is in flight)
-#ifdef TA_RECCOUNT
-                if (lane == 0 && fcount >= (uint32_t)TA_FDRAIN) atomicAdd(&cold_args(kp)->flags[11], 128u);
-                else if (lane == 0 && TA_FDRAIN1 && VPL == 8 && fcount >= 64u) atomicAdd(&cold_args(kp)->flags[11], 64u);
-                if (lane == 0 && rcount > 64u) atomicAdd(&cold_args(kp)->flags[12], 64u);
-#endif
-                if (fcount >= (uint32_t)TA_FDRAIN) drain_face_groups<2, LDS>(kp, S, W, lane, fcount);
-                else if (TA_FDRAIN1 && VPL == 8 && fcount >= 64u) drain_face_groups<1, LDS>(kp, S, W, lane, fcount);
-                if (rcount > 64u) drain_run_group<MOM2, LDS>(kp, S, W, EDGE, lane, rcount, first_label);
-            }
-            if constexpr (PINB != 0) {
+        if constexpr (PINB != 0) {
 #ifdef TA_STAMPS
-                const uint64_t t4 = TA_T();
+            const uint64_t t4 = TA_T();
 #endif
-                land(ZoneA{}, std::false_type{});
+            land();
 #ifdef TA_STAMPS
-                tk_land += TA_T() - t4;
+            tk_land += TA_T() - t4;
 #endif
-                if (p + 1 < p_hi) issue_plane();
-            }
-            process_plane(p);
+            if (p + 1 < p_hi) issue_plane();
         }
+        process_plane(p);
     }
 #ifdef TA_STAMPS
     if (lane == 0) {
@@ -1426,44 +1362,12 @@ static ScanSplit scan_split(const SweepArgs& a, int itemsize) {
     return s;
 }
 
-// The next tile of a persistent workgroup: from the list of its own XCD (workgroups are dealt round-robin over the 8 XCDs;
-// an XCD's list is every eighth CHUNK of TA_XCD_CHUNK consecutive tiles -- neighbours along axes 2 and 1, so that the halo
-// row a tile reads is the row its neighbour on the same XCD / L2 reads at about the same time -- plus its share of the last,
-// partial group of chunks), then from the other XCDs' lists.  Speed only: any workgroup may take any tile.
-__device__ __forceinline__ uint32_t claim_tile(uint32_t* queues, const uint32_t xcd, const uint32_t ntiles) {
-    constexpr uint32_t G = TA_XCD_CHUNK > 0 ? TA_XCD_CHUNK : 1;
-    const uint32_t per = (ntiles / (8u * G)) * G, full = per * 8u;          // tiles of the whole groups of chunks: per XCD, in all
-#if TA_PERSIST_SINGLE_QUEUE      // (experiment: one queue, tiles in plain order)
-    {
-        const uint32_t j = __hip_atomic_fetch_add(&queues[0], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        return j < ntiles ? j : NO_TILE;
-    }
-#endif
-#pragma nounroll
-    for (uint32_t s = 0; s < 8u; ++s) {
-        const uint32_t x = (xcd + s) & 7u;
-        const uint32_t nx = per + (ntiles - full + 7u - x) / 8u;            // ... plus every eighth tile of the rest
-        // (an empty list is seen by a plain load: at the end every workgroup walks all eight lists, and a thousand
-        //  read-modify-writes of one word take their time)
-        if (__hip_atomic_load(&queues[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= nx) continue;
-        const uint32_t j = __hip_atomic_fetch_add(&queues[x], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (j < nx) return j < per ? ((j / G) * 8u + x) * G + (j % G) : full + (j - per) * 8u + x;
-    }
-    return NO_TILE;
-}
-
-// PERSIST: the workgroup walks tiles until the queues are empty: its tables are emptied by the flush itself, the flush's global
-// atomics are left in flight while the next tile starts, and no workgroup has to be launched (and waited out) per tile.
-template <typename T, int VPL, int RB, bool ADJ, bool MOM2, bool EDGE, int PINB, bool PERSIST = false, int PINB2 = 0>
+template <typename T, int VPL, int RB, bool ADJ, bool MOM2, bool EDGE, int PINB>
 __device__ __forceinline__ void scan_kernel_body(const SweepArgs& A, const ScanSplit& sp, const uint32_t wg0) {
     constexpr int NW = MOM2 ? 4 : 2;
     constexpr int TC = 64 * VPL, TB = WAVES * RB;
     static_assert(TB <= 16 && TC <= 512, "packed LDS moment words assume <= 16 rows x 512 columns per tile");
-    static_assert(!PERSIST || !EDGE, "the persistent kernel walks the full tiles");
-    // two replicas of the label sums where the LDS has room at the kernel's occupancy (the tiles of eight voxels a lane: four
-    // workgroups a CU); the narrow uint32 tiles sit at five workgroups a CU and 31 KB, the moments-only kernels are not bound here
-    constexpr int REP = (ADJ && VPL == 8 && TA_LSUM_REP > 1) ? TA_LSUM_REP : 1;
-    using LDS = ScanLds<NW, ADJ, REP, SumPack<tile_planes_cap(ADJ, (int)sizeof(T), VPL), TB, TC>>;
+    using LDS = ScanLds<NW, ADJ, SumPack<tile_planes_cap(ADJ, (int)sizeof(T), VPL), TB, TC>>;
     __shared__ LDS S;
     // the arguments only the cold paths need are re-read from the kernarg segment there (see cold_args)
     const SweepArgs* kp = kernarg_args(A);
@@ -1473,101 +1377,81 @@ __device__ __forceinline__ void scan_kernel_body(const SweepArgs& A, const ScanS
     for (int i = tid; i < LSLOTS; i += WAVES * 64) {
         S.lkeys[i] = INVALID_LABEL;
 #pragma unroll
-        for (int k = 0; k < NW * REP; ++k) S.lsum[i * NW * REP + k] = 0ull;
+        for (int k = 0; k < NW; ++k) S.lsum[i * NW + k] = 0ull;
         S.lbox[i * 8 + 0] = 0xFFFFFFFFu; S.lbox[i * 8 + 1] = 0xFFFFFFFFu; S.lbox[i * 8 + 2] = 0xFFFFFFFFu;
         S.lbox[i * 8 + 3] = 0u; S.lbox[i * 8 + 4] = 0u; S.lbox[i * 8 + 5] = 0u;
     }
     if (ADJ) {
         for (int i = tid; i < PSLOTS; i += WAVES * 64) {
             S.pkeys[i] = EMPTY_KEY;
-#if TA_PCNT64
-            S.pcnt[i] = 0ull;
-#else
             S.pcnt[i * 3 + 0] = 0u; S.pcnt[i * 3 + 1] = 0u; S.pcnt[i * 3 + 2] = 0u;
-#endif
         }
     }
-    uint32_t tile = blockIdx.x;
-    if (PERSIST) {
-        if (tid == 0) S.frame[3] = claim_tile(cold_args(kp)->flags + QUEUE_WORD, blockIdx.x & 7u, sp.fc * sp.fb * sp.nbands);
-        __syncthreads();
-        tile = S.frame[3];
-    }
-    for (;;) {
-        if (PERSIST && tile == NO_TILE) break;
-        uint32_t t = tile, tc, tb, band;
+    const uint32_t tile = blockIdx.x;            // one workgroup walks one tile
+    uint32_t t = tile, tc, tb, band;
 #if TA_XCD_CHUNK > 0
-        // Workgroups are dealt round-robin over the 8 XCDs (speed only, never correctness: placement is not promised).
-        // Give each XCD CHUNKS of consecutive tiles -- neighbours along axes 2 and 1 -- so that the halo row a tile reads is
-        // the row its neighbour on the same XCD reads at about the same time (one HBM fetch, one L2), while chunks stay
-        // small enough that tissue and background tiles still spread evenly over the XCDs.  (PERSIST: claim_tile does it.)
-        if (!EDGE && !PERSIST) {
-            constexpr uint32_t G = TA_XCD_CHUNK;
-            const uint32_t full = (gridDim.x / (8u * G)) * (8u * G);
-            if (t < full) {
-                const uint32_t xcd = t % 8u, k = t / 8u;
-                t = ((k / G) * 8u + xcd) * G + (k % G);
-            }
+    // Workgroups are dealt round-robin over the 8 XCDs (speed only, never correctness: placement is not promised).
+    // Give each XCD CHUNKS of consecutive tiles -- neighbours along axes 2 and 1 -- so that the halo row a tile reads is
+    // the row its neighbour on the same XCD reads at about the same time (one HBM fetch, one L2), while chunks stay
+    // small enough that tissue and background tiles still spread evenly over the XCDs.
+    if (!EDGE) {
+        constexpr uint32_t G = TA_XCD_CHUNK;
+        const uint32_t full = (gridDim.x / (8u * G)) * (8u * G);
+        if (t < full) {
+            const uint32_t xcd = t % 8u, k = t / 8u;
+            t = ((k / G) * 8u + xcd) * G + (k % G);
         }
+    }
 #endif
-        if (!EDGE) {
-            tc = t % sp.fc; t /= sp.fc; tb = t % sp.fb; band = t / sp.fb;
-        } else {
-            const uint32_t per_band = sp.tiles_c * sp.tiles_b - sp.fc * sp.fb, strip = (sp.tiles_c - sp.fc) * sp.tiles_b;
-            band = t / per_band; t -= band * per_band;
-            if (t < strip) { tc = sp.fc + t % (sp.tiles_c - sp.fc); tb = t / (sp.tiles_c - sp.fc); }       // the last tile column(s)
-            else { t -= strip; tc = t % sp.fc; tb = sp.fb + t / sp.fc; }                                    // the last tile row(s)
-        }
-        // (the private hot-label row of a tile: numbered by the tile, whichever workgroup walks it)
-        if (TA_HOT_ADJ || !ADJ) hot_row_init(A, tid, wg0 + tile);
-        const uint32_t c_tile0 = tc * TC, b_tile0 = tb * TB;
-        const int32_t p_lo = A.first_owned + (int32_t)band * A.tile_planes;
-        int32_t p_hi = p_lo + A.tile_planes;
-        if (p_hi > (int32_t)A.n0) p_hi = (int32_t)A.n0;
-        const uint64_t A0 = (uint64_t)(A.a_origin + (p_lo - A.first_owned));
-        if (tid == 0) { S.frame[0] = (uint32_t)A0; S.frame[1] = b_tile0; S.frame[2] = c_tile0; }
-        __syncthreads();
+    if (!EDGE) {
+        tc = t % sp.fc; t /= sp.fc; tb = t % sp.fb; band = t / sp.fb;
+    } else {
+        const uint32_t per_band = sp.tiles_c * sp.tiles_b - sp.fc * sp.fb, strip = (sp.tiles_c - sp.fc) * sp.tiles_b;
+        band = t / per_band; t -= band * per_band;
+        if (t < strip) { tc = sp.fc + t % (sp.tiles_c - sp.fc); tb = t / (sp.tiles_c - sp.fc); }       // the last tile column(s)
+        else { t -= strip; tc = t % sp.fc; tb = sp.fb + t / sp.fc; }                                    // the last tile row(s)
+    }
+    // (the private hot-label row of a tile: numbered by the tile)
+    if (TA_HOT_ADJ || !ADJ) hot_row_init(A, tid, wg0 + tile);
+    const uint32_t c_tile0 = tc * TC, b_tile0 = tb * TB;
+    const int32_t p_lo = A.first_owned + (int32_t)band * A.tile_planes;
+    int32_t p_hi = p_lo + A.tile_planes;
+    if (p_hi > (int32_t)A.n0) p_hi = (int32_t)A.n0;
+    const uint64_t A0 = (uint64_t)(A.a_origin + (p_lo - A.first_owned));
+    if (tid == 0) { S.frame[0] = (uint32_t)A0; S.frame[1] = b_tile0; S.frame[2] = c_tile0; }
+    __syncthreads();
 
 #ifdef TA_BARSTAMP       // (instrumentation: where a workgroup's life goes -- flags[8..12] = cycles >> 8 summed over the waves)
-        const uint64_t tb_start = __builtin_amdgcn_s_memtime();
+    const uint64_t tb_start = __builtin_amdgcn_s_memtime();
 #endif
-        if (p_lo < p_hi)
-            wave_scan<T, VPL, RB, ADJ, MOM2, EDGE, PINB, PINB2>(A, kp, S, lane, w, c_tile0, b_tile0, p_lo, p_hi);
+    if (p_lo < p_hi)
+        wave_scan<T, VPL, RB, ADJ, MOM2, EDGE, PINB>(A, kp, S, lane, w, c_tile0, b_tile0, p_lo, p_hi);
 #ifdef TA_BARSTAMP
-        const uint64_t tb_scan = __builtin_amdgcn_s_memtime();
+    const uint64_t tb_scan = __builtin_amdgcn_s_memtime();
 #endif
-        __syncthreads();
+    __syncthreads();
 #ifdef TA_BARSTAMP
-        const uint64_t tb_bar = __builtin_amdgcn_s_memtime();
+    const uint64_t tb_bar = __builtin_amdgcn_s_memtime();
 #endif
-        // (everything the flush needs is re-read -- arguments from the kernarg segment, the tile origin from LDS --
-        //  rather than kept in scarce SGPRs across the sweep)
-        const KernelArgs ka = scalar_args(kp);
-        const SweepArgs& Ac = ka.a;
-        const uint32_t wg_ = ka.wg0 + tile;
-        uint32_t next = NO_TILE;
-        if (PERSIST && tid == 0)            // (asked for before the flush, needed after it; split: tiles_c, tiles_b, fc, fb, nbands, padded)
-            next = claim_tile(Ac.flags + QUEUE_WORD, blockIdx.x & 7u, ka.split[2] * ka.split[3] * ka.split[4]);
+    // (everything the flush needs is re-read -- arguments from the kernarg segment, the tile origin from LDS --
+    //  rather than kept in scarce SGPRs across the sweep)
+    const KernelArgs ka = scalar_args(kp);
+    const SweepArgs& Ac = ka.a;
+    const uint32_t wg_ = ka.wg0 + tile;
 #ifndef TA_ABL_NOFLUSH
-        flush_tables<NW, ADJ, MOM2, (TA_HOT_ADJ || !ADJ), LDS, WAVES * 64, PERSIST>(Ac, S, threadIdx.x, (uint64_t)S.frame[0], (uint64_t)S.frame[1], (uint64_t)S.frame[2],
-                                          (TA_HOT_ADJ || !ADJ) ? hot_label_of<T>(Ac) : 0u, wg_);
+    flush_tables<NW, ADJ, MOM2, (TA_HOT_ADJ || !ADJ), LDS>(Ac, S, threadIdx.x, (uint64_t)S.frame[0], (uint64_t)S.frame[1], (uint64_t)S.frame[2],
+                                      (TA_HOT_ADJ || !ADJ) ? hot_label_of<T>(Ac) : 0u, wg_);
 #else
-        if (wg_ == 0xffffffffu) S.frame[3] = 1;
+    if (wg_ == 0xffffffffu) S.frame[3] = 1;
 #endif
 #ifdef TA_BARSTAMP
-        if (lane == 0) {
-            uint32_t* fl = cold_args(kp)->flags;
-            const uint64_t tb_end = __builtin_amdgcn_s_memtime();
-            atomicAdd(&fl[8], (uint32_t)((tb_scan - tb_start) >> 8)); atomicAdd(&fl[9], (uint32_t)((tb_bar - tb_scan) >> 8));
-            atomicAdd(&fl[10], (uint32_t)((tb_end - tb_bar) >> 8)); atomicAdd(&fl[11], 1u);
-        }
-#endif
-        if (!PERSIST) break;
-        __syncthreads();                     // (the tile origin has been read by every thread's flush)
-        if (tid == 0) S.frame[3] = next;
-        __syncthreads();
-        tile = S.frame[3];
+    if (lane == 0) {
+        uint32_t* fl = cold_args(kp)->flags;
+        const uint64_t tb_end = __builtin_amdgcn_s_memtime();
+        atomicAdd(&fl[8], (uint32_t)((tb_scan - tb_start) >> 8)); atomicAdd(&fl[9], (uint32_t)((tb_bar - tb_scan) >> 8));
+        atomicAdd(&fl[10], (uint32_t)((tb_end - tb_bar) >> 8)); atomicAdd(&fl[11], 1u);
     }
+#endif
 }
 
 // (several entry points only because the VGPR budget is an attribute and must be a literal)
@@ -1575,14 +1459,11 @@ template <typename T, int VPL, int RB, bool MOM2, bool EDGE>
 __global__ void __launch_bounds__(WAVES * 64) __attribute__((amdgpu_num_vgpr(TA_CAP_ADJ))) scan_kernel(SweepArgs A, ScanSplit sp, uint32_t wg0) {
     scan_kernel_body<T, VPL, RB, true, MOM2, EDGE, EDGE ? 0 : TA_PIN_ADJ>(A, sp, wg0);
 }
-// the full tiles of a uint32 volume with adjacency: two rows per wave, five waves per SIMD.
-// TA_PERSIST (measured, NOT adopted: profiles/r04_NOTES.md): 1280 persistent workgroups that take tiles from per-XCD queues and
-// leave the flush's global atomics in flight.  C4 1.30 ms against 1.07 ms with a workgroup per tile -- the same instructions
-// (SQ_INSTS_* equal to 1 %), but the waves are parked twice as long (SQ_WAIT_ANY 2.3e9 against 1.1e9 quad-cycles).
+// the full tiles of a uint32 volume with adjacency: two rows per wave, five waves per SIMD
 template <typename T, int VPL, int RB, bool MOM2>
 __global__ void __launch_bounds__(WAVES * 64) __attribute__((amdgpu_num_vgpr(TA_CAP_ADJ2))) scan_two_rows_kernel(SweepArgs A, ScanSplit sp, uint32_t wg0) {
     static_assert(RB == 2 && VPL == 4, "the 13-register landing zone holds two rows of four voxels a lane");
-    scan_kernel_body<T, VPL, RB, true, MOM2, false, TA_PIN_ADJ2, TA_PERSIST != 0, (TA_PLANES_IN_FLIGHT == 2 ? TA_PIN_ADJ2B : 0)>(A, sp, wg0);
+    scan_kernel_body<T, VPL, RB, true, MOM2, false, TA_PIN_ADJ2>(A, sp, wg0);
 }
 template <typename T, int VPL, int RB, bool MOM2, bool EDGE>
 __global__ void __launch_bounds__(WAVES * 64) __attribute__((amdgpu_num_vgpr(TA_CAP_MOM))) scan_noadj_kernel(SweepArgs A, ScanSplit sp, uint32_t wg0) {
@@ -1628,8 +1509,7 @@ static void launch_scan_tt(hipStream_t s, const SweepArgs& a, hipEvent_t ev_star
         if (n_ed && !sp.padded) hipExtLaunchKernelGGL((scan_wide_kernel<T, VPL, RB, MOM2, true>), dim3(n_ed), block, 0, s, ed0, ed1, 0, a, sp, n_in);
     } else if constexpr (ADJ) {
         if constexpr (VPL == 4 && RB == 2) {
-            const uint32_t grid = TA_PERSIST ? (n_in < (uint32_t)TA_PERSIST_WGS ? n_in : (uint32_t)TA_PERSIST_WGS) : n_in;
-            if (n_in) hipExtLaunchKernelGGL((scan_two_rows_kernel<T, VPL, RB, MOM2>), dim3(grid), block, 0, s, in0, in1, 0, a, sp, 0u);
+            if (n_in) hipExtLaunchKernelGGL((scan_two_rows_kernel<T, VPL, RB, MOM2>), dim3(n_in), block, 0, s, in0, in1, 0, a, sp, 0u);
         } else {
             if (n_in) hipExtLaunchKernelGGL((scan_kernel<T, VPL, RB, MOM2, false>), dim3(n_in), block, 0, s, in0, in1, 0, a, sp, 0u);
         }

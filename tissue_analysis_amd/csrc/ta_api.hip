@@ -20,7 +20,7 @@ int fail(int code, const char* fmt, ...) {
 
 namespace {
 
-constexpr int SMALL_WORDS = ta::SMALL_WORDS_DEV;   // flags, cursor, max label, parked hot-row pointer (2 words), tile queues (8)
+constexpr int SMALL_WORDS = ta::SMALL_WORDS_DEV;   // flags, cursor, max label, parked hot-row pointer (2 words)
 
 uint32_t* flags_dev(ta_ctx* c) { return (uint32_t*)c->small.p; }
 uint32_t* cursor_dev(ta_ctx* c) { return (uint32_t*)c->small.p + ta::NFLAGS; }

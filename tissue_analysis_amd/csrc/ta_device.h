@@ -50,11 +50,7 @@ struct SweepArgs {
 // init_kernel and fetched with a scalar load where it is needed.
 constexpr int HOTW = 16;             // u64 words of a hot row: sums u64[NSUM] | boxes i32[NBOX] | padding
 constexpr int HOT_PTR_WORD = NFLAGS + 2;   // uint32 index into the flags buffer, 8-byte aligned
-// Tile queues of the persistent sweep kernel (one counter per XCD, zeroed by init_kernel before every sweep): a workgroup
-// takes the next tile of its own XCD's list -- consecutive tiles stay on one XCD's L2 -- and helps the others when it is empty.
-constexpr int QUEUE_WORD = NFLAGS + 4, NQUEUES = 8;
-constexpr int SMALL_WORDS_DEV = NFLAGS + 4 + NQUEUES;     // flags | pair cursor | max label | hot-row pointer (2) | tile queues
-constexpr uint32_t NO_TILE = 0xFFFFFFFFu;
+constexpr int SMALL_WORDS_DEV = NFLAGS + 4;               // flags | pair cursor | max label | hot-row pointer (2)
 
 __device__ __forceinline__ uint32_t hash_u32(uint32_t x) {
     x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
@@ -64,13 +60,9 @@ __device__ __forceinline__ uint32_t hash_pair(uint32_t lo, uint32_t hi) {
     return hash_u32(lo * 0x9E3779B1u ^ hash_u32(hi));
 }
 
-// the adds / minima of a tile flush into the device-global tables.  TA_FLUSH_SCOPE (ta_sweep_switches.h) is the memory scope they are
-// issued with: agent = performed where every XCD sees them; workgroup (an ABLATION: results wrong across XCDs) = in the issuing XCD's L2
-#ifndef TA_FLUSH_SCOPE
-#define TA_FLUSH_SCOPE __HIP_MEMORY_SCOPE_AGENT
-#endif
-__device__ __forceinline__ void flush_add(unsigned long long* p, unsigned long long v) { (void)__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, TA_FLUSH_SCOPE); }
-__device__ __forceinline__ void flush_min(int32_t* p, int32_t v) { (void)__hip_atomic_fetch_min(p, v, __ATOMIC_RELAXED, TA_FLUSH_SCOPE); }
+// the adds / minima of a tile flush into the device-global tables: agent scope = performed where every XCD sees them
+__device__ __forceinline__ void flush_add(unsigned long long* p, unsigned long long v) { (void)__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ void flush_min(int32_t* p, int32_t v) { (void)__hip_atomic_fetch_min(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 // Insert/accumulate one pair into the device-global table.  Slots only ever go EMPTY -> key
 // inside a launch, so a stale EMPTY read is repaired by the CAS and a non-EMPTY read is final.

@@ -18,11 +18,6 @@ constexpr int LPROBE = 16;        // max probes before spilling to global atomic
 constexpr int PPROBE = 32;
 constexpr int MAX_TILE_PLANES = 64;
 constexpr uint32_t LABEL_LIMIT = 1u << 28;    // max_label < 2^28: the two top bits of a record word are free
-// TA_PCNT64 (measured, not adopted): a pair's three per-axis face counts of ONE tile in a u64 LDS word, 21 bits each (a tile
-// holds at most 16 rows x 512 columns x 64 planes = 2^19 voxels, so a field cannot carry into the next): 8 bytes per slot
-// instead of 12, but every LDS atomic on it costs twice the cycles of a u32 one
-constexpr int PCNT_BITS = 21;
-constexpr uint64_t PCNT_MASK = (1ull << PCNT_BITS) - 1ull;
 
 __device__ __forceinline__ uint32_t lane_shr1(uint32_t src, uint32_t lane0_value) {
     // lane i <- src of lane i-1 ; lane 0 keeps lane0_value   (DPP wave_shr:1)
@@ -78,7 +73,7 @@ struct SumPack {
             w[2] = w[3] = 0ull;
         }
     }
-    // adds the words of one slot (one replica) to L
+    // adds the words of one slot to L
     template <bool MOM2>
     static __device__ __forceinline__ void unpack_add(const uint64_t* w, LocalSums& L) {
         if (MOM2) {
@@ -161,7 +156,6 @@ __device__ __forceinline__ void hot_row_init(const SweepArgs& A, const int tid, 
 __device__ __forceinline__ void hot_row_init(const SweepArgs& A, const int tid) { hot_row_init(A, tid, blockIdx.x); }
 
 // HOT = false compiles the hot-row path out (the naive cross-check kernel's rows; the sweep uses it for every mask).
-// RESET: every slot that held something is emptied again as it is read (the persistent kernel goes on with the next tile).
 //
 // DENSE flush.  A CU issues a global atomic wave-instruction about every 50 ns whatever the number of lanes that take part
 // (MI355X_MICROARCH.md), and a tile's tables are mostly empty -- ~38 of 128 label slots, ~120 of 512 pair slots on C4: walked
@@ -169,7 +163,7 @@ __device__ __forceinline__ void hot_row_init(const SweepArgs& A, const int tid) 
 // slots are first GATHERED into two lists (a ballot and an LDS counter per wave; the lists live in the record buffers of
 // waves 0 and 1, which nobody needs any more), and then the first K threads flush the K labels -- and the LAST K' threads
 // the K' pairs, so that the two kinds of global traffic start on different waves -- with every lane of an instruction alive.
-template <int NW, bool ADJ, bool MOM2, bool HOT, typename LDS, int NT = WAVES * 64, bool RESET = false>
+template <int NW, bool ADJ, bool MOM2, bool HOT, typename LDS>
 __device__ __forceinline__ void flush_tables(const SweepArgs& A, LDS& S, const int tid, const uint64_t A0,
                                              const uint64_t B0, const uint64_t C0, const uint32_t hot,
                                              const uint32_t wg) {
@@ -180,6 +174,7 @@ __device__ __forceinline__ void flush_tables(const SweepArgs& A, LDS& S, const i
                   "the slot lists of the flush live in the record buffers of the waves");
     uint16_t* const llist = reinterpret_cast<uint16_t*>(&S.wave[0].cql[0]);
     uint16_t* const plist = reinterpret_cast<uint16_t*>(&S.wave[1].cql[0]);
+    constexpr int NT = WAVES * 64;                         // threads of the workgroup: every one takes part
     const int lane = tid & 63;
     if (tid < 2) S.fcnt[tid] = 0u;
     __syncthreads();
@@ -212,7 +207,7 @@ __device__ __forceinline__ void flush_tables(const SweepArgs& A, LDS& S, const i
     // through LDS for that: the pair table's keys and counts are read into registers first (two pairs a thread at most; their home
     // slots' global reads are in flight from then on), the sums are staged where the pair table was, and the pairs' adds go last.
     constexpr int NS = MOM2 ? NSUM : 4;
-    constexpr bool TR = ADJ && !RESET && TA_FLUSH_TRANSPOSE != 0 && !TA_PCNT64 && PSLOTS <= 2 * NT &&
+    constexpr bool TR = ADJ && TA_FLUSH_TRANSPOSE != 0 && PSLOTS <= 2 * NT &&
                         (size_t)LSLOTS * NSUM * 8 <= sizeof(S.pkeys) + sizeof(S.pcnt);
     if constexpr (TR) {
         static_assert(!TR || offsetof(LDS, pcnt) == offsetof(LDS, pkeys) + sizeof(S.pkeys), "the staged sums run from the pair keys on into the pair counts");
@@ -242,11 +237,13 @@ __device__ __forceinline__ void flush_tables(const SweepArgs& A, LDS& S, const i
             const uint32_t label = S.lkeys[i];
             LocalSums L;
             L.n = L.sa = L.sb = L.sc = L.saa = L.sab = L.sac = L.sbb = L.sbc = L.scc = 0;
-#pragma unroll
-            for (int rp = 0; rp < LDS::REP; ++rp) {
+            // (ONE pass, written as a loop: the last trace of the replicated sums that were tried here.  Written straight,
+            //  the nine kernels with adjacency and without second moments come out with the same instructions in another
+            //  order and in other registers -- and the sweep is only changed against identical assembly, so the shape stays)
+            for (int pass = 0; pass < 1; ++pass) {
                 uint64_t w[4] = {0ull, 0ull, 0ull, 0ull};
 #pragma unroll
-                for (int k = 0; k < NW; ++k) w[k] = S.lsum[(i * LDS::REP + rp) * NW + k];
+                for (int k = 0; k < NW; ++k) w[k] = S.lsum[i * NW + k];
                 LDS::Pack::template unpack_add<MOM2>(w, L);
             }
             uint64_t g[NSUM];
@@ -299,15 +296,7 @@ __device__ __forceinline__ void flush_tables(const SweepArgs& A, LDS& S, const i
             const uint32_t lo = (uint32_t)(key >> 32), hi = (uint32_t)key;
             const uint32_t gh = hash_pair(lo, hi) & A.pairs.mask;
             const uint64_t gk = __hip_atomic_load(&A.pairs.keys[gh], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#if TA_PCNT64
-            const uint64_t c = S.pcnt[i];
-            const uint32_t f0 = (uint32_t)(c & PCNT_MASK), f1 = (uint32_t)((c >> PCNT_BITS) & PCNT_MASK), f2 = (uint32_t)(c >> (2 * PCNT_BITS));
-            if (RESET) S.pcnt[i] = 0ull;
-#else
             const uint32_t f0 = S.pcnt[i * 3 + 0], f1 = S.pcnt[i * 3 + 1], f2 = S.pcnt[i * 3 + 2];
-            if (RESET) { S.pcnt[i * 3 + 0] = 0u; S.pcnt[i * 3 + 1] = 0u; S.pcnt[i * 3 + 2] = 0u; }
-#endif
-            if (RESET) S.pkeys[i] = EMPTY_KEY;
             pair_add_global_from(A.pairs, lo, hi, f0, f1, f2, A.flags, gh, gk);
         }
     }
@@ -322,22 +311,12 @@ __device__ __forceinline__ void flush_tables(const SweepArgs& A, LDS& S, const i
         const uint32_t label = S.lkeys[i];
         LocalSums L;
         L.n = L.sa = L.sb = L.sc = L.saa = L.sab = L.sac = L.sbb = L.sbc = L.scc = 0;
+        uint64_t w[4] = {0ull, 0ull, 0ull, 0ull};
 #pragma unroll
-        for (int rp = 0; rp < LDS::REP; ++rp) {            // (the replicas a label's runs were spread over: see drain_run_group)
-            uint64_t w[4] = {0ull, 0ull, 0ull, 0ull};
-#pragma unroll
-            for (int k = 0; k < NW; ++k) w[k] = S.lsum[(i * LDS::REP + rp) * NW + k];
-            LDS::Pack::template unpack_add<MOM2>(w, L);
-        }
+        for (int k = 0; k < NW; ++k) w[k] = S.lsum[i * NW + k];
+        LDS::Pack::template unpack_add<MOM2>(w, L);
         const uint32_t bx0 = S.lbox[i * 8 + 0], bx1 = S.lbox[i * 8 + 1], bx2 = S.lbox[i * 8 + 2];
         const uint32_t bx3 = S.lbox[i * 8 + 3], bx4 = S.lbox[i * 8 + 4], bx5 = S.lbox[i * 8 + 5];
-        if (RESET) {
-            S.lkeys[i] = INVALID_LABEL;
-#pragma unroll
-            for (int k = 0; k < NW * LDS::REP; ++k) S.lsum[i * NW * LDS::REP + k] = 0ull;
-            S.lbox[i * 8 + 0] = 0xFFFFFFFFu; S.lbox[i * 8 + 1] = 0xFFFFFFFFu; S.lbox[i * 8 + 2] = 0xFFFFFFFFu;
-            S.lbox[i * 8 + 3] = 0u; S.lbox[i * 8 + 4] = 0u; S.lbox[i * 8 + 5] = 0u;
-        }
         if (label > A.max_label) { atomicOr(&A.flags[FLAG_RANGE], 1u); continue; }
         uint64_t g[NSUM];
         local_to_global(L, A0, B0, C0, g);

@@ -1,5 +1,5 @@
 // ta_sweep_switches.h -- every compile-time switch of the sweep (kernels_scan.hip, ta_sweep_common.h) in ONE place: what the product
-// is built with (the defaults below), what experiments measured and left off, and the instrumentation / ablation builds of
+// is built with (the defaults below), what experiments measured before they were deleted, and the instrumentation / ablation builds of
 // scripts/build_variant.py (`python scripts/build_variant.py NAME -DTA_...` -> scratch/libNAME.so; never the product library).
 // The switches are USED where the code they change lives; this header only names and documents them.
 #pragma once
@@ -63,25 +63,12 @@
 #define TA_U16_MOM_RB 2          // rows a wave of the moments-only uint16 kernel (512 columns each)
 #endif
 
-// ---- built, measured, left OFF (kept because they are one flag away from a same-call A/B) -----------------------------------
-#ifndef TA_LSUM_REP
-#define TA_LSUM_REP 1            // 2: two replicas of a label slot's sums by row parity (halves the lanes sharing an add's address): +4 % time
-#endif
-#ifndef TA_PCNT64
-#define TA_PCNT64 0              // 1: a pair's three face counts in one u64 LDS word (21 bits each): equal time, twice the cost per atomic
-#endif
-#ifndef TA_PERSIST
-#define TA_PERSIST 0             // 1: persistent workgroups on per-XCD tile queues for the narrow uint32 kernel: 1.30 against 1.07 ms (round 4)
-#endif
-#ifndef TA_PERSIST_WGS
-#define TA_PERSIST_WGS (256 * 5) // ... how many
-#endif
-#ifndef TA_PERSIST_SINGLE_QUEUE
-#define TA_PERSIST_SINGLE_QUEUE 0
-#endif
-#ifndef TA_PLANES_IN_FLIGHT
-#define TA_PLANES_IN_FLIGHT 1    // 2: a second landing zone for the narrow uint32 kernel (109 VGPRs, four waves): slower (round 4)
-#endif
+// ---- tried, measured, deleted (the code is in git history before the commit that removed these switches) -----------------
+// Persistent workgroups on per-XCD tile queues for the narrow uint32 kernel (TA_PERSIST): 1.30 against 1.07 ms on C4 (round 4).
+// A second landing zone, two planes in flight at 109 VGPRs and four waves (TA_PLANES_IN_FLIGHT = 2): slower (round 4).
+// Two replicas of a label slot's sums by row parity (TA_LSUM_REP = 2): +4 % time.  A pair's three face counts in one u64 LDS
+// word of 21-bit fields (TA_PCNT64): equal time, twice the cost per LDS atomic.  Gone with them: TA_LDS_PAD, TA_DBG_EMIT and
+// TA_FLUSH_SCOPE (gfx950 encodes agent and workgroup scope alike: there was nothing to measure).
 
 // ---- ablations (results WRONG by construction; only the time matters) and instrumentation ---------------------------------------
 //   TA_ABLATE = 1 records produced and stored, nothing consumed; 2 = placed, not stored; 3 = not even placed
@@ -91,11 +78,9 @@
 //   TA_ABL_NOFACE0 / TA_ABL_NOFACE1 no axis-0 / axis-1 face records;  TA_ABL_NOSUMS, TA_ABL_NOBOX, TA_ABL_NOBOXHOT, TA_ABL_NOPCNT, TA_ABL_NOLOOP,
 //   TA_ABL_SHARE1 (every lane of an add its own address), TA_ABL_L2 (every plane re-reads the tile's first: an L2-resident run)
 //   TA_ABL_NOHALO = 1 a workgroup's first wave reads no row above (the row another tile owns: 12.5 % of the bytes fetched); 2 = no wave does
-//   TA_FLUSH_SCOPE the memory scope of the flush's global adds (gfx950 encodes agent and workgroup scope alike: nothing to measure)
 //   TA_RECCOUNT   flags[8..12] = face / run records and calls through the in-plane drain, faces / runs through the top-of-plane drains
 //   TA_BARSTAMP   flags[8..11] = cycles >> 8 over the waves: sweep of the tile, wait at the barrier before the flush, flush; wave-tiles
-//   TA_STAMPS     per-phase s_memtime stamps of the narrow kernels (scripts/probe_stamps.py);  TA_DBG_EMIT an in-kernel check of the
-//                 predicated stores' offsets;  TA_LDS_PAD extra LDS per workgroup (fewer workgroups a CU)
+//   TA_STAMPS     per-phase s_memtime stamps of the narrow kernels (scripts/probe_stamps.py)
 #ifndef TA_ABLATE
 #define TA_ABLATE 0
 #endif
