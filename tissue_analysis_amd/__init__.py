@@ -20,12 +20,14 @@ from .cell_meshes import CellMeshes
 from .label_overlap import LabelOverlap, label_overlap, lineage_from_images
 from .cell_junctions import CellJunctions, cell_junctions
 from .wall_geometry import WallGeometry, wall_geometry
+from .components import LabelComponents, label_components
 from .property_graph import PropertyGraph
 from .graph_from_image import graph_from_image, property_graph_to_dataframe
 
 __all__ = ["SpatialImage", "NPLIST", "LIST", "DICT", "AbstractSpatialImageAnalysis",
            "SpatialImageAnalysis3D", "SpatialImageAnalysis", "Extraction", "extract_volume", "SignalStats", "CellMeshes",
            "LabelOverlap", "label_overlap", "lineage_from_images", "CellJunctions", "cell_junctions", "WallGeometry", "wall_geometry",
+           "LabelComponents", "label_components",
            "dilation", "dilation_by", "real_indices", "return_list_of_vectors", "hollow_out_cells", "wall", "contact_surface",
            "coordinates_centering3D", "compute_covariance_matrix", "eigen_values_vectors", "distance",
            "PropertyGraph", "graph_from_image", "property_graph_to_dataframe"]

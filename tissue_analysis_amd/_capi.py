@@ -64,6 +64,14 @@ JUNCTION_SYMBOLS = (
 # every symbol include/tissue_scan_wallgeo.h declares (same library)
 WALLGEO_SYMBOLS = ("ta_wallgeo_extract", "ta_wallgeo_get", "ta_wallgeo_spills", "ta_wallgeo_timing")
 
+# every symbol include/tissue_scan_components.h declares (same library)
+COMPONENT_SYMBOLS = (
+    "ta_components_extract", "ta_components_size", "ta_components_get", "ta_components_image", "ta_components_relabel",
+    "ta_components_timing",
+)
+COMPONENT_NONE = 0xFFFFFFFF            # TA_COMPONENT_NONE
+COMPONENT_MAX_VOXELS = 1 << 31         # voxels of a buffer the component pass takes
+
 
 def exchange_words(capacity_pairs):
     """uint64 words of one exchange block (TA_EXCHANGE_WORDS in include/tissue_scan.h)."""
@@ -182,8 +190,14 @@ def load():
         "ta_wallgeo_get": (ci, [vp, vp, vp, vp, vp]),
         "ta_wallgeo_spills": (ci, [vp, P(u32)]),
         "ta_wallgeo_timing": (ci, [vp, P(ctypes.c_double)]),
+        "ta_components_extract": (ci, [vp]),
+        "ta_components_size": (ci, [vp, P(u64)]),
+        "ta_components_get": (ci, [vp, vp, vp, vp, vp, vp]),
+        "ta_components_image": (ci, [vp, i64, i64, vp]),
+        "ta_components_relabel": (ci, [vp, vp, u64]),
+        "ta_components_timing": (ci, [vp, P(ctypes.c_double), P(ctypes.c_double)]),
     }
-    for name in SYMBOLS + SIGNAL_SYMBOLS + MESH_SYMBOLS + OVERLAP_SYMBOLS + JUNCTION_SYMBOLS + WALLGEO_SYMBOLS:
+    for name in SYMBOLS + SIGNAL_SYMBOLS + MESH_SYMBOLS + OVERLAP_SYMBOLS + JUNCTION_SYMBOLS + WALLGEO_SYMBOLS + COMPONENT_SYMBOLS:
         fn = getattr(lib, name)      # AttributeError here == the .so does not match the header
         fn.restype, fn.argtypes = sig[name]
     if lib.ta_version() != ABI_VERSION:
@@ -295,6 +309,7 @@ class Context(object):
                                        _i64x3(a.shape), _i64x3(a.strides)))
         self._vol_layout = (tuple(a.shape), tuple(s // a.dtype.itemsize for s in a.strides))
         self._owned_planes = int(a.shape[int(np.argmax(a.strides))])         # planes of the slowest MEMORY axis
+        self._halo_planes = 0
 
     def relabel(self, lut):
         """In place on the resident volume: v -> lut[v] for v < len(lut) (host uint32 table)."""
@@ -392,6 +407,7 @@ class Context(object):
         self._vol_layout = (tuple(d), (d[1] * d[2], d[2], 1))
         self._keep = [keep]
         self._owned_planes = int(buf_dims[0]) - (1 if has_low_halo else 0)
+        self._halo_planes = 1 if has_low_halo else 0
         # a torch tensor that is a view of a larger storage: tell the library how many bytes are readable behind it
         try:
             st = keep.untyped_storage()
@@ -595,6 +611,49 @@ class Context(object):
         ms = ctypes.c_double(0.0)
         _check(self._lib.ta_wallgeo_timing(self._h, ctypes.byref(ms)))
         return ms.value
+
+    # -- connected components of the labels (include/tissue_scan_components.h)
+    def components_extract(self):
+        """Enqueue the union-find over the label volume, up to the count of its components."""
+        _check(self._lib.ta_components_extract(self._h))
+
+    def components_size(self):
+        """Rows of the component table; settles it."""
+        n = ctypes.c_uint64(0)
+        _check(self._lib.ta_components_size(self._h, ctypes.byref(n)))
+        return int(n.value)
+
+    def components_get(self):
+        """(label u32[R], n u64[R], first i32[R, 3], bbox i32[R, 6], sum1 u64[R, 3]): one row per component, sorted by
+        (label, first), coordinates in array axes."""
+        R = self.components_size()
+        label, n = np.zeros(R, dtype=np.uint32), np.zeros(R, dtype=np.uint64)
+        first, bbox = np.zeros((R, 3), dtype=np.int32), np.zeros((R, 6), dtype=np.int32)
+        sum1 = np.zeros((R, 3), dtype=np.uint64)
+        _check(self._lib.ta_components_get(self._h, label.ctypes.data, n.ctypes.data, first.ctypes.data, bbox.ctypes.data, sum1.ctypes.data))
+        return label, n, first, bbox, sum1
+
+    def components_image(self, first_plane=0, nplanes=None):
+        """uint32 rows of the voxels of `nplanes` buffer planes from `first_plane` along memory axis 0 (None: all that follow), flat
+        and in memory order; COMPONENT_NONE where the voxel's component has no row."""
+        planes = self.owned_planes() + self._halo_planes          # (asked of the library: a size-1 axis moves the slowest MEMORY axis)
+        per_plane = int(np.prod(self._vol_layout[0])) // planes
+        if nplanes is None:
+            nplanes = planes - int(first_plane)
+        out = np.zeros(max(int(nplanes), 0) * per_plane, dtype=np.uint32)
+        _check(self._lib.ta_components_image(self._h, int(first_plane), int(nplanes), out.ctypes.data))
+        return out
+
+    def components_relabel(self, new_label):
+        """In place on the resident volume: every voxel of row r becomes new_label[r] (host uint32 table, one entry per row)."""
+        new_label = np.ascontiguousarray(new_label, dtype=np.uint32)
+        _check(self._lib.ta_components_relabel(self._h, ctypes.c_void_p(new_label.ctypes.data), int(new_label.size)))
+
+    def components_timing(self):
+        """(milliseconds of the kernels that walk the volume, milliseconds of everything after them) of a settled table."""
+        a, b = ctypes.c_double(0.0), ctypes.c_double(0.0)
+        _check(self._lib.ta_components_timing(self._h, ctypes.byref(a), ctypes.byref(b)))
+        return a.value, b.value
 
     def max_label(self):
         v = ctypes.c_uint32(0)

@@ -357,6 +357,17 @@ void companion_on_new_volume(const ta_ctx* c, Companion& v) {
     if (v.p && !companion_matches(c, v)) { v.p = nullptr; v.owned.release(); v.itemsize = 0; }
 }
 
+void volume_labels_changed(ta_ctx* c) {
+    drop_census(c);                 // (the ids changed: a compacted context goes back to dense rows until it is compacted again)
+    c->extracted = c->checked = false;
+    c->wall_median_count = -1;
+    c->wall_records = -1;           // the staged wall records carry the OLD labels: a fetch must ask for a fresh count
+    c->wall_region = 0; c->wall_not_staged = 0;
+    overlap_on_new_volume(c);
+    junctions_on_new_volume(c);
+    components_on_new_volume(c);
+}
+
 extern "C" {
 
 TA_API int ta_version(void) { return TA_ABI_VERSION; }
@@ -425,7 +436,7 @@ TA_API int ta_ctx_destroy(ta_ctx* c) {
     c->wall_stage.release();
     c->wall_medians.release();
     c->census.release(); c->census_ids.release(); c->compact_vol.release(); c->census_list.release();
-    c->sig.release(); c->mesh.release(); c->ov.release(); c->jn.release(); c->wg.release();
+    c->sig.release(); c->mesh.release(); c->ov.release(); c->jn.release(); c->wg.release(); c->cc.release();
     if (c->h_small) (void)hipHostFree(c->h_small);
     destroy_events(c->ev); destroy_events(c->tune_ev);
     for (auto& e : c->ring) if (e) (void)hipEventDestroy(e);
@@ -575,6 +586,7 @@ TA_API int ta_volume_set(ta_ctx* c, const void* host_ptr, int itemsize, const in
     wallgeo_on_new_volume(c);
     overlap_on_new_volume(c);
     junctions_on_new_volume(c);
+    components_on_new_volume(c);
     return TA_OK;
 }
 
@@ -603,6 +615,7 @@ TA_API int ta_volume_set_device(ta_ctx* c, const void* dev_ptr, int itemsize, co
     wallgeo_on_new_volume(c);
     overlap_on_new_volume(c);
     junctions_on_new_volume(c);
+    components_on_new_volume(c);
     return TA_OK;
 }
 
@@ -629,13 +642,7 @@ TA_API int ta_volume_relabel(ta_ctx* c, const uint32_t* lut, uint32_t lut_len) {
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     d.release();
     if (e != hipSuccess) return fail(TA_EHIP, "relabel: %s", hipGetErrorString(e));
-    drop_census(c);                 // (the ids changed: a compacted context goes back to dense rows until it is compacted again)
-    c->extracted = c->checked = false;
-    c->wall_median_count = -1;
-    c->wall_records = -1;           // the staged wall records carry the OLD labels: a fetch must ask for a fresh count
-    c->wall_region = 0; c->wall_not_staged = 0;
-    overlap_on_new_volume(c);
-    junctions_on_new_volume(c);
+    volume_labels_changed(c);
     return TA_OK;
 }
 
@@ -1189,6 +1196,7 @@ TA_API int ta_volume_rerank(ta_ctx* c) {
     c->rerank_check = true;
     c->vol_max = -1;
     junctions_on_new_volume(c);     // (the caller edited the labels in place)
+    components_on_new_volume(c);
     return TA_OK;
 }
 

@@ -146,6 +146,21 @@ struct WallGeoState {
     void release() { out.release(); hash.release(); destroy_events(ev); }
 };
 
+// connected components of the labels (include/tissue_scan_components.h)
+struct ComponentState {
+    DevBuf parent;                                      // u32[voxels]: the union-find forest, then root / flagged slot: the row image's source
+    DevBuf work;                                        // per wave: root counts u32[W] | slot offsets u64[W] | scan scratch
+    DevBuf slots;                                       // per slot: root u32[S] | row u32[S] | n u64[S] | sum1 u64[S][3] | first u64[S] | box i32[S][6]
+    DevBuf sort;                                        // sort keys u64[S] x 2 | order u32[S] x 2 | radix temp
+    DevBuf rows;                                        // the table, S rows of room: label u32 | n u64 | first i32[3] | bbox i32[6] | sum1 u64[3]
+    DevBuf small;                                       // slots with owned voxels u64
+    DevBuf image;                                       // staging of ta_components_image and of ta_components_relabel's table
+    int state = 0;                                      // 0 = no tables, 1 = union-find and count enqueued, 2 = settled
+    uint64_t waves = 0, nslots = 0, nrows = 0;
+    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // union-find begin, end | scan end | emit begin, statistics end | table end
+    void release() { parent.release(); work.release(); slots.release(); sort.release(); rows.release(); small.release(); image.release(); destroy_events(ev); }
+};
+
 struct ta_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -233,6 +248,7 @@ struct ta_ctx {
     OverlapState ov;
     JunctionState jn;
     WallGeoState wg;
+    ComponentState cc;
 };
 
 inline int use_device(ta_ctx* c) {
@@ -246,11 +262,16 @@ inline const void* sweep_vol(const ta_ctx* c) { return c->compact ? c->compact_v
 // Drain the stream and validate the flags of the last pass; grows the adjacency table and re-runs when it overflowed.
 int finish_extract(ta_ctx* c);
 
-// A new label volume (for the overlap and the junctions also: new label values in it).  Defined by the features, called by the core.
+// A new label volume (for the overlap, the junctions and the components also: new label values in it).  Defined by the features, called by the core.
 void signal_on_new_volume(ta_ctx* c);
 void overlap_on_new_volume(ta_ctx* c);
 void junctions_on_new_volume(ta_ctx* c);
 void wallgeo_on_new_volume(ta_ctx* c);
+void components_on_new_volume(ta_ctx* c);
+
+// New label values in the resident volume, written by the library itself (ta_volume_relabel, ta_components_relabel): the census
+// and a compacted state end, the extraction and everything keyed by the old labels is stale.  Defined by the core.
+void volume_labels_changed(ta_ctx* c);
 
 // Companions: these touch the companion's own fields only.  The setters check the arguments against the label volume and drain the
 // stream (a pass in flight may still read the old companion) before they change anything; a failure later leaves no companion set.

@@ -552,6 +552,41 @@ class ResidentVolume(object):
         self.ms["junctions"] = (time.perf_counter() - t0) * 1e3
         return j
 
+    def components(self, voxelsize=(1.0, 1.0, 1.0)):
+        """The connected components of the labels of the resident volume: a `LabelComponents` with one row per face-connected
+        blob of equal label, in the ids of the image and with coordinates in array axes.  A block-based union-find on the GPU;
+        no sweep is needed."""
+        import time
+        from .components import context_components
+        t0 = time.perf_counter()
+        cc = context_components(self.ctx, voxelsize)
+        self.ms["components"] = (time.perf_counter() - t0) * 1e3
+        return cc
+
+    def components_image(self, first_plane=0, nplanes=None):
+        """uint32 image of the row of `components()` every voxel belongs to, with the axes and the layout of the image; of
+        `nplanes` planes from `first_plane` along the slowest memory axis only when those are given."""
+        flat = self.ctx.components_image(first_plane, nplanes)
+        shape = list(self.host.shape)
+        strides = [s // self.host.dtype.itemsize * 4 for s in self.host.strides]
+        if flat.size != self.host.size:
+            slow = max((d for d in range(3) if shape[d] != 1), key=lambda d: strides[d])
+            shape[slow] = flat.size // (self.host.size // shape[slow])
+        return np.lib.stride_tricks.as_strided(flat, shape=shape, strides=strides)
+
+    def relabel_components(self, new_label, features=_capi.F_ALL):
+        """Every voxel of row r of `components()` becomes new_label[r], on the resident volume AND on `self.host` (copied back),
+        then sweep the new volume.  `LabelComponents.split_map()` and `.erase_map()` make such tables."""
+        new_label = np.asarray(new_label)
+        if new_label.size and (int(new_label.min()) < 0 or int(new_label.max()) > np.iinfo(self.host.dtype).max):
+            raise ValueError("a new label does not fit the image dtype %s" % self.host.dtype)
+        self.ctx.components_relabel(new_label)
+        if not self.host.flags.writeable:
+            self.host = self.host.copy()
+            self.is_input = False
+        self.ctx.get_volume(self.host)
+        return self.extract(features)
+
     def wall_geometry(self, voxelsize=(1.0, 1.0, 1.0)):
         """The geometry of every wall of the resident volume: a `WallGeometry` (signed face counts, first and second sums of the
         face centres) whose rows are the pairs of the current extraction (swept first when there is none), in the ids of the

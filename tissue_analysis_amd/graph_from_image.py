@@ -129,7 +129,8 @@ def tissue_tables(analysis, labels, background, properties, property_as_real=Tru
     `labels`: the vertex ids (any order, distinct).  Returns a PropertyGraph whose columns are plain numpy arrays.
     With an intensity image `signal`, 'mean_signal' (vertex: cell_signal's mean) and 'wall_signal' (edge: wall_signal's
     face-weighted mean) can be asked for too.  'wall_centroid', 'wall_normal' and 'wall_projected_area' (edge: the columns of
-    `analysis.wall_geometry()`) run the wall-geometry pass; a property list without them does not."""
+    `analysis.wall_geometry()`) run the wall-geometry pass; a property list without them does not.  'n_components' (vertex:
+    the face-connected blobs the label consists of, `analysis.label_components()`) runs the component pass, likewise."""
     x = analysis.extraction
     ids = np.asarray(labels, dtype=np.int64).reshape(-1)
     pairs = _PairView(analysis, ids, min_contact_area)
@@ -217,6 +218,9 @@ def tissue_tables(analysis, labels, background, properties, property_as_real=Tru
             graph.set_edge_column('wall_normal', np.where(found[:, None], geo.normal()[at], np.nan), found, _show_vector)
         if 'wall_projected_area' in properties:
             graph.set_edge_column('wall_projected_area', np.where(found, geo.projected_area(real)[at], np.nan), found)
+    if 'n_components' in properties:
+        blobs = analysis.label_components().per_label()
+        graph.set_vertex_column('n_components', np.array([blobs.get(l, 0) for l in ids.tolist()], dtype=np.int64), present)
     return graph
 
 

@@ -206,6 +206,7 @@ class AbstractSpatialImageAnalysis(object):
         self._mesh_cache = {}
         self._junctions = None
         self._wall_geometry = None
+        self._components = None
         try:
             self.filepath, self.filename = split(image.info["Filename"])
         except Exception:
@@ -252,6 +253,10 @@ class AbstractSpatialImageAnalysis(object):
         """Re-upload and re-run the sweep after ``self.image`` was modified in place."""
         self._resident().upload(np.asarray(self.image))
         self._x = self._sweep()
+        self._forget()
+
+    def _forget(self):
+        """Drop everything derived from the labels of the image."""
         self._labels = None
         self._bbox = None
         self._neighbors = None
@@ -263,6 +268,7 @@ class AbstractSpatialImageAnalysis(object):
         self._mesh_cache = {}
         self._junctions = None
         self._wall_geometry = None
+        self._components = None
         self._voxel_layer1 = None
         self._voxel_layer18 = None
 
@@ -620,6 +626,62 @@ class AbstractSpatialImageAnalysis(object):
         """{(a, b, c, d): xyz} of every point where four labels meet (none excluded)."""
         return self.cell_junctions().cell_vertices(real=real)
 
+    # -- connected components of the labels (include/tissue_scan_components.h; a union-find over the resident volume on the GPU)
+    def label_components(self):
+        """One row per face-connected blob of equal label: a `LabelComponents` in the ids of the image and with this analysis'
+        voxel size.  Nothing is excluded here (the background and the ignored labels have rows).  Cached until `refresh()` or
+        an edit of the image."""
+        if getattr(self, "_components", None) is None:
+            self._components = self._resident().components(tuple(float(v) for v in self._voxelsize))
+        return self._components
+
+    def disconnected_labels(self):
+        """{label: k} of the labels whose voxels form k > 1 separate blobs, without the ignored labels."""
+        return self.label_components().fragmented(exclude=self._ignoredlabels)
+
+    def _current_components(self):
+        """`label_components()`, run again when the context no longer holds the tables it was read from."""
+        cc = self.label_components()
+        try:
+            held = self._resident().ctx.components_size() == len(cc)
+        except _capi.TissueScanError:
+            held = False
+        if not held:
+            self._components = None
+            cc = self.label_components()
+        return cc
+
+    def _relabel_components(self, new_label):
+        """Rows of the component table the context holds -> new labels, on the resident volume and in the image."""
+        rv = self._resident()
+        img = np.asarray(self.image)
+        top = int(np.iinfo(rv.host.dtype).max)
+        if np.issubdtype(img.dtype, np.integer):           # (new ids: they must survive the write-back too)
+            top = min(top, int(np.iinfo(img.dtype).max))
+        self._edit_image(rv, np.asarray(new_label, dtype=np.int64), top, lambda rv, table: rv.relabel_components(table))
+
+    def split_disconnected_labels(self):
+        """Modify the image so that every label is one face-connected blob: the largest blob of a label keeps the label, every
+        other one gets a new id above the largest label, in the order of the component table.  Returns {new id: old label}.
+        Raises ValueError, with the image untouched, when a new id does not fit the image dtype."""
+        cc = self._current_components()
+        new = cc.split_map()
+        changed = new != cc.label
+        if changed.any():
+            self._relabel_components(new)
+        return dict(zip(new[changed].tolist(), cc.label[changed].tolist()))
+
+    def remove_small_fragments(self, min_voxels, erase_value=0):
+        """Modify the image so that the blobs of a label that are not its largest and have fewer than `min_voxels` voxels read
+        `erase_value` (which joins the ignored labels, as in `remove_labels_from_image`).  Returns the number of blobs erased."""
+        cc = self._current_components()
+        new = cc.erase_map(min_voxels, erase_value)
+        changed = new != cc.label
+        if changed.any():
+            self._relabel_components(new)
+            self._ignoredlabels.update([int(erase_value)])
+        return int(changed.sum())
+
     # -- wall geometry (include/tissue_scan_wallgeo.h; one pass over the resident volume on the GPU)
     def wall_geometry(self):
         """Signed face counts, centroid sums and second moments of every wall: a `WallGeometry` in the ids of the image and with
@@ -871,35 +933,31 @@ class AbstractSpatialImageAnalysis(object):
     # -- image mutation (SIA:1114-1176): one lookup-table sweep on the GPU instead of per-label crops.
     # The reference leaves its caches (_labels, _bbox, _neighbors ...) stale after these calls; here the
     # relabelled volume is swept again in the same upload, so every later answer describes the new image.
+    def _edit_image(self, rv, values, top, relabel):
+        """One relabel of the resident volume `rv` (`relabel(rv, table)` -> the Extraction of the new volume) whose new label
+        values are `values`, none above `top`; the image is written back when it does not share rv's memory; every cache goes."""
+        img = np.asarray(self.image)
+        for v in (values.min(), values.max()) if values.size else ():
+            if not (0 <= int(v) <= top):
+                raise ValueError("value %r does not fit the image dtype %s" % (int(v), img.dtype))
+        x = relabel(rv, values)                   # resident volume and rv.host are relabelled; no new upload
+        target = img if img.ndim == 3 else img[:, :, None]
+        if not np.shares_memory(target, rv.host):          # the image had another dtype / layout: write it back
+            np.copyto(target, rv.host.astype(img.dtype), casting="unsafe")
+        self._x = x
+        self._forget()
+
     def _relabel_image(self, mapping):
         rv = self._resident_rows()
         top = np.iinfo(rv.host.dtype).max
-        lut = self._x.labels_of(np.arange(self._x.nrows)).astype(np.uint32)       # one entry per ROW: the row's own id
+        lut = self._x.labels_of(np.arange(self._x.nrows)).astype(np.int64)        # one entry per ROW: the row's own id
         for old, new in mapping.items():
             if not (0 <= int(new) <= top):
                 raise ValueError("value %r does not fit the image dtype %s" % (new, rv.host.dtype))
             row = self._x.row_of(old)
             if row >= 0:
                 lut[row] = int(new)
-        x = rv.relabel(lut)                       # resident volume and rv.host are relabelled; no new upload
-        img = np.asarray(self.image)
-        target = img if img.ndim == 3 else img[:, :, None]
-        if not np.shares_memory(target, rv.host):          # the image had another dtype / layout: write it back
-            np.copyto(target, rv.host.astype(img.dtype), casting="unsafe")
-        self._x = x
-        self._labels = None
-        self._bbox = None
-        self._neighbors = None
-        self._cell_layer1 = None
-        self._center_of_mass = {}
-        self._walls = None
-        self._wall_medians = None
-        self._signal_cache = None
-        self._mesh_cache = {}
-        self._junctions = None
-        self._wall_geometry = None
-        self._voxel_layer1 = None
-        self._voxel_layer18 = None
+        self._edit_image(rv, lut, top, lambda rv, table: rv.relabel(table.astype(np.uint32)))
 
     def fuse_labels_in_image(self, labels, verbose=True):  # SIA:1114-1136
         """Modify the image so the given labels are fused (to the min value)."""
