@@ -17,9 +17,14 @@ MAKERS = [
     lambda: np.asfortranarray(voronoi((22, 26, 40), 20, 92, np.uint32)),
     lambda: random_blocks((9, 11, 23), 12, 93, np.uint16),
     lambda: voronoi((5, 9, 260), 14, 94, np.uint32),
+    # uint16 rows of whole 16-byte strips, more than one of them: the only rows on which hollow_kernel and layer18_kernel take
+    # their eight-voxel vector loads and stores (layer18: 8-byte stores); the other uint16 volumes here have 70, 23 and 1 columns
+    lambda: voronoi((6, 9, 264), 14, 97, np.uint16),
+    # C-ordered uint32 rows that are NOT whole strips (the Fortran volume's rows in memory are 22 voxels, the long rows whole strips)
+    lambda: voronoi((7, 9, 23), 10, 98, np.uint32),
     lambda: voronoi((3, 4, 1), 3, 95, np.uint16),
 ]
-IDS = ["voronoi_u16", "voronoi_u32_fortran", "blocks", "long_rows", "one_column"]
+IDS = ["voronoi_u16", "voronoi_u32_fortran", "blocks", "long_rows", "u16_whole_strips", "u32_ragged_rows", "one_column"]
 
 
 @pytest.mark.parametrize("make", MAKERS, ids=IDS)
@@ -53,7 +58,7 @@ def test_hollow_on_other_integer_types_and_wrapping_sums():
     assert np.array_equal(hollow_out_cells(flat, 1, verbose=False), sia_oracle.hollow_out_cells(flat, 1))
 
 
-@pytest.mark.parametrize("make", MAKERS[:4], ids=IDS[:4])
+@pytest.mark.parametrize("make", MAKERS[:-1], ids=IDS[:-1])
 def test_cells_voxel_layer(make):
     vol = make()
     sia = SpatialImageAnalysis(SpatialImage(vol, voxelsize=(1., 1., 1.)), ignoredlabels=0, return_type=DICT, background=1)
