@@ -59,3 +59,47 @@ def test_failed_ctx_create_leaks_nothing(sanitized, tmp_path):
     err = p.stderr.decode(errors="replace")
     assert p.returncode == 0, err[-3000:]
     assert "LeakSanitizer" not in err and "AddressSanitizer" not in err, err[-3000:]
+
+
+# what the entry points of ta_api_walls.hip, ta_api_sparse.hip and ta_api_exchange.hip said to a NULL context before they moved there
+NULL_CTX_ANSWERS = [
+    "ta_wall_voxels_count: -1 NULL argument",
+    "ta_wall_voxels_get: -1 ctx is NULL",
+    "ta_wall_voxels_get_by_pair: -1 ctx is NULL",
+    "ta_wall_medians: -1 NULL argument",
+    "ta_wall_medians_get: -1 ctx is NULL",
+    "ta_volume_max_label: -1 NULL argument",
+    "ta_volume_label_census: -1 ctx is NULL",
+    "ta_label_census_get: -1 NULL argument",
+    "ta_volume_compact_labels: -1 NULL argument",
+    "ta_volume_is_compact: -1 NULL argument",
+    "ta_volume_rerank: -1 ctx is NULL",
+    "ta_volume_uncompact: -1 ctx is NULL",
+    "ta_accumulators_reduced: -1 ctx is NULL",
+    "ta_accumulators_device: -1 ctx is NULL",
+    "ta_adjacency_device: -1 ctx is NULL",
+    "ta_adjacency_export: -1 ctx is NULL",
+    "ta_adjacency_merge: -1 ctx is NULL",
+    "ta_adjacency_pack: -1 NULL argument",
+    "ta_adjacency_pack_shared: -1 NULL argument",
+    "ta_adjacency_merge_blocks: -1 NULL argument",
+]
+
+
+def test_moved_entry_points_refuse_a_null_context(sanitized, tmp_path):
+    """tests/native/null_ctx_moved.c against the sanitized library: create / destroy, then every entry point of the three host files
+    split off the core once, with a NULL context -- TA_EINVAL and the text each had before it moved."""
+    rt, lib, _ = sanitized
+    clang = os.path.join(os.path.dirname(os.path.dirname(os.path.dirname(os.path.dirname(os.path.dirname(rt))))), "bin", "clang")
+    if not os.path.exists(clang):
+        clang = "/opt/rocm/lib/llvm/bin/clang"
+    exe = str(tmp_path / "null_ctx_moved")
+    subprocess.check_call([clang, "-g", "-O1", "-fsanitize=address,undefined", "-shared-libsan",
+                           "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "native", "null_ctx_moved.c"),
+                           "-o", exe, lib, "-Wl,-rpath," + os.path.dirname(lib), "-Wl,-rpath," + os.path.dirname(rt)])
+    p = subprocess.run([exe], env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1:halt_on_error=1"),
+                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
+    err = p.stderr.decode(errors="replace")
+    assert p.returncode == 0, err[-3000:]
+    assert "LeakSanitizer" not in err and "AddressSanitizer" not in err and "runtime error" not in err, err[-3000:]
+    assert p.stdout.decode().strip().split("\n") == NULL_CTX_ANSWERS

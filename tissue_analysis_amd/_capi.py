@@ -417,6 +417,25 @@ class Context(object):
         except AttributeError:
             pass
 
+    def _in_label_layout(self, a, what):
+        """`a` (a companion of the label volume: its signal, the second label volume) with the label volume's shape checked and in
+        its memory layout; `what` = what the two error texts call it."""
+        layout = getattr(self, "_vol_layout", None)
+        if layout is None:
+            raise ValueError("set a label volume before %s" % what[0])
+        shape, el = layout
+        if a.ndim == 2 and len(shape) == 3 and shape[2] == 1:
+            a = a[:, :, None]
+        if tuple(a.shape) != shape:
+            raise ValueError("the %s shape %s differs from the label volume's %s" % (what[1], tuple(a.shape), shape))
+        same = all(n == 1 or st == e * a.dtype.itemsize for n, st, e in zip(a.shape, a.strides, el))
+        if not same:              # the labels' layout: a flat buffer viewed with their element strides
+            flat = np.empty(int(np.prod(shape)), dtype=a.dtype)
+            view = np.lib.stride_tricks.as_strided(flat, shape=shape, strides=[e * a.dtype.itemsize for e in el])
+            view[...] = a
+            a = view
+        return a
+
     # -- signal image (include/tissue_scan_signal.h)
     def set_signal(self, array):
         """Upload a uint8 / uint16 intensity image of the label volume's shape.  One stored in another axis permutation than
@@ -424,20 +443,7 @@ class Context(object):
         a = np.asarray(array)
         if a.dtype not in SIGNAL_DTYPES:
             raise TypeError("signal images must be uint8 or uint16, not %s" % a.dtype)
-        layout = getattr(self, "_vol_layout", None)
-        if layout is None:
-            raise ValueError("set a label volume before its signal")
-        shape, el = layout
-        if a.ndim == 2 and len(shape) == 3 and shape[2] == 1:
-            a = a[:, :, None]
-        if tuple(a.shape) != shape:
-            raise ValueError("the signal's shape %s differs from the label volume's %s" % (tuple(a.shape), shape))
-        same = all(n == 1 or st == e * a.dtype.itemsize for n, st, e in zip(a.shape, a.strides, el))
-        if not same:              # the labels' layout: a flat buffer viewed with their element strides
-            flat = np.empty(int(np.prod(shape)), dtype=a.dtype)
-            view = np.lib.stride_tricks.as_strided(flat, shape=shape, strides=[e * a.dtype.itemsize for e in el])
-            view[...] = a
-            a = view
+        a = self._in_label_layout(a, ("its signal", "signal's"))
         _check(self._lib.ta_signal_set(self._h, ctypes.c_void_p(a.ctypes.data), a.dtype.itemsize, _i64x3(a.shape), _i64x3(a.strides)))
 
     def set_signal_device(self, dev_ptr, itemsize, keep=None):
@@ -506,20 +512,7 @@ class Context(object):
         a = np.asarray(array)
         if a.dtype not in (np.uint16, np.uint32):
             raise TypeError("label volumes must be uint16 or uint32, not %s" % a.dtype)
-        layout = getattr(self, "_vol_layout", None)
-        if layout is None:
-            raise ValueError("set a label volume before the one it is compared with")
-        shape, el = layout
-        if a.ndim == 2 and len(shape) == 3 and shape[2] == 1:
-            a = a[:, :, None]
-        if tuple(a.shape) != shape:
-            raise ValueError("the second volume's shape %s differs from the label volume's %s" % (tuple(a.shape), shape))
-        same = all(n == 1 or st == e * a.dtype.itemsize for n, st, e in zip(a.shape, a.strides, el))
-        if not same:              # the labels' layout: a flat buffer viewed with their element strides
-            flat = np.empty(int(np.prod(shape)), dtype=a.dtype)
-            view = np.lib.stride_tricks.as_strided(flat, shape=shape, strides=[e * a.dtype.itemsize for e in el])
-            view[...] = a
-            a = view
+        a = self._in_label_layout(a, ("the one it is compared with", "second volume's"))
         _check(self._lib.ta_overlap_set(self._h, ctypes.c_void_p(a.ctypes.data), a.dtype.itemsize, _i64x3(a.shape), _i64x3(a.strides)))
         self._keep_overlap = None
 

@@ -14,7 +14,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJDIR = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "libtissue_scan.so")
-SOURCES = ["ta_api.hip", "ta_api_signal.hip", "ta_api_mesh.hip", "ta_api_overlap.hip", "ta_api_junctions.hip", "ta_api_wallgeo.hip", "ta_api_components.hip",
+SOURCES = ["ta_api.hip", "ta_api_walls.hip", "ta_api_sparse.hip", "ta_api_exchange.hip", "ta_api_signal.hip", "ta_api_mesh.hip", "ta_api_overlap.hip", "ta_api_junctions.hip", "ta_api_wallgeo.hip", "ta_api_components.hip",
            "kernels_basic.hip", "kernels_scan.hip", "kernels_walls.hip", "kernels_wallsort.hip", "kernels_wallmedian.hip", "kernels_census.hip",
            "kernels_pairsort.hip", "kernels_signal.hip", "kernels_mesh.hip", "kernels_overlap.hip", "kernels_junctions.hip", "kernels_wallgeo.hip",
            "kernels_components.hip"]

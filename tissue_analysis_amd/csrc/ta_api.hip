@@ -1,4 +1,6 @@
-// ta_api.hip -- the core C ABI of include/tissue_scan.h on top of the gfx950 kernels (the features: ta_api_<feature>.hip).
+// ta_api.hip -- the core C ABI of include/tissue_scan.h on top of the gfx950 kernels: the context, its options and stream, the volume,
+// the sweep and its results, timing and memory helpers.  (Wall voxels: ta_api_walls.hip; sparse ids: ta_api_sparse.hip; rank exchange:
+// ta_api_exchange.hip; the features: ta_api_<feature>.hip.)
 #include "ta_ctx.h"
 
 #include <cstdarg>
@@ -20,24 +22,6 @@ int fail(int code, const char* fmt, ...) {
 
 namespace {
 
-constexpr int SMALL_WORDS = ta::SMALL_WORDS_DEV;   // flags, cursor, max label, parked hot-row pointer (2 words)
-
-uint32_t* flags_dev(ta_ctx* c) { return (uint32_t*)c->small.p; }
-uint32_t* cursor_dev(ta_ctx* c) { return (uint32_t*)c->small.p + ta::NFLAGS; }
-uint32_t* maxlab_dev(ta_ctx* c) { return (uint32_t*)c->small.p + ta::NFLAGS + 1; }
-
-void drop_census(ta_ctx* c) {          // (whenever the voxels change)
-    c->census_n = -1;
-    c->census_of_volume = false;
-    c->rerank_check = false;
-    c->vol_max = -1;
-    c->shape_pick = -1;
-    c->shape_density = -1.0;
-    c->tune_launched = 0;
-    for (bool& d : c->tune_done) d = false;
-    if (c->compact) { c->compact = false; c->extracted = c->checked = false; }
-}
-
 int ensure_pair_table(ta_ctx* c, int log2cap) {
     if (c->pair_log2 == log2cap && c->pkeys.p) return TA_OK;
     const uint64_t cap = 1ull << log2cap;
@@ -49,14 +33,6 @@ int ensure_pair_table(ta_ctx* c, int log2cap) {
     c->pair_log2 = log2cap;
     c->table_clean = false;
     return TA_OK;
-}
-
-ta::PairTable pair_table(ta_ctx* c) {
-    ta::PairTable pt;
-    pt.keys = (uint64_t*)c->pkeys.p;
-    pt.faces = (uint64_t*)c->pfaces.p;
-    pt.mask = (uint32_t)((1ull << c->pair_log2) - 1);
-    return pt;
 }
 
 int auto_pair_log2(uint32_t max_label) {
@@ -101,36 +77,36 @@ constexpr double WIDE_SHORTER_TILES_DENSITY = 0.02;       // (see run_extract: t
 int sweep_shape(ta_ctx* c, bool adjacency, int* tune) {
     *tune = -1;
     if (c->itemsize != 4 || !adjacency) return 0;
-    if (c->opt_shape >= 0) return c->opt_shape;
+    if (c->shape.opt >= 0) return c->shape.opt;
     // the wide tiles want whole 512-column tiles: the partial ones run a kernel with three waves per SIMD (1000^3: 1.24
     // against 1.05 ms), and a volume narrower than a tile has nothing else
     if (c->mdims[2] % 512 != 0) return 0;
-    if (c->shape_pick >= 0) return c->shape_pick;
-    if (c->opt_shape == -1) {
+    if (c->shape.pick >= 0) return c->shape.pick;
+    if (c->shape.opt == -1) {
         // decided BEFORE the first sweep, from the density of label changes in a sample of planes (a caller that sweeps a volume
         // once -- SpatialImageAnalysis(image) -- gets the faster shape on that sweep)
         const double density = sampled_event_density(c);
-        c->shape_density = density;
-        c->shape_pick = (density >= 0.0 && density > SHAPE_DENSITY_NARROW) ? 0 : 1;
-        return c->shape_pick;
+        c->shape.density = density;
+        c->shape.pick = (density >= 0.0 && density > SHAPE_DENSITY_NARROW) ? 0 : 1;
+        return c->shape.pick;
     }
     // TA_OPT_SWEEP_SHAPE = -2: the first four sweeps of the volume take turns (wide, narrow, wide, narrow), each between two
     // events of its own, and the faster shape keeps the volume
-    bool all = c->tune_launched == 4;
-    for (int k = 0; k < c->tune_launched; ++k) {
-        if (!c->tune_done[k]) {
-            if (hipEventQuery(c->tune_ev[2 * k + 1]) == hipSuccess &&
-                hipEventElapsedTime(&c->tune_ms[k], c->tune_ev[2 * k], c->tune_ev[2 * k + 1]) == hipSuccess) c->tune_done[k] = true;
+    bool all = c->shape.tune_launched == 4;
+    for (int k = 0; k < c->shape.tune_launched; ++k) {
+        if (!c->shape.tune_done[k]) {
+            if (hipEventQuery(c->shape.tune_ev[2 * k + 1]) == hipSuccess &&
+                hipEventElapsedTime(&c->shape.tune_ms[k], c->shape.tune_ev[2 * k], c->shape.tune_ev[2 * k + 1]) == hipSuccess) c->shape.tune_done[k] = true;
             else (void)hipGetLastError();             // (not ready: asked again by the next sweep)
         }
-        all = all && c->tune_done[k];
+        all = all && c->shape.tune_done[k];
     }
     if (all) {
-        c->shape_pick = std::min(c->tune_ms[0], c->tune_ms[2]) <= std::min(c->tune_ms[1], c->tune_ms[3]) ? 1 : 0;
-        return c->shape_pick;
+        c->shape.pick = std::min(c->shape.tune_ms[0], c->shape.tune_ms[2]) <= std::min(c->shape.tune_ms[1], c->shape.tune_ms[3]) ? 1 : 0;
+        return c->shape.pick;
     }
-    if (c->tune_launched < 4 && c->tune_ev[7]) {
-        *tune = c->tune_launched;                     // (counted as launched by run_extract once BOTH its events are on the stream)
+    if (c->shape.tune_launched < 4 && c->shape.tune_ev[7]) {
+        *tune = c->shape.tune_launched;                     // (counted as launched by run_extract once BOTH its events are on the stream)
         return (*tune & 1) ^ 1;                       // wide, narrow, wide, narrow
     }
     return 1;                                         // (measured sweeps still in flight)
@@ -146,13 +122,13 @@ int run_extract(ta_ctx* c) {
     a.first_owned = c->first_owned;
     int tune = -1;
     a.shape = sweep_shape(c, c->feature_mask & TA_F_ADJACENCY, &tune);
-    c->last_shape = a.shape;
+    c->shape.last = a.shape;
     a.tile_planes = c->tile_planes > 0 ? c->tile_planes : ta::sweep_default_tile_planes(c->feature_mask & TA_F_ADJACENCY, c->itemsize, a.shape);
     if (c->tile_planes <= 0) {
         // the wide tiles of a volume whose sampled planes change label often hold more labels and pairs a plane: a little shorter
         // (C4, 0.023 changes a voxel: 28 planes 0.948 against 0.954 ms at 32; C5, 0.014: 32 planes 6.546 against 6.562 at 28 --
         // profiles/r05_tile_planes.txt; without a measured density -- a forced shape -- the default stays)
-        if (a.shape == 1 && c->shape_density >= WIDE_SHORTER_TILES_DENSITY && a.tile_planes > 28) a.tile_planes = 28;
+        if (a.shape == 1 && c->shape.density >= WIDE_SHORTER_TILES_DENSITY && a.tile_planes > 28) a.tile_planes = 28;
         // automatic: small volumes get shorter tiles until the launch has >= 2048 workgroups (8 per CU)
         while (a.tile_planes > 8 && ta::sweep_grid_size(a, c->itemsize, c->feature_mask & TA_F_ADJACENCY) < 2048) a.tile_planes /= 2;
         // volumes whose cells are so small that a tile holds more labels than the workgroup tables (the contributions
@@ -167,7 +143,7 @@ int run_extract(ta_ctx* c) {
     // global loads are legal on gfx950 -- 6.2 TB/s from dword-aligned, 4.8 TB/s from odd addresses, measured -- and the
     // strip that straddles the end of the very last row reads into the slack ta_volume_set leaves behind the buffer)
     a.vec_ok = ((((uintptr_t)a.vol & 15) == 0) && ((a.n2 * c->itemsize) % 16 == 0)) || (a.vol == c->owned_vol.p && c->owned_vol.p) ||
-               c->compact || c->volume_slack >= 16;       // (an adopted buffer whose owner promises readable bytes behind it: TA_OPT_VOLUME_SLACK)
+               c->ids.compact || c->volume_slack >= 16;       // (an adopted buffer whose owner promises readable bytes behind it: TA_OPT_VOLUME_SLACK)
     a.max_label = c->max_label;
     a.sums = c->sums;
     a.boxes = c->boxes;
@@ -204,7 +180,7 @@ int run_extract(ta_ctx* c) {
     // the sweep kernel alone (what the roofline is quoted on): the two events ride on the sweep's own launches
     // (begin / end timestamps of the dispatch, no event-record packets on the queue); the naive kernel gets plain records
     const bool own_dims = c->mdims[0] - c->first_owned > 0 && c->mdims[1] > 0 && c->mdims[2] > 0;
-    if (tune >= 0) TA_HIP(hipEventRecord(c->tune_ev[2 * tune], c->stream));
+    if (tune >= 0) TA_HIP(hipEventRecord(c->shape.tune_ev[2 * tune], c->stream));
     if (c->impl == 1 || !own_dims) {
         if (ev_a) TA_HIP(hipEventRecord(ev_a, c->stream));
         if (c->impl == 1) ta::launch_naive(c->stream, a, c->itemsize, c->feature_mask);
@@ -213,8 +189,8 @@ int run_extract(ta_ctx* c) {
         ta::launch_scan(c->stream, a, c->itemsize, c->feature_mask, ev_a, ev_b);
     }
     if (tune >= 0) {
-        TA_HIP(hipEventRecord(c->tune_ev[2 * tune + 1], c->stream));
-        c->tune_launched = tune + 1;                  // (a slot counts only with both of its events recorded: an early return above leaves it to be measured again)
+        TA_HIP(hipEventRecord(c->shape.tune_ev[2 * tune + 1], c->stream));
+        c->shape.tune_launched = tune + 1;                  // (a slot counts only with both of its events recorded: an early return above leaves it to be measured again)
     }
     // Without adjacency the LAST kernel of the step (the hot-row fold) mirrors the flag words into host-mapped memory
     // itself: no device-to-host copy (a blit kernel and a queue barrier) at the end of the step.  With adjacency the pair
@@ -239,17 +215,6 @@ int run_extract(ta_ctx* c) {
     return TA_OK;
 }
 
-// The word ta_volume_rerank writes shares its place with the max-label passes: whoever is about to reuse it looks at it first.
-int settle_rerank(ta_ctx* c) {
-    if (!c->rerank_check) return TA_OK;
-    uint32_t status = 0;
-    TA_HIP(hipMemcpyAsync(&status, maxlab_dev(c), sizeof(status), hipMemcpyDeviceToHost, c->stream));
-    TA_HIP(hipStreamSynchronize(c->stream));
-    c->rerank_check = false;
-    if (status) { c->extracted = false; return fail(TA_ERANGE, "the refreshed volume holds a label id that is not in the list the context was compacted with"); }
-    return TA_OK;
-}
-
 }  // namespace
 
 // Drain the stream and validate the flags of the last pass; grows the adjacency table and
@@ -259,10 +224,8 @@ int finish_extract(ta_ctx* c) {
     if (c->checked) return TA_OK;
     if (c->exchanged) {       // the list came from other ranks too: a re-run is the host's call
         TA_HIP(hipStreamSynchronize(c->stream));
-        if (c->rerank_check) {
-            c->rerank_check = false;
-            if (c->h_small[ta::NFLAGS + 1]) { c->extracted = false; return fail(TA_ERANGE, "the refreshed volume holds a label id that is not in the list the context was compacted with"); }
-        }
+        int rc = rerank_verdict(c, c->h_small[ta::NFLAGS + 1]);
+        if (rc != TA_OK) return rc;
         if (c->h_small[ta::FLAG_RANGE])
             return fail(TA_ERANGE, "a rank saw a label above max_label=%u", c->max_label);
         if (c->h_small[ta::FLAG_EXCHANGE_OVERFLOW])
@@ -275,13 +238,8 @@ int finish_extract(ta_ctx* c) {
     }
     for (int attempt = 0; attempt < 8; ++attempt) {
         TA_HIP(hipStreamSynchronize(c->stream));
-        if (c->rerank_check) {          // (the word ta_volume_rerank left behind came back with this extraction's flags)
-            c->rerank_check = false;
-            if (c->h_small[ta::NFLAGS + 1]) {
-                c->extracted = false;
-                return fail(TA_ERANGE, "the refreshed volume holds a label id that is not in the list the context was compacted with");
-            }
-        }
+        int rc = rerank_verdict(c, c->h_small[ta::NFLAGS + 1]);      // (the word ta_volume_rerank left behind came back with this extraction's flags)
+        if (rc != TA_OK) return rc;
         if (c->h_small[ta::FLAG_RANGE])
             return fail(TA_ERANGE, "the volume holds a label above max_label=%u", c->max_label);
         if (!c->h_small[ta::FLAG_PAIR_OVERFLOW]) {
@@ -294,8 +252,7 @@ int finish_extract(ta_ctx* c) {
             return TA_OK;
         }
         if (c->pair_log2 >= 30) break;
-        int rc = ensure_pair_table(c, c->pair_log2 + 2);
-        if (rc != TA_OK) return rc;
+        if ((rc = ensure_pair_table(c, c->pair_log2 + 2)) != TA_OK) return rc;
         if (c->reduced)       // a local re-run would replace the reduced (global) rows by this rank's: the host redoes the step
             return fail(TA_ECAPACITY, "adjacency table overflow (grown to 2^%d slots): repeat the extraction on every rank", c->pair_log2);
         if ((rc = run_extract(c)) != TA_OK) return rc;
@@ -357,15 +314,28 @@ void companion_on_new_volume(const ta_ctx* c, Companion& v) {
     if (v.p && !companion_matches(c, v)) { v.p = nullptr; v.owned.release(); v.itemsize = 0; }
 }
 
-void volume_labels_changed(ta_ctx* c) {
-    drop_census(c);                 // (the ids changed: a compacted context goes back to dense rows until it is compacted again)
+// ---- the one invalidation path (ta_ctx.h) -----------------------------------------------------------------------------------
+
+static void voxels_changed(ta_ctx* c) {          // what every change of the voxels ends, whoever made it
+    sparse_on_new_volume(c);
+    c->shape.forget_choice();
     c->extracted = c->checked = false;
-    c->wall_median_count = -1;
-    c->wall_records = -1;           // the staged wall records carry the OLD labels: a fetch must ask for a fresh count
-    c->wall_region = 0; c->wall_not_staged = 0;
     overlap_on_new_volume(c);
     junctions_on_new_volume(c);
     components_on_new_volume(c);
+}
+
+void volume_labels_changed(ta_ctx* c) {
+    voxels_changed(c);
+    walls_on_new_labels(c);
+}
+
+void volume_replaced(ta_ctx* c) {
+    voxels_changed(c);
+    c->auto_tile_shift = 0;
+    walls_on_new_volume(c);
+    signal_on_new_volume(c);         // (these two are keyed by the extraction, which is gone; a signal of other dims is dropped)
+    wallgeo_on_new_volume(c);
 }
 
 extern "C" {
@@ -404,7 +374,7 @@ TA_API int ta_ctx_create(int device_id, ta_ctx** out) {
     for (auto& ev : c->ev) if (e == hipSuccess) e = hipEventCreate(&ev);
     try { c->ring.assign(2, nullptr); } catch (...) { rc = fail(TA_ENOMEM, "out of host memory"); }
     for (auto& ev : c->ring) if (e == hipSuccess && rc == TA_OK) e = hipEventCreate(&ev);
-    for (auto& ev : c->tune_ev) if (e == hipSuccess && rc == TA_OK) e = hipEventCreate(&ev);
+    for (auto& ev : c->shape.tune_ev) if (e == hipSuccess && rc == TA_OK) e = hipEventCreate(&ev);
     if (e == hipSuccess) rc = c->small.reserve(SMALL_WORDS * sizeof(uint32_t));
     if (e == hipSuccess && rc == TA_OK) e = hipHostMalloc((void**)&c->h_small, SMALL_WORDS * sizeof(uint32_t), hipHostMallocMapped);
     if (e == hipSuccess && rc == TA_OK) {
@@ -432,13 +402,10 @@ TA_API int ta_ctx_destroy(ta_ctx* c) {
     c->pkeys.release(); c->pfaces.release(); c->out_keys.release(); c->out_faces.release();
     c->small.release();
     c->hot_rows.release(); c->sort_buf.release(); c->h_pairs.release();
-    c->wall_counts.release();
-    c->wall_stage.release();
-    c->wall_medians.release();
-    c->census.release(); c->census_ids.release(); c->compact_vol.release(); c->census_list.release();
+    c->walls.release(); c->ids.release(); c->shape.release();
     c->sig.release(); c->mesh.release(); c->ov.release(); c->jn.release(); c->wg.release(); c->cc.release();
     if (c->h_small) (void)hipHostFree(c->h_small);
-    destroy_events(c->ev); destroy_events(c->tune_ev);
+    destroy_events(c->ev);
     for (auto& e : c->ring) if (e) (void)hipEventDestroy(e);
     if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
@@ -479,12 +446,9 @@ TA_API int ta_ctx_set_option(ta_ctx* c, int key, int64_t value) {
             c->opt_pair_log2 = (int)value; return TA_OK;
         case TA_OPT_SWEEP_SHAPE:
             if (value < -2 || value > 1) return fail(TA_EINVAL, "TA_OPT_SWEEP_SHAPE is -1 (by label-change density), -2 (by four timed sweeps), 0 or 1");
-            c->opt_shape = (int)value;
+            c->shape.opt = (int)value;
             c->auto_tile_shift = 0;
-            c->shape_pick = -1;                    // (decided again, by the new rule, at the next sweep)
-            c->shape_density = -1.0;
-            c->tune_launched = 0;
-            for (bool& d : c->tune_done) d = false;
+            c->shape.forget_choice();              // (decided again, by the new rule, at the next sweep)
             return TA_OK;
         case TA_OPT_VOLUME_SLACK:
             if (value < 0) return fail(TA_EINVAL, "TA_OPT_VOLUME_SLACK must be >= 0");
@@ -517,15 +481,15 @@ TA_API int ta_ctx_get_option(ta_ctx* c, int key, int64_t* value) {
     switch (key) {
         case TA_OPT_IMPL: *value = c->impl; return TA_OK;
         case TA_OPT_VOLUME_SLACK: *value = c->volume_slack; return TA_OK;
-        case TA_OPT_SWEEP_SHAPE: *value = c->opt_shape; return TA_OK;
-        case TA_OPT_SWEEP_SHAPE_USED: *value = c->last_shape; return TA_OK;
+        case TA_OPT_SWEEP_SHAPE: *value = c->shape.opt; return TA_OK;
+        case TA_OPT_SWEEP_SHAPE_USED: *value = c->shape.last; return TA_OK;
         case TA_OPT_TIMING: *value = c->timing; return TA_OK;
         case TA_OPT_TIMING_RING: *value = (int64_t)(c->ring.size() / 2); return TA_OK;
         case TA_OPT_TILE_PLANES: {
-            const int shape = c->opt_shape >= 0 ? c->opt_shape : (c->shape_pick >= 0 ? c->shape_pick : 1);
+            const int shape = c->shape.opt >= 0 ? c->shape.opt : (c->shape.pick >= 0 ? c->shape.pick : 1);
             int planes = c->tile_planes > 0 ? c->tile_planes : ta::sweep_default_tile_planes(c->feature_mask & TA_F_ADJACENCY, c->itemsize, shape);
             if (c->tile_planes <= 0 && c->itemsize == 4 && (c->feature_mask & TA_F_ADJACENCY) && shape == 1 &&
-                c->shape_density >= WIDE_SHORTER_TILES_DENSITY && planes > 28) planes = 28;      // (the rule of run_extract)
+                c->shape.density >= WIDE_SHORTER_TILES_DENSITY && planes > 28) planes = 28;      // (the rule of run_extract)
             *value = planes; return TA_OK;
         }
         case TA_OPT_PAIR_SLOTS: *value = c->pkeys.p ? c->pair_log2 : c->opt_pair_log2; return TA_OK;
@@ -572,21 +536,11 @@ TA_API int ta_volume_set(ta_ctx* c, const void* host_ptr, int itemsize, const in
     TA_HIP(hipMemcpyAsync(c->owned_vol.p, host_ptr, bytes, hipMemcpyHostToDevice, c->stream));
     TA_HIP(hipStreamSynchronize(c->stream));   // the host buffer may be freed after return
     c->vol = c->owned_vol.p;
-    drop_census(c);
-    c->auto_tile_shift = 0;
-    c->wall_records = -1;
-    c->wall_median_count = -1;
-    c->wall_stage.release();
     c->itemsize = itemsize;
     for (int k = 0; k < 3; ++k) { c->perm[k] = perm[k]; c->mdims[k] = dims[perm[k]]; }
     c->a_origin = 0;
     c->first_owned = 0;
-    c->extracted = c->checked = false;
-    signal_on_new_volume(c);
-    wallgeo_on_new_volume(c);
-    overlap_on_new_volume(c);
-    junctions_on_new_volume(c);
-    components_on_new_volume(c);
+    volume_replaced(c);              // (volume_slack stays as it is: the library's own upload never looks at it)
     return TA_OK;
 }
 
@@ -600,22 +554,12 @@ TA_API int ta_volume_set_device(ta_ctx* c, const void* dev_ptr, int itemsize, co
     if (a0_origin < 0) return fail(TA_EINVAL, "a0_origin must be >= 0");
     if (((uintptr_t)dev_ptr % itemsize) != 0) return fail(TA_EINVAL, "device pointer is not aligned to the label type");
     c->vol = dev_ptr;
-    drop_census(c);
-    c->volume_slack = 0;
-    c->auto_tile_shift = 0;
-    c->wall_records = -1;
-    c->wall_median_count = -1;
-    c->wall_stage.release();
+    c->volume_slack = 0;             // (told again by the owner of the new buffer)
     c->itemsize = itemsize;
     for (int k = 0; k < 3; ++k) { c->perm[k] = k; c->mdims[k] = buf_dims[k]; }
     c->a_origin = a0_origin;
     c->first_owned = has_low_halo ? 1 : 0;
-    c->extracted = c->checked = false;
-    signal_on_new_volume(c);
-    wallgeo_on_new_volume(c);
-    overlap_on_new_volume(c);
-    junctions_on_new_volume(c);
-    components_on_new_volume(c);
+    volume_replaced(c);
     return TA_OK;
 }
 
@@ -623,8 +567,8 @@ TA_API int ta_volume_relabel(ta_ctx* c, const uint32_t* lut, uint32_t lut_len) {
     if (!c || (!lut && lut_len)) return fail(TA_EINVAL, "NULL argument");
     if (!c->vol) return fail(TA_EINVAL, "no volume set");
     if (c->first_owned) return fail(TA_EINVAL, "cannot relabel a slab that carries a halo plane");
-    if (c->compact && lut_len != (uint32_t)c->census_n)
-        return fail(TA_EINVAL, "a compacted context relabels through one entry per rank: %u entries for %lld ranks", lut_len, (long long)c->census_n);
+    if (compact_rows(c) >= 0 && lut_len != (uint32_t)compact_rows(c))
+        return fail(TA_EINVAL, "a compacted context relabels through one entry per rank: %u entries for %lld ranks", lut_len, (long long)compact_rows(c));
     if (c->itemsize == 2)
         for (uint32_t i = 0; i < lut_len; ++i)
             if (lut[i] > 0xFFFFu) return fail(TA_ERANGE, "lut[%u]=%u does not fit the uint16 volume", i, lut[i]);
@@ -738,478 +682,6 @@ TA_API int ta_volume_layer18(ta_ctx* c, uint8_t* host_dst) {
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     dout.release();
     if (e != hipSuccess) return fail(TA_EHIP, "voxel layers: %s", hipGetErrorString(e));
-    return TA_OK;
-}
-
-namespace {
-// layout of ta_ctx::wall_counts: counts u32[cells] | cell_base u32[cells] (each padded to 8 bytes) | offsets u64[cells] |
-// block sums u64[scan_blocks] | total u64 + status u32[6] (the 32 bytes the host reads back) | cursors | todo u32[cells] |
-// lane counts u8[cells][64]
-uint64_t wall_bufs(void* base, const ta::WallPlan& p, ta::WallBuffers& b) {
-    const uint64_t counts_bytes = (p.cells * 4 + 7) & ~7ull;
-    char* at = (char*)base;
-    b.counts = (uint32_t*)at; at += counts_bytes;
-    b.cell_base = (uint32_t*)at; at += counts_bytes;
-    b.offsets = (uint64_t*)at; at += p.cells * 8;
-    b.block_sums = (uint64_t*)at; at += p.scan_blocks * 8;
-    b.total = (uint64_t*)at; b.status = (uint32_t*)(b.total + 1); at += 32;
-    b.cursors = (uint32_t*)at; at += ta::wall_cursor_bytes();
-    b.todo = (uint32_t*)at; at += counts_bytes;
-    b.lane_counts = (uint8_t*)at; at += p.cells * 64;
-    return (uint64_t)(at - (char*)base);
-}
-
-// Room for the records the count pass stages: half a record per voxel (tissue: 0.1 - 0.25), split into regions; a
-// volume with more takes the second walk for the cells that did not fit.  No memory for it: nothing is staged.
-void wall_stage(ta_ctx* c, const ta::WallPlan& p, ta::WallBuffers& b) {
-    const uint64_t nvox = (uint64_t)c->mdims[0] * c->mdims[1] * c->mdims[2];
-    uint64_t records = std::min<uint64_t>(std::max<uint64_t>(nvox / 2, 1u << 16), 1ull << 31);
-    // (tests: force the second walk / small regions.  Clamped: region_of_wave * region + got must stay below 2^32 in the kernel)
-    if (const char* env = getenv("TA_WALL_STAGE_RECORDS")) records = std::min<uint64_t>(std::strtoull(env, nullptr, 10), 1ull << 31);
-    const uint32_t regions = ta::wall_stage_regions();
-    b.region = (uint32_t)(records / regions);
-    b.stage = nullptr;
-    (void)p;
-    if (b.region == 0) return;
-    const uint64_t need = ta::wall_stage_bytes(b.region, c->itemsize);
-    if (c->wall_stage.bytes < need) {
-        c->wall_stage.release();
-        if (hipMalloc(&c->wall_stage.p, need) != hipSuccess) {
-            (void)hipGetLastError();
-            c->wall_stage.p = nullptr;
-            b.region = 0;
-            return;
-        }
-        c->wall_stage.bytes = need;
-    }
-    b.stage = c->wall_stage.p;
-}
-}  // namespace
-
-TA_API int ta_wall_voxels_count(ta_ctx* c, int64_t* nrecords) {
-    if (!c || !nrecords) return fail(TA_EINVAL, "NULL argument");
-    if (!c->vol) return fail(TA_EINVAL, "no volume set");
-    if (c->first_owned) return fail(TA_EINVAL, "wall voxels are not available on a slab that carries a halo plane");
-    int rc = use_device(c);
-    if (rc != TA_OK) return rc;
-    const ta::WallPlan plan = ta::wall_plan(c->mdims[0], c->mdims[1], c->mdims[2]);
-    if (plan.cells >= (1ull << 32)) return fail(TA_EINVAL, "volume too large for the wall voxel pass (%llu row strips)", (unsigned long long)plan.cells);
-    ta::WallBuffers wb;
-    if ((rc = c->wall_counts.reserve(wall_bufs(nullptr, plan, wb))) != TA_OK) return rc;
-    (void)wall_bufs(c->wall_counts.p, plan, wb);
-    wall_stage(c, plan, wb);
-    c->wall_region = wb.region;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    struct { uint64_t total; uint32_t not_staged, wide_seen, label_or, unused[3]; } line = {0, 0, 0, 0, {0, 0, 0}};
-    hipError_t e = hipEventCreate(&e0);
-    if (e == hipSuccess) e = hipEventCreate(&e1);
-    float ms_all = 0.f;
-    bool wide = false;
-    for (int attempt = 0; attempt < 2 && e == hipSuccess; ++attempt) {
-        e = hipEventRecord(e0, c->stream);
-        if (e == hipSuccess) {
-            // count + stage per (row, strip), scan on the device: the only thing the host needs before the fetch is one line
-            ta::launch_wall_count(c->stream, c->vol, c->itemsize, c->mdims[0], c->mdims[1], c->mdims[2], wb, wide);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipEventRecord(e1, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(&line, wb.total, 32, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        float ms = 0.f;
-        if (e == hipSuccess) (void)hipEventElapsedTime(&ms, e0, e1);
-        ms_all += ms;
-        if (!line.wide_seen || wide) break;
-        wide = true;                    // a label from 2^31 up: once more with the kernel that takes them
-    }
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    if (e != hipSuccess) return fail(TA_EHIP, "wall voxel count: %s", hipGetErrorString(e));
-    c->wall_records = (int64_t)line.total;
-    c->wall_median_count = -1;
-    c->wall_not_staged = line.not_staged;
-    c->wall_wide = wide;
-    c->wall_label_or = line.label_or;
-    c->wall_ms = ms_all;
-    if (getenv("TA_WALL_VERBOSE"))
-        fprintf(stderr, "[tissue_scan] wall voxels: %llu records in %llu cells of 256 voxels, %u cells not staged (regions of %u records), wide=%d, %.3f ms\n",
-                (unsigned long long)line.total, (unsigned long long)plan.cells, line.not_staged, wb.region, (int)wide, ms_all);
-    *nrecords = c->wall_records;
-    return TA_OK;
-}
-
-namespace {
-// The records of the last ta_wall_voxels_count on the DEVICE, in memory order or grouped by pair: `buf` owns them, *pairs_dev /
-// *coords_dev point into it; the launches are bracketed by e0 / e1 when given.  Only enqueues work (and allocates).
-int wall_records_device(ta_ctx* c, bool by_pair, DevBuf& buf, uint32_t** pairs_dev, int32_t** coords_dev, hipEvent_t e0, hipEvent_t e1) {
-    const uint64_t n = (uint64_t)c->wall_records;
-    int rc;
-    const ta::WallPlan plan = ta::wall_plan(c->mdims[0], c->mdims[1], c->mdims[2]);
-    ta::WallBuffers wb;
-    (void)wall_bufs(c->wall_counts.p, plan, wb);
-    wb.region = c->wall_region;
-    wb.stage = c->wall_region ? c->wall_stage.p : nullptr;
-    // one allocation: records in memory order | (grouped fetch) the same again grouped, sort keys / indices x 2, sort temp.
-    // A volume of fewer than 2^32 voxels is grouped from KEYS: the fetch writes sort keys and linear voxel indices straight into
-    // the sort's buffers (no records in memory order, no key pass, no gather of coordinates behind the last pass)
-    const uint64_t nvox = (uint64_t)c->mdims[0] * (uint64_t)c->mdims[1] * (uint64_t)c->mdims[2];
-    // (tests and same-call comparisons: TA_WALL_KEYED=0 sorts the records of the plain fetch, as volumes of 2^32 voxels and more do)
-    const char* env_keyed = getenv("TA_WALL_KEYED");
-    const bool keyed = by_pair && nvox < (1ull << 32) && !(env_keyed && env_keyed[0] == '0');
-    const uint64_t temp_bytes = by_pair ? ta::wall_sort_temp_bytes(n) : 0;
-    const uint64_t rec = n * 8, co = align16(n * 12), ix = align16(n * 4);
-    if ((rc = buf.reserve(by_pair ? (keyed ? 0 : rec + co) + rec + co + 2 * rec + 2 * ix + temp_bytes + 64 : rec + co)) != TA_OK) return rc;
-    char* p = (char*)buf.p;
-    int label_bits = 1;                                             // bits a label of this volume takes
-    while (label_bits < 32 && (c->wall_label_or >> label_bits) != 0u) ++label_bits;
-    uint32_t* dpa = nullptr; int32_t* dco = nullptr;
-    if (!keyed) { dpa = (uint32_t*)p; p += rec; dco = (int32_t*)p; p += co; }
-    uint32_t* gpa = dpa; int32_t* gco = dco;
-    uint64_t *k0 = nullptr, *k1 = nullptr; uint32_t *i0 = nullptr, *i1 = nullptr;
-    if (by_pair) {
-        gpa = (uint32_t*)p; p += rec;
-        gco = (int32_t*)p; p += co;
-        k0 = (uint64_t*)p; p += rec;
-        k1 = (uint64_t*)p; p += rec;
-        i0 = (uint32_t*)p; p += ix;
-        i1 = (uint32_t*)p; p += ix;
-    }
-    hipError_t e = e0 ? hipEventRecord(e0, c->stream) : hipSuccess;
-    if (e == hipSuccess) {
-        // records leave the kernels as (lo, hi) / coordinates in ARRAY-axis order -- or as keys / linear indices for the sort
-        ta::launch_wall_fetch(c->stream, c->vol, c->itemsize, c->mdims[0], c->mdims[1], c->mdims[2], wb, c->wall_wide,
-                              c->wall_not_staged, keyed ? (uint32_t*)k0 : dpa, keyed ? (int32_t*)i0 : dco, c->perm, keyed ? label_bits : 0);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess && keyed)
-        e = ta::launch_wall_group_keyed(c->stream, n, k0, k1, i0, i1, p, label_bits, c->mdims, c->perm, gpa, gco);
-    else if (e == hipSuccess && by_pair)
-        e = ta::launch_wall_group_by_pair(c->stream, dpa, dco, n, k0, k1, i0, i1, p, temp_bytes, label_bits, gpa, gco);
-    if (e == hipSuccess && e1) e = hipEventRecord(e1, c->stream);
-    if (e != hipSuccess) return fail(TA_EHIP, "wall voxels: %s", hipGetErrorString(e));
-    *pairs_dev = gpa; *coords_dev = gco;
-    return TA_OK;
-}
-
-int wall_voxels_fetch(ta_ctx* c, uint32_t* pairs, int32_t* coords, double* ms_out, bool by_pair) {
-    if (!c) return fail(TA_EINVAL, "ctx is NULL");
-    if (c->wall_records < 0) return fail(TA_EINVAL, "call ta_wall_voxels_count first");
-    int rc = use_device(c);
-    if (rc != TA_OK) return rc;
-    const uint64_t n = (uint64_t)c->wall_records;
-    if (ms_out) *ms_out = c->wall_ms;
-    if (n == 0) return TA_OK;
-    if (!pairs || !coords) return fail(TA_EINVAL, "NULL output array");
-    if (by_pair && n >= (1ull << 32)) return fail(TA_EINVAL, "too many records (%llu) for the grouped fetch", (unsigned long long)n);
-    DevBuf buf;
-    uint32_t* gpa = nullptr; int32_t* gco = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    hipError_t e = hipEventCreate(&e0);
-    if (e == hipSuccess) e = hipEventCreate(&e1);
-    if (e == hipSuccess && (rc = wall_records_device(c, by_pair, buf, &gpa, &gco, e0, e1)) != TA_OK) {
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
-        buf.release();
-        return rc;
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(pairs, gpa, n * 8, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(coords, gco, n * 12, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    float ms = 0.f;
-    if (e == hipSuccess) (void)hipEventElapsedTime(&ms, e0, e1);
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    buf.release();
-    if (e != hipSuccess) return fail(TA_EHIP, "wall voxels: %s", hipGetErrorString(e));
-    if (ms_out) *ms_out = c->wall_ms + ms;
-    return TA_OK;
-}
-}  // namespace
-
-TA_API int ta_wall_medians(ta_ctx* c, int max_iter, int64_t* nwalls, double* ms_out) {
-    if (!c || !nwalls) return fail(TA_EINVAL, "NULL argument");
-    if (c->wall_records < 0) return fail(TA_EINVAL, "call ta_wall_voxels_count first");
-    if (max_iter < 1) return fail(TA_EINVAL, "max_iter must be positive");
-    if (c->perm[0] != 0 || c->perm[1] != 1 || c->perm[2] != 2)
-        return fail(TA_EINVAL, "wall medians need a C-ordered volume (the order of a wall's voxels decides ties)");
-    if ((uint64_t)c->wall_records >= (1ull << 31)) return fail(TA_EINVAL, "too many records for the wall medians");
-    int rc = use_device(c);
-    if (rc != TA_OK) return rc;
-    const uint64_t n = (uint64_t)c->wall_records;
-    c->wall_median_count = -1;
-    *nwalls = 0;
-    if (ms_out) *ms_out = 0.0;
-    if (n == 0) { c->wall_median_count = 0; return TA_OK; }
-    if (n >= (1ull << 32)) return fail(TA_EINVAL, "too many records (%llu) for the grouped fetch", (unsigned long long)n);
-    DevBuf buf, scratch, starts;
-    uint32_t* gpa = nullptr; int32_t* gco = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    hipError_t e = hipEventCreate(&e0);
-    if (e == hipSuccess) e = hipEventCreate(&e1);
-    if (e == hipSuccess) e = hipEventRecord(e0, c->stream);
-    rc = e == hipSuccess ? wall_records_device(c, true, buf, &gpa, &gco, nullptr, nullptr) : TA_EHIP;
-    if (rc == TA_OK) rc = scratch.reserve(ta::wall_median_scratch_bytes(n));
-    if (rc == TA_OK) rc = starts.reserve(n * 4 + 16);
-    uint64_t E = 0;
-    uint32_t status = 0;
-    if (rc == TA_OK) {
-        uint64_t* total_dev = nullptr;
-        ta::launch_wall_starts(c->stream, gpa, n, scratch.p, (uint32_t*)starts.p, &total_dev);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(&E, total_dev, sizeof(E), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e == hipSuccess) rc = c->wall_medians.reserve(E * 24 + 16);
-        if (e == hipSuccess && rc == TA_OK) {
-            uint32_t* op = (uint32_t*)c->wall_medians.p;
-            uint32_t* os = op + 2 * E;
-            int32_t* om = (int32_t*)(os + E);
-            uint32_t* st = (uint32_t*)scratch.p;                          // (the flags are dead: their first word takes the status)
-            e = hipMemsetAsync(st, 0, 4, c->stream);
-            if (e == hipSuccess) {
-                ta::launch_wall_medians(c->stream, gpa, gco, (const uint32_t*)starts.p, (uint32_t)E, n, max_iter, op, os, om, st);
-                e = hipGetLastError();
-            }
-            if (e == hipSuccess) e = hipEventRecord(e1, c->stream);
-            if (e == hipSuccess) e = hipMemcpyAsync(&status, st, 4, hipMemcpyDeviceToHost, c->stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        }
-    }
-    float ms = 0.f;
-    if (rc == TA_OK && e == hipSuccess) (void)hipEventElapsedTime(&ms, e0, e1);
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    buf.release(); scratch.release(); starts.release();
-    if (rc != TA_OK) return rc;
-    if (e != hipSuccess) return fail(TA_EHIP, "wall medians: %s", hipGetErrorString(e));
-    // (walls still moving after max_iter passes are MARKED -- bit 31 of their size word -- not refused: a caller asks for
-    //  some walls, and one that nobody asks for -- the background's, say -- must not fail the rest)
-    c->wall_median_count = (int64_t)E;
-    *nwalls = (int64_t)E;
-    if (ms_out) *ms_out = ms;
-    return TA_OK;
-}
-
-TA_API int ta_wall_medians_get(ta_ctx* c, uint32_t* pairs, uint32_t* sizes, int32_t* medians) {
-    if (!c) return fail(TA_EINVAL, "ctx is NULL");
-    if (c->wall_median_count < 0) return fail(TA_EINVAL, "call ta_wall_medians first");
-    const uint64_t E = (uint64_t)c->wall_median_count;
-    if (E == 0) return TA_OK;
-    if (!pairs || !sizes || !medians) return fail(TA_EINVAL, "NULL output array");
-    int rc = use_device(c);
-    if (rc != TA_OK) return rc;
-    const uint32_t* op = (const uint32_t*)c->wall_medians.p;
-    TA_HIP(hipMemcpyAsync(pairs, op, E * 8, hipMemcpyDeviceToHost, c->stream));
-    TA_HIP(hipMemcpyAsync(sizes, op + 2 * E, E * 4, hipMemcpyDeviceToHost, c->stream));
-    TA_HIP(hipMemcpyAsync(medians, op + 3 * E, E * 12, hipMemcpyDeviceToHost, c->stream));
-    TA_HIP(hipStreamSynchronize(c->stream));
-    return TA_OK;
-}
-
-
-TA_API int ta_wall_voxels_get(ta_ctx* c, uint32_t* pairs, int32_t* coords, double* ms_out) {
-    return wall_voxels_fetch(c, pairs, coords, ms_out, false);
-}
-
-TA_API int ta_wall_voxels_get_by_pair(ta_ctx* c, uint32_t* pairs, int32_t* coords, double* ms_out) {
-    return wall_voxels_fetch(c, pairs, coords, ms_out, true);
-}
-
-TA_API int ta_volume_max_label(ta_ctx* c, uint32_t* max_label) {
-    if (!c || !max_label) return fail(TA_EINVAL, "NULL argument");
-    if (!c->vol) return fail(TA_EINVAL, "no volume set");
-    int rc = use_device(c);
-    if (rc != TA_OK) return rc;
-    const uint64_t nvox = (uint64_t)c->mdims[0] * c->mdims[1] * c->mdims[2];
-    if ((rc = settle_rerank(c)) != TA_OK) return rc;
-    ta::launch_max_label(c->stream, c->vol, c->itemsize, nvox, maxlab_dev(c));
-    uint32_t v = 0;
-    TA_HIP(hipMemcpyAsync(&v, maxlab_dev(c), sizeof(v), hipMemcpyDeviceToHost, c->stream));
-    TA_HIP(hipStreamSynchronize(c->stream));
-    TA_HIP(hipGetLastError());
-    *max_label = v;
-    c->vol_max = v;
-    return TA_OK;
-}
-
-// ---- sparse label ids -------------------------------------------------------------------------------------------
-namespace {
-// census of `ids` (host, ascending, unique; NULL: of the resident volume itself) on the context; leaves census_n / census_ids
-int build_census(ta_ctx* c, const uint32_t* ids, uint32_t n_ids) {
-    int rc;
-    const uint64_t nvox = (uint64_t)c->mdims[0] * c->mdims[1] * c->mdims[2];
-    uint32_t top = 0, listed = 0;
-    uint64_t cap = 0;
-    bool have_list = false;
-    DevBuf& list = c->census_list;                      // (kept: allocating and freeing it costs more than the pass it saves)
-    if (ids) {
-        for (uint32_t i = 1; i < n_ids; ++i)
-            if (ids[i] <= ids[i - 1]) return fail(TA_EINVAL, "ids must be ascending and unique (ids[%u]=%u after %u)", i, ids[i], ids[i - 1]);
-        top = n_ids ? ids[n_ids - 1] : 0u;
-    } else if (c->vol_max >= 0 && c->vol == c->owned_vol.p) {
-        top = (uint32_t)c->vol_max;                     // (ta_volume_max_label has been here, and only this library writes
-                                                        //  a volume it uploaded itself: no second pass)
-    } else {
-        // ONE pass over the voxels where the maximum is not known: the workgroups' label sets go to a list, the list gives the
-        // maximum (the table's size) and is marked afterwards -- a few hundred thousand entries against a second read of the volume
-        cap = ta::census_list_capacity(nvox);
-        const uint32_t parts = ta::census_list_parts();
-        if (list.reserve(ta::census_list_head_bytes() + (uint64_t)parts * cap * 4) == TA_OK) {
-            TA_HIP(hipMemsetAsync(list.p, 0, ta::census_list_head_bytes(), c->stream));
-            if (ta::launch_census_list(c->stream, c->vol, c->itemsize, nvox, c->mdims[2], list.p, (uint32_t)cap)) {
-                std::vector<uint32_t> head;
-                try { head.resize(2 * (size_t)parts); } catch (...) { return fail(TA_ENOMEM, "out of host memory"); }
-                TA_HIP(hipMemcpyAsync(head.data(), list.p, ta::census_list_head_bytes(), hipMemcpyDeviceToHost, c->stream));
-                TA_HIP(hipStreamSynchronize(c->stream));
-                have_list = true;
-                for (uint32_t p = 0; p < parts; ++p) {
-                    if (head[2 * p] > cap) have_list = false;
-                    if (head[2 * p] > listed) listed = head[2 * p];
-                    if (head[2 * p + 1] > top) top = head[2 * p + 1];
-                }
-                if (have_list) c->vol_max = top; else top = 0;
-            }
-        }
-        if (!have_list) {                               // (rows that are not whole vectors, or a volume of noise: the two passes)
-            ta::launch_max_label(c->stream, c->vol, c->itemsize, nvox, maxlab_dev(c));
-            TA_HIP(hipMemcpyAsync(&top, maxlab_dev(c), sizeof(top), hipMemcpyDeviceToHost, c->stream));
-            TA_HIP(hipStreamSynchronize(c->stream));
-            c->vol_max = top;
-        }
-    }
-    c->census_n = -1;
-    if ((rc = c->census.reserve(ta::census_bytes(top))) != TA_OK) return rc;
-    DevBuf scratch, staged;
-    if ((rc = scratch.reserve(ta::census_scratch_bytes(top))) != TA_OK) return rc;
-    hipError_t e = hipMemsetAsync(c->census.p, 0, ta::census_bytes(top), c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(scratch.p, 0, ta::census_scratch_bytes(top), c->stream);
-    if (e == hipSuccess && ids && n_ids) {
-        if ((rc = staged.reserve((uint64_t)n_ids * 4)) != TA_OK) { scratch.release(); return rc; }
-        e = hipMemcpyAsync(staged.p, ids, (uint64_t)n_ids * 4, hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) ta::launch_census_from_ids(c->stream, (const uint32_t*)staged.p, n_ids, c->census.p, scratch.p, top);
-    } else if (e == hipSuccess && !ids && have_list) {
-        ta::launch_census_from_list(c->stream, list.p, (uint32_t)cap, listed, c->census.p, scratch.p, top);
-    } else if (e == hipSuccess && !ids) {
-        ta::launch_census_mark(c->stream, c->vol, c->itemsize, nvox, c->mdims[2], c->census.p, scratch.p, top);
-    }
-    uint32_t* total_dev = nullptr;
-    uint32_t total = 0;
-    if (e == hipSuccess) {
-        ta::launch_census_scan(c->stream, c->census.p, top, scratch.p, nullptr, &total_dev);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(&total, total_dev, sizeof(total), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e == hipSuccess && total) {
-        rc = c->census_ids.reserve((uint64_t)total * 4);
-        if (rc != TA_OK) { scratch.release(); staged.release(); return rc; }
-        ta::launch_census_scan(c->stream, c->census.p, top, scratch.p, (uint32_t*)c->census_ids.p, nullptr);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    }
-    scratch.release();
-    staged.release();
-    if (e != hipSuccess) return fail(TA_EHIP, "label census: %s", hipGetErrorString(e));
-    c->census_max = top;
-    c->census_n = (int64_t)total;
-    c->census_of_volume = ids == nullptr;
-    return TA_OK;
-}
-}  // namespace
-
-TA_API int ta_volume_label_census(ta_ctx* c, uint32_t* max_label, uint32_t* n_present) {
-    if (!c) return fail(TA_EINVAL, "ctx is NULL");
-    if (!c->vol) return fail(TA_EINVAL, "no volume set");
-    int rc = use_device(c);
-    if (rc != TA_OK) return rc;
-    if (c->compact) return fail(TA_EINVAL, "the context is compacted: its census is the one it was compacted with");
-    if ((rc = build_census(c, nullptr, 0)) != TA_OK) return rc;
-    if (max_label) *max_label = c->census_max;
-    if (n_present) *n_present = (uint32_t)c->census_n;
-    return TA_OK;
-}
-
-TA_API int ta_label_census_get(ta_ctx* c, uint32_t* ids) {
-    if (!c || !ids) return fail(TA_EINVAL, "NULL argument");
-    if (c->census_n < 0) return fail(TA_EINVAL, "no label census on this context");
-    int rc = use_device(c);
-    if (rc != TA_OK) return rc;
-    if (c->census_n == 0) return TA_OK;
-    TA_HIP(hipMemcpyAsync(ids, c->census_ids.p, (uint64_t)c->census_n * 4, hipMemcpyDeviceToHost, c->stream));
-    TA_HIP(hipStreamSynchronize(c->stream));
-    return TA_OK;
-}
-
-TA_API int ta_volume_compact_labels(ta_ctx* c, const uint32_t* ids, uint32_t n_ids, uint32_t* n_rows) {
-    if (!c || (!ids && n_ids)) return fail(TA_EINVAL, "NULL argument");
-    if (!c->vol) return fail(TA_EINVAL, "no volume set");
-    int rc = use_device(c);
-    if (rc != TA_OK) return rc;
-    c->compact = false;
-    c->rerank_check = false;
-    c->extracted = c->checked = false;
-    if (ids || c->census_n < 0 || !c->census_of_volume)          // (ids == NULL means THIS volume's census: never a caller's list left behind)
-        if ((rc = build_census(c, ids, n_ids)) != TA_OK) return rc;
-    if (c->census_n >= (1ll << 28)) return fail(TA_ERANGE, "%lld label ids are present: too many for per-label rows", (long long)c->census_n);
-    const uint64_t nvox = (uint64_t)c->mdims[0] * c->mdims[1] * c->mdims[2];
-    if ((rc = c->compact_vol.reserve(nvox * c->itemsize + 64)) != TA_OK) return rc;
-    uint32_t status = 0;
-    hipError_t e = hipMemsetAsync(maxlab_dev(c), 0, sizeof(uint32_t), c->stream);       // (the word is free between max-label passes)
-    if (e == hipSuccess) {
-        ta::launch_census_rank(c->stream, c->vol, c->compact_vol.p, c->itemsize, nvox, c->census.p, c->census_max, maxlab_dev(c));
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(&status, maxlab_dev(c), sizeof(status), hipMemcpyDeviceToHost, c->stream);
-    try { c->h_ids.resize((size_t)c->census_n); } catch (...) { return fail(TA_ENOMEM, "out of host memory"); }
-    if (e == hipSuccess && c->census_n)
-        e = hipMemcpyAsync(c->h_ids.data(), c->census_ids.p, (uint64_t)c->census_n * 4, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) return fail(TA_EHIP, "compact labels: %s", hipGetErrorString(e));
-    if (status) return fail(TA_ERANGE, "the volume holds a label id that is not in the list it was to be compacted with");
-    c->compact = true;
-    c->auto_tile_shift = 0;
-    if (n_rows) *n_rows = (uint32_t)c->census_n;
-    return TA_OK;
-}
-
-TA_API int ta_volume_is_compact(ta_ctx* c, int* compact, uint32_t* n_rows) {
-    if (!c || !compact) return fail(TA_EINVAL, "NULL argument");
-    *compact = c->compact ? 1 : 0;
-    if (n_rows) *n_rows = c->compact ? (uint32_t)c->census_n : 0u;
-    return TA_OK;
-}
-
-TA_API int ta_volume_rerank(ta_ctx* c) {
-    if (!c) return fail(TA_EINVAL, "ctx is NULL");
-    if (!c->vol) return fail(TA_EINVAL, "no volume set");
-    if (!c->compact) return fail(TA_EINVAL, "the context is not compacted");
-    int rc = use_device(c);
-    if (rc != TA_OK) return rc;
-    const uint64_t nvox = (uint64_t)c->mdims[0] * c->mdims[1] * c->mdims[2];
-    c->extracted = c->checked = false;
-    // asynchronous on the context's stream: the "id not in the census" word travels to the host with the flags of the next
-    // extraction, whose getters then answer TA_ERANGE
-    hipError_t e = hipMemsetAsync(maxlab_dev(c), 0, sizeof(uint32_t), c->stream);
-    if (e == hipSuccess) {
-        ta::launch_census_rank(c->stream, c->vol, c->compact_vol.p, c->itemsize, nvox, c->census.p, c->census_max, maxlab_dev(c));
-        e = hipGetLastError();
-    }
-    if (e != hipSuccess) return fail(TA_EHIP, "re-rank: %s", hipGetErrorString(e));
-    c->rerank_check = true;
-    c->vol_max = -1;
-    junctions_on_new_volume(c);     // (the caller edited the labels in place)
-    components_on_new_volume(c);
-    return TA_OK;
-}
-
-TA_API int ta_volume_uncompact(ta_ctx* c) {
-    if (!c) return fail(TA_EINVAL, "ctx is NULL");
-    if (c->compact) {
-        if (c->stream) (void)hipStreamSynchronize(c->stream);
-        c->compact = false;
-        c->rerank_check = false;
-        c->extracted = c->checked = false;
-        c->compact_vol.release();
-        c->auto_tile_shift = 0;
-    }
     return TA_OK;
 }
 
@@ -1391,13 +863,13 @@ TA_API int ta_adjacency_get(ta_ctx* c, uint32_t* lo, uint32_t* hi, uint64_t* fac
     const bool identity = c->perm[0] == 0 && c->perm[1] == 1 && c->perm[2] == 2;
     const uint64_t* h_keys = (const uint64_t*)c->h_pairs.p;
     const uint64_t* h_faces = h_keys + n;
-    if (c->compact) {               // rows are ranks, label values are ids (order-preserving: the list stays sorted)
-        const uint64_t nid = c->h_ids.size();
+    if (c->ids.compact) {               // rows are ranks, label values are ids (order-preserving: the list stays sorted)
+        const uint64_t nid = c->ids.h_ids.size();
         for (uint64_t i = 0; i < n; ++i) {
             const uint64_t a = h_keys[i] >> 32, b = h_keys[i] & 0xffffffffu;
             if (a >= nid || b >= nid) return fail(TA_ERANGE, "adjacency holds rank %llu, the census has %llu ids", (unsigned long long)std::max(a, b), (unsigned long long)nid);
-            if (lo) lo[i] = c->h_ids[a];
-            if (hi) hi[i] = c->h_ids[b];
+            if (lo) lo[i] = c->ids.h_ids[a];
+            if (hi) hi[i] = c->ids.h_ids[b];
         }
     } else {
         if (lo) for (uint64_t i = 0; i < n; ++i) lo[i] = (uint32_t)(h_keys[i] >> 32);
@@ -1485,137 +957,6 @@ TA_API int ta_debug_counters(ta_ctx* c, uint32_t out[16]) {
     if (rc != TA_OK) return rc;
     TA_HIP(hipStreamSynchronize(c->stream));
     for (int i = 0; i < 16; ++i) out[i] = i < ta::NFLAGS ? c->h_small[i] : 0u;
-    return TA_OK;
-}
-
-TA_API int ta_accumulators_reduced(ta_ctx* c) {
-    if (!c) return fail(TA_EINVAL, "ctx is NULL");
-    if (!c->extracted) return fail(TA_EINVAL, "no extraction has been run on this context");
-    c->reduced = true;
-    return TA_OK;
-}
-
-TA_API int ta_accumulators_device(ta_ctx* c, void** sums_dev, void** boxes_dev, uint32_t* max_label) {
-    if (!c) return fail(TA_EINVAL, "ctx is NULL");
-    if (!c->extracted) return fail(TA_EINVAL, "no extraction has been run on this context");
-    if (sums_dev) *sums_dev = c->sums;
-    if (boxes_dev) *boxes_dev = c->boxes;
-    if (max_label) *max_label = c->max_label;
-    return TA_OK;
-}
-
-TA_API int ta_adjacency_device(ta_ctx* c, void** keys_dev, void** faces_dev, int64_t* npairs) {
-    if (!c) return fail(TA_EINVAL, "ctx is NULL");
-    int rc = use_device(c);
-    if (rc != TA_OK) return rc;
-    if ((rc = finish_extract(c)) != TA_OK) return rc;
-    if (keys_dev) *keys_dev = c->out_keys.p;
-    if (faces_dev) *faces_dev = c->out_faces.p;
-    if (npairs) *npairs = c->npairs;
-    return TA_OK;
-}
-
-TA_API int ta_adjacency_export(ta_ctx* c, void* keys_dst_dev, void* faces_dst_dev, int64_t capacity_pairs) {
-    if (!c) return fail(TA_EINVAL, "ctx is NULL");
-    int rc = use_device(c);
-    if (rc != TA_OK) return rc;
-    if ((rc = finish_extract(c)) != TA_OK) return rc;
-    if (capacity_pairs < c->npairs) return fail(TA_EINVAL, "export buffers hold %lld pairs, %lld needed", (long long)capacity_pairs, (long long)c->npairs);
-    if (c->npairs > 0) {
-        if (!keys_dst_dev || !faces_dst_dev) return fail(TA_EINVAL, "NULL export buffer");
-        TA_HIP(hipMemcpyAsync(keys_dst_dev, c->out_keys.p, (uint64_t)c->npairs * 8, hipMemcpyDeviceToDevice, c->stream));
-        TA_HIP(hipMemcpyAsync(faces_dst_dev, c->out_faces.p, (uint64_t)c->npairs * 24, hipMemcpyDeviceToDevice, c->stream));
-    }
-    return TA_OK;
-}
-
-TA_API int ta_adjacency_merge(ta_ctx* c, const void* keys_dev, const void* faces_dev, int64_t npairs) {
-    if (!c) return fail(TA_EINVAL, "ctx is NULL");
-    if (npairs < 0 || (npairs > 0 && (!keys_dev || !faces_dev))) return fail(TA_EINVAL, "bad pair list");
-    int rc = use_device(c);
-    if (rc != TA_OK) return rc;
-    if ((rc = finish_extract(c)) != TA_OK) return rc;
-    if (!(c->feature_mask & TA_F_ADJACENCY)) return fail(TA_EINVAL, "the last extraction did not request adjacency");
-    // local list (already collected, so the table is clean) + foreign list -> table -> collect again
-    ta::PairTable pt = pair_table(c);
-    DevBuf local_k, local_f;
-    const uint64_t nl = (uint64_t)c->npairs;
-    if ((rc = local_k.reserve(nl * 8 + 8)) != TA_OK) return rc;
-    if ((rc = local_f.reserve(nl * 24 + 8)) != TA_OK) { local_k.release(); return rc; }
-    hipError_t e = hipSuccess;
-    if (nl) {
-        e = hipMemcpyAsync(local_k.p, c->out_keys.p, nl * 8, hipMemcpyDeviceToDevice, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(local_f.p, c->out_faces.p, nl * 24, hipMemcpyDeviceToDevice, c->stream);
-    }
-    if (e == hipSuccess) e = hipMemsetAsync(c->small.p, 0, SMALL_WORDS * sizeof(uint32_t), c->stream);
-    if (e != hipSuccess) { local_k.release(); local_f.release(); return fail(TA_EHIP, "merge staging: %s", hipGetErrorString(e)); }
-    ta::launch_pairs_insert(c->stream, pt, (const uint64_t*)local_k.p, (const uint64_t*)local_f.p, nl, flags_dev(c));
-    ta::launch_pairs_insert(c->stream, pt, (const uint64_t*)keys_dev, (const uint64_t*)faces_dev, (uint64_t)npairs, flags_dev(c));
-    ta::launch_pairs_collect(c->stream, pt, (uint64_t*)c->out_keys.p, (uint64_t*)c->out_faces.p, cursor_dev(c));
-    e = hipMemcpyAsync(c->h_small, c->small.p, SMALL_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    local_k.release(); local_f.release();
-    if (e != hipSuccess) return fail(TA_EHIP, "merge: %s", hipGetErrorString(e));
-    if (c->h_small[ta::FLAG_PAIR_OVERFLOW])
-        return fail(TA_ECAPACITY, "adjacency table overflow while merging (2^%d slots); raise TA_OPT_PAIR_SLOTS", c->pair_log2);
-    c->npairs = (int64_t)c->h_small[ta::NFLAGS];
-    c->host_pairs_ready = false;
-    return TA_OK;
-}
-
-TA_API int ta_adjacency_pack(ta_ctx* c, void* block_dev, int64_t capacity_pairs) {
-    if (!c || !block_dev) return fail(TA_EINVAL, "NULL argument");
-    if (capacity_pairs < 1) return fail(TA_EINVAL, "capacity_pairs must be >= 1");
-    if (!c->extracted || !(c->feature_mask & TA_F_ADJACENCY))
-        return fail(TA_EINVAL, "no extraction with adjacency has been run on this context");
-    if (c->exchanged) return fail(TA_EINVAL, "the adjacency of this extraction was already exchanged");
-    int rc = use_device(c);
-    if (rc != TA_OK) return rc;
-    ta::launch_pairs_pack(c->stream, (const uint64_t*)c->out_keys.p, (const uint64_t*)c->out_faces.p, cursor_dev(c),
-                          flags_dev(c), (uint64_t*)block_dev, (uint64_t)capacity_pairs);
-    TA_HIP(hipGetLastError());
-    return TA_OK;
-}
-
-TA_API int ta_adjacency_pack_shared(ta_ctx* c, void* block_dev, int64_t capacity_pairs) {
-    if (!c || !block_dev) return fail(TA_EINVAL, "NULL argument");
-    if (capacity_pairs < 1) return fail(TA_EINVAL, "capacity_pairs must be >= 1");
-    if (!c->extracted || !(c->feature_mask & TA_F_ADJACENCY))
-        return fail(TA_EINVAL, "no extraction with adjacency has been run on this context");
-    if (c->exchanged) return fail(TA_EINVAL, "the adjacency of this extraction was already exchanged");
-    int rc = use_device(c);
-    if (rc != TA_OK) return rc;
-    const int64_t lo = c->a_origin, hi = c->a_origin + (c->mdims[0] - c->first_owned);
-    TA_HIP(hipMemsetAsync(block_dev, 0, 8, c->stream));          // the block's pair count: the kernel's append cursor
-    // (the local list can hold no more pairs than the table has slots)
-    ta::launch_pairs_pack_shared(c->stream, pair_table(c), (const uint64_t*)c->out_keys.p, (const uint64_t*)c->out_faces.p,
-                                 cursor_dev(c), flags_dev(c), c->boxes, c->max_label, lo, hi, (uint64_t*)block_dev,
-                                 (uint64_t)capacity_pairs, 1ull << c->pair_log2);
-    TA_HIP(hipGetLastError());
-    c->table_clean = false;          // holds this rank's private pairs until ta_adjacency_merge_blocks collects
-    c->shared_packed = true;
-    return TA_OK;
-}
-
-TA_API int ta_adjacency_merge_blocks(ta_ctx* c, const void* blocks_dev, int nblocks, int64_t capacity_pairs) {
-    if (!c || !blocks_dev) return fail(TA_EINVAL, "NULL argument");
-    if (nblocks < 1 || capacity_pairs < 1) return fail(TA_EINVAL, "nblocks and capacity_pairs must be >= 1");
-    if (!c->extracted || !(c->feature_mask & TA_F_ADJACENCY))
-        return fail(TA_EINVAL, "no extraction with adjacency has been run on this context");
-    int rc = use_device(c);
-    if (rc != TA_OK) return rc;
-    // the collect of the extraction left the table clean: rebuild it from every rank's block
-    ta::PairTable pt = pair_table(c);
-    TA_HIP(hipMemsetAsync(c->small.p, 0, SMALL_WORDS * sizeof(uint32_t), c->stream));
-    ta::launch_pairs_insert_blocks(c->stream, pt, (const uint64_t*)blocks_dev, nblocks, (uint64_t)capacity_pairs,
-                                   flags_dev(c));
-    ta::launch_pairs_collect(c->stream, pt, (uint64_t*)c->out_keys.p, (uint64_t*)c->out_faces.p, cursor_dev(c));
-    TA_HIP(hipMemcpyAsync(c->h_small, c->small.p, SMALL_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    TA_HIP(hipGetLastError());
-    c->table_clean = true;
-    c->exchanged = true;
-    c->checked = false;
-    c->host_pairs_ready = false;
     return TA_OK;
 }
 

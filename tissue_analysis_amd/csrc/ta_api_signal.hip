@@ -30,6 +30,25 @@ int signal_finish(ta_ctx* c) {
 
 }  // namespace
 
+// pair -> row: an open-addressed table of the sorted pair list (ta_adjacency_get sorts it on the device once per extraction)
+int build_pair_index(ta_ctx* c, DevBuf& into, const uint64_t** hkeys, const uint32_t** hrows, uint32_t* hmask) {
+    const uint64_t P = (uint64_t)c->npairs;
+    int rc = ta_adjacency_get(c, nullptr, nullptr, nullptr);
+    if (rc != TA_OK) return rc;
+    uint64_t cap = 64;
+    while (cap < 2 * P) cap <<= 1;
+    if (cap > (1ull << 32)) return fail(TA_EINVAL, "too many pairs (%llu)", (unsigned long long)P);
+    if ((rc = into.reserve(cap * 12 + P * 8)) != TA_OK) return rc;
+    uint64_t* keys = (uint64_t*)into.p;
+    uint64_t* sorted = keys + cap;
+    uint32_t* rows = (uint32_t*)(sorted + P);
+    TA_HIP(hipMemsetAsync(keys, 0xff, cap * 8, c->stream));
+    TA_HIP(hipMemcpyAsync(sorted, c->h_pairs.p, P * 8, hipMemcpyHostToDevice, c->stream));
+    ta::launch_signal_hash(c->stream, sorted, P, keys, rows, (uint32_t)(cap - 1));
+    *hkeys = keys; *hrows = rows; *hmask = (uint32_t)(cap - 1);
+    return TA_OK;
+}
+
 // a new label volume: the signal results are stale (extracted is false); a signal of other dims is dropped
 void signal_on_new_volume(ta_ctx* c) {
     c->sig.seq = 0;
@@ -71,19 +90,7 @@ TA_API int ta_signal_extract(ta_ctx* c, uint32_t what) {
     ta::SignalArgs a;
     a.hkeys = nullptr; a.hrows = nullptr; a.hmask = 0;
     if (walls && P) {
-        // pair -> row: an open-addressed table of the sorted pair list (ta_adjacency_get sorts it on the device once per extraction)
-        if ((rc = ta_adjacency_get(c, nullptr, nullptr, nullptr)) != TA_OK) return rc;
-        uint64_t cap = 64;
-        while (cap < 2 * P) cap <<= 1;
-        if (cap > (1ull << 32)) return fail(TA_EINVAL, "too many pairs (%llu)", (unsigned long long)P);
-        if ((rc = c->sig.hash.reserve(cap * 12 + P * 8)) != TA_OK) return rc;
-        uint64_t* hkeys = (uint64_t*)c->sig.hash.p;
-        uint64_t* sorted = hkeys + cap;
-        uint32_t* hrows = (uint32_t*)(sorted + P);
-        TA_HIP(hipMemsetAsync(hkeys, 0xff, cap * 8, c->stream));
-        TA_HIP(hipMemcpyAsync(sorted, c->h_pairs.p, P * 8, hipMemcpyHostToDevice, c->stream));
-        ta::launch_signal_hash(c->stream, sorted, P, hkeys, hrows, (uint32_t)(cap - 1));
-        a.hkeys = hkeys; a.hrows = hrows; a.hmask = (uint32_t)(cap - 1);
+        if ((rc = build_pair_index(c, c->sig.hash, &a.hkeys, &a.hrows, &a.hmask)) != TA_OK) return rc;
     }
     char* o = (char*)c->sig.out.p;
     TA_HIP(hipMemsetAsync(o, 0, L.bytes, c->stream));

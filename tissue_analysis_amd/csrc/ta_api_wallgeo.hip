@@ -1,7 +1,6 @@
 // ta_api_wallgeo.hip -- the C ABI of include/tissue_scan_wallgeo.h on top of kernels_wallgeo.hip.
 #include "../../include/tissue_scan_wallgeo.h"
 #include "ta_ctx.h"
-#include "ta_signal.h"
 #include "ta_wallgeo.h"
 
 namespace {
@@ -48,21 +47,7 @@ TA_API int ta_wallgeo_extract(ta_ctx* c) {
     if ((rc = c->wg.out.reserve(bytes)) != TA_OK) return rc;
     if ((rc = ensure_events(c->wg.ev)) != TA_OK) return rc;
     ta::WallGeoArgs a = {};
-    if (P) {
-        // pair -> row: an open-addressed table of the sorted pair list (ta_adjacency_get sorts it on the device once per extraction)
-        if ((rc = ta_adjacency_get(c, nullptr, nullptr, nullptr)) != TA_OK) return rc;
-        uint64_t cap = 64;
-        while (cap < 2 * P) cap <<= 1;
-        if (cap > (1ull << 32)) return fail(TA_EINVAL, "too many pairs (%llu)", (unsigned long long)P);
-        if ((rc = c->wg.hash.reserve(cap * 12 + P * 8)) != TA_OK) return rc;
-        uint64_t* hkeys = (uint64_t*)c->wg.hash.p;
-        uint64_t* sorted = hkeys + cap;
-        uint32_t* hrows = (uint32_t*)(sorted + P);
-        TA_HIP(hipMemsetAsync(hkeys, 0xff, cap * 8, c->stream));
-        TA_HIP(hipMemcpyAsync(sorted, c->h_pairs.p, P * 8, hipMemcpyHostToDevice, c->stream));
-        ta::launch_signal_hash(c->stream, sorted, P, hkeys, hrows, (uint32_t)(cap - 1));
-        a.hkeys = hkeys; a.hrows = hrows; a.hmask = (uint32_t)(cap - 1);
-    }
+    if (P && (rc = build_pair_index(c, c->wg.hash, &a.hkeys, &a.hrows, &a.hmask)) != TA_OK) return rc;
     char* o = (char*)c->wg.out.p;
     TA_HIP(hipMemsetAsync(o, 0, bytes, c->stream));
     a.vol = sweep_vol(c);

@@ -1,5 +1,7 @@
-// ta_ctx.h -- the context behind the C ABI and what the ta_api*.hip files share (host only, private to csrc/).  ta_api.hip holds
-// the core and defines what is declared here; a feature has one struct of state below and its entry points in ta_api_<feature>.hip.
+// ta_ctx.h -- the context behind the C ABI and what the ta_api*.hip files share (host only, private to csrc/).  Every concern has one
+// struct of state below and its entry points in a file of its own: ta_api.hip holds the core (context, volume, sweep, extraction)
+// and the sweep's tile shape; ta_api_walls.hip, ta_api_sparse.hip and ta_api_exchange.hip the wall voxels, the sparse label ids and
+// the rank exchange; ta_api_<feature>.hip a feature.  What crosses files is declared here, with the file that defines it.
 #pragma once
 #include "../../include/tissue_scan.h"
 #include "ta_kernels.h"
@@ -161,6 +163,54 @@ struct ComponentState {
     void release() { parent.release(); work.release(); slots.release(); sort.release(); rows.release(); small.release(); image.release(); destroy_events(ev); }
 };
 
+// wall voxels and wall medians (ta_api_walls.hip)
+struct WallVoxelState {
+    DevBuf counts;                                      // per-chunk record counts, then offsets
+    DevBuf stage;                                       // the records the count pass staged (kept until the volume is replaced)
+    DevBuf medians;                                     // ta_wall_medians: pairs u32[E][2] | sizes u32[E] | medians i32[E][3]
+    int64_t records = -1;                               // result of the last ta_wall_voxels_count, -1 = none
+    uint32_t region = 0, not_staged = 0;                // records per staging region of that call (0 = nothing staged); cells left to the second walk
+    int64_t median_count = -1;                          // E of the last ta_wall_medians, -1 = none
+    bool wide = false;                                  // that call met a label >= 2^31
+    uint32_t label_or = 0;                              // OR of all labels of the volume (that call): the bits a label takes
+    double ms = 0.0;
+    void release() { counts.release(); stage.release(); medians.release(); }
+};
+
+// sparse label ids (ta_api_sparse.hip): the census of the volume's ids and the copy of the volume in their ranks (what the sweep then reads)
+struct SparseIdState {
+    DevBuf census, census_ids, compact_vol, census_list;      // (census_list: the label list of the one-pass census, ~n / 256 entries)
+    uint32_t census_max = 0;            // ids 0 .. census_max have a bit
+    int64_t census_n = -1;              // ids present, -1 = no census
+    int64_t vol_max = -1;               // largest label of the resident buffer (halo included), -1 = not known
+    bool compact = false;               // per-label ROWS are ranks 0 .. census_n - 1; every label VALUE handed out is an id
+    bool census_of_volume = false;      // the census on the context was taken from THIS volume (not a caller's id list)
+    bool rerank_check = false;          // ta_volume_rerank's "id not in the list" word has not been looked at yet
+    std::vector<uint32_t> h_ids;        // rank -> id (host copy, compact mode)
+    void release() { census.release(); census_ids.release(); compact_vol.release(); census_list.release(); }
+};
+
+// the tile shape of the sweep of a uint32 volume with adjacency (kernels_scan.hip; state of ta_api.hip's sweep_shape): both give the
+// same results; which one is faster depends on the tissue (background around it: the wide one; cells everywhere: the narrow one), so
+// the first four sweeps of a volume take turns (wide, narrow, wide, narrow) between two events each, and the faster shape keeps the volume
+struct SweepShapeState {
+    int opt = -1;                                       // TA_OPT_SWEEP_SHAPE: -1 = measure, 0 / 1 = as told
+    int pick = -1;                                      // choice for this volume, -1 = not yet
+    double density = -1.0;                              // label changes per voxel in the sampled planes (what decided it), -1 = not measured
+    int last = 0;                                       // TA_OPT_SWEEP_SHAPE_USED: the shape of the last sweep
+    int tune_launched = 0;                              // measuring sweeps launched (0 .. 4)
+    hipEvent_t tune_ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    bool tune_done[4] = {false, false, false, false};
+    float tune_ms[4] = {0.f, 0.f, 0.f, 0.f};
+    void forget_choice() {                              // decided again at the next sweep (new voxels, or a new rule)
+        pick = -1;
+        density = -1.0;
+        tune_launched = 0;
+        for (bool& d : tune_done) d = false;
+    }
+    void release() { destroy_events(tune_ev); }
+};
+
 struct ta_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -179,16 +229,6 @@ struct ta_ctx {
     int64_t a_origin = 0;
     int first_owned = 0;
 
-    // sparse label ids: the census of the volume's ids and the copy of the volume in their ranks (what the sweep then reads)
-    DevBuf census, census_ids, compact_vol, census_list;      // (census_list: the label list of the one-pass census, ~n / 256 entries)
-    uint32_t census_max = 0;            // ids 0 .. census_max have a bit
-    int64_t census_n = -1;              // ids present, -1 = no census
-    int64_t vol_max = -1;               // largest label of the resident buffer (halo included), -1 = not known
-    bool compact = false;               // per-label ROWS are ranks 0 .. census_n - 1; every label VALUE handed out is an id
-    bool census_of_volume = false;      // the census on the context was taken from THIS volume (not a caller's id list)
-    bool rerank_check = false;          // ta_volume_rerank's "id not in the list" word has not been looked at yet
-    std::vector<uint32_t> h_ids;        // rank -> id (host copy, compact mode)
-
     // accumulators
     DevBuf own_sums, own_boxes;
     uint64_t* sums = nullptr;
@@ -201,15 +241,6 @@ struct ta_ctx {
     DevBuf pkeys, pfaces, out_keys, out_faces, small;   // small: flags[NFLAGS] | cursor | maxlabel
     DevBuf hot_rows;                                    // [workgroups][16] private rows of the hot label
     DevBuf sort_buf;                                    // scratch of ta_adjacency_get's device sort (kept between calls)
-    DevBuf wall_counts;                                 // wall voxels: per-chunk record counts, then offsets
-    DevBuf wall_stage;                                  // wall voxels: the records the count pass staged (kept until the volume changes)
-    int64_t wall_records = -1;                          // result of the last ta_wall_voxels_count, -1 = none
-    uint32_t wall_region = 0, wall_not_staged = 0;      // records per staging region of that call (0 = nothing staged); cells left to the second walk
-    DevBuf wall_medians;                                // ta_wall_medians: pairs u32[E][2] | sizes u32[E] | medians i32[E][3]
-    int64_t wall_median_count = -1;                     // E of the last ta_wall_medians, -1 = none
-    bool wall_wide = false;                             // that call met a label >= 2^31
-    uint32_t wall_label_or = 0;                         // OR of all labels of the volume (that call): the bits a label takes
-    double wall_ms = 0.0;
     int pair_log2 = 0;                                  // current table log2 capacity
     int opt_pair_log2 = 0;
     bool table_clean = false;
@@ -219,17 +250,6 @@ struct ta_ctx {
     // options / state
     int impl = 0;
     int tile_planes = 0;
-    // the tile shape of the sweep of a uint32 volume with adjacency (kernels_scan.hip): both give the same results; which one
-    // is faster depends on the tissue (background around it: the wide one; cells everywhere: the narrow one), so the first four
-    // sweeps of a volume take turns (wide, narrow, wide, narrow) between two events each, and the faster shape keeps the volume
-    int opt_shape = -1;                                 // TA_OPT_SWEEP_SHAPE: -1 = measure, 0 / 1 = as told
-    int shape_pick = -1;                                // choice for this volume, -1 = not yet
-    double shape_density = -1.0;                        // label changes per voxel in the sampled planes (what decided it), -1 = not measured
-    int last_shape = 0;                                 // TA_OPT_SWEEP_SHAPE_USED: the shape of the last sweep
-    int tune_launched = 0;                              // measuring sweeps launched (0 .. 4)
-    hipEvent_t tune_ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    bool tune_done[4] = {false, false, false, false};
-    float tune_ms[4] = {0.f, 0.f, 0.f, 0.f};
     int64_t volume_slack = 0;                           // TA_OPT_VOLUME_SLACK: bytes readable behind an adopted volume
     int auto_tile_shift = 0;                            // automatic tile height halved this many times (table spills seen)
     uint64_t last_grid = 0;                             // workgroups of the last sweep
@@ -242,7 +262,10 @@ struct ta_ctx {
     PinnedBuf h_pairs;                                  // sorted host copy for ta_adjacency_get: keys u64[n], then faces u64[n][3]
     bool host_pairs_ready = false;
 
-    // the features: each one's state is read and written by its own ta_api_<feature>.hip only
+    // one struct per concern: each one's state is written by its own file only (the core reads ids.compact / h_ids for the sweep)
+    WallVoxelState walls;
+    SparseIdState ids;
+    SweepShapeState shape;
     SignalState sig;
     MeshState mesh;
     OverlapState ov;
@@ -257,21 +280,52 @@ inline int use_device(ta_ctx* c) {
 }
 
 // the volume the sweep reads: the rank copy in compact mode
-inline const void* sweep_vol(const ta_ctx* c) { return c->compact ? c->compact_vol.p : c->vol; }
+inline const void* sweep_vol(const ta_ctx* c) { return c->ids.compact ? c->ids.compact_vol.p : c->vol; }
+inline int64_t compact_rows(const ta_ctx* c) { return c->ids.compact ? c->ids.census_n : -1; }      // rows of a compacted context, -1 = dense
 
-// Drain the stream and validate the flags of the last pass; grows the adjacency table and re-runs when it overflowed.
+// ta_ctx::small and its host mirror h_small: flags, cursor, max label, parked hot-row pointer (2 words)
+constexpr int SMALL_WORDS = ta::SMALL_WORDS_DEV;
+inline uint32_t* flags_dev(ta_ctx* c) { return (uint32_t*)c->small.p; }
+inline uint32_t* cursor_dev(ta_ctx* c) { return (uint32_t*)c->small.p + ta::NFLAGS; }
+inline uint32_t* maxlab_dev(ta_ctx* c) { return (uint32_t*)c->small.p + ta::NFLAGS + 1; }
+inline ta::PairTable pair_table(ta_ctx* c) {
+    ta::PairTable pt;
+    pt.keys = (uint64_t*)c->pkeys.p;
+    pt.faces = (uint64_t*)c->pfaces.p;
+    pt.mask = (uint32_t)((1ull << c->pair_log2) - 1);
+    return pt;
+}
+
+// Drain the stream and validate the flags of the last pass; grows the adjacency table and re-runs when it overflowed.  ta_api.hip.
 int finish_extract(ta_ctx* c);
 
-// A new label volume (for the overlap, the junctions and the components also: new label values in it).  Defined by the features, called by the core.
+// A new label volume (for the sparse ids, the overlap, the junctions and the components also: new label values in it).  Defined by
+// the file of each concern, called by the core's volume_replaced / volume_labels_changed (the junctions' and the components' also by
+// ta_volume_rerank: the caller edited the labels in place).
+void walls_on_new_volume(ta_ctx* c);
+void sparse_on_new_volume(ta_ctx* c);
 void signal_on_new_volume(ta_ctx* c);
 void overlap_on_new_volume(ta_ctx* c);
 void junctions_on_new_volume(ta_ctx* c);
 void wallgeo_on_new_volume(ta_ctx* c);
 void components_on_new_volume(ta_ctx* c);
+void walls_on_new_labels(ta_ctx* c);                  // new label values in the same volume: the staging buffer is kept.  ta_api_walls.hip
 
-// New label values in the resident volume, written by the library itself (ta_volume_relabel, ta_components_relabel): the census
-// and a compacted state end, the extraction and everything keyed by the old labels is stale.  Defined by the core.
+// The two ways the voxels change (ta_api.hip).  volume_replaced: the tail of ta_volume_set / ta_volume_set_device, called once vol,
+// itemsize, dims and layout are in place.  volume_labels_changed: new label values written by the library itself (ta_volume_relabel,
+// ta_components_relabel): the census and a compacted state end, the extraction and everything keyed by the old labels is stale.
+void volume_replaced(ta_ctx* c);
 void volume_labels_changed(ta_ctx* c);
+
+// The word ta_volume_rerank leaves on the device shares its place with the max-label passes.  rerank_verdict takes the word wherever
+// it was read (nothing to do unless a rerank is unchecked): clears the check, and on an id that is not in the list ends the extraction
+// and fails.  settle_rerank reads the word from the device first: for whoever is about to reuse its place.  ta_api_sparse.hip.
+int rerank_verdict(ta_ctx* c, uint32_t status);
+int settle_rerank(ta_ctx* c);
+
+// The pair -> row hash of the sorted pair list of the settled extraction (c->npairs > 0 pairs), built into `into` on the stream:
+// keys u64[cap] | sorted keys u64[P] | rows u32[cap].  Each caller keeps a buffer of its own.  ta_api_signal.hip.
+int build_pair_index(ta_ctx* c, DevBuf& into, const uint64_t** hkeys, const uint32_t** hrows, uint32_t* hmask);
 
 // Companions: these touch the companion's own fields only.  The setters check the arguments against the label volume and drain the
 // stream (a pass in flight may still read the old companion) before they change anything; a failure later leaves no companion set.
