@@ -72,6 +72,11 @@ COMPONENT_SYMBOLS = (
 COMPONENT_NONE = 0xFFFFFFFF            # TA_COMPONENT_NONE
 COMPONENT_MAX_VOXELS = 1 << 31         # voxels of a buffer the component pass takes
 
+# every symbol include/tissue_scan_distance.h declares (same library)
+DISTANCE_SYMBOLS = ("ta_distance_extract", "ta_distance_get", "ta_distance_image", "ta_distance_timing", "ta_distance_set_batch")
+DIST_OWN_WALL, DIST_FROM_LABEL = 0, 1  # TA_DIST_OWN_WALL / TA_DIST_FROM_LABEL
+DIST_EDGE_IS_SITE = 1                  # TA_DIST_EDGE_IS_SITE
+
 
 def exchange_words(capacity_pairs):
     """uint64 words of one exchange block (TA_EXCHANGE_WORDS in include/tissue_scan.h)."""
@@ -196,8 +201,14 @@ def load():
         "ta_components_image": (ci, [vp, i64, i64, vp]),
         "ta_components_relabel": (ci, [vp, vp, u64]),
         "ta_components_timing": (ci, [vp, P(ctypes.c_double), P(ctypes.c_double)]),
+        "ta_distance_extract": (ci, [vp, ci, u32, P(ctypes.c_double), u32]),
+        "ta_distance_get": (ci, [vp, vp, vp, vp]),
+        "ta_distance_image": (ci, [vp, i64, i64, vp]),
+        "ta_distance_timing": (ci, [vp, P(ctypes.c_double), P(ctypes.c_double)]),
+        "ta_distance_set_batch": (ci, [vp, i64]),
     }
-    for name in SYMBOLS + SIGNAL_SYMBOLS + MESH_SYMBOLS + OVERLAP_SYMBOLS + JUNCTION_SYMBOLS + WALLGEO_SYMBOLS + COMPONENT_SYMBOLS:
+    for name in (SYMBOLS + SIGNAL_SYMBOLS + MESH_SYMBOLS + OVERLAP_SYMBOLS + JUNCTION_SYMBOLS + WALLGEO_SYMBOLS + COMPONENT_SYMBOLS
+                 + DISTANCE_SYMBOLS):
         fn = getattr(lib, name)      # AttributeError here == the .so does not match the header
         fn.restype, fn.argtypes = sig[name]
     if lib.ta_version() != ABI_VERSION:
@@ -647,6 +658,44 @@ class Context(object):
         a, b = ctypes.c_double(0.0), ctypes.c_double(0.0)
         _check(self._lib.ta_components_timing(self._h, ctypes.byref(a), ctypes.byref(b)))
         return a.value, b.value
+
+    # -- distance maps (include/tissue_scan_distance.h)
+    def distance_extract(self, mode=DIST_OWN_WALL, site_label=0, spacing=(1.0, 1.0, 1.0), flags=0):
+        """Enqueue the three passes of the exact squared distance transform over the current extraction, and its table.  spacing
+        in array-axis order; site_label (an id) is read with DIST_FROM_LABEL only."""
+        sp = [float(v) for v in spacing]
+        if len(sp) != 3:
+            raise ValueError("spacing must have three entries")
+        _check(self._lib.ta_distance_extract(self._h, int(mode), int(site_label) & 0xFFFFFFFF, (ctypes.c_double * 3)(*sp), int(flags)))
+
+    def distance_get(self):
+        """(min2 f64[R], max2 f64[R], pole i32[R, 3]), rows as labels(); +inf, +inf, (-1, -1, -1) for a row without voxels."""
+        R = getattr(self, "_max_label", 0) + 1          # (no extraction yet: the library answers TA_EINVAL)
+        min2, max2 = np.zeros(R, dtype=np.float64), np.zeros(R, dtype=np.float64)
+        pole = np.zeros((R, 3), dtype=np.int32)
+        _check(self._lib.ta_distance_get(self._h, min2.ctypes.data, max2.ctypes.data, pole.ctypes.data))
+        return min2, max2, pole
+
+    def distance_image(self, first_plane=0, nplanes=None):
+        """float64 squared distances of the voxels of `nplanes` buffer planes from `first_plane` along memory axis 0 (None: all that
+        follow), flat and in memory order."""
+        planes = self.owned_planes() + self._halo_planes
+        per_plane = int(np.prod(self._vol_layout[0])) // planes
+        if nplanes is None:
+            nplanes = planes - int(first_plane)
+        out = np.zeros(max(int(nplanes), 0) * per_plane, dtype=np.float64)
+        _check(self._lib.ta_distance_image(self._h, int(first_plane), int(nplanes), out.ctypes.data))
+        return out
+
+    def distance_timing(self):
+        """(milliseconds of the row pass and the two column passes, milliseconds of the table passes)."""
+        a, b = ctypes.c_double(0.0), ctypes.c_double(0.0)
+        _check(self._lib.ta_distance_timing(self._h, ctypes.byref(a), ctypes.byref(b)))
+        return a.value, b.value
+
+    def distance_set_batch(self, columns=0):
+        """Columns a launch of a column pass takes (0 = automatic); the results do not depend on it."""
+        _check(self._lib.ta_distance_set_batch(self._h, int(columns)))
 
     def max_label(self):
         v = ctypes.c_uint32(0)

@@ -163,6 +163,18 @@ struct ComponentState {
     void release() { parent.release(); work.release(); slots.release(); sort.release(); rows.release(); small.release(); image.release(); destroy_events(ev); }
 };
 
+// distance maps (include/tissue_scan_distance.h)
+struct DistanceState {
+    DevBuf d2;                                          // f64[voxels]: the image
+    DevBuf work;                                        // envelope stacks of a batch of columns: f f64[len][B] | boundaries f64[len][B] | positions i32[len][B]
+    DevBuf table;                                       // min2 u64[R] | max2 u64[R] | pole u64[R] | flags u32[4]
+    uint64_t seq = 0;                                   // extract_seq of the extraction the results belong to, 0 = none
+    uint32_t rows = 0;                                  // max_label + 1 of that extraction
+    int64_t opt_batch = 0;                              // ta_distance_set_batch: 0 = automatic
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};     // passes begin, end | table end
+    void release() { d2.release(); work.release(); table.release(); destroy_events(ev); }
+};
+
 // wall voxels and wall medians (ta_api_walls.hip)
 struct WallVoxelState {
     DevBuf counts;                                      // per-chunk record counts, then offsets
@@ -272,6 +284,7 @@ struct ta_ctx {
     JunctionState jn;
     WallGeoState wg;
     ComponentState cc;
+    DistanceState dist;
 };
 
 inline int use_device(ta_ctx* c) {
@@ -299,7 +312,7 @@ inline ta::PairTable pair_table(ta_ctx* c) {
 // Drain the stream and validate the flags of the last pass; grows the adjacency table and re-runs when it overflowed.  ta_api.hip.
 int finish_extract(ta_ctx* c);
 
-// A new label volume (for the sparse ids, the overlap, the junctions and the components also: new label values in it).  Defined by
+// A new label volume (for the sparse ids, the overlap, the junctions, the components and the distance maps also: new label values in it).  Defined by
 // the file of each concern, called by the core's volume_replaced / volume_labels_changed (the junctions' and the components' also by
 // ta_volume_rerank: the caller edited the labels in place).
 void walls_on_new_volume(ta_ctx* c);
@@ -309,6 +322,7 @@ void overlap_on_new_volume(ta_ctx* c);
 void junctions_on_new_volume(ta_ctx* c);
 void wallgeo_on_new_volume(ta_ctx* c);
 void components_on_new_volume(ta_ctx* c);
+void distance_on_new_volume(ta_ctx* c);
 void walls_on_new_labels(ta_ctx* c);                  // new label values in the same volume: the staging buffer is kept.  ta_api_walls.hip
 
 // The two ways the voxels change (ta_api.hip).  volume_replaced: the tail of ta_volume_set / ta_volume_set_device, called once vol,

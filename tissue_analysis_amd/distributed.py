@@ -315,6 +315,10 @@ class SlabJob(object):
         self._unverified = False
         self.redo_count = 0                     # steps repeated because a block / table was too small
 
+    def distance_map(self, *args, **kwargs):
+        raise NotImplementedError("the distance maps (tissue_scan_distance.h) do not run on a slab: an exact Euclidean distance "
+                                  "transform needs halos of unbounded depth")
+
     def owned_view(self):
         return self.vol[1:] if self.has_low_halo else self.vol
 
@@ -590,6 +594,10 @@ class PipelinedSlabJob(object):
     def last(self):
         """The SlabJob that ran the most recent step (its ctx holds that step's adjacency)."""
         return self.jobs[(self._issued - 1) % len(self.jobs)]
+
+    def distance_map(self, *args, **kwargs):
+        raise NotImplementedError("the distance maps (tissue_scan_distance.h) do not run on a slab: an exact Euclidean distance "
+                                  "transform needs halos of unbounded depth")
 
     def owned_view(self):
         return self.jobs[0].owned_view()

@@ -587,6 +587,29 @@ class ResidentVolume(object):
         self.ctx.get_volume(self.host)
         return self.extract(features)
 
+    def distance_map(self, mode=0, site_label=None, voxelsize=(1.0, 1.0, 1.0), edge=False):
+        """The exact Euclidean distance of every voxel of the resident volume to the nearest voxel of another label (mode 0) or of
+        `site_label` (mode 1), with `edge` also to the image margin: a `DistanceMap` (per label the smallest and the largest squared
+        distance and the voxel of the largest) whose rows are those of the current extraction (swept first when there is none), in
+        the ids of the image.  Three passes over the volume on the GPU; `.image()` of the result downloads the distances."""
+        import time
+        from .distance_map import resident_distance_map
+        t0 = time.perf_counter()
+        dm = resident_distance_map(self, mode, site_label, voxelsize, edge)
+        self.ms["distance_map"] = (time.perf_counter() - t0) * 1e3
+        return dm
+
+    def distance_image(self, first_plane=0, nplanes=None):
+        """float64 image of the SQUARED distances of the last `distance_map()`, with the axes and the layout of the image; of
+        `nplanes` planes from `first_plane` along the slowest memory axis only when those are given."""
+        flat = self.ctx.distance_image(first_plane, nplanes)
+        shape = list(self.host.shape)
+        strides = [s // self.host.dtype.itemsize * 8 for s in self.host.strides]
+        if flat.size != self.host.size:
+            slow = max((d for d in range(3) if shape[d] != 1), key=lambda d: strides[d])
+            shape[slow] = flat.size // (self.host.size // shape[slow])
+        return np.lib.stride_tricks.as_strided(flat, shape=shape, strides=strides)
+
     def wall_geometry(self, voxelsize=(1.0, 1.0, 1.0)):
         """The geometry of every wall of the resident volume: a `WallGeometry` (signed face counts, first and second sums of the
         face centres) whose rows are the pairs of the current extraction (swept first when there is none), in the ids of the

@@ -130,7 +130,9 @@ def tissue_tables(analysis, labels, background, properties, property_as_real=Tru
     With an intensity image `signal`, 'mean_signal' (vertex: cell_signal's mean) and 'wall_signal' (edge: wall_signal's
     face-weighted mean) can be asked for too.  'wall_centroid', 'wall_normal' and 'wall_projected_area' (edge: the columns of
     `analysis.wall_geometry()`) run the wall-geometry pass; a property list without them does not.  'n_components' (vertex:
-    the face-connected blobs the label consists of, `analysis.label_components()`) runs the component pass, likewise."""
+    the face-connected blobs the label consists of, `analysis.label_components()`) runs the component pass, likewise; and so do
+    'inscribed_radius' (vertex: `analysis.inscribed_radius()`) and 'depth' (vertex: `analysis.cell_depth()`, which needs a
+    background) with the distance pass, in real units with `property_as_real`."""
     x = analysis.extraction
     ids = np.asarray(labels, dtype=np.int64).reshape(-1)
     pairs = _PairView(analysis, ids, min_contact_area)
@@ -221,6 +223,10 @@ def tissue_tables(analysis, labels, background, properties, property_as_real=Tru
     if 'n_components' in properties:
         blobs = analysis.label_components().per_label()
         graph.set_vertex_column('n_components', np.array([blobs.get(l, 0) for l in ids.tolist()], dtype=np.int64), present)
+    if 'inscribed_radius' in properties:
+        graph.set_vertex_column('inscribed_radius', analysis.wall_distance(real=real).of_labels(ids, 'max2'), asked)
+    if 'depth' in properties:
+        graph.set_vertex_column('depth', analysis.distance_from(real=real).of_labels(ids, 'min2'), asked)
     return graph
 
 

@@ -207,6 +207,7 @@ class AbstractSpatialImageAnalysis(object):
         self._junctions = None
         self._wall_geometry = None
         self._components = None
+        self._distance_cache = {}
         try:
             self.filepath, self.filename = split(image.info["Filename"])
         except Exception:
@@ -269,6 +270,7 @@ class AbstractSpatialImageAnalysis(object):
         self._junctions = None
         self._wall_geometry = None
         self._components = None
+        self._distance_cache = {}
         self._voxel_layer1 = None
         self._voxel_layer18 = None
 
@@ -638,6 +640,44 @@ class AbstractSpatialImageAnalysis(object):
     def disconnected_labels(self):
         """{label: k} of the labels whose voxels form k > 1 separate blobs, without the ignored labels."""
         return self.label_components().fragmented(exclude=self._ignoredlabels)
+
+    # -- exact Euclidean distance maps (include/tissue_scan_distance.h; three passes over the resident volume on the GPU)
+    def _distance_map(self, mode, label, edge, real):
+        cache = getattr(self, "_distance_cache", None)
+        if cache is None:
+            cache = self._distance_cache = {}
+        key = (int(mode), None if label is None else int(label), bool(edge), bool(real))
+        if key not in cache:
+            vs = tuple(float(v) for v in self._voxelsize) if real else (1.0, 1.0, 1.0)
+            cache[key] = self._resident_rows().distance_map(mode, label, vs, bool(edge))
+        return cache[key]
+
+    def wall_distance(self, edge_is_wall=False, real=True):
+        """The distance of every voxel to the nearest voxel of another label -- to its own cell's wall: a `DistanceMap` in the ids of
+        the image, with this analysis' voxel size (ones with real=False).  With `edge_is_wall` the image margin bounds the cells it
+        cuts.  Nothing is excluded here; `.image()` downloads the distances.  Cached per argument set until `refresh()` or an edit
+        of the image."""
+        return self._distance_map(_capi.DIST_OWN_WALL, None, edge_is_wall, real)
+
+    def distance_from(self, label=None, edge_is_wall=False, real=True):
+        """The distance of every voxel to the nearest voxel of `label` (default: the background): a `DistanceMap`, as above."""
+        if label is None:
+            label = self.background()
+        if label is None:
+            raise ValueError("distance_from needs a label (this analysis has no background)")
+        return self._distance_map(_capi.DIST_FROM_LABEL, int(label), edge_is_wall, real)
+
+    def inscribed_radius(self, labels=None, real=True):
+        """Per label the radius of its largest inscribed sphere centred on a voxel: the largest distance of its voxels to a voxel
+        of another label (+inf for an image of one label); returned like volume().  `wall_distance().pole()` is where it sits."""
+        labels = self.label_request(labels)
+        return self.convert_return(self.wall_distance(real=real).of_labels(labels, "max2"), labels)
+
+    def cell_depth(self, labels=None, real=True):
+        """Per label the smallest distance of its voxels to the background: a continuous depth below the tissue surface, where
+        cell_first_layer() gives a layer index; returned like volume()."""
+        labels = self.label_request(labels)
+        return self.convert_return(self.distance_from(real=real).of_labels(labels, "min2"), labels)
 
     def _current_components(self):
         """`label_components()`, run again when the context no longer holds the tables it was read from."""
