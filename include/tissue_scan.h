@@ -81,6 +81,8 @@ extern "C" {
                                * resident volume.  -2: the first four sweeps of a volume take turns between two events each and the
                                * faster shape keeps the volume (round 4's rule). */
 #define TA_OPT_SWEEP_SHAPE_USED 8 /* read only: the shape the last sweep of this context ran with (0 where the shape does not apply) */
+#define TA_OPT_TILE_PLANES_USED 9 /* read only: the tile height handed to the launch of this context's last sweep -- after the automatic
+                               * halving for small volumes and the clamp to what the kernel packs its sums for; 0 before any sweep */
 #define TA_OPT_VOLUME_SLACK 6 /* bytes that are readable behind the volume adopted by ta_volume_set_device (reset to 0 by that
                                * call): with >= 16 the sweep uses 16-byte loads whatever the row length -- the strip that
                                * straddles the end of the last row reads up to 16 - itemsize bytes past the volume        */

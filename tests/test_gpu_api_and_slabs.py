@@ -223,3 +223,29 @@ def test_graph_from_image_end_to_end_on_gpu():
     assert g.nb_vertices() > 10 and g.nb_edges() > 10
     compare_graph(g, want)
     assert len(property_graph_to_dataframe(g, 'vertex')) == g.nb_vertices()
+
+
+def test_tile_planes_used_is_read_only_and_zero_before_a_sweep():
+    """TA_OPT_TILE_PLANES_USED: 0 on a context that has not swept, TA_EINVAL when set, and after a sweep the height the launch
+    got -- a small volume's automatic height is halved below the default that TA_OPT_TILE_PLANES answers, and a request above
+    the kernel's cap (uint16 with adjacency: 32 planes) is clamped to it."""
+    ctx = _capi.Context(0)
+    try:
+        assert ctx.get_option(_capi.OPT_TILE_PLANES_USED) == 0
+        for value in (0, 16):
+            with pytest.raises(_capi.TissueScanError) as e:
+                ctx.set_option(_capi.OPT_TILE_PLANES_USED, value)
+            assert e.value.code == _capi.TA_EINVAL
+        vol = voronoi((70, 16, 512), 12, 44, np.uint16)
+        ctx.set_volume(vol)
+        assert ctx.get_option(_capi.OPT_TILE_PLANES_USED) == 0           # a volume alone is no sweep
+        ctx.extract(_capi.F_ALL, int(vol.max()))
+        assert ctx.get_option(_capi.OPT_TILE_PLANES) == 28
+        assert ctx.get_option(_capi.OPT_TILE_PLANES_USED) == 7           # far fewer than 2048 workgroups: halved while above 8 planes, 28 -> 14 -> 7
+        ctx.set_option(_capi.OPT_TILE_PLANES, 64)
+        assert ctx.get_option(_capi.OPT_TILE_PLANES_USED) == 7           # the LAST sweep's, not the next one's
+        ctx.extract(_capi.F_ALL, int(vol.max()))
+        assert ctx.get_option(_capi.OPT_TILE_PLANES) == 64
+        assert ctx.get_option(_capi.OPT_TILE_PLANES_USED) == 32
+    finally:
+        ctx.close()

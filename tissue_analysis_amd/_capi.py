@@ -21,6 +21,7 @@ ABI_VERSION = 5          # TA_ABI_VERSION of include/tissue_scan.h this binding 
 FEATURES = dict(VOLUME=F_VOLUME, BBOX=F_BBOX, MOMENT1=F_MOMENT1, MOMENT2=F_MOMENT2,
                 ADJACENCY=F_ADJACENCY)
 OPT_IMPL, OPT_TILE_PLANES, OPT_PAIR_SLOTS, OPT_TIMING, OPT_TIMING_RING, OPT_VOLUME_SLACK, OPT_SWEEP_SHAPE, OPT_SWEEP_SHAPE_USED = 1, 2, 3, 4, 5, 6, 7, 8
+OPT_TILE_PLANES_USED = 9         # read only: the tile height the last sweep was launched with (0 before any sweep)
 STREAM_LEGACY_DEFAULT = 1          # TA_STREAM_LEGACY_DEFAULT of include/tissue_scan.h
 
 # every symbol include/tissue_scan.h declares

@@ -139,6 +139,7 @@ int run_extract(ta_ctx* c) {
         const int cap = ta::sweep_max_tile_planes(c->feature_mask & TA_F_ADJACENCY, c->itemsize, a.shape);
         if (a.tile_planes > cap) a.tile_planes = cap;
     }
+    c->tile_planes_used = a.tile_planes;
     // 16-byte loads: rows that are 16-byte aligned, or ANY rows of a volume the library uploaded itself (unaligned 16-byte
     // global loads are legal on gfx950 -- 6.2 TB/s from dword-aligned, 4.8 TB/s from odd addresses, measured -- and the
     // strip that straddles the end of the very last row reads into the slack ta_volume_set leaves behind the buffer)
@@ -472,6 +473,9 @@ TA_API int ta_ctx_set_option(ta_ctx* c, int key, int64_t value) {
             c->ring_since = c->extract_seq;          // the kept durations start with the next extraction
             return TA_OK;
         }
+        case TA_OPT_SWEEP_SHAPE_USED:
+        case TA_OPT_TILE_PLANES_USED:
+            return fail(TA_EINVAL, "option key %d is read only", key);
         default:
             return fail(TA_EINVAL, "unknown option key %d", key);
     }
@@ -484,6 +488,7 @@ TA_API int ta_ctx_get_option(ta_ctx* c, int key, int64_t* value) {
         case TA_OPT_VOLUME_SLACK: *value = c->volume_slack; return TA_OK;
         case TA_OPT_SWEEP_SHAPE: *value = c->shape.opt; return TA_OK;
         case TA_OPT_SWEEP_SHAPE_USED: *value = c->shape.last; return TA_OK;
+        case TA_OPT_TILE_PLANES_USED: *value = c->tile_planes_used; return TA_OK;
         case TA_OPT_TIMING: *value = c->timing; return TA_OK;
         case TA_OPT_TIMING_RING: *value = (int64_t)(c->ring.size() / 2); return TA_OK;
         case TA_OPT_TILE_PLANES: {

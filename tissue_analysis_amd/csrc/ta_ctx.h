@@ -262,6 +262,7 @@ struct ta_ctx {
     // options / state
     int impl = 0;
     int tile_planes = 0;
+    int tile_planes_used = 0;                           // TA_OPT_TILE_PLANES_USED: the height the last sweep was launched with
     int64_t volume_slack = 0;                           // TA_OPT_VOLUME_SLACK: bytes readable behind an adopted volume
     int auto_tile_shift = 0;                            // automatic tile height halved this many times (table spills seen)
     uint64_t last_grid = 0;                             // workgroups of the last sweep

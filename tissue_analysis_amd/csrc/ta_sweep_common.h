@@ -36,7 +36,7 @@ __device__ __forceinline__ uint32_t load_uniform_voxel(const T* p) {
 
 // local sums of one label contribution (tile-local coordinates)
 struct LocalSums { uint64_t n, sa, sb, sc, saa, sab, sac, sbb, sbc, scc; };
-// one run's contribution: every term fits 32 bits (n <= 64, a < 64, b < 16, c < 512)
+// one run's contribution: every term fits 32 bits (n <= 512 -- a run may be a whole row of the widest tile --, a < 64, b < 16, c < 512)
 struct RunSums { uint32_t n, sa, sb, sc, saa, sab, sac, sbb, sbc, scc; };
 
 // ---- the ten tile-local sums of a label slot, PACKED into four u64 words (two without second moments) --------------------
