@@ -225,7 +225,10 @@ TA_API int ta_adjacency_device(ta_ctx* ctx, void** keys_dev, void** faces_dev, i
 TA_API int ta_adjacency_export(ta_ctx* ctx, void* keys_dst_dev, void* faces_dst_dev, int64_t capacity_pairs);
 
 /* Merge foreign pair lists (other ranks' ta_adjacency_device output, gathered by the host with
- * RCCL) into this context's adjacency: sums face counts of equal keys. */
+ * RCCL) into this context's adjacency: sums face counts of equal keys.  The merged list must fit the table of the
+ * extraction (it does not grow here): when it does not, the call answers TA_ECAPACITY and the extraction is LOST -- the
+ * merge has overwritten its pair list -- so every getter, ta_adjacency_scope and the exchange calls answer TA_EINVAL
+ * until the next ta_extract (raise TA_OPT_PAIR_SLOTS first). */
 TA_API int ta_adjacency_merge(ta_ctx* ctx, const void* keys_dev, const void* faces_dev, int64_t npairs);
 
 /* Which pairs the adjacency getters (ta_adjacency_size / _get / _device / _export) answer with right now:

@@ -1,14 +1,18 @@
-"""The adjacency exchange of the multi-GPU step without any process group: two contexts on one GPU hold the two Z-slabs
-of a volume, their accumulators are reduced with plain torch ops, the exchange blocks are concatenated by hand.
-ta_adjacency_pack (every pair travels) and ta_adjacency_pack_shared (only pairs a slab face can split) must both end in
-the unsharded adjacency."""
+"""The adjacency exchange of the multi-GPU step without any process group: a context per Z-slab of a volume on one GPU, their
+accumulators reduced with plain torch ops, the exchange blocks concatenated by hand.  ta_adjacency_pack (every pair travels)
+and ta_adjacency_pack_shared (only pairs a slab face can split) must both end in the unsharded adjacency -- at every cut of a
+small volume (slabs of one plane, labels that end exactly at and just above the last exclusive plane), with three and four
+blocks, for both label types, with blocks exactly full and one pair short, with a status word that carries another rank's
+range error.  What must travel, what stays and what each rank ends with is computed on the CPU (pair_table_model.py) from the C
+oracle and distributed.slab_exclusive."""
 import numpy as np
 import pytest
 
-from oracle import onepass_c
+from oracle import onepass, onepass_c
 from tissue_analysis_amd import _capi, distributed as tad
 
-from helpers import voronoi
+import pair_table_model as ptm
+from helpers import assert_same_accumulators, voronoi
 
 pytestmark = pytest.mark.gpu
 
@@ -17,81 +21,311 @@ def _slab_job(vol, lo, hi, L):
     import torch
     halo = 1 if lo > 0 else 0
     part = np.ascontiguousarray(vol[lo - halo:hi])
-    t = torch.from_numpy(part.view(np.int32).copy()).to("cuda:0")
+    t = torch.from_numpy(part.view({2: np.int16, 4: np.int32}[vol.dtype.itemsize]).copy()).to("cuda:0")
     ctx = _capi.Context(0)
     sums = torch.zeros((L + 1, 10), dtype=torch.int64, device="cuda:0")
     boxes = torch.zeros((L + 1, 6), dtype=torch.int32, device="cuda:0")
-    ctx.set_volume_device(t.data_ptr(), 4, part.shape, a0_origin=lo, has_low_halo=bool(halo), keep=t)
+    ctx.set_volume_device(t.data_ptr(), vol.dtype.itemsize, part.shape, a0_origin=lo, has_low_halo=bool(halo), keep=t)
     ctx.bind_accumulators(sums.data_ptr(), boxes.data_ptr(), L, keep=(sums, boxes))
     return ctx, sums, boxes
 
 
-@pytest.mark.parametrize("shared", [False, True], ids=["pack_all", "pack_shared"])
-def test_two_slabs_exchange_blocks_by_hand(shared):
-    import torch
-    vol = voronoi((36, 40, 264), 70, 41, np.uint32)
-    want = onepass_c.extract(vol)
-    L = int(vol.max())
-    cut = 17
-    jobs = [_slab_job(vol, 0, cut, L), _slab_job(vol, cut, vol.shape[0], L)]
-    try:
-        for ctx, _, _ in jobs:
-            ctx.extract(_capi.F_ALL, L)
-        npairs = [ctx.adjacency_size() for ctx, _, _ in jobs]
-        # per-label reduce, as the two all-reduces would do it
-        sums = jobs[0][1] + jobs[1][1]
-        boxes = torch.minimum(jobs[0][2], jobs[1][2])
+class _Ranks(object):
+    """One context per slab [cuts[r], cuts[r + 1]) of `vol`, with bound accumulators."""
+
+    def __init__(self, vol, cuts, L):
+        self.L, self.cuts = L, list(cuts)
+        self.jobs = []
+        try:
+            for lo, hi in zip(cuts[:-1], cuts[1:]):
+                self.jobs.append(_slab_job(vol, lo, hi, L))
+        except Exception:
+            self.close()
+            raise
+        self.ctxs = [j[0] for j in self.jobs]
+
+    def close(self):
+        for ctx, _, _ in self.jobs:
+            ctx.close()
+
+    def extract(self):
+        for ctx in self.ctxs:
+            ctx.extract(_capi.F_ALL, self.L)
+
+    def reduce(self):
+        """The per-label reduce, as the two all-reduces would do it; answers the reduced rows (device layout, on the host)."""
+        import torch
+        for ctx in self.ctxs:                      # (the sweeps run on the contexts' own streams)
+            ctx.synchronize()
+        sums, boxes = self.jobs[0][1].clone(), self.jobs[0][2].clone()
+        for _, s, b in self.jobs[1:]:
+            sums += s
+            boxes = torch.minimum(boxes, b)
         torch.cuda.synchronize()
-        for _, s, b in jobs:
+        for ctx, s, b in self.jobs:
             s.copy_(sums); b.copy_(boxes)
-        got = tad.from_device_layout(sums.cpu().numpy(), boxes.cpu().numpy())
-        for k in ("count", "bbox", "sum1", "sum2"):
-            assert np.array_equal(got[k], want[k]), k
-        for ctx, _, _ in jobs:
+        torch.cuda.synchronize()
+        for ctx in self.ctxs:
             ctx.accumulators_reduced()
-        cap = max(npairs) + 8
+        return sums.cpu().numpy(), boxes.cpu().numpy()
+
+    def pack(self, shared, cap):
+        """Every rank's block, of exactly the documented size, side by side: (the gathered blocks, the pair count word of each)."""
+        import torch
         words = _capi.exchange_words(cap)
-        blocks = torch.empty((2 * words,), dtype=torch.int64, device="cuda:0")
-        for r, (ctx, _, _) in enumerate(jobs):
+        n = len(self.ctxs)
+        blocks = torch.empty((n * words,), dtype=torch.int64, device="cuda:0")
+        for r, ctx in enumerate(self.ctxs):
             ptr = blocks[r * words:(r + 1) * words].data_ptr()
             (ctx.adjacency_pack_shared if shared else ctx.adjacency_pack)(ptr, cap)
+        for ctx in self.ctxs:
+            ctx.synchronize()
         torch.cuda.synchronize()
-        sent = [int(blocks[r * words].item()) for r in range(2)]
-        if shared:
-            assert all(s <= n for s, n in zip(sent, npairs)) and sum(sent) < sum(npairs), (sent, npairs)     # something stayed at home
-        else:
-            assert sent == npairs
+        return blocks, [int(blocks[r * words].item()) for r in range(n)]
+
+    def merge(self, blocks, cap):
+        for ctx in self.ctxs:
+            ctx.adjacency_merge_blocks(blocks.data_ptr(), len(self.ctxs), cap)
+
+
+def _exchange(vol, cuts, shared, cap=None, dtype=None, ranks=None):
+    """extract -> reduce -> pack -> merge on one context per slab: (per-rank lists, sent counts, what else the callers look at).
+    cap None: the largest local list + 8, as a host that knows nothing would size it.  `ranks`: contexts to run on again."""
+    if dtype is not None:
+        vol = vol.astype(dtype)
+    L = int(vol.max())
+    own = ranks is None
+    if own:
+        ranks = _Ranks(vol, cuts, L)
+    try:
+        ranks.extract()
+        npairs = [ctx.adjacency_size() for ctx in ranks.ctxs]
+        sums, boxes = ranks.reduce()
+        if cap is None:
+            cap = max(npairs) + 8
+        blocks, sent = ranks.pack(shared, cap)
         lists = []
-        for ctx, _, _ in jobs:
+        for ctx in ranks.ctxs:
             assert ctx.adjacency_scope() == _capi.ADJ_LOCAL
-            ctx.adjacency_merge_blocks(blocks.data_ptr(), 2, cap)
+        ranks.merge(blocks, cap)
+        for ctx in ranks.ctxs:
             assert ctx.adjacency_scope() == (_capi.ADJ_PARTIAL if shared else _capi.ADJ_MERGED)
             if shared:                     # a partial list is handed out only when asked for by name
                 with pytest.raises(_capi.TissueScanError):
                     ctx.adjacency()
             lists.append(ctx.adjacency(allow_partial=True))
-        if not shared:                     # every rank holds the global list
-            for lo, hi, faces in lists:
-                assert np.array_equal(lo, want["pair_lo"]) and np.array_equal(hi, want["pair_hi"]) and np.array_equal(faces, want["pair_faces"])
-        else:                              # private lists are disjoint; their union with the merged travelling pairs is global
-            a0 = [0, cut]; a1 = [cut, vol.shape[0]]
-            bx = boxes.cpu().numpy()
-            merged = {}
-            for r, (lo, hi, faces) in enumerate(lists):
-                excl = tad.slab_exclusive(bx, a0[r], a1[r])
-                for a, b, f in zip(lo.tolist(), hi.tolist(), faces):
-                    private = bool(excl[a] or excl[b])
-                    key = (a, b)
-                    if private:
-                        assert key not in merged, key
-                        merged[key] = f
-                    elif key in merged:
-                        assert np.array_equal(merged[key], f), key          # the travelling part is the same on both ranks
-                    else:
-                        merged[key] = f
-            keys = sorted(merged)
-            assert keys == list(zip(want["pair_lo"].tolist(), want["pair_hi"].tolist()))
-            assert np.array_equal(np.array([merged[k] for k in keys]), want["pair_faces"])
+        return lists, sent, dict(npairs=npairs, sums=sums, boxes=boxes)
     finally:
-        for ctx, _, _ in jobs:
-            ctx.close()
+        if own:
+            ranks.close()
+
+
+def _assert_rows(info, want):
+    got = tad.from_device_layout(info["sums"], info["boxes"])
+    for k in ("count", "bbox", "sum1", "sum2"):
+        assert np.array_equal(got[k], want[k]), k
+
+
+def _assert_global(lists, shared, boxes, cuts, want):
+    """Every rank holds the global list (pack), or: private lists are disjoint and their union with the merged travelling pairs
+    -- the same on every rank -- is the global list (pack_shared)."""
+    if not shared:
+        for lo, hi, faces in lists:
+            assert np.array_equal(lo, want["pair_lo"]) and np.array_equal(hi, want["pair_hi"]) and np.array_equal(faces, want["pair_faces"])
+        return
+    merged = {}
+    for r, (lo, hi, faces) in enumerate(lists):
+        excl = tad.slab_exclusive(boxes, cuts[r], cuts[r + 1])
+        for a, b, f in zip(lo.tolist(), hi.tolist(), faces):
+            private = bool(excl[a] or excl[b])
+            key = (a, b)
+            if private:
+                assert key not in merged, key
+                merged[key] = f
+            elif key in merged:
+                assert np.array_equal(merged[key], f), key          # the travelling part is the same on both ranks
+            else:
+                merged[key] = f
+    keys = sorted(merged)
+    assert keys == list(zip(want["pair_lo"].tolist(), want["pair_hi"].tolist()))
+    assert np.array_equal(np.array([merged[k] for k in keys]), want["pair_faces"])
+
+
+@pytest.mark.parametrize("shared", [False, True], ids=["pack_all", "pack_shared"])
+def test_two_slabs_exchange_blocks_by_hand(shared):
+    vol = voronoi((36, 40, 264), 70, 41, np.uint32)
+    want = onepass_c.extract(vol)
+    cuts = [0, 17, vol.shape[0]]
+    lists, sent, info = _exchange(vol, cuts, shared)
+    _assert_rows(info, want)
+    npairs = info["npairs"]
+    if shared:
+        assert all(s <= n for s, n in zip(sent, npairs)) and sum(sent) < sum(npairs), (sent, npairs)     # something stayed at home
+    else:
+        assert sent == npairs
+    _assert_global(lists, shared, info["boxes"], cuts, want)
+
+
+# ---- the same at the edges: what travels and what each rank ends with, from the CPU model
+_MODEL = {}
+
+
+def _model(dtype):
+    """The exchange volume, the unsharded oracle and its boxes in the device layout: computed once, left unchanged."""
+    key = np.dtype(dtype).name
+    if key not in _MODEL:
+        vol = ptm.exchange_volume(dtype)
+        vol.setflags(write=False)
+        want = onepass_c.extract(vol)
+        _MODEL[key] = (vol, want, ptm.device_boxes(want["bbox"]))
+    return _MODEL[key]
+
+
+def _expected(vol, want, boxes, cuts, shared):
+    """Per rank: (pairs in its block, the list it holds after the merge)."""
+    L = int(want["max_label"])
+    spans = list(zip(cuts[:-1], cuts[1:]))
+    local = [ptm.slab_local(vol, lo, hi, L) for lo, hi in spans]
+    if not shared:
+        return [p["pair_lo"].size for p in local], [(want["pair_lo"], want["pair_hi"], want["pair_faces"])] * len(spans)
+    sent = [ptm.travelling(p, boxes, lo, hi) for p, (lo, hi) in zip(local, spans)]
+    held = []
+    for p, (lo, hi) in zip(local, spans):
+        parts = [ptm.private(p, boxes, lo, hi)] + sent
+        held.append(onepass.compact_pairs(*[np.concatenate([x[k] for x in parts]) for k in range(3)]))
+    return [s[0].size for s in sent], held
+
+
+def _assert_lists(lists, held, what):
+    for r, (got, exp) in enumerate(zip(lists, held)):
+        for g, e, name in zip(got, exp, ("lo", "hi", "faces")):
+            assert np.array_equal(g, e), "%s rank %d %s" % (what, r, name)
+
+
+def _check_exchange(dtype, cuts, shared, cap=None):
+    vol, want, boxes = _model(dtype)
+    counts, held = _expected(vol, want, boxes, cuts, shared)
+    lists, sent, info = _exchange(vol, cuts, shared, cap=cap)
+    what = "cuts=%s shared=%s %s" % (cuts, shared, np.dtype(dtype).name)
+    _assert_rows(info, want)
+    assert np.array_equal(info["boxes"], boxes), what            # (the model's boxes are the reduced ones)
+    assert sent == counts, (what, sent, counts)
+    _assert_lists(lists, held, what)
+    _assert_global(lists, shared, boxes, cuts, want)
+    return counts
+
+
+@pytest.mark.parametrize("shared", [False, True], ids=["pack_all", "pack_shared"])
+def test_two_slabs_at_every_cut(shared):
+    """Cuts 1 .. 11 of 12 planes: first and last slabs of one plane (hi - 2 < lo: nothing is exclusive), labels whose last plane
+    is exactly hi - 2 (exclusive) and hi - 1 (in the next slab's halo: not) -- test_pair_table_cpu.py shows both occur."""
+    some_private = 0
+    for cuts in ptm.EVERY_CUT:
+        counts = _check_exchange(np.uint32, cuts, shared)
+        if shared:
+            vol, want, boxes = _model(np.uint32)
+            local = [ptm.slab_local(vol, lo, hi, int(want["max_label"]))["pair_lo"].size for lo, hi in zip(cuts[:-1], cuts[1:])]
+            some_private += sum(local) - sum(counts)
+    assert not shared or some_private > 0
+
+
+@pytest.mark.parametrize("dtype", [np.uint16, np.uint32], ids=["u16", "u32"])
+@pytest.mark.parametrize("shared", [False, True], ids=["pack_all", "pack_shared"])
+@pytest.mark.parametrize("cuts", ptm.MORE_SLABS, ids=["4_blocks", "3_blocks"])
+def test_three_and_four_blocks(cuts, shared, dtype):
+    _check_exchange(dtype, cuts, shared)
+
+
+def _raises(code, call, what):
+    with pytest.raises(_capi.TissueScanError) as e:
+        call()
+    assert e.value.code == code, (what, e.value)
+
+
+@pytest.mark.parametrize("shared", [False, True], ids=["pack_all", "pack_shared"])
+def test_blocks_exactly_full_and_one_pair_short(shared):
+    dtype, cuts = np.uint32, ptm.MORE_SLABS[1]
+    vol, want, boxes = _model(dtype)
+    counts, held = _expected(vol, want, boxes, cuts, shared)
+    assert min(counts) >= 2 and len(set(counts)) > 1             # (one block full, the others with room)
+    _check_exchange(dtype, cuts, shared, cap=max(counts))        # exactly full
+    L = int(want["max_label"])
+    ranks = _Ranks(vol, cuts, L)
+    try:
+        # one pair short: the full block says so in its count word, and EVERY context that merged it answers TA_ECAPACITY
+        cap = max(counts) - 1
+        ranks.extract()
+        ranks.reduce()
+        blocks, sent = ranks.pack(shared, cap)
+        assert sent == counts                                    # (the count word is the list's length, not what fitted)
+        ranks.merge(blocks, cap)
+        for r, ctx in enumerate(ranks.ctxs):
+            for getter in (lambda: ctx.adjacency(allow_partial=True), ctx.adjacency_size, ctx.labels):
+                _raises(_capi.TA_ECAPACITY, getter, "cap one short, rank %d" % r)
+        # ... then the step again with room, on the same contexts
+        lists, sent, info = _exchange(vol, cuts, shared, cap=max(counts), ranks=ranks)
+        _assert_rows(info, want)
+        assert sent == counts
+        _assert_lists(lists, held, "after the short block")
+        _assert_global(lists, shared, boxes, cuts, want)
+    finally:
+        ranks.close()
+
+
+@pytest.mark.parametrize("shared", [False, True], ids=["pack_all", "pack_shared"])
+def test_a_range_error_travels_in_the_status_word(shared):
+    """One voxel of label L + 1 in the last slab, max_label = L everywhere: after the exchange every context answers TA_ERANGE,
+    the ones whose own slabs were in range too."""
+    vol, want, _ = _model(np.uint32)
+    L = int(want["max_label"])
+    cuts = ptm.MORE_SLABS[1]
+    bad = vol.copy()
+    bad[cuts[-2] + 2, 3, 10] = L + 1
+    ranks = _Ranks(bad, cuts, L)
+    try:
+        ranks.extract()                                          # (no getter before the exchange: no rank knows yet)
+        ranks.reduce()
+        cap = want["pair_lo"].size + 8
+        blocks, _ = ranks.pack(shared, cap)
+        ranks.merge(blocks, cap)
+        for r, ctx in enumerate(ranks.ctxs):
+            for getter in (lambda: ctx.adjacency(allow_partial=True), ctx.labels):
+                _raises(_capi.TA_ERANGE, getter, "rank %d" % r)
+        # the volume in range again on the same contexts (the last slab gets its voxels back)
+    finally:
+        ranks.close()
+    _check_exchange(np.uint32, cuts, shared)
+
+
+def test_pack_shared_without_a_merge_then_a_new_extraction():
+    """ta_adjacency_pack_shared puts the private pairs back into the table; without ta_adjacency_merge_blocks nobody collects
+    them.  The next extraction must start from a clean table all the same: the slab's own list, nothing left over or doubled."""
+    vol, want, boxes = _model(np.uint32)
+    L = int(want["max_label"])
+    cuts = ptm.MORE_SLABS[1]
+    local = [ptm.slab_local(vol, lo, hi, L) for lo, hi in zip(cuts[:-1], cuts[1:])]
+    assert any(ptm.private(p, boxes, lo, hi)[0].size for p, lo, hi in zip(local, cuts[:-1], cuts[1:]))
+    ranks = _Ranks(vol, cuts, L)
+    try:
+        for _ in range(2):
+            ranks.extract()
+            ranks.reduce()
+            cap = want["pair_lo"].size
+            blocks, sent = ranks.pack(True, cap)
+            assert sent == [ptm.travelling(p, boxes, lo, hi)[0].size for p, lo, hi in zip(local, cuts[:-1], cuts[1:])]
+        ranks.extract()
+        for r, (ctx, p) in enumerate(zip(ranks.ctxs, local)):
+            assert ctx.adjacency_scope() == _capi.ADJ_LOCAL
+            count, bbox, sum1, sum2 = ctx.labels()
+            lo, hi, faces = ctx.adjacency()
+            got = dict(count=count, bbox=bbox, sum1=sum1, sum2=sum2, pair_lo=lo, pair_hi=hi, pair_faces=faces)
+            assert_same_accumulators(got, p, "rank %d after pack_shared without merge" % r)
+        # a whole exchange, then a second pack of either kind on the exchanged extraction
+        ranks.reduce()
+        blocks, _ = ranks.pack(True, cap)
+        ranks.merge(blocks, cap)
+        for ctx in ranks.ctxs:
+            for pack in (ctx.adjacency_pack, ctx.adjacency_pack_shared):
+                _raises(_capi.TA_EINVAL, lambda: pack(blocks.data_ptr(), cap), "second pack")
+    finally:
+        ranks.close()

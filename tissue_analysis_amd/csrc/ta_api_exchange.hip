@@ -72,8 +72,13 @@ TA_API int ta_adjacency_merge(ta_ctx* c, const void* keys_dev, const void* faces
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     local_k.release(); local_f.release();
     if (e != hipSuccess) return fail(TA_EHIP, "merge: %s", hipGetErrorString(e));
-    if (c->h_small[ta::FLAG_PAIR_OVERFLOW])
-        return fail(TA_ECAPACITY, "adjacency table overflow while merging (2^%d slots); raise TA_OPT_PAIR_SLOTS", c->pair_log2);
+    if (c->h_small[ta::FLAG_PAIR_OVERFLOW]) {
+        // the collect has written the pairs that did fit over the local list: the extraction's adjacency is gone, and with it the
+        // extraction (the getters, ta_adjacency_scope and the exchange calls answer TA_EINVAL until the next ta_extract)
+        c->extracted = c->checked = false;
+        c->host_pairs_ready = false;
+        return fail(TA_ECAPACITY, "adjacency table overflow while merging (2^%d slots): the extraction is lost; raise TA_OPT_PAIR_SLOTS and run ta_extract again", c->pair_log2);
+    }
     c->npairs = (int64_t)c->h_small[ta::NFLAGS];
     c->host_pairs_ready = false;
     return TA_OK;
