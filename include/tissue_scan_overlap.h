@@ -46,6 +46,11 @@ TA_API int ta_overlap_size(ta_ctx* ctx, uint64_t* npairs);
 /* The rows, ta_overlap_size of them, sorted by (a, b); any pointer may be NULL.  Synchronises (and settles, as above, before
  * anything is written to caller memory). */
 TA_API int ta_overlap_get(ta_ctx* ctx, uint32_t* a, uint32_t* b, uint64_t* n);
+/* Diagnostics of the last run of the pass kernel, for tests: out[0] records that found no slot in a workgroup's LDS table and
+ * went to the device table directly (the results are the same); out[1] the runs of the pass kernel (as
+ * ta_overlap_timing_compaction); out[2] the tiles a workgroup took, out[3] the workgroups.  Synchronises and settles, as
+ * ta_overlap_size. */
+TA_API int ta_overlap_debug(ta_ctx* ctx, uint32_t out[4]);
 /* Milliseconds between two HIP events around the pass kernel of the last ta_overlap_extract (the last run of it, when the
  * table had to grow). */
 TA_API int ta_overlap_timing(ta_ctx* ctx, double* ms);

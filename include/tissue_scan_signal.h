@@ -47,6 +47,10 @@ TA_API int ta_signal_get_labels(ta_ctx* ctx, uint64_t* n, uint64_t* sum, uint64_
                                 uint32_t* max);
 /* Per-wall sums, one per pair of ta_adjacency_get (ta_adjacency_size of them); either pointer may be NULL.  Synchronises. */
 TA_API int ta_signal_get_walls(ta_ctx* ctx, uint64_t* side_lo, uint64_t* side_hi);
+/* Diagnostics of the last pass, for tests: out[0] per-label records and out[1] per-wall records that found no slot in a
+ * workgroup's LDS tables and went to the global rows directly (the results are the same); out[2] the tiles a workgroup took,
+ * out[3] the workgroups.  Valid when either getter above is; TA_ERANGE as they answer it.  Synchronises. */
+TA_API int ta_signal_debug(ta_ctx* ctx, uint32_t out[4]);
 /* Milliseconds between two HIP events around the pass kernel of the last ta_signal_extract (the pair table is built before). */
 TA_API int ta_signal_timing(ta_ctx* ctx, double* ms);
 

@@ -27,7 +27,8 @@
  *  - Range.  ta_wallgeo_extract answers TA_ERANGE before the pass when 3 nvox (2 E)^2 >= 2^64, E the largest global extent
  *    (a0_origin + owned planes, n1, n2): no sum can wrap, and 2048^3 is far inside.  Never a silently wrapped sum.
  *  - A face whose pair the list does not hold cannot happen; if the pass flags one (the volume changed behind the library's
- *    back) the getters fail with TA_ERANGE.  Never short sums.
+ *    back) the getters fail with TA_ERANGE.  Never short sums.  The one exception: an extraction without any pair has no row
+ *    to add to and launches no pass, so its getters answer TA_OK with no rows whatever the volume holds by then.
  */
 #ifndef TISSUE_SCAN_WALLGEO_H
 #define TISSUE_SCAN_WALLGEO_H
@@ -48,6 +49,9 @@ TA_API int ta_wallgeo_get(ta_ctx* ctx, uint64_t* fwd, uint64_t* rev, uint64_t* s
 /* Diagnostics of the last pass: records that found no slot in a workgroup's LDS table and went to the global rows directly
  * (the results are the same).  Synchronises. */
 TA_API int ta_wallgeo_spills(ta_ctx* ctx, uint32_t* spills);
+/* The same and the launch plan, for tests: out[0] the spills, out[1] 0, out[2] the tiles a workgroup took, out[3] the
+ * workgroups (0 and 0 when the extraction has no pair: the pass is then not launched at all).  Synchronises. */
+TA_API int ta_wallgeo_debug(ta_ctx* ctx, uint32_t out[4]);
 /* Milliseconds between two HIP events around the pass kernel of the last ta_wallgeo_extract (the pair table is built before). */
 TA_API int ta_wallgeo_timing(ta_ctx* ctx, double* ms);
 

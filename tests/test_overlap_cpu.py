@@ -175,6 +175,7 @@ def test_library_exports_the_overlap_symbols_and_they_reject_a_null_context():
         "ta_overlap_get": (None, buf, buf, buf),
         "ta_overlap_timing": (None, ctypes.byref(dbl)),
         "ta_overlap_timing_compaction": (None, ctypes.byref(dbl), None),
+        "ta_overlap_debug": (None, (ctypes.c_uint32 * 4)()),
     }
     assert sorted(calls) == sorted(_capi.OVERLAP_SYMBOLS)
     for name in declared_symbols("tissue_scan_overlap.h"):

@@ -94,6 +94,7 @@ def test_library_exports_the_signal_symbols_and_they_reject_a_null_context():
         "ta_signal_get_labels": (None, buf, buf, buf, buf, buf),
         "ta_signal_get_walls": (None, buf, buf),
         "ta_signal_timing": (None, ctypes.byref(dbl)),
+        "ta_signal_debug": (None, (ctypes.c_uint32 * 4)()),
     }
     assert sorted(calls) == sorted(_capi.SIGNAL_SYMBOLS)
     for name in declared_signal_symbols():

@@ -41,6 +41,8 @@ def test_library_exports_the_symbols_and_rejects_a_null_context():
     assert lib.ta_wallgeo_extract(None) == _capi.TA_EINVAL
     assert b"NULL" in lib.ta_last_error()
     assert lib.ta_wallgeo_get(None, None, None, None, None) == _capi.TA_EINVAL
+    assert lib.ta_wallgeo_debug(None, None) == _capi.TA_EINVAL
+    assert b"NULL" in lib.ta_last_error()
     assert lib.ta_version() == 5
 
 

@@ -42,7 +42,7 @@ SYMBOLS = (
 # every symbol include/tissue_scan_signal.h declares (same library; kept apart from SYMBOLS, which is tissue_scan.h's list)
 SIGNAL_SYMBOLS = (
     "ta_signal_set", "ta_signal_set_device", "ta_signal_extract", "ta_signal_get_labels", "ta_signal_get_walls",
-    "ta_signal_timing",
+    "ta_signal_timing", "ta_signal_debug",
 )
 SIG_LABELS, SIG_WALLS = 1, 2           # TA_SIG_LABELS / TA_SIG_WALLS
 
@@ -54,7 +54,7 @@ SIGNAL_DTYPES = (np.uint8, np.uint16)
 # every symbol include/tissue_scan_overlap.h declares (same library)
 OVERLAP_SYMBOLS = (
     "ta_overlap_set", "ta_overlap_set_device", "ta_overlap_set_capacity", "ta_overlap_extract", "ta_overlap_size", "ta_overlap_get",
-    "ta_overlap_timing", "ta_overlap_timing_compaction",
+    "ta_overlap_timing", "ta_overlap_timing_compaction", "ta_overlap_debug",
 )
 
 # every symbol include/tissue_scan_junctions.h declares (same library)
@@ -63,7 +63,7 @@ JUNCTION_SYMBOLS = (
 )
 
 # every symbol include/tissue_scan_wallgeo.h declares (same library)
-WALLGEO_SYMBOLS = ("ta_wallgeo_extract", "ta_wallgeo_get", "ta_wallgeo_spills", "ta_wallgeo_timing")
+WALLGEO_SYMBOLS = ("ta_wallgeo_extract", "ta_wallgeo_get", "ta_wallgeo_spills", "ta_wallgeo_debug", "ta_wallgeo_timing")
 
 # every symbol include/tissue_scan_components.h declares (same library)
 COMPONENT_SYMBOLS = (
@@ -175,6 +175,7 @@ def load():
         "ta_signal_get_labels": (ci, [vp, vp, vp, vp, vp, vp]),
         "ta_signal_get_walls": (ci, [vp, vp, vp]),
         "ta_signal_timing": (ci, [vp, P(ctypes.c_double)]),
+        "ta_signal_debug": (ci, [vp, P(u32)]),
         "ta_mesh_extract": (ci, [vp, ci, vp]),
         "ta_mesh_size": (ci, [vp, P(u64), P(u64), P(u64)]),
         "ta_mesh_get": (ci, [vp, vp, vp, vp, vp, vp, vp, vp]),
@@ -187,6 +188,7 @@ def load():
         "ta_overlap_get": (ci, [vp, vp, vp, vp]),
         "ta_overlap_timing": (ci, [vp, P(ctypes.c_double)]),
         "ta_overlap_timing_compaction": (ci, [vp, P(ctypes.c_double), P(ci)]),
+        "ta_overlap_debug": (ci, [vp, P(u32)]),
         "ta_junctions_extract": (ci, [vp]),
         "ta_junctions_size": (ci, [vp, P(u64), P(u64), P(u64)]),
         "ta_junctions_get_edges": (ci, [vp, vp, vp, vp]),
@@ -195,6 +197,7 @@ def load():
         "ta_wallgeo_extract": (ci, [vp]),
         "ta_wallgeo_get": (ci, [vp, vp, vp, vp, vp]),
         "ta_wallgeo_spills": (ci, [vp, P(u32)]),
+        "ta_wallgeo_debug": (ci, [vp, P(u32)]),
         "ta_wallgeo_timing": (ci, [vp, P(ctypes.c_double)]),
         "ta_components_extract": (ci, [vp]),
         "ta_components_size": (ci, [vp, P(u64)]),
@@ -483,6 +486,13 @@ class Context(object):
         _check(self._lib.ta_signal_get_walls(self._h, lo.ctypes.data, hi.ctypes.data))
         return lo, hi
 
+    def signal_debug(self):
+        """Diagnostics of the last signal pass: records that missed a workgroup's LDS tables (label_spills, pair_spills) and the
+        launch plan (tiles_per_group, groups)."""
+        out = (ctypes.c_uint32 * 4)()
+        _check(self._lib.ta_signal_debug(self._h, out))
+        return dict(label_spills=int(out[0]), pair_spills=int(out[1]), tiles_per_group=int(out[2]), groups=int(out[3]))
+
     def signal_timing(self):
         ms = ctypes.c_double(0.0)
         _check(self._lib.ta_signal_timing(self._h, ctypes.byref(ms)))
@@ -554,6 +564,13 @@ class Context(object):
         _check(self._lib.ta_overlap_get(self._h, a.ctypes.data, b.ctypes.data, n.ctypes.data))
         return a, b, n
 
+    def overlap_debug(self):
+        """Diagnostics of the last run of the overlap pass kernel: records that missed a workgroup's LDS table (spills), the runs
+        it took (passes) and the launch plan (tiles_per_group, groups).  Settles the table."""
+        out = (ctypes.c_uint32 * 4)()
+        _check(self._lib.ta_overlap_debug(self._h, out))
+        return dict(spills=int(out[0]), passes=int(out[1]), tiles_per_group=int(out[2]), groups=int(out[3]))
+
     def overlap_timing(self):
         """Milliseconds of the pass kernel of the last overlap_extract."""
         ms = ctypes.c_double(0.0)
@@ -611,6 +628,12 @@ class Context(object):
         n = ctypes.c_uint32(0)
         _check(self._lib.ta_wallgeo_spills(self._h, ctypes.byref(n)))
         return int(n.value)
+
+    def wallgeo_debug(self):
+        """wallgeo_spills() and the launch plan (tiles_per_group, groups; 0 and 0 when there was no pair and no launch)."""
+        out = (ctypes.c_uint32 * 4)()
+        _check(self._lib.ta_wallgeo_debug(self._h, out))
+        return dict(spills=int(out[0]), tiles_per_group=int(out[2]), groups=int(out[3]))
 
     def wallgeo_timing(self):
         ms = ctypes.c_double(0.0)

@@ -244,11 +244,12 @@ void launch_types(hipStream_t s, const OverlapArgs& a, bool vec, int64_t groups)
 
 }  // namespace
 
-void launch_overlap(hipStream_t s, OverlapArgs a, int itemsize_a, int itemsize_b) {
+RangePlan launch_overlap(hipStream_t s, OverlapArgs a, int itemsize_a, int itemsize_b) {
     const int vpl = 16 / itemsize_a;
     const int64_t cols = 64 * vpl;
     const int64_t owned = a.n0 - a.first_owned;
-    if (owned <= 0 || a.n1 <= 0 || a.n2 <= 0) return;
+    RangePlan plan;
+    if (owned <= 0 || a.n1 <= 0 || a.n2 <= 0) return plan;
     const int64_t tiles = ((a.n2 + cols - 1) / cols) * ((a.n1 + OV_WAVES - 1) / OV_WAVES) * ((owned + OV_PLANES - 1) / OV_PLANES);
     // a lane's record and a workgroup's LDS slots count voxels in u32: fewer than 2^31 voxels a workgroup
     const int64_t most = ((int64_t)1 << 31) / (OV_WAVES * cols * OV_PLANES);
@@ -262,6 +263,8 @@ void launch_overlap(hipStream_t s, OverlapArgs a, int itemsize_a, int itemsize_b
     else if (itemsize_a == 2) launch_types<uint16_t, uint32_t>(s, a, vec, groups);
     else if (itemsize_b == 2) launch_types<uint32_t, uint16_t>(s, a, vec, groups);
     else launch_types<uint32_t, uint32_t>(s, a, vec, groups);
+    plan.tiles_per_group = (uint32_t)per; plan.groups = (uint32_t)groups;
+    return plan;
 }
 
 void launch_overlap_count(hipStream_t s, const unsigned long long* keys, uint64_t slots, uint32_t* block_counts) {

@@ -53,6 +53,7 @@ __device__ void label_add_global(const SignalArgs& A, uint32_t l, uint64_t n, ui
 }
 
 __device__ void pair_add_global_row(const SignalArgs& A, uint64_t key, uint64_t slo, uint64_t shi) {
+    if (!A.hkeys) { atomicOr(&A.flags[SIG_FLAG_PAIR_MISS], 1u); return; }      // an extraction without pairs has no index: every face is a miss
     uint32_t h = hash_pair((uint32_t)(key >> 32), (uint32_t)key) & A.hmask;
     for (uint32_t probe = 0; probe <= A.hmask; ++probe) {
         const uint64_t k = A.hkeys[h];
@@ -347,11 +348,12 @@ void launch_signal_hash(hipStream_t s, const uint64_t* keys, uint64_t n, uint64_
     hipLaunchKernelGGL(signal_hash_kernel, dim3((unsigned)blocks), dim3(256), 0, s, keys, n, (unsigned long long*)hkeys, hrows, hmask);
 }
 
-void launch_signal(hipStream_t s, SignalArgs a, int label_itemsize, int signal_itemsize, uint32_t what) {
+RangePlan launch_signal(hipStream_t s, SignalArgs a, int label_itemsize, int signal_itemsize, uint32_t what) {
     const int vpl = 16 / label_itemsize;
     const int64_t cols = 64 * vpl;
     const int64_t owned = a.n0 - a.first_owned;
-    if (owned <= 0 || a.n1 <= 0 || a.n2 <= 0 || !(what & (SIG_LABELS | SIG_WALLS))) return;
+    RangePlan plan;
+    if (owned <= 0 || a.n1 <= 0 || a.n2 <= 0 || !(what & (SIG_LABELS | SIG_WALLS))) return plan;
     const int64_t tiles = ((a.n2 + cols - 1) / cols) * ((a.n1 + SIG_WAVES - 1) / SIG_WAVES) * ((owned + SIG_PLANES - 1) / SIG_PLANES);
     // a workgroup's LDS rows count voxels in u32: fewer than 2^31 voxels a workgroup
     const int64_t most = ((int64_t)1 << 31) / (SIG_WAVES * cols * SIG_PLANES);
@@ -364,6 +366,8 @@ void launch_signal(hipStream_t s, SignalArgs a, int label_itemsize, int signal_i
     else if (label_itemsize == 2) launch_types<uint16_t, uint16_t>(s, a, what, vec, groups);
     else if (signal_itemsize == 1) launch_types<uint32_t, uint8_t>(s, a, what, vec, groups);
     else launch_types<uint32_t, uint16_t>(s, a, what, vec, groups);
+    plan.tiles_per_group = (uint32_t)per; plan.groups = (uint32_t)groups;
+    return plan;
 }
 
 }  // namespace ta

@@ -287,11 +287,12 @@ __global__ __launch_bounds__(WG_THREADS) void wallgeo_kernel(const WallGeoArgs A
 
 }  // namespace
 
-void launch_wallgeo(hipStream_t s, WallGeoArgs a, int label_itemsize) {
+RangePlan launch_wallgeo(hipStream_t s, WallGeoArgs a, int label_itemsize) {
     const int vpl = 16 / label_itemsize;
     const int64_t cols = 64 * vpl;
     const int64_t owned = a.n0 - a.first_owned;
-    if (owned <= 0 || a.n1 <= 0 || a.n2 <= 0) return;
+    RangePlan plan;
+    if (owned <= 0 || a.n1 <= 0 || a.n2 <= 0) return plan;
     const int64_t tiles = ((a.n2 + cols - 1) / cols) * ((a.n1 + WG_WAVES - 1) / WG_WAVES) * ((owned + WG_PLANES - 1) / WG_PLANES);
     // a workgroup's LDS rows count faces in u32: fewer than 2^30 voxels (three faces each) a workgroup
     const int64_t most = ((int64_t)1 << 30) / (WG_WAVES * cols * WG_PLANES);
@@ -307,6 +308,8 @@ void launch_wallgeo(hipStream_t s, WallGeoArgs a, int label_itemsize) {
         if (vec) hipLaunchKernelGGL((wallgeo_kernel<uint32_t, true>), dim3((unsigned)groups), dim3(WG_THREADS), 0, s, a);
         else hipLaunchKernelGGL((wallgeo_kernel<uint32_t, false>), dim3((unsigned)groups), dim3(WG_THREADS), 0, s, a);
     }
+    plan.tiles_per_group = (uint32_t)per; plan.groups = (uint32_t)groups;
+    return plan;
 }
 
 }  // namespace ta

@@ -48,7 +48,7 @@ int overlap_launch(ta_ctx* c) {
     TA_HIP(hipMemsetAsync(a.counts, 0, slots * 8, c->stream));
     TA_HIP(hipMemsetAsync(c->ov.small.p, 0, 32, c->stream));
     TA_HIP(hipEventRecord(c->ov.ev[0], c->stream));
-    ta::launch_overlap(c->stream, a, c->itemsize, c->ov.b.itemsize);
+    c->ov.plan = ta::launch_overlap(c->stream, a, c->itemsize, c->ov.b.itemsize);
     TA_HIP(hipGetLastError());
     TA_HIP(hipEventRecord(c->ov.ev[1], c->stream));
     char* w = (char*)c->ov.work.p;
@@ -74,6 +74,7 @@ int overlap_settle(ta_ctx* c) {
         TA_HIP(hipMemcpyAsync(&occupied, ta::scan_u32_total((char*)c->ov.work.p + scratch_at, blocks), 8, hipMemcpyDeviceToHost, c->stream));
         TA_HIP(hipStreamSynchronize(c->stream));
         memcpy(&top, &small[4], 8);
+        c->ov.lds_spills = small[ta::OV_FLAG_LDS_SPILL];               // (of the run just read: in the end, of the last one)
         if (!small[ta::OV_FLAG_OVERFLOW]) break;
         const int most = overlap_top_log2(c);
         if (c->ov.log2 >= most) {
@@ -184,6 +185,16 @@ TA_API int ta_overlap_get(ta_ctx* c, uint32_t* a, uint32_t* b, uint64_t* n) {
     if (b) TA_HIP(hipMemcpyAsync(b, ra + P, 4 * P, hipMemcpyDeviceToHost, c->stream));
     if (n) TA_HIP(hipMemcpyAsync(n, ra + 2 * P, 8 * P, hipMemcpyDeviceToHost, c->stream));
     TA_HIP(hipStreamSynchronize(c->stream));
+    return TA_OK;
+}
+
+TA_API int ta_overlap_debug(ta_ctx* c, uint32_t out[4]) {
+    if (!c) return fail(TA_EINVAL, "ctx is NULL");
+    if (c->ov.state == 0) return fail(TA_EINVAL, "no overlap table for the current volume and B (run ta_overlap_extract)");
+    int rc = use_device(c);
+    if (rc != TA_OK) return rc;
+    if ((rc = overlap_settle(c)) != TA_OK) return rc;
+    if (out) { out[0] = c->ov.lds_spills; out[1] = (uint32_t)c->ov.passes; out[2] = c->ov.plan.tiles_per_group; out[3] = c->ov.plan.groups; }
     return TA_OK;
 }
 

@@ -18,13 +18,14 @@ struct SignalLayout {
     }
 };
 
-// drain the stream and look at the pass's flag words
-int signal_finish(ta_ctx* c) {
+// drain the stream and look at the pass's flag words; spills: label records, pair records that missed a workgroup's LDS tables
+int signal_finish(ta_ctx* c, uint32_t* spills = nullptr) {
     uint32_t flags[ta::SIG_NFLAGS] = {0, 0, 0, 0};
     TA_HIP(hipMemcpyAsync(flags, c->sig.out.p, sizeof(flags), hipMemcpyDeviceToHost, c->stream));
     TA_HIP(hipStreamSynchronize(c->stream));
     if (flags[ta::SIG_FLAG_RANGE]) return fail(TA_ERANGE, "the signal pass met a label above max_label=%u (the volume changed since ta_extract)", c->max_label);
     if (flags[ta::SIG_FLAG_PAIR_MISS]) return fail(TA_ERANGE, "the signal pass met a pair the extraction does not hold (the volume changed since ta_extract)");
+    if (spills) { spills[0] = flags[ta::SIG_FLAG_LABEL_SPILL]; spills[1] = flags[ta::SIG_FLAG_PAIR_SPILL]; }
     return TA_OK;
 }
 
@@ -110,7 +111,7 @@ TA_API int ta_signal_extract(ta_ctx* c, uint32_t what) {
     a.flags = (uint32_t*)o;
     a.tiles_per_group = 0;
     TA_HIP(hipEventRecord(c->sig.ev[0], c->stream));
-    ta::launch_signal(c->stream, a, c->itemsize, c->sig.img.itemsize, (what & TA_SIG_LABELS ? ta::SIG_LABELS : 0u) | (walls ? ta::SIG_WALLS : 0u));
+    c->sig.plan = ta::launch_signal(c->stream, a, c->itemsize, c->sig.img.itemsize, (what & TA_SIG_LABELS ? ta::SIG_LABELS : 0u) | (walls ? ta::SIG_WALLS : 0u));
     TA_HIP(hipGetLastError());
     TA_HIP(hipEventRecord(c->sig.ev[1], c->stream));
     c->sig.seq = c->extract_seq;
@@ -152,6 +153,17 @@ TA_API int ta_signal_get_walls(ta_ctx* c, uint64_t* side_lo, uint64_t* side_hi) 
     if (side_lo && P) TA_HIP(hipMemcpyAsync(side_lo, o + L.side_lo, 8 * P, hipMemcpyDeviceToHost, c->stream));
     if (side_hi && P) TA_HIP(hipMemcpyAsync(side_hi, o + L.side_hi, 8 * P, hipMemcpyDeviceToHost, c->stream));
     TA_HIP(hipStreamSynchronize(c->stream));
+    return TA_OK;
+}
+
+TA_API int ta_signal_debug(ta_ctx* c, uint32_t out[4]) {
+    if (!c) return fail(TA_EINVAL, "ctx is NULL");
+    if (!signal_current(c)) return fail(TA_EINVAL, "no signal results for the current extraction (run ta_signal_extract)");
+    int rc = use_device(c);
+    if (rc != TA_OK) return rc;
+    uint32_t spills[2] = {0, 0};
+    if ((rc = signal_finish(c, spills)) != TA_OK) return rc;
+    if (out) { out[0] = spills[0]; out[1] = spills[1]; out[2] = c->sig.plan.tiles_per_group; out[3] = c->sig.plan.groups; }
     return TA_OK;
 }
 

@@ -58,7 +58,7 @@ TA_API int ta_wallgeo_extract(ta_ctx* c) {
     a.flags = (uint32_t*)o;
     TA_HIP(hipEventRecord(c->wg.ev[0], c->stream));
     // (a volume of one label has no pair and no row to add to: nothing to launch)
-    if (P) ta::launch_wallgeo(c->stream, a, c->itemsize);
+    c->wg.plan = P ? ta::launch_wallgeo(c->stream, a, c->itemsize) : ta::RangePlan();
     TA_HIP(hipGetLastError());
     TA_HIP(hipEventRecord(c->wg.ev[1], c->stream));
     c->wg.seq = c->extract_seq;
@@ -101,6 +101,17 @@ TA_API int ta_wallgeo_spills(ta_ctx* c, uint32_t* spills) {
     int rc = use_device(c);
     if (rc != TA_OK) return rc;
     return wallgeo_finish(c, spills);
+}
+
+TA_API int ta_wallgeo_debug(ta_ctx* c, uint32_t out[4]) {
+    if (!c) return fail(TA_EINVAL, "ctx is NULL");
+    if (!wallgeo_current(c)) return fail(TA_EINVAL, "no wall-geometry rows for the current extraction (run ta_wallgeo_extract)");
+    int rc = use_device(c);
+    if (rc != TA_OK) return rc;
+    uint32_t spills = 0;
+    if ((rc = wallgeo_finish(c, &spills)) != TA_OK) return rc;
+    if (out) { out[0] = spills; out[1] = 0u; out[2] = c->wg.plan.tiles_per_group; out[3] = c->wg.plan.groups; }
+    return TA_OK;
 }
 
 TA_API int ta_wallgeo_timing(ta_ctx* c, double* ms) {

@@ -86,6 +86,7 @@ struct SignalState {
     uint32_t what = 0;
     uint32_t rows = 0;                                  // max_label + 1 of that extraction
     int64_t npairs = 0;
+    ta::RangePlan plan;                                 // what the last pass was launched with (ta_signal_debug)
     hipEvent_t ev[2] = {nullptr, nullptr};
     void release() { img.owned.release(); out.release(); hash.release(); destroy_events(ev); }
 };
@@ -119,6 +120,8 @@ struct OverlapState {
     int log2 = 0;                                       // slots of the table of the pass in flight
     int state = 0;                                      // 0 = no table, 1 = pass enqueued, 2 = settled (rows holds npairs rows)
     int passes = 0;                                     // runs of the pass kernel for this table
+    ta::RangePlan plan;                                 // what the last run was launched with (ta_overlap_debug)
+    uint32_t lds_spills = 0;                            // OV_FLAG_LDS_SPILL of the last run, kept by overlap_settle
     uint64_t npairs = 0;
     hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // pass begin, end | count + scan end | emit begin, rows end
     void release() { b.owned.release(); table.release(); small.release(); work.release(); sort.release(); rows.release(); destroy_events(ev); }
@@ -144,6 +147,7 @@ struct WallGeoState {
     DevBuf hash;                                        // pair -> row table of the sorted pair list: keys u64[cap] | sorted keys | rows u32[cap]
     uint64_t seq = 0;                                   // extract_seq of the extraction the rows belong to, 0 = none
     int64_t npairs = 0;
+    ta::RangePlan plan;                                 // what the last pass was launched with; 0, 0 when it had no pair and was not launched
     hipEvent_t ev[2] = {nullptr, nullptr};
     void release() { out.release(); hash.release(); destroy_events(ev); }
 };

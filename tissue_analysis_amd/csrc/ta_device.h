@@ -23,6 +23,10 @@ enum { FLAG_RANGE = 0, FLAG_PAIR_OVERFLOW = 1, FLAG_LDS_LABEL_SPILL = 2, FLAG_LD
 constexpr int XHDR = 2;
 constexpr uint64_t XSTATUS_RANGE = 1, XSTATUS_PAIR_OVERFLOW = 2;
 
+// What launch_signal, launch_overlap and launch_wallgeo launched: every workgroup takes `tiles_per_group` consecutive tiles (the
+// last one what is left); 0, 0 when there was nothing to launch.  The host layer keeps it for the ta_*_debug getters.
+struct RangePlan { uint32_t tiles_per_group = 0, groups = 0; };
+
 struct PairTable {           // device-global open-addressing hash: key = lo<<32|hi
     uint64_t* keys;          // [cap], EMPTY_KEY when free
     uint64_t* faces;         // [cap][3] per memory axis

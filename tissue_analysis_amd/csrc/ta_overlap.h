@@ -22,7 +22,8 @@ struct OverlapArgs {
 };
 
 // one streaming pass over A and B.  keys must hold EMPTY_KEY everywhere (memset 0xff); counts, flags and *top zero.
-void launch_overlap(hipStream_t s, OverlapArgs a, int itemsize_a, int itemsize_b);
+// Returns the plan it launched.
+RangePlan launch_overlap(hipStream_t s, OverlapArgs a, int itemsize_a, int itemsize_b);
 
 // compaction of the occupied slots: count per block of OV_COMPACT_BLOCK slots, (the caller scans the counts,) emit.
 constexpr uint32_t OV_COMPACT_BLOCK = 1024;

@@ -34,6 +34,7 @@ struct SignalArgs {
 void launch_signal_hash(hipStream_t s, const uint64_t* keys, uint64_t n, uint64_t* hkeys, uint32_t* hrows, uint32_t hmask);
 // one streaming pass over labels + signal; `what` = SIG_LABELS | SIG_WALLS.  The rows must be initialised by the caller
 // (n, sum, sumsq, vmax: 0; vmin: 0xff bytes; side_lo / side_hi: 0; flags: 0).
-void launch_signal(hipStream_t s, SignalArgs a, int label_itemsize, int signal_itemsize, uint32_t what);
+// Returns the plan it launched.
+RangePlan launch_signal(hipStream_t s, SignalArgs a, int label_itemsize, int signal_itemsize, uint32_t what);
 
 }  // namespace ta

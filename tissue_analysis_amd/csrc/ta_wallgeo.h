@@ -24,6 +24,7 @@ struct WallGeoArgs {
 };
 
 // one streaming pass over the labels; the pair -> row table is launch_signal_hash's (ta_signal.h)
-void launch_wallgeo(hipStream_t s, WallGeoArgs a, int label_itemsize);
+// Returns the plan it launched.
+RangePlan launch_wallgeo(hipStream_t s, WallGeoArgs a, int label_itemsize);
 
 }  // namespace ta
