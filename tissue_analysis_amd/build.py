@@ -7,6 +7,7 @@ hipcc cross-compiles without a GPU; the built .so is git-ignored but travels wit
 from __future__ import annotations
 
 import os
+import re
 import subprocess
 import sys
 
@@ -46,24 +47,42 @@ def _stale(target, deps):
     return any(os.path.getmtime(d) > t for d in deps)
 
 
-def _check_pinned(hipcc, verbose=False):
-    """kernels_scan.hip keeps the plane in flight in 21 VGPRs it names itself, above an amdgpu_num_vgpr budget
-    that the compiler treats as a request, not a limit: refuse a build in which compiler-allocated code of an
-    interior kernel (or of a device function they call) reaches them."""
-    import re
-    asm = os.path.join(OBJDIR, "kernels_scan.check.s")
-    cmd = [hipcc] + FLAGS + EXTRA_FLAGS.get("kernels_scan.hip", []) + ["--cuda-device-only", "-S", os.path.join(CSRC, "kernels_scan.hip"), "-o", asm]
-    if verbose:
-        print(" ".join(cmd))
-    subprocess.check_call(cmd, cwd=OBJDIR)
-    bases = {}
-    for line in open(os.path.join(CSRC, "kernels_scan.hip")):
-        m = re.match(r"#define TA_PIN_(ADJ8_PAD|ADJ8|ADJ2_PAD|ADJ_PAD|MOM_PAD|ADJ2|ADJ|MOM) (\d+)", line)
-        if m:
-            bases[m.group(1)] = int(m.group(2))
+ZONE_REGS = {"ROWS_HALO": 21, "ROWS": 16, "TWO_ROWS": 13, "WIDE": 25}      # registers of a landing zone, by the layout names of SCAN_VARIANTS
+EDGE_LAST = ("scan_kernel", "scan_noadj_kernel", "scan_wide_kernel")       # entry points whose last template argument is EDGE
+
+
+def read_variants(path=os.path.join(CSRC, "kernels_scan.hip")):
+    """The rows of SCAN_VARIANTS in kernels_scan.hip: [(entry point, layout of its landing zone, first pinned register)]."""
+    return [(n, z, int(b)) for n, z, b in re.findall(r"^\s*X\((scan_\w+),\s*(\w+),\s*(\d+)\)", open(path).read(), re.M)]
+
+
+def _zones_of(sym, is_kernel, zones):
+    """The register ranges [lo, hi) that compiler-allocated code of the function `sym` must stay clear of."""
+    m = re.match(r"_ZN2ta(\d+)", sym)
+    name, args = (sym[m.end():][:int(m.group(1))], sym[m.end() + int(m.group(1)):]) if m else (sym, "")
+    if not (is_kernel and name.startswith("scan_")):
+        return list(zones.values())      # a device function: callable from any of them
+    if name not in zones:
+        raise RuntimeError("kernel %s is in no row of SCAN_VARIANTS (kernels_scan.hip): its landing zone is unknown" % sym)
+    if name in EDGE_LAST and args.split("EEEv")[0].endswith("Lb1"):
+        return []                        # edge kernels issue no hand-pinned loads: any register is theirs
+    return [zones[name]]
+
+
+def pinned_violations(asm, variants):
+    """kernels_scan.hip keeps the plane in flight in VGPRs it names itself, above an amdgpu_num_vgpr budget that the
+    compiler treats as a request, not a limit.  Returns the lines of the assembly text `asm` (outside the inline asm
+    that owns them) in which a pinned kernel names a register of its own landing zone, or a device function one of
+    any zone; `variants` is what read_variants() returns."""
+    unknown = [v for v in variants if v[1] not in ZONE_REGS]
+    zones = {n: (b, b + ZONE_REGS[z]) for n, z, b in variants if z in ZONE_REGS}
+    if len(zones) < 8 or unknown:
+        raise RuntimeError("the table of pinned entry points (SCAN_VARIANTS in kernels_scan.hip) is incomplete: %d entry points "
+                           "read, the sweep has eight; rows of unknown layout: %s" % (len(zones), unknown))
+    kernels = set(re.findall(r"^\s*\.amdhsa_kernel\s+(\S+)", asm, re.M))
     reg = re.compile(r"\bv(\d+)\b|\bv\[(\d+):(\d+)\]")
-    in_asm, func, bad = False, "", []
-    for ln, line in enumerate(open(asm), 1):
+    in_asm, func, ranges, bad = False, "", list(zones.values()), []
+    for ln, line in enumerate(asm.split("\n"), 1):
         t = line.strip()
         if t.startswith(";;#ASMSTART"):
             in_asm = True
@@ -73,35 +92,27 @@ def _check_pinned(hipcc, verbose=False):
             m = re.match(r"^(_Z\w+):", line)
             if m:
                 func = m.group(1)
+                ranges = _zones_of(func, func in kernels, zones)
                 continue
             if in_asm or not t or t[0] in ";.":
                 continue
-            if re.search(r"scan_(noadj_|wide_)?kernelI\w*Lb1EEEvNS_9SweepArgs", func):
-                continue              # edge kernels issue no hand-pinned loads: any register is theirs
-            if "scan_wide_pad_kernel" in func:
-                ranges = [bases["ADJ8_PAD"], bases["ADJ8_PAD"] + 4]      # (25 registers: two overlapping windows of 21)
-            elif "scan_wide_kernel" in func:
-                ranges = [bases["ADJ8"], bases["ADJ8"] + 4]
-            elif "scan_noadj_pad_kernel" in func:
-                ranges = [bases["MOM_PAD"]]
-            elif "scan_pad2_kernel" in func:
-                ranges = [bases["ADJ2_PAD"]]
-            elif "scan_pad_kernel" in func:
-                ranges = [bases["ADJ_PAD"]]
-            elif "scan_noadj_kernel" in func:
-                ranges = [bases["MOM"]]
-            elif "scan_two_rows_kernel" in func:
-                ranges = [bases["ADJ2"]]
-            elif "scan_kernel" in func:
-                ranges = [bases["ADJ"]]
-            else:
-                ranges = list(bases.values())      # a device function: callable from any of them
             for m in reg.finditer(t.split(";")[0]):
                 lo = int(m.group(1) or m.group(2)); hi = int(m.group(1) or m.group(3))
-                if any(hi >= b and lo < b + 21 for b in ranges):      # (21 pinned with adjacency, 16 without: the wider check is safe)
+                if any(hi >= a and lo < b for a, b in ranges):
                     bad.append("%s:%d: %s" % (func, ln, t))
                     break
-    if bad or len(bases) != 8:
+    return bad
+
+
+def _check_pinned(hipcc, verbose=False):
+    """Refuse a build in which compiler-allocated code reaches the hand-pinned registers (pinned_violations)."""
+    asm = os.path.join(OBJDIR, "kernels_scan.check.s")
+    cmd = [hipcc] + FLAGS + EXTRA_FLAGS.get("kernels_scan.hip", []) + ["--cuda-device-only", "-S", os.path.join(CSRC, "kernels_scan.hip"), "-o", asm]
+    if verbose:
+        print(" ".join(cmd))
+    subprocess.check_call(cmd, cwd=OBJDIR)
+    bad = pinned_violations(open(asm).read(), read_variants())
+    if bad:
         raise RuntimeError("compiler-allocated VGPRs reach the hand-pinned registers in kernels_scan.hip:\n  %s"
                            % "\n  ".join(bad[:10]))
 

@@ -703,44 +703,41 @@ __device__ __forceinline__ void scan_load_strip(const bool EDGE, const T* row_c0
 // unpacked into the working registers, a whole plane of compute after they were issued.
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
-// The plane in flight lives in registers the compiler never allocates: the kernels are compiled with
-// amdgpu_num_vgpr(BASE), and v[BASE ..] are named explicitly in Pin<BASE>: the first quads = the rows of the
-// wave tile, the next quad = the row above it, then one register for lanes 0..RB-1: the voxel left of each row.
+// The plane in flight lives in registers the compiler never allocates: every pinned entry point asks for a VGPR
+// budget below its landing zone, and the zone's registers v[PIN ..] are named explicitly in Pin<PIN>.
 // (Loading into ordinary asm outputs does not work: the register allocator copies a loop-carried output at the
 // back edge, i.e. reads it while the load is still in flight; accumulation registers make the compiler split the
 // unified file in halves.)
-#ifndef TA_PIN_ADJ
-#define TA_PIN_ADJ 104        // kernels with adjacency: 104 compiler-allocated VGPRs + 21 pinned = 125: four waves per SIMD
-#endif
-#define TA_PIN_MOM 76         // kernels without (rows only: no row above, no voxel to the left): 76 + 16 = 92: five waves
+//
+// One row per pinned entry point: X(entry point, layout of its landing zone, first pinned register).  These rows are
+// read as text by scripts/gen_pin_tables.py (one Pin<> a row, into ta_pin_tables.inc) and by tissue_analysis_amd/build.py
+// (which checks each kernel's generated code against its row): a budget or a layout is stated here and nowhere else.
+//   ROWS_HALO  21 registers: four rows of the wave tile (a quad each), the row above, then one register for lanes 0..RB-1:
+//              the voxel left of each row
+//   ROWS       16: the rows only (no adjacency: no row above, no voxel to the left)
+//   TWO_ROWS   13: two rows, the row above, the voxel (uint32 volumes with adjacency run TWO rows per wave, RB = 2: half
+//              the plane state of the four-row tiles)
+//   WIDE       25: two rows of EIGHT uint32 voxels a lane (TA_U32_SHAPE = 1): six quads and the voxel (an even first
+//              register: 16-byte loads want even register pairs)
+// First pinned + zone = the kernel's VGPRs, which set the waves per SIMD.  The *_pad* kernels (partial tiles of a volume
+// whose rows are 16-byte aligned: interior-style loads, edge-style semantics) carry more state than the interior ones
+// (1000^3 is a quarter partial tiles; real volumes are rarely multiples of 8 x 256).
+#define SCAN_VARIANTS(X)                                                             \
+    X(scan_kernel,           ROWS_HALO, 104)     /* 104 + 21 = 125: four waves */    \
+    X(scan_pad_kernel,       ROWS_HALO, 120)     /* 120 + 21 = 141: three */         \
+    X(scan_noadj_kernel,     ROWS,       76)     /*  76 + 16 =  92: five */          \
+    X(scan_noadj_pad_kernel, ROWS,       80)     /*  80 + 16 =  96: five */          \
+    X(scan_two_rows_kernel,  TWO_ROWS,   82)     /*  82 + 13 =  95: FIVE */          \
+    X(scan_pad2_kernel,      TWO_ROWS,  112)     /* 112 + 13 = 125: four */          \
+    X(scan_wide_kernel,      WIDE,      102)     /* 102 + 25 = 127: four */          \
+    X(scan_wide_pad_kernel,  WIDE,      116)     /* 116 + 25 = 141: three */
 // amdgpu_num_vgpr is a request the allocator overshoots when it would have to spill: ask for less than the first
 // pinned register; the build checks the generated code (tissue_analysis_amd/build.py).
-#ifndef TA_CAP_ADJ
-#define TA_CAP_ADJ 100
-#endif
-// uint32 volumes with adjacency run TWO rows per wave (RB = 2: half the plane state of the four-row tiles): 82 compiler-allocated
-// VGPRs + 13 pinned (two rows, the row above, the voxel to the left) = 95: FIVE waves per SIMD
-#define TA_PIN_ADJ2 82
-#define TA_CAP_ADJ2 78
-#define TA_CAP_MOM 72
-// the PADDED kernels (partial tiles of a volume whose rows are 16-byte aligned: interior-style loads, edge-style
-// semantics) carry more state: with adjacency 116 + 21 = 137 (three waves per SIMD), without 80 + 16 = 96 (five, like the
-// interior kernel)
-// two rows of EIGHT uint32 voxels a lane (TA_U32_SHAPE = 1): 25 pinned registers (an even base: 16-byte loads want even register pairs), 102 + 25 = 127: four waves per SIMD
-#define TA_PIN_ADJ8 102
-#define TA_CAP_ADJ8 98
-#define TA_PIN_ADJ8_PAD 116
-#define TA_CAP_ADJ8_PAD 112
-#define TA_PIN_ADJ_PAD 120
-#define TA_PIN_MOM_PAD 80
-#define TA_CAP_ADJ_PAD 116
-#define TA_CAP_MOM_PAD 76
-// ... and with two rows per wave (uint32 volumes with adjacency) the landing zone is 13 registers: 112 + 13 = 125, FOUR waves
-// per SIMD for the partial tiles (1000^3 is a quarter partial tiles; real volumes are rarely multiples of 8 x 256)
-#define TA_PIN_ADJ2_PAD 112
-#define TA_CAP_ADJ2_PAD 108
+#define X(NAME, ZONE, FIRST) constexpr int PIN_##NAME = FIRST, CAP_##NAME = FIRST - 4;
+SCAN_VARIANTS(X)
+#undef X
 template <int BASE> struct Pin;
-#include "ta_pin_tables.inc"        // Pin<104>, Pin<120>, Pin<76>, Pin<80>, Pin<82>, Pin<112>: generated by scripts/gen_pin_tables.py
+#include "ta_pin_tables.inc"        // one Pin<first pinned register> per row of SCAN_VARIANTS: generated by scripts/gen_pin_tables.py
 template <typename T, int VPL>
 __device__ __forceinline__ void unpack_strip(const u32x4& x, uint32_t (&dst)[VPL]) {
     if (sizeof(T) == 4) {
@@ -840,7 +837,7 @@ __device__ __forceinline__ void wave_scan(const SweepArgs& A, const SweepArgs* k
     const uint32_t left_off = (uint32_t)(PAD && b_wave0 + (lane & (RB - 1)) >= n1 ? 0 : (lane & (RB - 1))) * rowbytes;    // (the VGPR offset of a load is unsigned)
     const int64_t plane_bytes = plane * (int64_t)sizeof(T);
     const char* next_row0 = reinterpret_cast<const char*>(vol + (int64_t)(has_prev ? p_lo - 1 : p_lo) * plane + b_base * n2 + c_tile0);
-    using Zone = Pin<(PINB ? PINB : TA_PIN_ADJ)>;          // the landing zone of the plane in flight
+    using Zone = Pin<(PINB ? PINB : PIN_scan_kernel)>;     // the landing zone of the plane in flight (PINB = 0 issues nothing into it)
     auto issue_plane = [&]() {                            // issues the plane at `next_row0` into the landing zone and steps it
         const char* row0 = next_row0;
 #ifndef TA_ABL_L2
@@ -1454,42 +1451,43 @@ __device__ __forceinline__ void scan_kernel_body(const SweepArgs& A, const ScanS
 #endif
 }
 
-// (several entry points only because the VGPR budget is an attribute and must be a literal)
+// (several entry points only because the VGPR budget is an attribute and may not depend on a template parameter: one per
+// row of SCAN_VARIANTS, and the EDGE instantiations of three of them, which pin nothing)
 template <typename T, int VPL, int RB, bool MOM2, bool EDGE>
-__global__ void __launch_bounds__(WAVES * 64) __attribute__((amdgpu_num_vgpr(TA_CAP_ADJ))) scan_kernel(SweepArgs A, ScanSplit sp, uint32_t wg0) {
-    scan_kernel_body<T, VPL, RB, true, MOM2, EDGE, EDGE ? 0 : TA_PIN_ADJ>(A, sp, wg0);
+__global__ void __launch_bounds__(WAVES * 64) __attribute__((amdgpu_num_vgpr(CAP_scan_kernel))) scan_kernel(SweepArgs A, ScanSplit sp, uint32_t wg0) {
+    scan_kernel_body<T, VPL, RB, true, MOM2, EDGE, EDGE ? 0 : PIN_scan_kernel>(A, sp, wg0);
 }
 // the full tiles of a uint32 volume with adjacency: two rows per wave, five waves per SIMD
 template <typename T, int VPL, int RB, bool MOM2>
-__global__ void __launch_bounds__(WAVES * 64) __attribute__((amdgpu_num_vgpr(TA_CAP_ADJ2))) scan_two_rows_kernel(SweepArgs A, ScanSplit sp, uint32_t wg0) {
+__global__ void __launch_bounds__(WAVES * 64) __attribute__((amdgpu_num_vgpr(CAP_scan_two_rows_kernel))) scan_two_rows_kernel(SweepArgs A, ScanSplit sp, uint32_t wg0) {
     static_assert(RB == 2 && VPL == 4, "the 13-register landing zone holds two rows of four voxels a lane");
-    scan_kernel_body<T, VPL, RB, true, MOM2, false, TA_PIN_ADJ2>(A, sp, wg0);
+    scan_kernel_body<T, VPL, RB, true, MOM2, false, PIN_scan_two_rows_kernel>(A, sp, wg0);
 }
 template <typename T, int VPL, int RB, bool MOM2, bool EDGE>
-__global__ void __launch_bounds__(WAVES * 64) __attribute__((amdgpu_num_vgpr(TA_CAP_MOM))) scan_noadj_kernel(SweepArgs A, ScanSplit sp, uint32_t wg0) {
-    scan_kernel_body<T, VPL, RB, false, MOM2, EDGE, EDGE ? 0 : TA_PIN_MOM>(A, sp, wg0);
+__global__ void __launch_bounds__(WAVES * 64) __attribute__((amdgpu_num_vgpr(CAP_scan_noadj_kernel))) scan_noadj_kernel(SweepArgs A, ScanSplit sp, uint32_t wg0) {
+    scan_kernel_body<T, VPL, RB, false, MOM2, EDGE, EDGE ? 0 : PIN_scan_noadj_kernel>(A, sp, wg0);
 }
 // the partial tiles of a volume with 16-byte aligned rows: hand-issued loads like the interior tiles, filler like the edge tiles
 template <typename T, int VPL, int RB, bool MOM2>
-__global__ void __launch_bounds__(WAVES * 64) __attribute__((amdgpu_num_vgpr(TA_CAP_ADJ_PAD))) scan_pad_kernel(SweepArgs A, ScanSplit sp, uint32_t wg0) {
-    scan_kernel_body<T, VPL, RB, true, MOM2, true, TA_PIN_ADJ_PAD>(A, sp, wg0);
+__global__ void __launch_bounds__(WAVES * 64) __attribute__((amdgpu_num_vgpr(CAP_scan_pad_kernel))) scan_pad_kernel(SweepArgs A, ScanSplit sp, uint32_t wg0) {
+    scan_kernel_body<T, VPL, RB, true, MOM2, true, PIN_scan_pad_kernel>(A, sp, wg0);
 }
 template <typename T, int VPL, int RB, bool MOM2, bool EDGE>
-__global__ void __launch_bounds__(WAVES * 64) __attribute__((amdgpu_num_vgpr(TA_CAP_ADJ8))) scan_wide_kernel(SweepArgs A, ScanSplit sp, uint32_t wg0) {
-    scan_kernel_body<T, VPL, RB, true, MOM2, EDGE, EDGE ? 0 : TA_PIN_ADJ8>(A, sp, wg0);
+__global__ void __launch_bounds__(WAVES * 64) __attribute__((amdgpu_num_vgpr(CAP_scan_wide_kernel))) scan_wide_kernel(SweepArgs A, ScanSplit sp, uint32_t wg0) {
+    scan_kernel_body<T, VPL, RB, true, MOM2, EDGE, EDGE ? 0 : PIN_scan_wide_kernel>(A, sp, wg0);
 }
 template <typename T, int VPL, int RB, bool MOM2>
-__global__ void __launch_bounds__(WAVES * 64) __attribute__((amdgpu_num_vgpr(TA_CAP_ADJ8_PAD))) scan_wide_pad_kernel(SweepArgs A, ScanSplit sp, uint32_t wg0) {
-    scan_kernel_body<T, VPL, RB, true, MOM2, true, TA_PIN_ADJ8_PAD>(A, sp, wg0);
+__global__ void __launch_bounds__(WAVES * 64) __attribute__((amdgpu_num_vgpr(CAP_scan_wide_pad_kernel))) scan_wide_pad_kernel(SweepArgs A, ScanSplit sp, uint32_t wg0) {
+    scan_kernel_body<T, VPL, RB, true, MOM2, true, PIN_scan_wide_pad_kernel>(A, sp, wg0);
 }
 template <typename T, int VPL, int RB, bool MOM2>
-__global__ void __launch_bounds__(WAVES * 64) __attribute__((amdgpu_num_vgpr(TA_CAP_ADJ2_PAD))) scan_pad2_kernel(SweepArgs A, ScanSplit sp, uint32_t wg0) {
+__global__ void __launch_bounds__(WAVES * 64) __attribute__((amdgpu_num_vgpr(CAP_scan_pad2_kernel))) scan_pad2_kernel(SweepArgs A, ScanSplit sp, uint32_t wg0) {
     static_assert(RB == 2 && VPL == 4, "the 13-register landing zone holds two rows of four voxels a lane");
-    scan_kernel_body<T, VPL, RB, true, MOM2, true, TA_PIN_ADJ2_PAD>(A, sp, wg0);
+    scan_kernel_body<T, VPL, RB, true, MOM2, true, PIN_scan_pad2_kernel>(A, sp, wg0);
 }
 template <typename T, int VPL, int RB, bool MOM2>
-__global__ void __launch_bounds__(WAVES * 64) __attribute__((amdgpu_num_vgpr(TA_CAP_MOM_PAD))) scan_noadj_pad_kernel(SweepArgs A, ScanSplit sp, uint32_t wg0) {
-    scan_kernel_body<T, VPL, RB, false, MOM2, true, TA_PIN_MOM_PAD>(A, sp, wg0);
+__global__ void __launch_bounds__(WAVES * 64) __attribute__((amdgpu_num_vgpr(CAP_scan_noadj_pad_kernel))) scan_noadj_pad_kernel(SweepArgs A, ScanSplit sp, uint32_t wg0) {
+    scan_kernel_body<T, VPL, RB, false, MOM2, true, PIN_scan_noadj_pad_kernel>(A, sp, wg0);
 }
 
 // ev_start / ev_stop (optional): HIP events attached to the launches themselves (hipExtLaunchKernelGGL) -- they carry the
@@ -1527,20 +1525,34 @@ static void launch_scan_tt(hipStream_t s, const SweepArgs& a, hipEvent_t ev_star
 }
 
 // Rows per wave: uint16 volumes 2 x 512 columns; uint32 volumes 4 x 256 without adjacency (four rows in flight per wave: the
-// moments-only kernel is bound by the stream) and 2 x 256 with it (half the plane state: 95 VGPRs and 31 KB of LDS make five
+// moments-only kernel is bound by the stream) and 2 x 256 with it (half the plane state: its VGPRs -- SCAN_VARIANTS -- and 31 KB of LDS make five
 // waves per SIMD of a kernel that is bound by latency at four -- C4 1.13 -> 1.06 ms, tissue-filled 1.51 -> 1.40 ms at 48-plane tiles).
-// uint32 volumes with adjacency: TA_U32_SHAPE 0 = two rows of 256 columns a wave (four voxels a lane, the 13-register landing
-// zone, 95 VGPRs, five waves per SIMD); 1 = two rows of 512 columns (eight voxels a lane through two 16-byte loads a row, a
-// 25-register zone, 128 VGPRs, four waves): the shape of the uint16 kernel, twice the voxels per plane step of a wave
+// uint32 volumes with adjacency: TA_U32_SHAPE 0 = two rows of 256 columns a wave (four voxels a lane, the TWO_ROWS landing
+// zone, five waves per SIMD); 1 = two rows of 512 columns (eight voxels a lane through two 16-byte loads a row, the
+// WIDE zone, four waves): the shape of the uint16 kernel, twice the voxels per plane step of a wave
 constexpr int RB32_ADJ = 2, RB32_MOM = 4;
 // uint16 volumes with adjacency: 4 voxels a lane like the uint32 kernel (8-byte strips read as the first half of a 16-byte
-// load: the same 13-register landing zone, the same plane state, five waves per SIMD) or 8 (the pre-round-3 shape, 125 VGPRs)
+// load: the same TWO_ROWS landing zone, the same plane state, five waves per SIMD) or 8 (the pre-round-3 shape, four waves)
 constexpr int VPL16_ADJ = TA_U16_VPL;
 constexpr int RB16_MOM = TA_U16_MOM_RB;
 
+// The tile shape of a volume class, derived HERE for the launch, the grid size (which sizes the private hot-label rows:
+// one per workgroup) and the tile height: `f` is called with the TileShape of (item size, adjacency, TA_OPT_SWEEP_SHAPE).
+template <typename T_, int VPL_, int RB_, bool ADJ_>
+struct TileShape { using T = T_; static constexpr int VPL = VPL_, RB = RB_; static constexpr bool ADJ = ADJ_; };
+template <typename F>
+static auto with_tile_shape(int itemsize, bool adjacency, int shape, F&& f) {
+    if (itemsize == 2) return adjacency ? f(TileShape<uint16_t, VPL16_ADJ, 2, true>{}) : f(TileShape<uint16_t, 8, RB16_MOM, false>{});
+    if (!adjacency)    return f(TileShape<uint32_t, 4, RB32_MOM, false>{});
+    return shape ? f(TileShape<uint32_t, 8, RB32_ADJ, true>{}) : f(TileShape<uint32_t, 4, RB32_ADJ, true>{});
+}
+
 uint64_t sweep_grid_size(const SweepArgs& a, int itemsize, bool adjacency) {
-    const ScanSplit sp = itemsize == 2 ? (adjacency ? scan_split<VPL16_ADJ, 2>(a, 2) : scan_split<8, RB16_MOM>(a, 2)) : (adjacency ? (a.shape ? scan_split<8, RB32_ADJ>(a, 4) : scan_split<4, RB32_ADJ>(a, 4)) : scan_split<4, RB32_MOM>(a, 4));
-    return (uint64_t)sp.tiles_c * sp.tiles_b * sp.nbands;
+    return with_tile_shape(itemsize, adjacency, a.shape, [&](auto sh) {
+        using S = decltype(sh);
+        const ScanSplit sp = scan_split<S::VPL, S::RB>(a, (int)sizeof(typename S::T));
+        return (uint64_t)sp.tiles_c * sp.tiles_b * sp.nbands;
+    });
 }
 // measured on C4 / C5 (profiles/r03_ablations.txt, gpurun_out/r3_rb2_tp.txt): shorter tiles = more workgroups to balance over
 // the CUs against more table inits / flushes.  The two-row tiles of uint32 volumes with adjacency cover half the rows, so
@@ -1554,24 +1566,20 @@ int sweep_default_tile_planes(bool adjacency, int itemsize, int shape) { return 
 int sweep_tile_planes_limit() { return MAX_TILE_PLANES; }
 // the tile height a kernel's packed sums are sized for (SumPack; results do not depend on the tile height)
 int sweep_max_tile_planes(bool adjacency, int itemsize, int shape) {
-    const int vpl = adjacency ? (itemsize == 2 ? VPL16_ADJ : (shape ? 8 : 4)) : (itemsize == 2 ? 8 : 4);
-    const int cap = tile_planes_cap(adjacency, itemsize, vpl);
-    return cap < MAX_TILE_PLANES ? cap : MAX_TILE_PLANES;
+    return with_tile_shape(itemsize, adjacency, shape, [](auto sh) {
+        using S = decltype(sh);
+        constexpr int cap = tile_planes_cap(S::ADJ, (int)sizeof(typename S::T), S::VPL);
+        return cap < MAX_TILE_PLANES ? cap : MAX_TILE_PLANES;
+    });
 }
 
 void launch_scan(hipStream_t s, const SweepArgs& a, int itemsize, uint32_t feature_mask, hipEvent_t ev_start, hipEvent_t ev_stop) {
-    const bool adj = feature_mask & 16u, mom2 = feature_mask & 8u;
-    if (itemsize == 2) {
-        if (adj && mom2)       launch_scan_tt<uint16_t, VPL16_ADJ, 2, true, true>(s, a, ev_start, ev_stop);
-        else if (adj)          launch_scan_tt<uint16_t, VPL16_ADJ, 2, true, false>(s, a, ev_start, ev_stop);
-        else if (mom2)         launch_scan_tt<uint16_t, 8, RB16_MOM, false, true>(s, a, ev_start, ev_stop);
-        else                   launch_scan_tt<uint16_t, 8, RB16_MOM, false, false>(s, a, ev_start, ev_stop);
-    } else {
-        if (adj && mom2)       { if (a.shape) launch_scan_tt<uint32_t, 8, RB32_ADJ, true, true>(s, a, ev_start, ev_stop); else launch_scan_tt<uint32_t, 4, RB32_ADJ, true, true>(s, a, ev_start, ev_stop); }
-        else if (adj)          { if (a.shape) launch_scan_tt<uint32_t, 8, RB32_ADJ, true, false>(s, a, ev_start, ev_stop); else launch_scan_tt<uint32_t, 4, RB32_ADJ, true, false>(s, a, ev_start, ev_stop); }
-        else if (mom2)         launch_scan_tt<uint32_t, 4, RB32_MOM, false, true>(s, a, ev_start, ev_stop);
-        else                   launch_scan_tt<uint32_t, 4, RB32_MOM, false, false>(s, a, ev_start, ev_stop);
-    }
+    const bool mom2 = feature_mask & 8u;
+    with_tile_shape(itemsize, feature_mask & 16u, a.shape, [&](auto sh) {
+        using S = decltype(sh);
+        if (mom2) launch_scan_tt<typename S::T, S::VPL, S::RB, S::ADJ, true>(s, a, ev_start, ev_stop);
+        else      launch_scan_tt<typename S::T, S::VPL, S::RB, S::ADJ, false>(s, a, ev_start, ev_stop);
+    });
 }
 
 }  // namespace ta
