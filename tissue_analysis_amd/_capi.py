@@ -78,6 +78,12 @@ DISTANCE_SYMBOLS = ("ta_distance_extract", "ta_distance_get", "ta_distance_image
 DIST_OWN_WALL, DIST_FROM_LABEL = 0, 1  # TA_DIST_OWN_WALL / TA_DIST_FROM_LABEL
 DIST_EDGE_IS_SITE = 1                  # TA_DIST_EDGE_IS_SITE
 
+# every symbol include/tissue_scan_profile.h declares (same library)
+PROFILE_SYMBOLS = ("ta_profile_extract", "ta_profile_get", "ta_profile_debug", "ta_profile_timing")
+PROF_SIGNAL = 1                        # TA_PROF_SIGNAL
+PROFILE_MAX_BINS = 64                  # TA_PROF_MAX_BINS
+PROFILE_SLOTS = 1024                   # PROF_SLOTS of csrc/ta_profile.h: slots of a workgroup's LDS table
+
 
 def exchange_words(capacity_pairs):
     """uint64 words of one exchange block (TA_EXCHANGE_WORDS in include/tissue_scan.h)."""
@@ -210,9 +216,13 @@ def load():
         "ta_distance_image": (ci, [vp, i64, i64, vp]),
         "ta_distance_timing": (ci, [vp, P(ctypes.c_double), P(ctypes.c_double)]),
         "ta_distance_set_batch": (ci, [vp, i64]),
+        "ta_profile_extract": (ci, [vp, ci, P(ctypes.c_double), u32]),
+        "ta_profile_get": (ci, [vp, vp, vp, vp, vp, vp]),
+        "ta_profile_debug": (ci, [vp, P(u32)]),
+        "ta_profile_timing": (ci, [vp, P(ctypes.c_double)]),
     }
     for name in (SYMBOLS + SIGNAL_SYMBOLS + MESH_SYMBOLS + OVERLAP_SYMBOLS + JUNCTION_SYMBOLS + WALLGEO_SYMBOLS + COMPONENT_SYMBOLS
-                 + DISTANCE_SYMBOLS):
+                 + DISTANCE_SYMBOLS + PROFILE_SYMBOLS):
         fn = getattr(lib, name)      # AttributeError here == the .so does not match the header
         fn.restype, fn.argtypes = sig[name]
     if lib.ta_version() != ABI_VERSION:
@@ -720,6 +730,40 @@ class Context(object):
     def distance_set_batch(self, columns=0):
         """Columns a launch of a column pass takes (0 = automatic); the results do not depend on it."""
         _check(self._lib.ta_distance_set_batch(self._h, int(columns)))
+
+    # -- distance-shell profiles (include/tissue_scan_profile.h)
+    def profile_extract(self, edges2, signal=False):
+        """Enqueue the profile pass over the current distance map: edges2 = K + 1 ascending SQUARED distances (float64); with
+        `signal` also the statistics of the signal image of the context."""
+        e = np.ascontiguousarray(edges2, dtype=np.float64).reshape(-1)
+        _check(self._lib.ta_profile_extract(self._h, int(e.size) - 1, e.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                                            PROF_SIGNAL if signal else 0))
+        self._profile_shape = (self._max_label + 1, int(e.size) - 1, bool(signal))
+
+    def profile_get(self):
+        """(n u64[R, K], sum u64[R, K], sumsq u64[R, K, 2] (lo, hi words), min u32[R, K], max u32[R, K]), rows as labels(); the
+        four signal columns are None for a pass without signal."""
+        R, K, signal = getattr(self, "_profile_shape", (1, 1, False))        # (no pass yet: the library answers TA_EINVAL)
+        n = np.zeros((R, K), dtype=np.uint64)
+        if not signal:
+            _check(self._lib.ta_profile_get(self._h, n.ctypes.data, None, None, None, None))
+            return n, None, None, None, None
+        s, q = np.zeros((R, K), dtype=np.uint64), np.zeros((R, K, 2), dtype=np.uint64)
+        mn, mx = np.zeros((R, K), dtype=np.uint32), np.zeros((R, K), dtype=np.uint32)
+        _check(self._lib.ta_profile_get(self._h, n.ctypes.data, s.ctypes.data, q.ctypes.data, mn.ctypes.data, mx.ctypes.data))
+        return n, s, q, mn, mx
+
+    def profile_debug(self):
+        """Diagnostics of the last profile pass: records that missed a workgroup's LDS table (spills) and the launch plan
+        (tiles_per_group, groups)."""
+        out = (ctypes.c_uint32 * 4)()
+        _check(self._lib.ta_profile_debug(self._h, out))
+        return dict(spills=int(out[0]), tiles_per_group=int(out[2]), groups=int(out[3]))
+
+    def profile_timing(self):
+        ms = ctypes.c_double(0.0)
+        _check(self._lib.ta_profile_timing(self._h, ctypes.byref(ms)))
+        return ms.value
 
     def max_label(self):
         v = ctypes.c_uint32(0)

@@ -62,6 +62,7 @@ TA_API int ta_distance_extract(ta_ctx* c, int mode, uint32_t site_label, const d
     if (!c->extracted) return fail(TA_EINVAL, "the distance pass needs a ta_extract of the current volume first");
     if ((rc = finish_extract(c)) != TA_OK) return rc;
     c->dist.seq = 0;
+    profile_on_new_distance(c);
     const uint64_t nvox = voxels(c), R = (uint64_t)c->max_label + 1;
     const DistanceLayout L(R);
 

@@ -179,6 +179,18 @@ struct DistanceState {
     void release() { d2.release(); work.release(); table.release(); destroy_events(ev); }
 };
 
+// distance-shell profiles (include/tissue_scan_profile.h)
+struct ProfileState {
+    DevBuf out;                                         // flags u32[4] | edges f64[65] | n u64[R][K] | with a signal: sum | sumsq[2] | min u32 | max u32
+    double edges[65] = {0.0};                           // what the last pass's edges were copied to the device from: edges2[0 .. K], +inf behind
+    uint64_t seq = 0;                                   // extract_seq of the extraction (and of the distance map) the table belongs to, 0 = none
+    uint32_t rows = 0, bins = 0;                        // R = max_label + 1 of that extraction, K
+    bool with_signal = false;                           // the pass read the signal: a new signal makes the table stale
+    ta::RangePlan plan;                                 // what the last pass was launched with (ta_profile_debug)
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    void release() { out.release(); destroy_events(ev); }
+};
+
 // wall voxels and wall medians (ta_api_walls.hip)
 struct WallVoxelState {
     DevBuf counts;                                      // per-chunk record counts, then offsets
@@ -290,6 +302,7 @@ struct ta_ctx {
     WallGeoState wg;
     ComponentState cc;
     DistanceState dist;
+    ProfileState prof;
 };
 
 inline int use_device(ta_ctx* c) {
@@ -317,7 +330,7 @@ inline ta::PairTable pair_table(ta_ctx* c) {
 // Drain the stream and validate the flags of the last pass; grows the adjacency table and re-runs when it overflowed.  ta_api.hip.
 int finish_extract(ta_ctx* c);
 
-// A new label volume (for the sparse ids, the overlap, the junctions, the components and the distance maps also: new label values in it).  Defined by
+// A new label volume (for the sparse ids, the overlap, the junctions, the components, the distance maps and their profiles also: new label values in it).  Defined by
 // the file of each concern, called by the core's volume_replaced / volume_labels_changed (the junctions' and the components' also by
 // ta_volume_rerank: the caller edited the labels in place).
 void walls_on_new_volume(ta_ctx* c);
@@ -328,6 +341,9 @@ void junctions_on_new_volume(ta_ctx* c);
 void wallgeo_on_new_volume(ta_ctx* c);
 void components_on_new_volume(ta_ctx* c);
 void distance_on_new_volume(ta_ctx* c);
+void profile_on_new_volume(ta_ctx* c);
+void profile_on_new_distance(ta_ctx* c);              // a new ta_distance_extract: the image the table was read from is gone.  ta_api_profile.hip
+void profile_on_new_signal(ta_ctx* c);                // a new signal image: stale when the pass read the old one.  ta_api_profile.hip
 void walls_on_new_labels(ta_ctx* c);                  // new label values in the same volume: the staging buffer is kept.  ta_api_walls.hip
 
 // The two ways the voxels change (ta_api.hip).  volume_replaced: the tail of ta_volume_set / ta_volume_set_device, called once vol,

@@ -29,7 +29,7 @@ class DistanceMap(object):
     """
 
     def __init__(self, labels, min2, max2, pole, voxelsize=(1.0, 1.0, 1.0), mode=OWN_WALL, ms=None, site_label=None, edge=False,
-                 image=None):
+                 image=None, profile=None):
         self.labels = np.asarray(labels).astype(np.int64).reshape(-1)
         R = self.labels.size
         self.min2 = np.asarray(min2, dtype=np.float64).reshape(-1)
@@ -57,6 +57,7 @@ class DistanceMap(object):
         self.edge = bool(edge)
         self.ms = ms
         self._image = image                # callable: the float64 image of SQUARED distances, shaped like the label image
+        self._profile = profile            # callable (edges, signal): the ShellProfile of the image over shells of distance
 
     def __len__(self):
         return int(self.labels.size)
@@ -125,6 +126,16 @@ class DistanceMap(object):
             raise ValueError("this distance table was built on the host: it has no image")
         return np.sqrt(self._image())
 
+    def profile(self, edges, signal=None):
+        """The `ShellProfile` of this map over the shells between `edges` (distances in real units, strictly ascending from >= 0,
+        64 shells at most; the last may be inf): per label and shell the voxels and, with `signal` (uint8 / uint16, the image's
+        shape), its sum, sum of squares and extremes.  One pass over labels, distances and signal on the device: only for a map
+        that came from one, and only while the volume it was made from is still swept as it was (the distance pass runs again
+        when a later map has taken its image's place)."""
+        if self._profile is None:
+            raise ValueError("this distance table was built on the host: it has no image to profile")
+        return self._profile(edges, signal)
+
 
 def resident_distance_map(resident, mode=OWN_WALL, site_label=None, voxelsize=(1.0, 1.0, 1.0), edge=False):
     """The distance pass over the volume resident in `resident` (a ResidentVolume), with the rows of its current extraction --
@@ -155,17 +166,30 @@ def resident_distance_map(resident, mode=OWN_WALL, site_label=None, voxelsize=(1
     labels = x.ids if x.sparse else np.arange(x.nrows, dtype=np.int64)
     run = [_next_run(resident)]
 
-    def image():
+    def held():
         # the context keeps ONE image: the pass runs again when a later distance map has taken its place
         if resident.ctx is None or resident.last is not x:
             raise RuntimeError("the volume was swept again since this distance map was made: its image is gone")
         if resident._distance_run != run[0]:
             resident.ctx.distance_extract(mode, site, vs, flags)
             run[0] = _next_run(resident)
+
+    def image():
+        held()
         return resident.distance_image()
 
+    def profile(edges, signal=None):
+        from .shell_profile import ShellProfile
+        held()
+        e = np.asarray(edges, dtype=np.float64).reshape(-1)
+        if signal is not None:
+            resident.ctx.set_signal(np.asarray(signal))
+        resident.ctx.profile_extract(np.square(e), signal is not None)
+        n, s, q, mn, mx = resident.ctx.profile_get()
+        return ShellProfile(labels, e, n, s, q, mn, mx, vs, present=pole[:, 0] >= 0, ms=resident.ctx.profile_timing())
+
     return DistanceMap(labels, min2, max2, pole, vs, mode, ms=ctx.distance_timing(), site_label=site_label if mode == FROM_LABEL else None,
-                       edge=edge, image=image)
+                       edge=edge, image=image, profile=profile)
 
 
 def _next_run(resident):
@@ -185,7 +209,7 @@ def distance_map(image, mode=OWN_WALL, site_label=None, edge=False, device=0):
     try:
         dm = rv.distance_map(mode, site_label, voxelsize, edge)
         img = dm.image().reshape(a.shape)
-        dm._image = None
+        dm._image = dm._profile = None
         return dm, img
     finally:
         rv.close()

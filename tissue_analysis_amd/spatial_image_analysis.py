@@ -679,6 +679,41 @@ class AbstractSpatialImageAnalysis(object):
         labels = self.label_request(labels)
         return self.convert_return(self.distance_from(real=real).of_labels(labels, "min2"), labels)
 
+    # -- distance-shell profiles (include/tissue_scan_profile.h; one pass over labels, distances and signal on the GPU)
+    def _shell_profile(self, edges, signal, from_label, edge_is_wall, real=True):
+        dm = self.wall_distance(edge_is_wall, real) if from_label is None else self.distance_from(from_label, edge_is_wall, real)
+        return dm.profile(edges, signal)
+
+    def shell_volumes(self, edges, labels=None, real=True, from_label=None, edge_is_wall=False):
+        """Per label the volumes of its shells of distance: entry k is the volume of the label's voxels whose distance to the
+        cell's own wall (`from_label`: to the nearest voxel of that label) lies in [edges[k], edges[k + 1]); `edges` ascend
+        strictly from >= 0 (64 shells at most, the last edge may be inf), in real units and the volumes too, or both in voxels
+        with real=False.  One (K,) array per label, returned like volume()."""
+        labels = self.label_request(labels)
+        prof = self._shell_profile(edges, None, from_label, edge_is_wall, real)
+        unit = float(np.prod(prof.voxelsize))
+        values = self._shell_rows(prof, prof.n.astype(np.float64) * unit, labels, 0.0)
+        return self.convert_return(values, labels)
+
+    def signal_profile(self, signal, edges, labels=None, statistic='mean', from_label=None, edge_is_wall=False):
+        """Per label the `statistic` ('mean', 'std', 'min', 'max', 'sum', or 'fraction': the shell's share of the label's counted
+        signal) of the intensity image `signal` (uint8 / uint16, the image's shape) in every shell of distance, the shells as in
+        shell_volumes() with distances in real units.  One (K,) array per label, returned like cell_signal()."""
+        methods = dict(mean="mean", std="std", min="minimum", max="maximum", sum="total", fraction="fraction")
+        if statistic not in methods:
+            raise ValueError("statistic must be one of %s, not %r" % ("|".join(methods), statistic))
+        labels = self.label_request(labels)
+        prof = self._shell_profile(edges, signal, from_label, edge_is_wall)
+        by_label = getattr(prof, methods[statistic])(labels=labels)
+        empty = np.zeros(prof.shells, dtype=np.uint64) if statistic == "sum" else np.full(prof.shells, np.nan)
+        values = [by_label.get(int(l), empty) for l in labels]
+        return self.convert_return(values, labels)
+
+    @staticmethod
+    def _shell_rows(prof, column, labels, missing):
+        rows = prof.rows_of(labels)
+        return [column[r] if r >= 0 else np.full(prof.shells, missing) for r in rows.tolist()]
+
     def _current_components(self):
         """`label_components()`, run again when the context no longer holds the tables it was read from."""
         cc = self.label_components()
