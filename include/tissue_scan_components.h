@@ -70,6 +70,11 @@ TA_API int ta_components_image(ta_ctx* ctx, int64_t first_plane, int64_t nplanes
  * these tables.  TA_EINVAL when nrows is not the table's row count, TA_ERANGE when a value does not fit the volume's item size:
  * both before the volume is touched. */
 TA_API int ta_components_relabel(ta_ctx* ctx, const uint32_t* new_label, uint64_t nrows);
+/* Diagnostics for tests: what the last pass launched.  out[0] the tiles (= workgroups) of the local pass, out[1] the workgroups
+ * of the seam pass, out[2] the workgroups of the last ta_components_image or ta_components_relabel launch since the extract (0 if
+ * none), out[3] the workgroups of the kernel that writes the sort keys.  Fewer workgroups than rows (seam pass) or than 256-item
+ * chunks (the others) means that the kernel strode over its work.  Synchronises and settles; TA_EINVAL as the getters above. */
+TA_API int ta_components_debug(ta_ctx* ctx, uint32_t out[4]);
 /* Milliseconds between HIP events.  ms_pass: the kernels that walk the volume (local pass, seams, flatten and count, emit,
  * statistics).  ms_after: everything else on the device, from the scan of the counts to the sorted table (it spans the host's
  * read of the slot count).  Settled tables only (ask ta_components_size first), else TA_EINVAL; either pointer may be NULL. */

@@ -66,6 +66,11 @@ TA_API int ta_distance_image(ta_ctx* ctx, int64_t first_plane, int64_t nplanes, 
 /* Milliseconds between HIP events.  ms_pass: the row pass and the two column passes.  ms_after: the two table passes.  Either
  * pointer may be NULL. */
 TA_API int ta_distance_timing(ta_ctx* ctx, double* ms_pass, double* ms_after);
+/* Diagnostics for tests: what the last ta_distance_extract launched.  out[0] the workgroups of the row pass (four rows each at a
+ * time), out[1] those of the extremes and of the pole kernel (256 voxels each at a time), out[2] those of the table initialisation
+ * (256 rows each at a time), out[3] the launches of the column kernel, both axes together.  Fewer workgroups than work means that
+ * the kernel strode over it.  TA_EINVAL as the getters above. */
+TA_API int ta_distance_debug(ta_ctx* ctx, uint32_t out[4]);
 /* Columns a launch of a column pass takes (tuning and tests): 0 = automatic (what fits the work buffer's cap), else rounded up to
  * whole waves of 64.  The results do not depend on it. */
 TA_API int ta_distance_set_batch(ta_ctx* ctx, int64_t columns);

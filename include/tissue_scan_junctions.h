@@ -49,6 +49,10 @@ TA_API int ta_junctions_size(ta_ctx* ctx, uint64_t* nedges, uint64_t* nvertices,
 TA_API int ta_junctions_get_edges(ta_ctx* ctx, uint32_t* labels, uint64_t* n, uint64_t* sums);
 /* The vertex table: labels [nvertices][4], n [nvertices], sums [nvertices][3]. */
 TA_API int ta_junctions_get_vertices(ta_ctx* ctx, uint32_t* labels, uint64_t* n, uint64_t* sums);
+/* Diagnostics for tests: what the last pass launched.  out[0] the tasks of a walk (one wave each), out[1] and out[2] the
+ * workgroups of the kernel that writes the sort keys of the edge and of the vertex records (0 without records; fewer than
+ * records / 256 means that it strode over them), out[3] 0.  Synchronises and settles; TA_EINVAL as the getters above. */
+TA_API int ta_junctions_debug(ta_ctx* ctx, uint32_t out[4]);
 /* Milliseconds between HIP events.  ms_pass: the two walks over the volume (counting and emitting).  ms_after: everything else
  * on the device, from the scans of the counts to the finished tables (it spans the host's read of the row counts).  Settled
  * tables only (ask ta_junctions_size first), else TA_EINVAL; either pointer may be NULL. */

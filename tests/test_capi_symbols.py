@@ -26,6 +26,24 @@ def test_library_exports_every_declared_symbol():
     assert lib.ta_version() == _capi.ABI_VERSION == 5
 
 
+@pytest.mark.parametrize("header,symbols,count", [
+    ("tissue_scan_components.h", _capi.COMPONENT_SYMBOLS, 7),
+    ("tissue_scan_junctions.h", _capi.JUNCTION_SYMBOLS, 6),
+    ("tissue_scan_distance.h", _capi.DISTANCE_SYMBOLS, 6),
+])
+def test_feature_headers_and_binding_agree(header, symbols, count):
+    text = open(os.path.join(ROOT, "include", header)).read()
+    declared = sorted(set(re.findall(r"TA_API\s+int\s+(ta_\w+)\s*\(", text)))
+    assert declared == sorted(symbols) and len(declared) == count
+    assert not set(symbols) & set(_capi.SYMBOLS)
+    debug = [name for name in declared if name.endswith("_debug")]
+    assert len(debug) == 1 and re.search(r"TA_API\s+int\s+%s\s*\(ta_ctx\*\s*ctx,\s*uint32_t\s+out\[4\]\)" % debug[0], text)
+    lib = _capi.load()
+    for name in declared:
+        assert hasattr(lib, name), name
+        assert getattr(lib, name).argtypes is not None, name
+
+
 def test_bad_arguments_are_rejected_without_a_gpu():
     lib = _capi.load()
     assert lib.ta_ctx_destroy(None) == _capi.TA_OK

@@ -169,4 +169,5 @@ def test_null_context_is_rejected_without_a_gpu():
     assert lib.ta_components_image(None, 0, 0, None) == _capi.TA_EINVAL
     assert lib.ta_components_relabel(None, None, 0) == _capi.TA_EINVAL
     assert lib.ta_components_timing(None, None, None) == _capi.TA_EINVAL
+    assert lib.ta_components_debug(None, None) == _capi.TA_EINVAL
     assert lib.ta_version() == 5

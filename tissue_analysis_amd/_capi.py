@@ -60,6 +60,7 @@ OVERLAP_SYMBOLS = (
 # every symbol include/tissue_scan_junctions.h declares (same library)
 JUNCTION_SYMBOLS = (
     "ta_junctions_extract", "ta_junctions_size", "ta_junctions_get_edges", "ta_junctions_get_vertices", "ta_junctions_timing",
+    "ta_junctions_debug",
 )
 
 # every symbol include/tissue_scan_wallgeo.h declares (same library)
@@ -68,13 +69,14 @@ WALLGEO_SYMBOLS = ("ta_wallgeo_extract", "ta_wallgeo_get", "ta_wallgeo_spills", 
 # every symbol include/tissue_scan_components.h declares (same library)
 COMPONENT_SYMBOLS = (
     "ta_components_extract", "ta_components_size", "ta_components_get", "ta_components_image", "ta_components_relabel",
-    "ta_components_timing",
+    "ta_components_timing", "ta_components_debug",
 )
 COMPONENT_NONE = 0xFFFFFFFF            # TA_COMPONENT_NONE
 COMPONENT_MAX_VOXELS = 1 << 31         # voxels of a buffer the component pass takes
 
 # every symbol include/tissue_scan_distance.h declares (same library)
-DISTANCE_SYMBOLS = ("ta_distance_extract", "ta_distance_get", "ta_distance_image", "ta_distance_timing", "ta_distance_set_batch")
+DISTANCE_SYMBOLS = ("ta_distance_extract", "ta_distance_get", "ta_distance_image", "ta_distance_timing", "ta_distance_set_batch",
+                    "ta_distance_debug")
 DIST_OWN_WALL, DIST_FROM_LABEL = 0, 1  # TA_DIST_OWN_WALL / TA_DIST_FROM_LABEL
 DIST_EDGE_IS_SITE = 1                  # TA_DIST_EDGE_IS_SITE
 
@@ -200,6 +202,7 @@ def load():
         "ta_junctions_get_edges": (ci, [vp, vp, vp, vp]),
         "ta_junctions_get_vertices": (ci, [vp, vp, vp, vp]),
         "ta_junctions_timing": (ci, [vp, P(ctypes.c_double), P(ctypes.c_double)]),
+        "ta_junctions_debug": (ci, [vp, P(u32)]),
         "ta_wallgeo_extract": (ci, [vp]),
         "ta_wallgeo_get": (ci, [vp, vp, vp, vp, vp]),
         "ta_wallgeo_spills": (ci, [vp, P(u32)]),
@@ -211,11 +214,13 @@ def load():
         "ta_components_image": (ci, [vp, i64, i64, vp]),
         "ta_components_relabel": (ci, [vp, vp, u64]),
         "ta_components_timing": (ci, [vp, P(ctypes.c_double), P(ctypes.c_double)]),
+        "ta_components_debug": (ci, [vp, P(u32)]),
         "ta_distance_extract": (ci, [vp, ci, u32, P(ctypes.c_double), u32]),
         "ta_distance_get": (ci, [vp, vp, vp, vp]),
         "ta_distance_image": (ci, [vp, i64, i64, vp]),
         "ta_distance_timing": (ci, [vp, P(ctypes.c_double), P(ctypes.c_double)]),
         "ta_distance_set_batch": (ci, [vp, i64]),
+        "ta_distance_debug": (ci, [vp, P(u32)]),
         "ta_profile_extract": (ci, [vp, ci, P(ctypes.c_double), u32]),
         "ta_profile_get": (ci, [vp, vp, vp, vp, vp, vp]),
         "ta_profile_debug": (ci, [vp, P(u32)]),
@@ -620,6 +625,13 @@ class Context(object):
         _check(self._lib.ta_junctions_timing(self._h, ctypes.byref(a), ctypes.byref(b)))
         return a.value, b.value
 
+    def junctions_debug(self):
+        """What the last pass launched: the tasks of a walk, and the workgroups of the kernel that writes the sort keys of the edge
+        and of the vertex records (0 without records).  Settles the tables."""
+        out = (ctypes.c_uint32 * 4)()
+        _check(self._lib.ta_junctions_debug(self._h, out))
+        return dict(tasks=int(out[0]), edge_key_groups=int(out[1]), vertex_key_groups=int(out[2]))
+
     # -- wall geometry (include/tissue_scan_wallgeo.h)
     def wallgeo_extract(self):
         """Enqueue the wall-geometry pass over the current extraction (which needs its adjacency)."""
@@ -693,6 +705,13 @@ class Context(object):
         _check(self._lib.ta_components_timing(self._h, ctypes.byref(a), ctypes.byref(b)))
         return a.value, b.value
 
+    def components_debug(self):
+        """What the last pass launched: the tiles of the local pass, the workgroups of the seam pass, of the last image or relabel
+        launch since the extract (0 if none) and of the key kernel.  Settles the table."""
+        out = (ctypes.c_uint32 * 4)()
+        _check(self._lib.ta_components_debug(self._h, out))
+        return dict(tiles=int(out[0]), seam_groups=int(out[1]), stream_groups=int(out[2]), key_groups=int(out[3]))
+
     # -- distance maps (include/tissue_scan_distance.h)
     def distance_extract(self, mode=DIST_OWN_WALL, site_label=0, spacing=(1.0, 1.0, 1.0), flags=0):
         """Enqueue the three passes of the exact squared distance transform over the current extraction, and its table.  spacing
@@ -730,6 +749,13 @@ class Context(object):
     def distance_set_batch(self, columns=0):
         """Columns a launch of a column pass takes (0 = automatic); the results do not depend on it."""
         _check(self._lib.ta_distance_set_batch(self._h, int(columns)))
+
+    def distance_debug(self):
+        """What the last distance_extract launched: the workgroups of the row pass, of the extremes and pole kernels and of the
+        table initialisation, and the launches of the column kernel along both axes together."""
+        out = (ctypes.c_uint32 * 4)()
+        _check(self._lib.ta_distance_debug(self._h, out))
+        return dict(row_groups=int(out[0]), voxel_groups=int(out[1]), init_groups=int(out[2]), column_launches=int(out[3]))
 
     # -- distance-shell profiles (include/tissue_scan_profile.h)
     def profile_extract(self, edges2, signal=False):

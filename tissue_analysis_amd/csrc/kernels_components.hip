@@ -572,7 +572,7 @@ __global__ __launch_bounds__(256) void component_relabel_kernel(const uint32_t* 
     }
 }
 
-unsigned grid_for(uint64_t n) { return (unsigned)std::min<uint64_t>(std::max<uint64_t>((n + 255) / 256, 1), 65536); }
+unsigned grid_for(uint64_t n) { return (unsigned)std::min<uint64_t>(std::max<uint64_t>((n + 255) / 256, 1), CC_STREAM_MAX_GROUPS); }
 
 }  // namespace
 
@@ -596,12 +596,13 @@ void launch_component_local(hipStream_t s, const ComponentArgs& a, int itemsize)
     }
 }
 
-void launch_component_seams(hipStream_t s, const ComponentArgs& a, int itemsize) {
+uint32_t launch_component_seams(hipStream_t s, const ComponentArgs& a, int itemsize) {
     const uint64_t rows = (uint64_t)a.n0 * (uint64_t)a.n1;
-    if (!rows) return;
-    const dim3 grid((unsigned)std::min<uint64_t>(rows, 1u << 18)), block(CC_THREADS);
+    if (!rows) return 0u;
+    const dim3 grid((unsigned)std::min<uint64_t>(rows, CC_SEAM_MAX_GROUPS)), block(CC_THREADS);
     if (itemsize == 2) hipLaunchKernelGGL(component_seam_kernel<uint16_t>, grid, block, 0, s, a);
     else hipLaunchKernelGGL(component_seam_kernel<uint32_t>, grid, block, 0, s, a);
+    return grid.x;
 }
 
 void launch_component_flatten(hipStream_t s, uint32_t* parent, uint64_t nvox, int64_t n1, int64_t n2, uint32_t* wave_counts) {
@@ -623,11 +624,12 @@ void launch_component_stats(hipStream_t s, const uint32_t* parent, const Compone
     hipLaunchKernelGGL(component_stats_kernel, dim3((unsigned)((g.nvox + per_group - 1) / per_group)), dim3(CC_THREADS), 0, s, parent, g, t);
 }
 
-void launch_component_keys(hipStream_t s, const void* vol, int itemsize, const uint32_t* root_of_slot, const ComponentStats& t, uint64_t nslots,
-                           uint64_t* keys_out, uint32_t* index_out, unsigned long long* nonempty) {
-    if (!nslots) return;
+uint32_t launch_component_keys(hipStream_t s, const void* vol, int itemsize, const uint32_t* root_of_slot, const ComponentStats& t, uint64_t nslots,
+                               uint64_t* keys_out, uint32_t* index_out, unsigned long long* nonempty) {
+    if (!nslots) return 0u;
     hipLaunchKernelGGL(component_keys_kernel, dim3(grid_for(nslots)), dim3(256), 0, s, vol, itemsize, root_of_slot, t, nslots, keys_out, index_out,
                        nonempty);
+    return grid_for(nslots);
 }
 
 void launch_component_rows(hipStream_t s, const void* vol, int itemsize, const uint32_t* root_of_slot, const ComponentStats& t,
@@ -638,16 +640,18 @@ void launch_component_rows(hipStream_t s, const void* vol, int itemsize, const u
                        row_of_slot, rows);
 }
 
-void launch_component_image(hipStream_t s, const uint32_t* parent, const uint32_t* row_of_slot, uint64_t first, uint64_t count, uint32_t* rows_out) {
-    if (!count) return;
+uint32_t launch_component_image(hipStream_t s, const uint32_t* parent, const uint32_t* row_of_slot, uint64_t first, uint64_t count, uint32_t* rows_out) {
+    if (!count) return 0u;
     hipLaunchKernelGGL(component_image_kernel, dim3(grid_for(count)), dim3(256), 0, s, parent, row_of_slot, first, count, rows_out);
+    return grid_for(count);
 }
 
-void launch_component_relabel(hipStream_t s, const uint32_t* parent, const uint32_t* row_of_slot, uint64_t nvox, const uint32_t* new_label,
-                              void* vol, int itemsize) {
-    if (!nvox) return;
+uint32_t launch_component_relabel(hipStream_t s, const uint32_t* parent, const uint32_t* row_of_slot, uint64_t nvox, const uint32_t* new_label,
+                                  void* vol, int itemsize) {
+    if (!nvox) return 0u;
     if (itemsize == 2) hipLaunchKernelGGL(component_relabel_kernel<uint16_t>, dim3(grid_for(nvox)), dim3(256), 0, s, parent, row_of_slot, nvox, new_label, (uint16_t*)vol);
     else hipLaunchKernelGGL(component_relabel_kernel<uint32_t>, dim3(grid_for(nvox)), dim3(256), 0, s, parent, row_of_slot, nvox, new_label, (uint32_t*)vol);
+    return grid_for(nvox);
 }
 
 }  // namespace ta

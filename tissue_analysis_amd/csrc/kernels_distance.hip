@@ -202,11 +202,12 @@ uint32_t blocks_for(uint64_t threads, uint32_t cap) {
 
 }  // namespace
 
-void launch_distance_rows(hipStream_t s, const DistanceArgs& a, int itemsize) {
+uint32_t launch_distance_rows(hipStream_t s, const DistanceArgs& a, int itemsize) {
     const uint64_t rows = (uint64_t)a.n0 * (uint64_t)a.n1;
-    const uint32_t grid = blocks_for(rows * 64, 1u << 16);
+    const uint32_t grid = blocks_for(rows * 64, DIST_ROW_MAX_GROUPS);
     if (itemsize == 2) hipLaunchKernelGGL(distance_row_kernel<uint16_t>, dim3(grid), dim3(256), 0, s, a);
     else hipLaunchKernelGGL(distance_row_kernel<uint32_t>, dim3(grid), dim3(256), 0, s, a);
+    return grid;
 }
 
 uint64_t distance_columns(const DistanceArgs& a, int axis) {
@@ -233,10 +234,12 @@ void launch_distance_columns(hipStream_t s, const DistanceArgs& a, int itemsize,
                            columns, sv, sf, sz, stride);
 }
 
-void launch_distance_table(hipStream_t s, const DistanceArgs& a, int itemsize, const DistanceTable& t) {
+void launch_distance_table(hipStream_t s, const DistanceArgs& a, int itemsize, const DistanceTable& t, DistanceLaunch& launched) {
     const uint64_t nvox = (uint64_t)a.n0 * (uint64_t)a.n1 * (uint64_t)a.n2;
-    const uint32_t grid = blocks_for(nvox, 1u << 14);
-    hipLaunchKernelGGL(distance_table_init_kernel, dim3(blocks_for((uint64_t)t.max_label + 1, 1u << 12)), dim3(256), 0, s, t);
+    const uint32_t grid = blocks_for(nvox, DIST_VOXEL_MAX_GROUPS), init = blocks_for((uint64_t)t.max_label + 1, DIST_INIT_MAX_GROUPS);
+    launched.voxel_groups = grid;
+    launched.init_groups = init;
+    hipLaunchKernelGGL(distance_table_init_kernel, dim3(init), dim3(256), 0, s, t);
     if (itemsize == 2) {
         hipLaunchKernelGGL(distance_extremes_kernel<uint16_t>, dim3(grid), dim3(256), 0, s, a, t, nvox);
         hipLaunchKernelGGL(distance_pole_kernel<uint16_t>, dim3(grid), dim3(256), 0, s, a, t, nvox);

@@ -316,7 +316,7 @@ void launch_pass_type(hipStream_t s, const JunctionArgs& a, bool vec, bool emit,
     else hipLaunchKernelGGL((junction_pass_kernel<E, false, false>), dim3(groups), dim3(JN_THREADS), 0, s, a);
 }
 
-unsigned grid_for(uint64_t n) { return (unsigned)std::min<uint64_t>(std::max<uint64_t>((n + 255) / 256, 1), 8192); }
+unsigned grid_for(uint64_t n) { return (unsigned)std::min<uint64_t>(std::max<uint64_t>((n + 255) / 256, 1), JN_KEY_MAX_GROUPS); }
 
 }  // namespace
 
@@ -340,11 +340,12 @@ void launch_junction_pass(hipStream_t s, const JunctionArgs& a, int itemsize, bo
     else launch_pass_type<uint32_t>(s, a, vec, emit, groups);
 }
 
-void launch_junction_keys(hipStream_t s, const uint32_t* labels, int K, uint64_t n, const uint32_t* order, int col_hi, int col_lo,
-                          int label_bits, uint64_t* keys_out, uint32_t* index_out) {
-    if (!n) return;
+uint32_t launch_junction_keys(hipStream_t s, const uint32_t* labels, int K, uint64_t n, const uint32_t* order, int col_hi, int col_lo,
+                              int label_bits, uint64_t* keys_out, uint32_t* index_out) {
+    if (!n) return 0u;
     hipLaunchKernelGGL(junction_keys_kernel, dim3(grid_for(n)), dim3(256), 0, s, labels, K, n, order, col_hi, col_lo, label_bits, keys_out,
                        index_out);
+    return grid_for(n);
 }
 
 void launch_junction_heads(hipStream_t s, const uint32_t* labels, int K, const uint32_t* order, uint64_t n, uint32_t* block_counts) {

@@ -108,7 +108,7 @@ int components_settle(ta_ctx* c) {
     char* op = (char*)c->cc.sort.p;
     uint64_t* k0 = (uint64_t*)(op + sl.keys[0]); uint64_t* k1 = (uint64_t*)(op + sl.keys[1]);
     uint32_t* i0 = (uint32_t*)(op + sl.idx[0]); uint32_t* i1 = (uint32_t*)(op + sl.idx[1]);
-    ta::launch_component_keys(c->stream, c->vol, c->itemsize, root_of_slot, stats, S, k0, i0, nonempty);
+    c->cc.launched[3] = ta::launch_component_keys(c->stream, c->vol, c->itemsize, root_of_slot, stats, S, k0, i0, nonempty);
     uint64_t* ks = k0; uint32_t* is = i0;
     TA_HIP(ta::launch_radix_sort_u64(c->stream, S, k0, k1, i0, i1, op + sl.temp, 64, &ks, &is));
     char* tp = (char*)c->cc.rows.p;
@@ -166,7 +166,9 @@ TA_API int ta_components_extract(ta_ctx* c) {
     char* wp = (char*)c->cc.work.p;
     TA_HIP(hipEventRecord(c->cc.ev[0], c->stream));
     ta::launch_component_local(c->stream, a, c->itemsize);
-    ta::launch_component_seams(c->stream, a, c->itemsize);
+    c->cc.launched[0] = (uint32_t)std::min<uint64_t>(ta::component_tiles(a), 0xFFFFFFFFull);
+    c->cc.launched[1] = ta::launch_component_seams(c->stream, a, c->itemsize);
+    c->cc.launched[2] = c->cc.launched[3] = 0u;
     ta::launch_component_flatten(c->stream, a.parent, nvox, a.n1, a.n2, (uint32_t*)(wp + w.counts));
     TA_HIP(hipGetLastError());
     TA_HIP(hipEventRecord(c->cc.ev[1], c->stream));
@@ -211,8 +213,8 @@ TA_API int ta_components_image(ta_ctx* c, int64_t first_plane, int64_t nplanes, 
     const uint64_t plane = (uint64_t)c->mdims[1] * (uint64_t)c->mdims[2], count = (uint64_t)nplanes * plane;
     if ((rc = c->cc.image.reserve(count * 4)) != TA_OK) return rc;
     const ComponentSlots q(c->cc.nslots);
-    ta::launch_component_image(c->stream, (const uint32_t*)c->cc.parent.p, (const uint32_t*)((const char*)c->cc.slots.p + q.row),
-                               (uint64_t)first_plane * plane, count, (uint32_t*)c->cc.image.p);
+    c->cc.launched[2] = ta::launch_component_image(c->stream, (const uint32_t*)c->cc.parent.p, (const uint32_t*)((const char*)c->cc.slots.p + q.row),
+                                                   (uint64_t)first_plane * plane, count, (uint32_t*)c->cc.image.p);
     TA_HIP(hipGetLastError());
     TA_HIP(hipMemcpyAsync(rows, c->cc.image.p, count * 4, hipMemcpyDeviceToHost, c->stream));
     TA_HIP(hipStreamSynchronize(c->stream));
@@ -233,12 +235,19 @@ TA_API int ta_components_relabel(ta_ctx* c, const uint32_t* new_label, uint64_t 
         if ((rc = c->cc.image.reserve(nrows * 4)) != TA_OK) return rc;
         const ComponentSlots q(c->cc.nslots);
         TA_HIP(hipMemcpyAsync(c->cc.image.p, new_label, nrows * 4, hipMemcpyHostToDevice, c->stream));
-        ta::launch_component_relabel(c->stream, (const uint32_t*)c->cc.parent.p, (const uint32_t*)((const char*)c->cc.slots.p + q.row), voxels(c),
-                                     (const uint32_t*)c->cc.image.p, const_cast<void*>(c->vol), c->itemsize);
+        c->cc.launched[2] = ta::launch_component_relabel(c->stream, (const uint32_t*)c->cc.parent.p, (const uint32_t*)((const char*)c->cc.slots.p + q.row),
+                                                         voxels(c), (const uint32_t*)c->cc.image.p, const_cast<void*>(c->vol), c->itemsize);
         TA_HIP(hipGetLastError());
         TA_HIP(hipStreamSynchronize(c->stream));   // (the caller's table may be freed after return)
     }
     volume_labels_changed(c);
+    return TA_OK;
+}
+
+TA_API int ta_components_debug(ta_ctx* c, uint32_t out[4]) {
+    int rc = components_ready(c);
+    if (rc != TA_OK) return rc;
+    if (out) std::copy(c->cc.launched, c->cc.launched + 4, out);
     return TA_OK;
 }
 

@@ -97,11 +97,12 @@ TA_API int ta_distance_extract(ta_ctx* c, int mode, uint32_t site_label, const d
     a.d2 = (double*)c->dist.d2.p;
 
     TA_HIP(hipEventRecord(c->dist.ev[0], c->stream));
-    ta::launch_distance_rows(c->stream, a, c->itemsize);
+    ta::DistanceLaunch launched;
+    launched.row_groups = ta::launch_distance_rows(c->stream, a, c->itemsize);
     for (int k = 0; k < 2; ++k) {
         const int axis = 1 - k;
         const uint64_t columns = ta::distance_columns(a, axis);
-        for (uint64_t first = 0; first < columns; first += batch[k])
+        for (uint64_t first = 0; first < columns; first += batch[k], ++launched.column_launches)
             ta::launch_distance_columns(c->stream, a, c->itemsize, axis, first, std::min(batch[k], columns - first), c->dist.work.p, batch[k]);
     }
     TA_HIP(hipGetLastError());
@@ -115,9 +116,10 @@ TA_API int ta_distance_extract(ta_ctx* c, int mode, uint32_t site_label, const d
     for (int k = 0; k < 3; ++k) dims[c->perm[k]] = c->mdims[k];
     const uint64_t array_stride[3] = {(uint64_t)dims[1] * (uint64_t)dims[2], (uint64_t)dims[2], 1ull};
     for (int k = 0; k < 3; ++k) t.key_stride[k] = array_stride[c->perm[k]];
-    ta::launch_distance_table(c->stream, a, c->itemsize, t);
+    ta::launch_distance_table(c->stream, a, c->itemsize, t, launched);
     TA_HIP(hipGetLastError());
     TA_HIP(hipEventRecord(c->dist.ev[2], c->stream));
+    c->dist.launched = launched;
     c->dist.seq = c->extract_seq;
     c->dist.rows = (uint32_t)R;
     return TA_OK;
@@ -168,6 +170,14 @@ TA_API int ta_distance_image(ta_ctx* c, int64_t first_plane, int64_t nplanes, do
     TA_HIP(hipMemcpyAsync(d2, (const double*)c->dist.d2.p + (uint64_t)first_plane * plane, (uint64_t)nplanes * plane * 8, hipMemcpyDeviceToHost,
                           c->stream));
     TA_HIP(hipStreamSynchronize(c->stream));
+    return TA_OK;
+}
+
+TA_API int ta_distance_debug(ta_ctx* c, uint32_t out[4]) {
+    int rc = distance_ready(c);
+    if (rc != TA_OK) return rc;
+    const ta::DistanceLaunch& l = c->dist.launched;
+    if (out) { out[0] = l.row_groups; out[1] = l.voxel_groups; out[2] = l.init_groups; out[3] = l.column_launches; }
     return TA_OK;
 }
 

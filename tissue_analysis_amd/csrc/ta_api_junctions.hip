@@ -81,12 +81,13 @@ int junctions_settle(ta_ctx* c) {
     uint64_t R[2] = {0, 0};
     for (int k = 0; k < 2; ++k) {
         const uint64_t n = N[k];
+        c->jn.key_groups[k] = 0u;
         if (!n) continue;
         const JunctionSort q(n);
         char* sp = (char*)c->jn.sort[k].p;
         uint64_t* k0 = (uint64_t*)(sp + q.sort.keys[0]); uint64_t* k1 = (uint64_t*)(sp + q.sort.keys[1]);
         uint32_t* i0 = (uint32_t*)(sp + q.sort.idx[0]); uint32_t* i1 = (uint32_t*)(sp + q.sort.idx[1]);
-        ta::launch_junction_keys(c->stream, labels[k], K[k], n, nullptr, K[k] - 2, K[k] - 1, lb, k0, i0);
+        c->jn.key_groups[k] = ta::launch_junction_keys(c->stream, labels[k], K[k], n, nullptr, K[k] - 2, K[k] - 1, lb, k0, i0);
         uint64_t* ks = k0; uint32_t* is = i0;
         TA_HIP(ta::launch_radix_sort_u64(c->stream, n, k0, k1, i0, i1, sp + q.sort.temp, 2 * lb, &ks, &is));
         // the leading columns of the records in that order, into the key buffer the order came out with
@@ -195,6 +196,19 @@ TA_API int ta_junctions_size(ta_ctx* c, uint64_t* nedges, uint64_t* nvertices, u
 TA_API int ta_junctions_get_edges(ta_ctx* c, uint32_t* labels, uint64_t* n, uint64_t* sums) { return junctions_get(c, 0, labels, n, sums); }
 
 TA_API int ta_junctions_get_vertices(ta_ctx* c, uint32_t* labels, uint64_t* n, uint64_t* sums) { return junctions_get(c, 1, labels, n, sums); }
+
+TA_API int ta_junctions_debug(ta_ctx* c, uint32_t out[4]) {
+    if (!c) return fail(TA_EINVAL, "ctx is NULL");
+    if (c->jn.state == 0) return fail(TA_EINVAL, "no junction tables for the current volume (run ta_junctions_extract)");
+    int rc = use_device(c);
+    if (rc != TA_OK) return rc;
+    if ((rc = junctions_settle(c)) != TA_OK) return rc;
+    if (out) {
+        out[0] = (uint32_t)std::min<uint64_t>(c->jn.waves, 0xFFFFFFFFull);
+        out[1] = c->jn.key_groups[0]; out[2] = c->jn.key_groups[1]; out[3] = 0u;
+    }
+    return TA_OK;
+}
 
 TA_API int ta_junctions_timing(ta_ctx* c, double* ms_pass, double* ms_after) {
     if (!c) return fail(TA_EINVAL, "ctx is NULL");

@@ -10,6 +10,8 @@ constexpr int CC_TILE_PLANES = 4, CC_TILE_ROWS = 4, CC_TILE_COLS = 256;
 constexpr uint32_t CC_SLOT_FLAG = 0x80000000u;      // parent[root] = CC_SLOT_FLAG | slot once the slots are handed out
 constexpr uint32_t CC_NO_ROW = 0xFFFFFFFFu;         // row image: a voxel of a component without an owned voxel
 constexpr uint64_t CC_MAX_VOXELS = 1ull << 31;      // buffer voxels (halo included): an index and a flagged slot share a word
+constexpr uint32_t CC_SEAM_MAX_GROUPS = 1u << 18;   // workgroups of the seam pass at most: one takes every CC_SEAM_MAX_GROUPS-th row
+constexpr uint32_t CC_STREAM_MAX_GROUPS = 65536;    // ... of the key, row, image and relabel kernels, which stride over their items
 
 struct ComponentArgs {
     const void* vol;             // labels, dense C-ordered [n0][n1][n2] (u16 or u32), the ids as the caller stored them
@@ -21,8 +23,8 @@ struct ComponentArgs {
 uint64_t component_tiles(const ComponentArgs& a);
 // local pass: every tile's components in LDS; parent[v] = the smallest voxel of v's component INSIDE its tile
 void launch_component_local(hipStream_t s, const ComponentArgs& a, int itemsize);
-// seam pass: the pairs of equal label across tile faces, united in `parent` by agent-scope atomics
-void launch_component_seams(hipStream_t s, const ComponentArgs& a, int itemsize);
+// seam pass: the pairs of equal label across tile faces, united in `parent` by agent-scope atomics.  Returns its workgroups.
+uint32_t launch_component_seams(hipStream_t s, const ComponentArgs& a, int itemsize);
 
 // a wave of the flatten / emit kernels holds 256 consecutive voxels
 inline uint64_t component_waves(uint64_t nvox) { return ((nvox + 1023) / 1024) * 4; }
@@ -47,9 +49,9 @@ struct ComponentGeometry {
 void launch_component_stats(hipStream_t s, const uint32_t* parent, const ComponentGeometry& g, const ComponentStats& t);
 
 // sort keys of the slots: label << 32 | first for a slot with owned voxels (counted in *nonempty, zeroed by the caller), all
-// bits set for the others, which therefore sort behind every row; index_out[i] = i
-void launch_component_keys(hipStream_t s, const void* vol, int itemsize, const uint32_t* root_of_slot, const ComponentStats& t, uint64_t nslots,
-                           uint64_t* keys_out, uint32_t* index_out, unsigned long long* nonempty);
+// bits set for the others, which therefore sort behind every row; index_out[i] = i.  Returns its workgroups.
+uint32_t launch_component_keys(hipStream_t s, const void* vol, int itemsize, const uint32_t* root_of_slot, const ComponentStats& t, uint64_t nslots,
+                               uint64_t* keys_out, uint32_t* index_out, unsigned long long* nonempty);
 
 struct ComponentRows {
     uint32_t* label;             // [R]
@@ -67,10 +69,10 @@ void launch_component_rows(hipStream_t s, const void* vol, int itemsize, const u
                            const uint32_t* order, uint64_t nslots, const unsigned long long* nonempty, uint32_t* row_of_slot,
                            const ComponentRows& rows);
 
-// rows_out[i] = row of voxel first + i
-void launch_component_image(hipStream_t s, const uint32_t* parent, const uint32_t* row_of_slot, uint64_t first, uint64_t count, uint32_t* rows_out);
+// rows_out[i] = row of voxel first + i.  This one and the next return their workgroups.
+uint32_t launch_component_image(hipStream_t s, const uint32_t* parent, const uint32_t* row_of_slot, uint64_t first, uint64_t count, uint32_t* rows_out);
 // vol[v] = new_label[row of v] for every voxel that has a row
-void launch_component_relabel(hipStream_t s, const uint32_t* parent, const uint32_t* row_of_slot, uint64_t nvox, const uint32_t* new_label,
-                              void* vol, int itemsize);
+uint32_t launch_component_relabel(hipStream_t s, const uint32_t* parent, const uint32_t* row_of_slot, uint64_t nvox, const uint32_t* new_label,
+                                  void* vol, int itemsize);
 
 }  // namespace ta

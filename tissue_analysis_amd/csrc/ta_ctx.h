@@ -137,6 +137,7 @@ struct JunctionState {
     int state = 0;                                      // 0 = no tables, 1 = counting walk enqueued, 2 = settled
     uint64_t waves = 0;                                 // waves (= tasks) of a walk
     uint64_t nrows[2] = {0, 0}, degenerate = 0;
+    uint32_t key_groups[2] = {0, 0};                    // workgroups of the key kernel of the last settle (ta_junctions_debug), 0 = no records
     hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // count begin, end | scans end | emit begin, end | tables end
     void release() { small.release(); work.release(); rec.release(); for (int k = 0; k < 2; ++k) { sort[k].release(); rows[k].release(); } destroy_events(ev); }
 };
@@ -163,6 +164,7 @@ struct ComponentState {
     DevBuf image;                                       // staging of ta_components_image and of ta_components_relabel's table
     int state = 0;                                      // 0 = no tables, 1 = union-find and count enqueued, 2 = settled
     uint64_t waves = 0, nslots = 0, nrows = 0;
+    uint32_t launched[4] = {0, 0, 0, 0};                // what the last pass launched (ta_components_debug): local tiles | seam groups | last image or relabel groups | key groups
     hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // union-find begin, end | scan end | emit begin, statistics end | table end
     void release() { parent.release(); work.release(); slots.release(); sort.release(); rows.release(); small.release(); image.release(); destroy_events(ev); }
 };
@@ -175,6 +177,7 @@ struct DistanceState {
     uint64_t seq = 0;                                   // extract_seq of the extraction the results belong to, 0 = none
     uint32_t rows = 0;                                  // max_label + 1 of that extraction
     int64_t opt_batch = 0;                              // ta_distance_set_batch: 0 = automatic
+    ta::DistanceLaunch launched;                        // what the last pass launched (ta_distance_debug)
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};     // passes begin, end | table end
     void release() { d2.release(); work.release(); table.release(); destroy_events(ev); }
 };

@@ -10,6 +10,9 @@ enum { DIST_FLAG_RANGE = 0, DIST_NFLAGS = 4 };
 constexpr uint64_t DIST_WORK_CAP = 1ull << 30;      // bytes of the column passes' envelope stacks, unless one wave of columns needs more
 constexpr uint64_t DIST_STACK_ENTRY = 20;           // bytes of an envelope entry: position i32 | f f64 | left boundary f64
 constexpr uint64_t DIST_NO_POLE = ~0ull;
+// workgroups at most of the kernels that stride over their items: the row pass (four rows a workgroup at a time), the extremes
+// and pole kernels (256 voxels), the table initialisation (256 rows)
+constexpr uint32_t DIST_ROW_MAX_GROUPS = 1u << 16, DIST_VOXEL_MAX_GROUPS = 1u << 14, DIST_INIT_MAX_GROUPS = 1u << 12;
 
 struct DistanceArgs {
     const void* vol;             // labels (ranks in a compacted context), dense C-ordered [n0][n1][n2] (u16 or u32)
@@ -22,8 +25,9 @@ struct DistanceArgs {
 };
 
 // Row pass along memory axis 2: d2 = (w2 * distance to the nearest end of the voxel's run)^2, +inf where neither end has a site
-// behind it; 0 on the site voxels of mode 1.  One wave per row, 64 voxels at a time, forwards and then backwards.
-void launch_distance_rows(hipStream_t s, const DistanceArgs& a, int itemsize);
+// behind it; 0 on the site voxels of mode 1.  One wave per row, 64 voxels at a time, forwards and then backwards.  Returns its
+// workgroups.
+uint32_t launch_distance_rows(hipStream_t s, const DistanceArgs& a, int itemsize);
 
 // Column pass along memory axis `axis` (1 or 0), in place on d2: per run of equal class the lower envelope of the run's own
 // parabolas and of a zero parabola on the voxel behind either end.  One lane per column; `columns` of them from `first` per launch.
@@ -41,7 +45,8 @@ struct DistanceTable {
     uint32_t max_label;
     uint64_t key_stride[3];      // of memory axis k in the C order of the ARRAY axes
 };
-// the rows set to their starting values, then two streaming passes over labels and d2: the extremes, then the pole
-void launch_distance_table(hipStream_t s, const DistanceArgs& a, int itemsize, const DistanceTable& t);
+// the rows set to their starting values, then two streaming passes over labels and d2: the extremes, then the pole; their
+// workgroups go to launched.init_groups and launched.voxel_groups
+void launch_distance_table(hipStream_t s, const DistanceArgs& a, int itemsize, const DistanceTable& t, DistanceLaunch& launched);
 
 }  // namespace ta

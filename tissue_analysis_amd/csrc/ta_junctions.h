@@ -29,9 +29,11 @@ uint64_t junction_plan(JunctionArgs& a, int itemsize);
 void launch_junction_pass(hipStream_t s, const JunctionArgs& a, int itemsize, bool emit);
 
 // sort keys of the records in the order `order` (NULL: 0, 1, 2, ..., which is then also written to index_out): the label
-// columns col_hi (< 0: none) and col_lo of a record of K labels, packed as hi << label_bits | lo
-void launch_junction_keys(hipStream_t s, const uint32_t* labels, int K, uint64_t n, const uint32_t* order, int col_hi, int col_lo,
-                          int label_bits, uint64_t* keys_out, uint32_t* index_out);
+// columns col_hi (< 0: none) and col_lo of a record of K labels, packed as hi << label_bits | lo.  The kernel strides over the
+// records behind JN_KEY_MAX_GROUPS workgroups at most; returns its workgroups.
+constexpr uint32_t JN_KEY_MAX_GROUPS = 8192;
+uint32_t launch_junction_keys(hipStream_t s, const uint32_t* labels, int K, uint64_t n, const uint32_t* order, int col_hi, int col_lo,
+                              int label_bits, uint64_t* keys_out, uint32_t* index_out);
 
 // the sorted records order[0 .. n): a record whose labels differ from its predecessor's starts a row
 constexpr uint32_t JN_ROW_BLOCK = 256;
