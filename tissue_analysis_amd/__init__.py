@@ -16,6 +16,7 @@ from .spatial_image_analysis import (NPLIST, LIST, DICT, AbstractSpatialImageAna
                                      eigen_values_vectors, distance)
 from .extraction import Extraction, extract_volume
 from .signal_stats import SignalStats
+from .signal_quantiles import SignalHistogram, SignalQuantiles
 from .cell_meshes import CellMeshes
 from .label_overlap import LabelOverlap, label_overlap, lineage_from_images
 from .cell_junctions import CellJunctions, cell_junctions
@@ -27,7 +28,7 @@ from .property_graph import PropertyGraph
 from .graph_from_image import graph_from_image, property_graph_to_dataframe
 
 __all__ = ["SpatialImage", "NPLIST", "LIST", "DICT", "AbstractSpatialImageAnalysis",
-           "SpatialImageAnalysis3D", "SpatialImageAnalysis", "Extraction", "extract_volume", "SignalStats", "CellMeshes",
+           "SpatialImageAnalysis3D", "SpatialImageAnalysis", "Extraction", "extract_volume", "SignalStats", "SignalHistogram", "SignalQuantiles", "CellMeshes",
            "LabelOverlap", "label_overlap", "lineage_from_images", "CellJunctions", "cell_junctions", "WallGeometry", "wall_geometry",
            "LabelComponents", "label_components", "DistanceMap", "distance_map", "ShellProfile",
            "dilation", "dilation_by", "real_indices", "return_list_of_vectors", "hollow_out_cells", "wall", "contact_surface",

@@ -86,6 +86,14 @@ PROF_SIGNAL = 1                        # TA_PROF_SIGNAL
 PROFILE_MAX_BINS = 64                  # TA_PROF_MAX_BINS
 PROFILE_SLOTS = 1024                   # PROF_SLOTS of csrc/ta_profile.h: slots of a workgroup's LDS table
 
+# every symbol include/tissue_scan_sighist.h declares (same library)
+SIGHIST_SYMBOLS = ("ta_sighist_extract", "ta_sighist_get", "ta_sigrank_extract", "ta_sigrank_get", "ta_sighist_debug",
+                   "ta_sighist_timing")
+SIGRANK_MAX_RANKS = 8                  # TA_SIGRANK_MAX_RANKS
+SIGRANK_NONE = 0xFFFFFFFF              # value of a rank >= n
+SIGHIST_SLOTS = 39                     # TA_SH_SLOTS of csrc/ta_sighist.h: rows of 256 counters in a workgroup's LDS table
+SIGHIST_MAX_GROUPS = 65536             # TA_SH_MAX_GROUPS: workgroups of the digit pass at most (the plan: tests/sighist_reference.py)
+
 
 def exchange_words(capacity_pairs):
     """uint64 words of one exchange block (TA_EXCHANGE_WORDS in include/tissue_scan.h)."""
@@ -225,9 +233,15 @@ def load():
         "ta_profile_get": (ci, [vp, vp, vp, vp, vp, vp]),
         "ta_profile_debug": (ci, [vp, P(u32)]),
         "ta_profile_timing": (ci, [vp, P(ctypes.c_double)]),
+        "ta_sighist_extract": (ci, [vp, ci]),
+        "ta_sighist_get": (ci, [vp, vp]),
+        "ta_sigrank_extract": (ci, [vp, ci, vp]),
+        "ta_sigrank_get": (ci, [vp, vp]),
+        "ta_sighist_debug": (ci, [vp, P(u32)]),
+        "ta_sighist_timing": (ci, [vp, P(ctypes.c_double), P(ctypes.c_double)]),
     }
     for name in (SYMBOLS + SIGNAL_SYMBOLS + MESH_SYMBOLS + OVERLAP_SYMBOLS + JUNCTION_SYMBOLS + WALLGEO_SYMBOLS + COMPONENT_SYMBOLS
-                 + DISTANCE_SYMBOLS + PROFILE_SYMBOLS):
+                 + DISTANCE_SYMBOLS + PROFILE_SYMBOLS + SIGHIST_SYMBOLS):
         fn = getattr(lib, name)      # AttributeError here == the .so does not match the header
         fn.restype, fn.argtypes = sig[name]
     if lib.ta_version() != ABI_VERSION:
@@ -475,11 +489,13 @@ class Context(object):
             raise TypeError("signal images must be uint8 or uint16, not %s" % a.dtype)
         a = self._in_label_layout(a, ("its signal", "signal's"))
         _check(self._lib.ta_signal_set(self._h, ctypes.c_void_p(a.ctypes.data), a.dtype.itemsize, _i64x3(a.shape), _i64x3(a.strides)))
+        self._signal_itemsize = a.dtype.itemsize
 
     def set_signal_device(self, dev_ptr, itemsize, keep=None):
         """Adopt a device-resident signal: dense C order with the label volume's buffer dims (halo plane included)."""
         _check(self._lib.ta_signal_set_device(self._h, ctypes.c_void_p(int(dev_ptr)), int(itemsize)))
         self._keep_sig = keep
+        self._signal_itemsize = int(itemsize)
 
     def signal_extract(self, what=SIG_LABELS | SIG_WALLS):
         """Enqueue the signal pass over the current extraction (SIG_LABELS | SIG_WALLS)."""
@@ -790,6 +806,49 @@ class Context(object):
         ms = ctypes.c_double(0.0)
         _check(self._lib.ta_profile_timing(self._h, ctypes.byref(ms)))
         return ms.value
+
+    # -- signal histograms and order statistics (include/tissue_scan_sighist.h)
+    def sighist_extract(self, log2_width):
+        """Enqueue the histogram pass over the current extraction: bin = S >> log2_width, 2^(bits - log2_width) <= 256 bins."""
+        _check(self._lib.ta_sighist_extract(self._h, int(log2_width)))
+        self._sighist_shape = (self._max_label + 1, 1 << (8 * self._signal_itemsize - int(log2_width)))
+
+    def sighist_get(self):
+        """counts u64[R, B], rows as labels()."""
+        counts = np.zeros(getattr(self, "_sighist_shape", (1, 1)), dtype=np.uint64)      # (no pass yet: the library answers TA_EINVAL)
+        _check(self._lib.ta_sighist_get(self._h, counts.ctypes.data))
+        return counts
+
+    def sigrank_extract(self, ranks):
+        """Enqueue the radix select over the current extraction: ranks u64[R, n] (n <= SIGRANK_MAX_RANKS), 0-based, per row of
+        labels(); a rank at or above the row's voxels (conventionally 2^64 - 1) gives SIGRANK_NONE."""
+        r = np.ascontiguousarray(ranks, dtype=np.uint64)
+        rows = getattr(self, "_max_label", None)               # (no extraction yet: the library answers TA_EINVAL)
+        if r.ndim != 2 or (rows is not None and r.shape[0] != rows + 1):
+            raise ValueError("ranks must be [%s, n], not %s" % ("rows" if rows is None else rows + 1, r.shape))
+        _check(self._lib.ta_sigrank_extract(self._h, int(r.shape[1]), r.ctypes.data))
+        self._sigrank_shape = r.shape
+
+    def sigrank_get(self):
+        """values u32[R, n]: the order statistics, SIGRANK_NONE where the rank was not below the row's voxels."""
+        values = np.zeros(getattr(self, "_sigrank_shape", (1, 1)), dtype=np.uint32)
+        _check(self._lib.ta_sigrank_get(self._h, values.ctypes.data))
+        return values
+
+    def sighist_debug(self):
+        """Diagnostics of the last digit-kernel launch of either pass: counts that missed a workgroup's LDS table (spills) and the
+        launch plan (tiles_per_group, groups)."""
+        out = (ctypes.c_uint32 * 4)()
+        _check(self._lib.ta_sighist_debug(self._h, out))
+        return dict(spills=int(out[0]), tiles_per_group=int(out[2]), groups=int(out[3]))
+
+    def sighist_timing(self):
+        """(ms_hist, ms_rank): HIP-event milliseconds of the last histogram pass and of all kernels of the last select; None for
+        one without valid results."""
+        a, b = ctypes.c_double(0.0), ctypes.c_double(0.0)
+        _check(self._lib.ta_sighist_timing(self._h, ctypes.byref(a), ctypes.byref(b)))
+        some = lambda v: None if v != v else v
+        return some(a.value), some(b.value)
 
     def max_label(self):
         v = ctypes.c_uint32(0)

@@ -194,6 +194,21 @@ struct ProfileState {
     void release() { out.release(); destroy_events(ev); }
 };
 
+// signal histograms and order statistics (include/tissue_scan_sighist.h)
+struct SigHistState {
+    DevBuf out;                                         // flags u32[4] | counts u64[R][B]
+    DevBuf rank;                                        // flags u32[2][4] | ranks u64[R][n] | rem u64[R][n] | hi, sel, map, values u32[R][n] | counts u64[R][256] | uint16: counts u64[R][n][256]
+    std::vector<uint64_t> h_ranks;                      // what the last ta_sigrank_extract's ranks were copied to the device from
+    uint64_t hist_seq = 0, rank_seq = 0;                // extract_seq of the extraction each table belongs to, 0 = none
+    uint32_t rows = 0, bins = 0;                        // R = max_label + 1 of the histogram's extraction, B
+    uint32_t rank_rows = 0, nranks = 0;                 // R and n of the order statistics
+    int rank_passes = 0;                                // digit passes of the last ta_sigrank_extract: 1 (uint8) or 2 (uint16)
+    int last = 0;                                       // whose digit pass ran last (ta_sighist_debug): 1 = histogram, 2 = order statistics
+    ta::RangePlan plan;                                 // what that pass was launched with
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};       // histogram begin, end | order statistics begin, end
+    void release() { out.release(); rank.release(); destroy_events(ev); }
+};
+
 // wall voxels and wall medians (ta_api_walls.hip)
 struct WallVoxelState {
     DevBuf counts;                                      // per-chunk record counts, then offsets
@@ -306,6 +321,7 @@ struct ta_ctx {
     ComponentState cc;
     DistanceState dist;
     ProfileState prof;
+    SigHistState sh;
 };
 
 inline int use_device(ta_ctx* c) {
@@ -347,6 +363,8 @@ void distance_on_new_volume(ta_ctx* c);
 void profile_on_new_volume(ta_ctx* c);
 void profile_on_new_distance(ta_ctx* c);              // a new ta_distance_extract: the image the table was read from is gone.  ta_api_profile.hip
 void profile_on_new_signal(ta_ctx* c);                // a new signal image: stale when the pass read the old one.  ta_api_profile.hip
+void sighist_on_new_volume(ta_ctx* c);
+void sighist_on_new_signal(ta_ctx* c);                // a new signal image: both tables read the old one.  ta_api_sighist.hip
 void walls_on_new_labels(ta_ctx* c);                  // new label values in the same volume: the staging buffer is kept.  ta_api_walls.hip
 
 // The two ways the voxels change (ta_api.hip).  volume_replaced: the tail of ta_volume_set / ta_volume_set_device, called once vol,

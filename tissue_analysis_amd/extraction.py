@@ -519,6 +519,28 @@ class ResidentVolume(object):
         self.ms["signal"] = (time.perf_counter() - t0) * 1e3
         return st
 
+    def signal_histogram(self, signal, bin_width=None):
+        """Per-label histogram of an intensity image (uint8 / uint16, the shape of the labels): a `SignalHistogram` whose rows
+        line up with the last extraction.  bin_width: a power of two leaving at most 256 bins (default 1 for uint8, 256 for
+        uint16).  One upload of the signal and one pass over labels + signal on the GPU."""
+        import time
+        from .signal_quantiles import resident_signal_histogram
+        t0 = time.perf_counter()
+        h = resident_signal_histogram(self, signal, bin_width)
+        self.ms["signal_histogram"] = (time.perf_counter() - t0) * 1e3
+        return h
+
+    def signal_quantiles(self, signal, q, method='linear'):
+        """Per-label quantiles `q` (in [0, 1]) of an intensity image by numpy's rule for `method` ('linear', 'lower', 'higher',
+        'midpoint'), from exact order statistics selected on the GPU: a `SignalQuantiles` whose rows line up with the last
+        extraction.  One or two passes over labels + signal (uint8 / uint16) for every eight ranks a row."""
+        import time
+        from .signal_quantiles import resident_signal_quantiles
+        t0 = time.perf_counter()
+        sq = resident_signal_quantiles(self, signal, q, method)
+        self.ms["signal_quantiles"] = (time.perf_counter() - t0) * 1e3
+        return sq
+
     def meshes(self, labels=None, sub_factor=1, voxelsize=(1.0, 1.0, 1.0)):
         """The exact voxel-face surface meshes of the cells `labels` (ids; None = every label, background included) of
         host[::s, ::s, ::s]: a `CellMeshes`.  Count, scan and emit on the GPU, over the current extraction (swept first when

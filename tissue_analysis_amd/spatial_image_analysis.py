@@ -592,6 +592,30 @@ class AbstractSpatialImageAnalysis(object):
         a, b = stats.wall_side_means
         return dict((k, (float(a[r]), float(b[r])) if r >= 0 else (float('nan'), float('nan'))) for k, r in zip(keys, rows.tolist()))
 
+    # -- exact histograms, medians and quantiles of a signal image (include/tissue_scan_sighist.h; radix select on the GPU)
+    def signal_quantiles(self, signal, q, labels=None, method='linear'):
+        """Per label the quantiles `q` (a sequence in [0, 1]) of the intensity image `signal` (uint8 / uint16, the image's shape),
+        by numpy.quantile's rule for `method` ('linear', 'lower', 'higher' or 'midpoint') over the exact order statistics of the
+        label's voxels.  One array of len(q) per label, returned like volume() (NPLIST: an array [labels, len(q)])."""
+        labels = self.label_request(labels)
+        sq = self._resident_rows().signal_quantiles(np.asarray(signal), q, method)
+        return self.convert_return(sq.of_labels(labels), labels)
+
+    def signal_median(self, signal, labels=None):
+        """Per label the median of the intensity image `signal` over the label's voxels (float64, what numpy.median of them
+        gives, NaN for a label without voxels); returned like volume()."""
+        labels = self.label_request(labels)
+        sq = self._resident_rows().signal_quantiles(np.asarray(signal), [0.5], 'midpoint')
+        return self.convert_return(sq.of_labels(labels)[:, 0], labels)
+
+    def signal_histogram(self, signal, labels=None, bin_width=None):
+        """Per label the histogram of the intensity image `signal`: uint64 counts of the bins [b * bin_width, (b + 1) * bin_width),
+        `bin_width` a power of two that leaves at most 256 bins (default 1 for uint8, 256 for uint16).  One array per label,
+        returned like volume() (NPLIST: an array [labels, bins])."""
+        labels = self.label_request(labels)
+        h = self._resident_rows().signal_histogram(np.asarray(signal), bin_width)
+        return self.convert_return(h.of_labels(labels), labels)
+
     # -- cell surface meshes (include/tissue_scan_mesh.h; count, scan and emit on the GPU)
     def cell_meshes(self, labels=None, sub_factor=1):
         """The exact voxel-face surface meshes of `labels` (default: labels(), so no background and no ignored label) on
