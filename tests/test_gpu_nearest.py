@@ -1,0 +1,434 @@
+"""The nearest-label maps on the GPU (include/tissue_scan_nearest.h) against tests/nearest_reference.py: N and D2 through
+ta_nearest_image, the counts through ta_nearest_get, the filled volume through ta_nearest_apply, bit for bit where every spacing is a
+power of two, for uint16 and uint32 and every memory layout.
+
+Few labels on small integer grids make ties common, and every test asserts that its reference has voxels with two labels equally
+near, so the tie rule (the smallest label) cannot go untested.  The shapes are the smallest at which the passes can still go wrong:
+rows across the 64-voxel chunk of the row pass with the site carried over (130, 70), more columns than one 256-lane workgroup, more
+than one batch of columns (the batch is set to one wave of 64 through ta_nearest_set_batch), axes of one voxel, a long axis 0."""
+import ctypes
+import functools
+import itertools
+
+import numpy as np
+import pytest
+
+import nearest_reference as ref
+from tissue_analysis_amd import DICT, SpatialImage, SpatialImageAnalysis, _capi, synth
+from tissue_analysis_amd.extraction import ResidentVolume
+
+pytestmark = pytest.mark.gpu
+
+INF = float("inf")
+UNIT, HALF, MIXED, OTHER = (1.0, 1.0, 1.0), (0.5, 1.0, 2.0), (2.0, 0.25, 1.0), (0.3, 0.7, 1.1)
+BG = synth.BACKGROUND
+PERMS = list(itertools.permutations(range(3)))
+
+
+def _code(call, *args):
+    try:
+        call(*args)
+    except _capi.TissueScanError as e:
+        return e.code
+    return _capi.TA_OK
+
+
+def in_layout(V, perm):
+    """The same array with memory axes perm (slowest first)."""
+    return np.ascontiguousarray(V.transpose(perm)).transpose(np.argsort(perm))
+
+
+@functools.lru_cache(maxsize=None)
+def noise(shape, labels, seed=7):
+    """About half the voxels empty (0), the others one of `labels` labels."""
+    rng = np.random.default_rng(seed)
+    V = (rng.integers(1, labels + 1, shape) * (rng.random(shape) < 0.5)).astype(np.uint16)
+    V.setflags(write=False)
+    return V
+
+
+@functools.lru_cache(maxsize=None)
+def brute(shape, labels, spacing, not_from=None):
+    out = ref.brute(noise(shape, labels), 0, spacing, not_from, ties=True)
+    for a in out:
+        a.setflags(write=False)
+    return out
+
+
+def device(rv, empty=0, spacing=UNIT, not_from=None, max_d2=INF):
+    """(N, D2 with the axes of the volume, gained, filled, left) of one pass over the volume resident in rv."""
+    if rv.last is None:
+        rv.extract(_capi.F_VOLUME, sparse=False)
+    rv.ctx.nearest_extract(empty, not_from, spacing, max_d2)
+    n, d2 = rv.nearest_images()
+    return (np.array(n), np.array(d2)) + rv.ctx.nearest_get()
+
+
+def same(got, V, n, d2, empty=0, max_d2=INF, rows=None):
+    """The device's answer `got` is the reference's, bit for bit."""
+    image, gained, filled, left = ref.result(V, n, d2, empty, max_d2, int(V.max()) + 1 if rows is None else rows)
+    assert got[0].dtype == np.uint32 and got[0].shape == V.shape and np.array_equal(got[0], n)
+    assert got[1].dtype == np.float64 and np.array_equal(got[1], d2)
+    assert got[2].dtype == np.uint64 and np.array_equal(got[2].astype(np.int64), gained)
+    assert got[3:] == (filled, left)
+    return image
+
+
+# ---- parity with brute force ----------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("dtype", [np.uint16, np.uint32])
+@pytest.mark.parametrize("shape,labels", [((3, 5, 130), 5), ((5, 3, 130), 7), ((7, 9, 11), 12), ((1, 6, 70), 5), ((130, 5, 3), 6)])
+def test_parity_with_brute_force(shape, labels, dtype):
+    V = noise(shape, labels).astype(dtype)
+    for spacing in (UNIT, HALF, MIXED):
+        assert brute(shape, labels, spacing)[2].any()      # voxels with two labels equally near
+    for perm in PERMS:
+        layout = in_layout(V, perm)
+        rv = ResidentVolume(layout)
+        try:
+            for spacing in (UNIT, HALF, MIXED):
+                n, d2, _ = brute(shape, labels, spacing)
+                rv.ctx.nearest_set_batch(64)
+                same(device(rv, 0, spacing), V, n, d2)
+                assert rv.ctx.nearest_debug()["column_launches"] > 2
+                rv.ctx.nearest_set_batch(0)
+                same(device(rv, 0, spacing), V, n, d2)
+                assert rv.ctx.nearest_debug()["column_launches"] == 2
+            n, d2, ties = brute(shape, labels, MIXED, 1)   # the voxels of label 1 are no sites
+            assert ties.any()
+            got = device(rv, 0, MIXED, 1)
+            same(got, V, n, d2)
+            assert got[2][1] == 0 and not (got[0] == 1).any()
+        finally:
+            rv.close()
+
+
+def test_debug_and_batch_arguments():
+    V = noise((7, 9, 11), 12)
+    rv = ResidentVolume(V)
+    try:
+        rv.extract(_capi.F_VOLUME, sparse=False)
+        assert _code(rv.ctx.nearest_debug) == _code(rv.ctx.nearest_get) == _capi.TA_EINVAL          # no pass yet
+        assert _code(rv.ctx.nearest_set_batch, -1) == _capi.TA_EINVAL
+        rv.ctx.nearest_set_batch(1)                        # rounded up to one wave: 11 * 7 / 64 and 11 * 9 / 64 launches, rounded up
+        rv.ctx.nearest_extract(0, None, UNIT)
+        assert rv.ctx.nearest_debug() == dict(row_groups=(7 * 9 + 3) // 4, count_groups=3, apply_groups=3, column_launches=2 + 2)
+        assert rv.ctx._lib.ta_nearest_debug(rv.ctx._h, None) == _capi.TA_OK
+        assert all(ms >= 0.0 for ms in rv.ctx.nearest_timing())
+        n, d2 = rv.ctx.nearest_image(2, 3)
+        want_n, want_d2, _ = brute((7, 9, 11), 12, UNIT)
+        assert np.array_equal(n, want_n[2:5].reshape(-1)) and np.array_equal(d2, want_d2[2:5].reshape(-1))
+        assert rv.ctx.nearest_image(0, None, d2=False)[1] is None and rv.ctx.nearest_image(7, 0)[0].size == 0
+        assert _code(rv.ctx.nearest_image, 6, 2) == _capi.TA_EINVAL and _code(rv.ctx.nearest_image, -1, 1) == _capi.TA_EINVAL
+        for bad in ((0, None, (0.0, 1.0, 1.0)), (0, None, (1.0, -1.0, 1.0)), (0, None, (1.0, 1.0, INF)), (0, None, (float("nan"), 1.0, 1.0)),
+                    (0, None, UNIT, -1.0), (0, None, UNIT, float("nan"))):
+            assert _code(rv.ctx.nearest_extract, *bad) == _capi.TA_EINVAL
+        spacing = (ctypes.c_double * 3)(1.0, 1.0, 1.0)
+        assert rv.ctx._lib.ta_nearest_extract(rv.ctx._h, 0, 0, spacing, INF, 2) == _capi.TA_EINVAL       # an unknown flag
+        assert rv.ctx._lib.ta_nearest_extract(rv.ctx._h, 0, 0, None, INF, 0) == _capi.TA_EINVAL
+    finally:
+        rv.close()
+
+
+# ---- edge cases -----------------------------------------------------------------------------------------------------------------
+def test_no_site_at_all():
+    V = np.zeros((3, 4, 70), dtype=np.uint16)
+    rv = ResidentVolume(V)
+    try:
+        n, d2, gained, filled, left = device(rv)
+        assert (n == ref.NONE).all() and np.isinf(d2).all() and not gained.any() and (filled, left) == (0, V.size)
+        rv.apply_nearest()
+        assert not rv.host.any()
+        W = np.where(V == 0, 3, V).astype(np.uint16)       # every voxel of one label that is no site: the same
+        rv.upload(W)
+        n, d2, gained, filled, left = device(rv, 0, UNIT, 3)
+        assert (n == ref.NONE).all() and np.isinf(d2).all() and (filled, left) == (0, 0)
+    finally:
+        rv.close()
+
+
+def test_no_empty_voxel_and_an_empty_label_the_volume_does_not_hold():
+    V = (noise((7, 9, 11), 12) + 1).astype(np.uint16)
+    rv = ResidentVolume(V)
+    try:
+        for empty in (0, 500, 70000):                      # absent below, between and above what uint16 can hold
+            n, d2, gained, filled, left = device(rv, empty, HALF)
+            assert np.array_equal(n, V) and not d2.any() and not gained.any() and (filled, left) == (0, 0)
+        x = rv.apply_nearest()
+        assert np.array_equal(rv.host, V) and x.count[1:].sum() == V.size
+    finally:
+        rv.close()
+
+
+@pytest.mark.parametrize("dtype", [np.uint16, np.uint32])
+def test_one_site_in_a_corner_and_one_on_the_last_voxel(dtype):
+    V = np.zeros((5, 7, 71), dtype=dtype)                  # odd axes: the voxel in the middle is equally near to both
+    V[0, 0, 0], V[-1, -1, -1] = 9, 4
+    g = np.indices(V.shape).astype(np.float64)
+    for perm in (PERMS[0], PERMS[3], PERMS[5]):
+        rv = ResidentVolume(in_layout(V, perm))
+        try:
+            for spacing in (UNIT, MIXED):
+                first = sum((spacing[a] * g[a]) ** 2 for a in range(3))
+                last = sum((spacing[a] * (g[a] - (V.shape[a] - 1))) ** 2 for a in range(3))
+                want_n = np.where(first < last, 9, 4).astype(np.uint32)          # (ties go to 4, the smaller label)
+                assert (first == last).any()
+                same(device(rv, 0, spacing), V, want_n, np.minimum(first, last))
+        finally:
+            rv.close()
+
+
+def test_not_from_the_background():
+    """A hole next to the background goes to a cell, not to the background."""
+    V = np.full((4, 6, 70), BG, dtype=np.uint16)
+    V[:, 2:5, 10:40] = 5
+    V[:, 2:5, 40:66] = 3
+    V[:, 2:5, 37:42] = 0                                   # a hole across the wall between the two cells, open to the background
+    V[:, 0:3, 20:30] = 0                                   # a hole that reaches into the background
+    rv = ResidentVolume(V)
+    try:
+        n, d2, (ids, stack) = ref.by_label_edt(V, 0, UNIT, BG, per_label=True)
+        tie = np.sort(stack, axis=0)
+        assert ids.tolist() == [3, 5] and ((tie[0] == tie[1]) & (V == 0)).any()     # the middle of the hole is equally near to both
+        image = same(device(rv, 0, UNIT, BG), V, n, d2)
+        with_bg = ref.by_label_edt(V, 0, UNIT)[0]
+        assert (with_bg[V == 0] == BG).any() and not (n[V == 0] == BG).any() and (n[V == BG] != BG).all()
+        rv.apply_nearest()
+        assert np.array_equal(rv.host, image) and not (image == 0).any() and (image == BG).sum() == (V == BG).sum()
+    finally:
+        rv.close()
+
+
+# ---- the limit ------------------------------------------------------------------------------------------------------------------
+def test_max_distance_is_inclusive():
+    shape, labels = (7, 9, 11), 12
+    V = noise(shape, labels)
+    n, d2, ties = brute(shape, labels, HALF)
+    assert ties.any()
+    values = np.unique(d2[V == 0])
+    limit = float(values[len(values) // 2])                # a D2 that occurs among the empty voxels
+    assert limit > 0 and (d2[V == 0] > limit).any()
+    rv = ResidentVolume(V)
+    try:
+        at = device(rv, 0, HALF, None, limit)
+        image = same(at, V, n, d2, 0, limit)
+        below = device(rv, 0, HALF, None, float(np.nextafter(limit, 0.0)))
+        same(below, V, n, d2, 0, float(np.nextafter(limit, 0.0)))
+        assert at[3] - below[3] == int((d2[V == 0] == limit).sum()) > 0
+        nothing = device(rv, 0, HALF, None, 0.0)
+        assert nothing[3:] == (0, int((V == 0).sum())) and not nothing[2].any()
+        device(rv, 0, HALF, None, limit)
+        rv.apply_nearest()
+        assert np.array_equal(rv.host, image) and (image == 0).sum() == at[4] > 0
+    finally:
+        rv.close()
+
+
+# ---- medium size ----------------------------------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def grown():
+    """(40, 48, 70) uint16: 12 labels grown from seeds, then 3 of them erased to 0."""
+    rng = np.random.default_rng(12)
+    shape = (40, 48, 70)
+    seeds = np.zeros(shape, dtype=np.uint16)
+    for l in range(1, 13):
+        seeds[tuple(rng.integers(0, s) for s in shape)] = l
+    V = ref.by_label_edt(seeds, 0, UNIT)[0].astype(np.uint16)
+    V[np.isin(V, (2, 7, 11))] = 0
+    V.setflags(write=False)
+    return V
+
+
+@pytest.mark.parametrize("spacing", [UNIT, HALF, OTHER], ids=["unit", "dyadic", "other"])
+def test_medium_volume_against_the_per_label_transform(spacing):
+    V = grown()
+    n, d2, (ids, stack) = ref.by_label_edt(V, 0, spacing, per_label=True)
+    tie = np.sort(stack, axis=0)
+    assert ids.size == 9 and ((tie[0] == tie[1]) & (V == 0)).any()                  # empty voxels with two labels equally near
+    for perm in (PERMS[0], PERMS[4]):
+        rv = ResidentVolume(in_layout(V, perm))
+        try:
+            got = device(rv, 0, spacing)
+            if ref.is_dyadic(spacing):
+                same(got, V, n, d2)
+                continue
+            assert np.all(np.abs(got[1] - d2) <= 1e-12 * d2)
+            assert np.isin(got[0], ids).all()
+            own = np.take_along_axis(stack, np.searchsorted(ids, got[0])[None], axis=0)[0]          # the chosen label's own distance
+            assert np.all(own <= d2 * (1 + 1e-12))
+            assert got[3:] == (int((V == 0).sum()), 0) and int(got[2].sum()) == got[3]
+        finally:
+            rv.close()
+
+
+# ---- sparse ids -----------------------------------------------------------------------------------------------------------------
+def test_sparse_ids():
+    ids = np.array([0, 7, 70000, 2 ** 31 + 5], dtype=np.uint32)
+    rank = noise((5, 3, 130), 3)
+    V = ids[rank]
+    n, d2, ties = ref.brute(rank, 0, HALF, ties=True)
+    assert ties.any()
+    rv = ResidentVolume(V)
+    try:
+        x = rv.extract(_capi.F_VOLUME, sparse=True)
+        assert rv.ctx.is_compact() and np.array_equal(x.ids, ids)
+        got = device(rv, 0, HALF)
+        assert np.array_equal(got[0], ids[n]) and np.array_equal(got[1], d2)        # images in ids ...
+        _, gained, filled, left = ref.result(rank, n, d2)
+        assert np.array_equal(got[2].astype(np.int64), gained) and got[3:] == (filled, left)       # ... and gained by row of Extraction.ids
+        n7, d7 = ref.brute(rank, 2, HALF, 1)               # empty = 70000, not from 7: ids that are looked up
+        got = device(rv, 70000, HALF, 7)
+        assert np.array_equal(got[0], ids[n7]) and np.array_equal(got[1], d7)
+        assert np.array_equal(got[2].astype(np.int64), ref.result(rank, n7, d7, 2)[1])
+        for absent in (2, 5, 4000000000):                  # a rank, a value between two ids, a value above them: nothing is empty
+            got = device(rv, absent, HALF)
+            assert np.array_equal(got[0], V) and not got[1].any() and got[3:] == (0, 0)
+        nl = rv.nearest_labels(0, None, HALF)
+        assert np.array_equal(nl.labels, ids) and nl.gained() == dict((int(ids[r]), int(g)) for r, g in enumerate(gained) if g)
+        want = np.where(rank == 0, ids[n], V)
+        assert np.array_equal(nl.image(), want)
+        x = nl.apply()
+        assert np.array_equal(rv.host, want) and np.array_equal(x.ids, ids[1:])
+    finally:
+        rv.close()
+
+
+# ---- apply, through the analysis ------------------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def tissue():
+    V = synth.voronoi_labels((24, 40, 56), 30, 3, dtype=np.uint16)
+    V.setflags(write=False)
+    return V
+
+
+def test_fill_erased_voxels():
+    V, vs = tissue(), (0.5, 0.5, 1.0)
+    sia = SpatialImageAnalysis(SpatialImage(V.copy(), voxelsize=vs), return_type=DICT, background=BG)
+    gone = [int(l) for l in sia.labels()[3:9:2]]
+    sia.remove_labels_from_image(list(gone), verbose=False)
+    erased = np.asarray(sia.image).copy()
+    assert (erased == 0).sum() == np.isin(V, gone).sum() > 0
+    before = sia.volume(real=False)
+    wall = sia.wall_distance()                             # a distance map taken before the fill
+    n, d2, (ids, stack) = ref.by_label_edt(erased, 0, vs, per_label=True)
+    tie = np.sort(stack, axis=0)
+    assert ((tie[0] == tie[1]) & (erased == 0)).any()
+    want, gained, filled, left = ref.result(erased, n, d2)
+    assert sia.nearest_labels().gained() == dict((l, int(g)) for l, g in enumerate(gained) if g)
+    assert np.array_equal(sia.nearest_labels().image(), want)
+    got = sia.fill_erased_voxels()
+    assert got == dict((l, int(g)) for l, g in enumerate(gained) if g) and sum(got.values()) == filled and left == 0
+    assert np.array_equal(np.asarray(sia.image), want)
+    after = sia.volume(real=False)
+    assert 0 not in sia._x.present().tolist() and 0 not in sia.labels() and not set(gone) & set(sia.labels())
+    assert all(after[l] == before[l] + got.get(l, 0) for l in after)
+    assert sia._distance_cache == {} and sia.wall_distance() is not wall
+    with pytest.raises(RuntimeError):
+        wall.image()
+    assert sia.fill_erased_voxels() == {}                  # nothing is empty any more
+
+
+def test_apply_makes_the_tables_stale():
+    V = noise((7, 9, 11), 12)
+    ctx = _capi.Context(0)
+    try:
+        ctx.set_volume(V)
+        assert _code(ctx.nearest_extract) == _capi.TA_EINVAL                        # no extraction
+        ctx.extract(_capi.F_VOLUME, 12)
+        ctx.distance_extract(_capi.DIST_OWN_WALL, 0, UNIT, 0)
+        ctx.nearest_extract(0, None, UNIT)
+        assert _code(ctx.distance_get) == _code(ctx.nearest_get) == _capi.TA_OK      # both are current: they share no buffer
+        assert np.array_equal(ctx.nearest_image()[0].reshape(V.shape), brute((7, 9, 11), 12, UNIT)[0])
+        ctx.nearest_apply()
+        for getter in (ctx.distance_get, ctx.distance_image, ctx.nearest_get, ctx.nearest_image, ctx.nearest_debug, ctx.nearest_timing,
+                       ctx.nearest_apply, ctx.nearest_extract):
+            assert _code(getter) == _capi.TA_EINVAL
+        out = np.empty_like(V)
+        ctx.get_volume(out)
+        assert np.array_equal(out, ref.result(V, *brute((7, 9, 11), 12, UNIT)[:2])[0])
+        ctx.extract(_capi.F_VOLUME, 12)
+        ctx.nearest_extract(0, None, UNIT)
+        assert ctx.nearest_get()[1:] == (0, 0)
+        ctx.extract(_capi.F_VOLUME, 12)                    # a new ta_extract
+        assert _code(ctx.nearest_get) == _capi.TA_EINVAL
+        ctx.nearest_extract(0, None, UNIT)
+        ctx.set_volume(V)                                  # a new volume
+        assert _code(ctx.nearest_get) == _capi.TA_EINVAL
+    finally:
+        ctx.close()
+
+
+def test_slabs_are_refused():
+    import torch
+    V = noise((7, 9, 11), 12)
+    ctx = _capi.Context(0)
+    try:
+        for origin, halo in ((0, True), (7, False)):
+            t = torch.from_numpy(V.view(np.int16).copy()).cuda()
+            torch.cuda.synchronize()
+            ctx.set_volume_device(t.data_ptr(), 2, V.shape, a0_origin=origin, has_low_halo=halo, keep=t)
+            ctx.extract(_capi.F_VOLUME, 12)
+            assert _code(ctx.nearest_extract) == _capi.TA_EINVAL and _code(ctx.nearest_get) == _capi.TA_EINVAL
+    finally:
+        ctx.close()
+
+
+def test_an_image_of_another_dtype_and_layout_is_written_back():
+    V = tissue()
+    img = np.asfortranarray(V.astype(np.int32))            # neither the dtype nor the layout of the resident copy
+    sia = SpatialImageAnalysis(SpatialImage(img, voxelsize=(1.0, 1.0, 1.0)), return_type=DICT, background=BG)
+    cell = int(sia.labels()[4])
+    sia.remove_labels_from_image([cell], verbose=False)
+    erased = np.asarray(sia.image).copy()
+    assert erased.dtype == np.int32 and (erased == 0).sum() == (V == cell).sum()
+    n, d2 = ref.by_label_edt(erased, 0, UNIT)
+    want = ref.result(erased, n, d2)[0]
+    sia.fill_erased_voxels()
+    assert np.asarray(sia.image).dtype == np.int32 and np.array_equal(np.asarray(sia.image), want)
+
+
+def interior_cell(V):
+    """A label whose voxels touch neither the background nor the image margin."""
+    from scipy import ndimage
+    for l in np.unique(V):
+        around = ndimage.binary_dilation(V == l)
+        if l != BG and BG not in V[around] and not (around[[0, -1]].any() or around[:, [0, -1]].any() or around[:, :, [0, -1]].any()):
+            return int(l)
+    raise AssertionError("no interior cell")
+
+
+def test_round_trip_of_an_interior_cell():
+    V = synth.voronoi_labels((40, 48, 56), 50, 3, dtype=np.uint16)
+    sia = SpatialImageAnalysis(SpatialImage(V.copy(), voxelsize=(1.0, 1.0, 1.0)), return_type=DICT, background=BG)
+    cell = interior_cell(V)
+    size = int((V == cell).sum())
+    sia.remove_labels_from_image([cell], verbose=False)
+    gained = sia.fill_erased_voxels(not_from=BG)
+    filled = np.asarray(sia.image)
+    assert sum(gained.values()) == size and cell not in gained and BG not in gained
+    assert np.array_equal(filled[V != cell], V[V != cell]) and not np.isin(filled[V == cell], (0, cell, BG)).any()
+    assert dict((int(l), int(c)) for l, c in zip(*np.unique(filled[V == cell], return_counts=True))) == gained
+
+
+def test_expand_labels():
+    V, vs = tissue(), (0.5, 0.5, 1.0)
+    n, d2, (ids, stack) = ref.by_label_edt(V, BG, vs, per_label=True)
+    tie = np.sort(stack, axis=0)
+    assert ((tie[0] == tie[1]) & (V == BG) & (d2 <= 2.25)).any()
+    want, gained, filled, left = ref.result(V, n, d2, BG, 1.5 ** 2)
+    sia = SpatialImageAnalysis(SpatialImage(V.copy(), voxelsize=vs), return_type=DICT, background=BG)
+    got = sia.expand_labels(1.5)
+    assert got == dict((l, int(g)) for l, g in enumerate(gained) if g) and left > 0 and filled > 0
+    assert np.array_equal(np.asarray(sia.image), want)
+    voxels = SpatialImageAnalysis(SpatialImage(V.copy(), voxelsize=vs), return_type=DICT, background=BG)
+    voxels.expand_labels(2, real=False)                    # in voxels
+    n1, d1 = ref.by_label_edt(V, BG, UNIT)
+    assert np.array_equal(np.asarray(voxels.image), ref.result(V, n1, d1, BG, 4.0)[0])
+    into = SpatialImageAnalysis(SpatialImage(V.copy(), voxelsize=vs), return_type=DICT, background=BG)
+    cell = int(into.labels()[2])
+    into.expand_labels(1.0, into=cell)                     # the neighbours of one cell grow into it
+    nc, dc = ref.by_label_edt(V, cell, vs)
+    assert np.array_equal(np.asarray(into.image), ref.result(V, nc, dc, cell, 1.0)[0])
+    with pytest.warns(UserWarning):
+        bare = SpatialImageAnalysis(SpatialImage(V.copy(), voxelsize=vs), return_type=DICT)
+    with pytest.raises(ValueError):
+        bare.expand_labels(1.5)

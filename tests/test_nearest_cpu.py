@@ -1,0 +1,154 @@
+"""The references of the nearest-label maps against each other, the host side of the feature (NearestLabels on injected arrays), and
+the C ABI of include/tissue_scan_nearest.h as far as it goes without a GPU."""
+import ctypes
+import os
+import re
+
+import numpy as np
+import pytest
+
+import nearest_reference as ref
+from tissue_analysis_amd import NearestLabels, _capi
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+DYADIC = [(1.0, 1.0, 1.0), (0.5, 1.0, 2.0), (2.0, 0.25, 1.0)]
+OTHER = (0.3, 0.7, 1.1)
+
+
+def volumes():
+    rng = np.random.default_rng(21)
+    for shape in ((6, 7, 9), (1, 9, 40), (5, 1, 33), (1, 1, 50), (9, 8, 7)):
+        for labels in (5, 12):
+            yield (rng.integers(1, labels + 1, shape) * (rng.random(shape) < 0.5)).astype(np.uint16)
+
+
+def test_references_agree():
+    tie_volumes = 0
+    for V in volumes():
+        for not_from in (None, 1):
+            for spacing in DYADIC:
+                n, d2, ties = ref.brute(V, 0, spacing, not_from, ties=True)
+                m, e2 = ref.by_label_edt(V, 0, spacing, not_from)
+                assert n.dtype == m.dtype == np.uint32 and np.array_equal(n, m) and np.array_equal(d2, e2), (V.shape, spacing)
+                tie_volumes += bool(ties.any())
+            n, d2 = ref.brute(V, 0, OTHER, not_from)
+            m, e2, (ids, stack) = ref.by_label_edt(V, 0, OTHER, not_from, per_label=True)
+            assert np.all(np.abs(d2 - e2) <= 1e-12 * e2)
+            own = np.take_along_axis(stack, np.searchsorted(ids, n)[None], axis=0)[0]       # the chosen label's own distance
+            assert np.all(own <= e2 * (1 + 1e-12))
+    assert tie_volumes > 20
+
+
+def test_reference_known_values():
+    V = np.array([[[3, 0, 0, 0, 2, 0, 1]]])
+    n, d2, ties = ref.brute(V, 0, (1, 1, 0.5), ties=True)
+    assert n[0, 0].tolist() == [3, 3, 2, 2, 2, 1, 1] and d2[0, 0].tolist() == [0, 0.25, 1, 0.25, 0, 0.25, 0]
+    assert ties[0, 0].tolist() == [False, False, True, False, False, True, False]          # the smaller label wins both ties
+    n, d2 = ref.brute(V, 0, (1, 1, 1), not_from=2)
+    assert n[0, 0].tolist() == [3, 3, 3, 1, 1, 1, 1] and d2[0, 0].tolist() == [0, 1, 4, 9, 4, 1, 0]
+    image, gained, filled, left = ref.result(V, n, d2, 0, 1.0)
+    assert image[0, 0].tolist() == [3, 3, 0, 0, 2, 1, 1] and gained.tolist() == [0, 1, 0, 1] and (filled, left) == (2, 2)
+    n, d2 = ref.by_label_edt(np.zeros((2, 3, 4), dtype=np.uint16))
+    assert (n == ref.NONE).all() and np.isinf(d2).all()
+    image, gained, filled, left = ref.result(np.zeros((2, 3, 4), dtype=np.uint16), n, d2)
+    assert not image.any() and gained.tolist() == [0] and (filled, left) == (0, 24)          # without a site nothing is filled
+    n, d2 = ref.brute(V, 9)                                                                 # an empty label the volume does not hold
+    assert np.array_equal(n, V) and (d2 == 0).all()
+
+
+# ---- NearestLabels on host arrays ---------------------------------------------------------------------------------------------
+def host_table(V, empty=0, max_distance=None, spacing=(1.0, 1.0, 1.0), **kw):
+    n, d2 = ref.by_label_edt(V, empty, spacing)
+    max_d2 = np.inf if max_distance is None else max_distance ** 2
+    rows = int(V.max()) + 1
+    _, gained, filled, left = ref.result(V, n, d2, empty, max_d2, rows)
+    return NearestLabels(np.arange(rows), gained, filled, left, empty, None, max_distance, spacing, **kw), (n, d2)
+
+
+def test_nearest_labels_host_logic():
+    V = np.asfortranarray(np.array([[[3, 0, 0, 0, 2, 0, 1], [0, 0, 0, 0, 0, 0, 0]]], dtype=np.uint16))
+    applied = []
+    nl, (n, d2) = host_table(V, max_distance=1.0, source=lambda: V, images=lambda: (n, d2), apply=lambda: applied.append(1) or "swept")
+    assert len(nl) == 4 and nl.filled == 6 and nl.remaining == 5 and nl.max_d2 == 1.0 and nl.ms is None
+    assert nl.gained() == {1: 2, 2: 2, 3: 2} and nl.gained_voxels.tolist() == [0, 2, 2, 2]
+    assert np.array_equal(nl.nearest(), n) and np.array_equal(nl.distance(), np.sqrt(d2))
+    image = nl.image()
+    assert image.dtype == V.dtype and image.strides == V.strides
+    assert image[0].tolist() == [[3, 3, 0, 2, 2, 1, 1], [3, 0, 0, 0, 2, 0, 1]]
+    assert nl.filled_mask().sum() == 6 and V[0, 0].tolist() == [3, 0, 0, 0, 2, 0, 1]      # (the source is left alone)
+    assert nl.apply() == "swept" and applied == [1]
+    everything, _ = host_table(V, source=lambda: V, images=lambda: (n, d2))
+    assert everything.max_d2 == np.inf and everything.remaining == 0 and not (everything.image() == 0).any()
+    with pytest.raises(ValueError):
+        everything.apply()
+    bare, _ = host_table(V)
+    for call in (bare.nearest, bare.distance, bare.image, bare.apply):
+        with pytest.raises(ValueError):
+            call()
+    two = NearestLabels([4, 9], [0, 3], 3, 1, voxelsize=(0.5, 0.25), empty=7, not_from=4)
+    assert two.voxelsize == (0.5, 0.25, 1.0) and two.gained() == {9: 3} and (two.empty, two.not_from) == (7, 4)
+
+
+def test_nearest_labels_shape_errors():
+    with pytest.raises(ValueError):
+        NearestLabels([1, 2], [1], 1, 0)
+    with pytest.raises(ValueError):
+        NearestLabels([2, 1], [1, 0], 1, 0)
+    with pytest.raises(ValueError):
+        NearestLabels([1, 2], [1, 1], 3, 0)                # the rows do not sum to the total
+    with pytest.raises(ValueError):
+        NearestLabels([1], [0], 0, 0, voxelsize=(1.0,))
+    with pytest.raises(ValueError):
+        NearestLabels([1], [0], 0, 0, max_distance=-1.0).max_d2
+
+
+def test_analysis_methods_need_a_target():
+    from oracle import onepass
+    from tissue_analysis_amd import Extraction, SpatialImageAnalysis3D
+    V = np.ones((2, 2, 2), dtype=np.uint16)
+    with pytest.warns(UserWarning):
+        sia = SpatialImageAnalysis3D(V, extraction=Extraction.from_arrays(V.shape, onepass.extract(V)))
+    with pytest.raises(ValueError, match="background"):
+        sia.expand_labels(2.0)
+
+
+def test_slab_jobs_name_the_pass():
+    from tissue_analysis_amd.distributed import PipelinedSlabJob, SlabJob
+    for cls in (SlabJob, PipelinedSlabJob):
+        with pytest.raises(NotImplementedError, match="nearest"):
+            cls.nearest_labels(object.__new__(cls))
+
+
+# ---- the C ABI without a GPU --------------------------------------------------------------------------------------------------
+def declared():
+    text = open(os.path.join(ROOT, "include", "tissue_scan_nearest.h")).read()
+    return text, sorted(set(re.findall(r"TA_API\s+int\s+(ta_\w+)\s*\(", text)))
+
+
+def test_header_and_binding_agree():
+    text, names = declared()
+    assert names == sorted(_capi.NEAREST_SYMBOLS) and len(names) == 7
+    assert not set(_capi.NEAREST_SYMBOLS) & set(_capi.SYMBOLS)
+    assert re.search(r"TA_API\s+int\s+ta_nearest_debug\s*\(ta_ctx\*\s*ctx,\s*uint32_t\s+out\[4\]\)", text)
+    assert not re.search(r"TA_API\s+(?!int\s)", text)      # every entry point answers an int
+    lib = _capi.load()
+    for name in names:
+        assert hasattr(lib, name), name
+        assert getattr(lib, name).argtypes is not None and getattr(lib, name).restype is ctypes.c_int, name
+    assert lib.ta_version() == _capi.ABI_VERSION == 5
+    assert _capi.NEAREST_NOT_FROM == int(re.search(r"#define\s+TA_NEAREST_NOT_FROM\s+(\d+)u", text).group(1))
+    assert _capi.NEAREST_NONE == int(re.search(r"#define\s+TA_NEAREST_NONE\s+(0x[0-9A-F]+)u", text).group(1), 16) == ref.NONE
+
+
+def test_null_context_is_rejected_without_a_gpu():
+    lib = _capi.load()
+    spacing = (ctypes.c_double * 3)(1.0, 1.0, 1.0)
+    out = (ctypes.c_uint32 * 4)()
+    ms = ctypes.c_double(0.0)
+    calls = dict(ta_nearest_extract=(None, 0, 0, spacing, float("inf"), 0), ta_nearest_get=(None, None, None),
+                 ta_nearest_image=(None, 0, 0, None, None), ta_nearest_apply=(None,), ta_nearest_timing=(None, ctypes.byref(ms), None),
+                 ta_nearest_debug=(None, out), ta_nearest_set_batch=(None, 0))
+    assert sorted(calls) == sorted(_capi.NEAREST_SYMBOLS)
+    for name, args in calls.items():
+        assert getattr(lib, name)(*args) == _capi.TA_EINVAL, name
+        assert b"NULL" in lib.ta_last_error(), name

@@ -23,6 +23,7 @@ from .cell_junctions import CellJunctions, cell_junctions
 from .wall_geometry import WallGeometry, wall_geometry
 from .components import LabelComponents, label_components
 from .distance_map import DistanceMap, distance_map
+from .nearest_labels import NearestLabels
 from .shell_profile import ShellProfile
 from .property_graph import PropertyGraph
 from .graph_from_image import graph_from_image, property_graph_to_dataframe
@@ -30,7 +31,7 @@ from .graph_from_image import graph_from_image, property_graph_to_dataframe
 __all__ = ["SpatialImage", "NPLIST", "LIST", "DICT", "AbstractSpatialImageAnalysis",
            "SpatialImageAnalysis3D", "SpatialImageAnalysis", "Extraction", "extract_volume", "SignalStats", "SignalHistogram", "SignalQuantiles", "CellMeshes",
            "LabelOverlap", "label_overlap", "lineage_from_images", "CellJunctions", "cell_junctions", "WallGeometry", "wall_geometry",
-           "LabelComponents", "label_components", "DistanceMap", "distance_map", "ShellProfile",
+           "LabelComponents", "label_components", "DistanceMap", "distance_map", "NearestLabels", "ShellProfile",
            "dilation", "dilation_by", "real_indices", "return_list_of_vectors", "hollow_out_cells", "wall", "contact_surface",
            "coordinates_centering3D", "compute_covariance_matrix", "eigen_values_vectors", "distance",
            "PropertyGraph", "graph_from_image", "property_graph_to_dataframe"]

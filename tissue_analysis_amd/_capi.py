@@ -80,6 +80,12 @@ DISTANCE_SYMBOLS = ("ta_distance_extract", "ta_distance_get", "ta_distance_image
 DIST_OWN_WALL, DIST_FROM_LABEL = 0, 1  # TA_DIST_OWN_WALL / TA_DIST_FROM_LABEL
 DIST_EDGE_IS_SITE = 1                  # TA_DIST_EDGE_IS_SITE
 
+# every symbol include/tissue_scan_nearest.h declares (same library)
+NEAREST_SYMBOLS = ("ta_nearest_extract", "ta_nearest_get", "ta_nearest_image", "ta_nearest_apply", "ta_nearest_timing",
+                   "ta_nearest_debug", "ta_nearest_set_batch")
+NEAREST_NOT_FROM = 1                   # TA_NEAREST_NOT_FROM
+NEAREST_NONE = 0xFFFFFFFF              # TA_NEAREST_NONE
+
 # every symbol include/tissue_scan_profile.h declares (same library)
 PROFILE_SYMBOLS = ("ta_profile_extract", "ta_profile_get", "ta_profile_debug", "ta_profile_timing")
 PROF_SIGNAL = 1                        # TA_PROF_SIGNAL
@@ -229,6 +235,13 @@ def load():
         "ta_distance_timing": (ci, [vp, P(ctypes.c_double), P(ctypes.c_double)]),
         "ta_distance_set_batch": (ci, [vp, i64]),
         "ta_distance_debug": (ci, [vp, P(u32)]),
+        "ta_nearest_extract": (ci, [vp, u32, u32, P(ctypes.c_double), ctypes.c_double, u32]),
+        "ta_nearest_get": (ci, [vp, vp, vp]),
+        "ta_nearest_image": (ci, [vp, i64, i64, vp, vp]),
+        "ta_nearest_apply": (ci, [vp]),
+        "ta_nearest_timing": (ci, [vp, P(ctypes.c_double), P(ctypes.c_double)]),
+        "ta_nearest_debug": (ci, [vp, P(u32)]),
+        "ta_nearest_set_batch": (ci, [vp, i64]),
         "ta_profile_extract": (ci, [vp, ci, P(ctypes.c_double), u32]),
         "ta_profile_get": (ci, [vp, vp, vp, vp, vp, vp]),
         "ta_profile_debug": (ci, [vp, P(u32)]),
@@ -241,7 +254,7 @@ def load():
         "ta_sighist_timing": (ci, [vp, P(ctypes.c_double), P(ctypes.c_double)]),
     }
     for name in (SYMBOLS + SIGNAL_SYMBOLS + MESH_SYMBOLS + OVERLAP_SYMBOLS + JUNCTION_SYMBOLS + WALLGEO_SYMBOLS + COMPONENT_SYMBOLS
-                 + DISTANCE_SYMBOLS + PROFILE_SYMBOLS + SIGHIST_SYMBOLS):
+                 + DISTANCE_SYMBOLS + NEAREST_SYMBOLS + PROFILE_SYMBOLS + SIGHIST_SYMBOLS):
         fn = getattr(lib, name)      # AttributeError here == the .so does not match the header
         fn.restype, fn.argtypes = sig[name]
     if lib.ta_version() != ABI_VERSION:
@@ -772,6 +785,62 @@ class Context(object):
         out = (ctypes.c_uint32 * 4)()
         _check(self._lib.ta_distance_debug(self._h, out))
         return dict(row_groups=int(out[0]), voxel_groups=int(out[1]), init_groups=int(out[2]), column_launches=int(out[3]))
+
+    # -- nearest-label maps (include/tissue_scan_nearest.h)
+    def nearest_extract(self, empty_label=0, not_from_label=None, spacing=(1.0, 1.0, 1.0), max_d2=float("inf")):
+        """Enqueue the three passes of the exact nearest-label transform over the current extraction, and the counts of the voxels
+        every label gains: the voxels of `empty_label` (an id) are filled from all others, those of `not_from_label` (an id, None =
+        nothing excluded) are neither sites nor filled; an empty voxel is filled when its squared distance is <= max_d2.  spacing
+        in array-axis order."""
+        sp = [float(v) for v in spacing]
+        if len(sp) != 3:
+            raise ValueError("spacing must have three entries")
+        flags = 0 if not_from_label is None else NEAREST_NOT_FROM
+        _check(self._lib.ta_nearest_extract(self._h, int(empty_label) & 0xFFFFFFFF, int(not_from_label or 0) & 0xFFFFFFFF,
+                                            (ctypes.c_double * 3)(*sp), float(max_d2), flags))
+
+    def nearest_get(self):
+        """(gained u64[R], filled voxels, empty voxels left unfilled), rows as labels()."""
+        gained = np.zeros(getattr(self, "_max_label", 0) + 1, dtype=np.uint64)          # (no extraction yet: the library answers TA_EINVAL)
+        totals = np.zeros(2, dtype=np.uint64)
+        _check(self._lib.ta_nearest_get(self._h, gained.ctypes.data, totals.ctypes.data))
+        return gained, int(totals[0]), int(totals[1])
+
+    def nearest_image(self, first_plane=0, nplanes=None, nearest=True, d2=True):
+        """(uint32 nearest labels (ids; NEAREST_NONE without a site), float64 squared distances) of the voxels of `nplanes` buffer
+        planes from `first_plane` along memory axis 0 (None: all that follow), flat and in memory order; None for the one not asked
+        for."""
+        planes = self.owned_planes() + self._halo_planes
+        per_plane = int(np.prod(self._vol_layout[0])) // planes
+        if nplanes is None:
+            nplanes = planes - int(first_plane)
+        count = max(int(nplanes), 0) * per_plane
+        n = np.zeros(count, dtype=np.uint32) if nearest else None
+        d = np.zeros(count, dtype=np.float64) if d2 else None
+        _check(self._lib.ta_nearest_image(self._h, int(first_plane), int(nplanes), None if n is None else n.ctypes.data,
+                                          None if d is None else d.ctypes.data))
+        return n, d
+
+    def nearest_apply(self):
+        """In place on the resident volume: every filled voxel takes its nearest label.  Every table is stale afterwards."""
+        _check(self._lib.ta_nearest_apply(self._h))
+
+    def nearest_timing(self):
+        """(milliseconds of the row pass and the two column passes, milliseconds of the counting pass)."""
+        a, b = ctypes.c_double(0.0), ctypes.c_double(0.0)
+        _check(self._lib.ta_nearest_timing(self._h, ctypes.byref(a), ctypes.byref(b)))
+        return a.value, b.value
+
+    def nearest_set_batch(self, columns=0):
+        """Columns a launch of a column pass takes (0 = automatic); the results do not depend on it."""
+        _check(self._lib.ta_nearest_set_batch(self._h, int(columns)))
+
+    def nearest_debug(self):
+        """What the last nearest_extract launched: the workgroups of the row pass, of the counting pass and of the apply pass, and
+        the launches of the column kernel along both axes together."""
+        out = (ctypes.c_uint32 * 4)()
+        _check(self._lib.ta_nearest_debug(self._h, out))
+        return dict(row_groups=int(out[0]), count_groups=int(out[1]), apply_groups=int(out[2]), column_launches=int(out[3]))
 
     # -- distance-shell profiles (include/tissue_scan_profile.h)
     def profile_extract(self, edges2, signal=False):

@@ -1,0 +1,190 @@
+// ta_api_nearest.hip -- the C ABI of include/tissue_scan_nearest.h on top of kernels_nearest.hip.
+#include "../../include/tissue_scan_nearest.h"
+#include "ta_ctx.h"
+
+#include <cmath>
+
+namespace {
+
+const char* const NO_RESULTS = "no nearest-label map for the current extraction (run ta_nearest_extract)";
+
+bool nearest_current(const ta_ctx* c) { return c->near.seq != 0 && c->extracted && c->near.seq == c->extract_seq; }
+
+uint64_t voxels(const ta_ctx* c) { return (uint64_t)c->mdims[0] * (uint64_t)c->mdims[1] * (uint64_t)c->mdims[2]; }
+
+// byte offsets of the parts of NearestState::table for R rows
+struct NearestLayout {
+    uint64_t gained = 0, totals, flags, bytes;
+    explicit NearestLayout(uint64_t R) { totals = 8 * R; flags = totals + 16; bytes = flags + 4 * ta::NEAR_NFLAGS; }
+};
+
+// columns of a launch along an axis of `len` voxels with `columns` columns: whole waves; what the option says, else what fits the cap
+uint64_t batch_columns(const ta_ctx* c, uint64_t len, uint64_t columns) {
+    const uint64_t b = c->near.opt_batch > 0 ? ((uint64_t)c->near.opt_batch + 63) / 64 * 64
+                                             : std::max<uint64_t>(64, ta::NEAR_WORK_CAP / (len * ta::NEAR_STACK_ENTRY) / 64 * 64);
+    return std::min(b, (columns + 63) / 64 * 64);
+}
+
+// an id as the volume the passes read stores it; false when no voxel can hold it
+bool stored_label(const ta_ctx* c, uint32_t id, uint32_t* stored) {
+    *stored = id;
+    if (!c->ids.compact) return c->itemsize == 4 || id <= 0xFFFFu;
+    const auto& ids = c->ids.h_ids;                 // the passes read ranks: the id's rank, if the volume holds it
+    const auto it = std::lower_bound(ids.begin(), ids.end(), id);
+    *stored = (uint32_t)(it - ids.begin());
+    return it != ids.end() && *it == id;
+}
+
+int nearest_ready(ta_ctx* c) {
+    if (!c) return fail(TA_EINVAL, "ctx is NULL");
+    if (!nearest_current(c)) return fail(TA_EINVAL, NO_RESULTS);
+    return use_device(c);
+}
+
+}  // namespace
+
+// a new label volume (or new label values in it): the images and the counts are stale
+void nearest_on_new_volume(ta_ctx* c) { c->near.seq = 0; }
+
+extern "C" {
+
+TA_API int ta_nearest_set_batch(ta_ctx* c, int64_t columns) {
+    if (!c) return fail(TA_EINVAL, "ctx is NULL");
+    if (columns < 0 || columns > (1ll << 30)) return fail(TA_EINVAL, "the columns of a batch must be 0 (automatic) or in [1, 2^30]");
+    c->near.opt_batch = columns;
+    return TA_OK;
+}
+
+TA_API int ta_nearest_extract(ta_ctx* c, uint32_t empty_label, uint32_t not_from_label, const double spacing[3], double max_d2, uint32_t flags) {
+    if (!c) return fail(TA_EINVAL, "ctx is NULL");
+    if (flags & ~TA_NEAREST_NOT_FROM) return fail(TA_EINVAL, "bad nearest-label flags 0x%x", flags);
+    if (!spacing) return fail(TA_EINVAL, "spacing is NULL");
+    for (int k = 0; k < 3; ++k)
+        if (!(spacing[k] > 0.0) || !std::isfinite(spacing[k])) return fail(TA_EINVAL, "spacing[%d]=%g is not positive and finite", k, spacing[k]);
+    if (!(max_d2 >= 0.0)) return fail(TA_EINVAL, "max_d2=%g is negative or not a number", max_d2);
+    if (!c->vol) return fail(TA_EINVAL, "no label volume set");
+    if (c->first_owned != 0 || c->a_origin != 0)
+        return fail(TA_EINVAL, "the nearest-label pass does not take a slab (an exact transform needs halos of unbounded depth)");
+    int rc = use_device(c);
+    if (rc != TA_OK) return rc;
+    if (!c->extracted) return fail(TA_EINVAL, "the nearest-label pass needs a ta_extract of the current volume first");
+    if ((rc = finish_extract(c)) != TA_OK) return rc;
+    c->near.seq = 0;
+    const uint64_t nvox = voxels(c), R = (uint64_t)c->max_label + 1;
+    const NearestLayout L(R);
+
+    ta::NearestArgs a = {};
+    a.vol = sweep_vol(c);
+    a.n0 = c->mdims[0]; a.n1 = c->mdims[1]; a.n2 = c->mdims[2];
+    for (int k = 0; k < 3; ++k) a.w[k] = spacing[c->perm[k]];
+    a.max_d2 = max_d2;
+    a.has_empty = stored_label(c, empty_label, &a.empty);
+    if (flags & TA_NEAREST_NOT_FROM) a.has_not_from = stored_label(c, not_from_label, &a.not_from);
+
+    uint64_t batch[2], work = 0;                    // [0]: along memory axis 1, [1]: along memory axis 0
+    for (int k = 0; k < 2; ++k) {
+        const int axis = 1 - k;
+        const uint64_t len = (uint64_t)c->mdims[axis];
+        batch[k] = batch_columns(c, len, ta::nearest_columns(a, axis));
+        work = std::max(work, len * batch[k] * ta::NEAR_STACK_ENTRY);
+    }
+    if ((rc = c->near.f.reserve(nvox * 8)) != TA_OK) return rc;
+    if ((rc = c->near.lab.reserve(nvox * 4)) != TA_OK) return rc;
+    if ((rc = c->near.work.reserve(work)) != TA_OK) return rc;
+    if ((rc = c->near.table.reserve(L.bytes)) != TA_OK) return rc;
+    if ((rc = ensure_events(c->near.ev)) != TA_OK) return rc;
+    a.f = (double*)c->near.f.p;
+    a.lab = (uint32_t*)c->near.lab.p;
+
+    TA_HIP(hipEventRecord(c->near.ev[0], c->stream));
+    uint32_t launched[4] = {0, 0, 0, 0};
+    launched[0] = ta::launch_nearest_rows(c->stream, a, c->itemsize);
+    for (int k = 0; k < 2; ++k) {
+        const int axis = 1 - k;
+        const uint64_t columns = ta::nearest_columns(a, axis);
+        for (uint64_t first = 0; first < columns; first += batch[k], ++launched[3])
+            ta::launch_nearest_columns(c->stream, a, axis, first, std::min(batch[k], columns - first), c->near.work.p, batch[k]);
+    }
+    TA_HIP(hipGetLastError());
+    TA_HIP(hipEventRecord(c->near.ev[1], c->stream));
+    char* tp = (char*)c->near.table.p;
+    ta::NearestTable t = {};
+    t.gained = (unsigned long long*)(tp + L.gained); t.totals = (unsigned long long*)(tp + L.totals); t.flags = (uint32_t*)(tp + L.flags);
+    t.max_label = c->max_label;
+    TA_HIP(hipMemsetAsync(tp, 0, L.bytes, c->stream));
+    launched[1] = ta::launch_nearest_count(c->stream, a, c->itemsize, t);
+    launched[2] = ta::nearest_voxel_groups(a);
+    TA_HIP(hipGetLastError());
+    TA_HIP(hipEventRecord(c->near.ev[2], c->stream));
+    std::copy(launched, launched + 4, c->near.launched);
+    c->near.args = a;
+    c->near.seq = c->extract_seq;
+    c->near.rows = (uint32_t)R;
+    return TA_OK;
+}
+
+TA_API int ta_nearest_get(ta_ctx* c, uint64_t* gained, uint64_t totals[2]) {
+    int rc = nearest_ready(c);
+    if (rc != TA_OK) return rc;
+    const uint64_t R = c->near.rows;
+    const NearestLayout L(R);
+    const char* tp = (const char*)c->near.table.p;
+    uint32_t flags[ta::NEAR_NFLAGS] = {0, 0, 0, 0};
+    TA_HIP(hipMemcpyAsync(flags, tp + L.flags, sizeof(flags), hipMemcpyDeviceToHost, c->stream));
+    if (gained) TA_HIP(hipMemcpyAsync(gained, tp + L.gained, 8 * R, hipMemcpyDeviceToHost, c->stream));
+    if (totals) TA_HIP(hipMemcpyAsync(totals, tp + L.totals, 16, hipMemcpyDeviceToHost, c->stream));
+    TA_HIP(hipStreamSynchronize(c->stream));
+    if (flags[ta::NEAR_FLAG_RANGE])
+        return fail(TA_ERANGE, "the nearest-label pass met a label above max_label=%u (the volume changed since ta_extract)", c->max_label);
+    return TA_OK;
+}
+
+TA_API int ta_nearest_image(ta_ctx* c, int64_t first_plane, int64_t nplanes, uint32_t* nearest, double* d2) {
+    int rc = nearest_ready(c);
+    if (rc != TA_OK) return rc;
+    if (first_plane < 0 || nplanes < 0 || first_plane > c->mdims[0] || nplanes > c->mdims[0] - first_plane)
+        return fail(TA_EINVAL, "planes %lld .. %lld are not inside the buffer's %lld", (long long)first_plane, (long long)(first_plane + nplanes),
+                    (long long)c->mdims[0]);
+    if (!nplanes) return TA_OK;
+    const uint64_t plane = (uint64_t)c->mdims[1] * (uint64_t)c->mdims[2], from = (uint64_t)first_plane * plane, count = (uint64_t)nplanes * plane;
+    if (nearest) TA_HIP(hipMemcpyAsync(nearest, (const uint32_t*)c->near.lab.p + from, count * 4, hipMemcpyDeviceToHost, c->stream));
+    if (d2) TA_HIP(hipMemcpyAsync(d2, (const double*)c->near.f.p + from, count * 8, hipMemcpyDeviceToHost, c->stream));
+    TA_HIP(hipStreamSynchronize(c->stream));
+    if (nearest && c->ids.compact) {                // ranks -> ids
+        const auto& ids = c->ids.h_ids;
+        for (uint64_t v = 0; v < count; ++v)
+            if (nearest[v] < ids.size()) nearest[v] = ids[nearest[v]];
+    }
+    return TA_OK;
+}
+
+TA_API int ta_nearest_apply(ta_ctx* c) {
+    int rc = nearest_ready(c);
+    if (rc != TA_OK) return rc;
+    const bool compact = c->ids.compact;
+    (void)ta::launch_nearest_apply(c->stream, c->near.args, c->itemsize, const_cast<void*>(c->vol), compact ? c->ids.compact_vol.p : nullptr,
+                                   compact ? (const uint32_t*)c->ids.census_ids.p : nullptr, compact ? (uint32_t)c->ids.census_n : 0u);
+    TA_HIP(hipGetLastError());
+    volume_labels_changed(c);
+    return TA_OK;
+}
+
+TA_API int ta_nearest_debug(ta_ctx* c, uint32_t out[4]) {
+    int rc = nearest_ready(c);
+    if (rc != TA_OK) return rc;
+    if (out) std::copy(c->near.launched, c->near.launched + 4, out);
+    return TA_OK;
+}
+
+TA_API int ta_nearest_timing(ta_ctx* c, double* ms_pass, double* ms_after) {
+    int rc = nearest_ready(c);
+    if (rc != TA_OK) return rc;
+    TA_HIP(hipEventSynchronize(c->near.ev[2]));
+    double pass = 0.0, after = 0.0;
+    if ((rc = elapsed_ms(c->near.ev[0], c->near.ev[1], &pass)) != TA_OK || (rc = elapsed_ms(c->near.ev[1], c->near.ev[2], &after)) != TA_OK) return rc;
+    if (ms_pass) *ms_pass = pass;
+    if (ms_after) *ms_after = after;
+    return TA_OK;
+}
+
+}  // extern "C"

@@ -5,6 +5,7 @@
 #pragma once
 #include "../../include/tissue_scan.h"
 #include "ta_kernels.h"
+#include "ta_nearest.h"
 
 #include <algorithm>
 #include <cstring>
@@ -182,6 +183,21 @@ struct DistanceState {
     void release() { d2.release(); work.release(); table.release(); destroy_events(ev); }
 };
 
+// nearest-label maps (include/tissue_scan_nearest.h)
+struct NearestState {
+    DevBuf f;                                           // f64[voxels]: D2
+    DevBuf lab;                                         // u32[voxels]: N, as the volume the passes read stores labels
+    DevBuf work;                                        // envelope stacks of a batch of columns: f f64[len][B] | boundaries f64 | positions i32 | labels u32 | boundary labels u32
+    DevBuf table;                                       // gained u64[R] | totals u64[2] | flags u32[4]
+    uint64_t seq = 0;                                   // extract_seq of the extraction the results belong to, 0 = none
+    uint32_t rows = 0;                                  // max_label + 1 of that extraction
+    int64_t opt_batch = 0;                              // ta_nearest_set_batch: 0 = automatic
+    ta::NearestArgs args = {};                          // what the last pass ran with: ta_nearest_apply fills by the same rule
+    uint32_t launched[4] = {0, 0, 0, 0};                // what the last pass launched (ta_nearest_debug)
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};     // passes begin, end | counts end
+    void release() { f.release(); lab.release(); work.release(); table.release(); destroy_events(ev); }
+};
+
 // distance-shell profiles (include/tissue_scan_profile.h)
 struct ProfileState {
     DevBuf out;                                         // flags u32[4] | edges f64[65] | n u64[R][K] | with a signal: sum | sumsq[2] | min u32 | max u32
@@ -320,6 +336,7 @@ struct ta_ctx {
     WallGeoState wg;
     ComponentState cc;
     DistanceState dist;
+    NearestState near;
     ProfileState prof;
     SigHistState sh;
 };
@@ -349,7 +366,7 @@ inline ta::PairTable pair_table(ta_ctx* c) {
 // Drain the stream and validate the flags of the last pass; grows the adjacency table and re-runs when it overflowed.  ta_api.hip.
 int finish_extract(ta_ctx* c);
 
-// A new label volume (for the sparse ids, the overlap, the junctions, the components, the distance maps and their profiles also: new label values in it).  Defined by
+// A new label volume (for the sparse ids, the overlap, the junctions, the components, the distance maps and their profiles, the nearest-label maps also: new label values in it).  Defined by
 // the file of each concern, called by the core's volume_replaced / volume_labels_changed (the junctions' and the components' also by
 // ta_volume_rerank: the caller edited the labels in place).
 void walls_on_new_volume(ta_ctx* c);
@@ -360,6 +377,7 @@ void junctions_on_new_volume(ta_ctx* c);
 void wallgeo_on_new_volume(ta_ctx* c);
 void components_on_new_volume(ta_ctx* c);
 void distance_on_new_volume(ta_ctx* c);
+void nearest_on_new_volume(ta_ctx* c);
 void profile_on_new_volume(ta_ctx* c);
 void profile_on_new_distance(ta_ctx* c);              // a new ta_distance_extract: the image the table was read from is gone.  ta_api_profile.hip
 void profile_on_new_signal(ta_ctx* c);                // a new signal image: stale when the pass read the old one.  ta_api_profile.hip

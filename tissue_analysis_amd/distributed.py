@@ -319,6 +319,10 @@ class SlabJob(object):
         raise NotImplementedError("the distance maps (tissue_scan_distance.h) do not run on a slab: an exact Euclidean distance "
                                   "transform needs halos of unbounded depth")
 
+    def nearest_labels(self, *args, **kwargs):
+        raise NotImplementedError("the nearest-label maps (tissue_scan_nearest.h) do not run on a slab: an exact Euclidean "
+                                  "transform needs halos of unbounded depth")
+
     def owned_view(self):
         return self.vol[1:] if self.has_low_halo else self.vol
 
@@ -597,6 +601,10 @@ class PipelinedSlabJob(object):
 
     def distance_map(self, *args, **kwargs):
         raise NotImplementedError("the distance maps (tissue_scan_distance.h) do not run on a slab: an exact Euclidean distance "
+                                  "transform needs halos of unbounded depth")
+
+    def nearest_labels(self, *args, **kwargs):
+        raise NotImplementedError("the nearest-label maps (tissue_scan_nearest.h) do not run on a slab: an exact Euclidean "
                                   "transform needs halos of unbounded depth")
 
     def owned_view(self):

@@ -632,6 +632,42 @@ class ResidentVolume(object):
             shape[slow] = flat.size // (self.host.size // shape[slow])
         return np.lib.stride_tricks.as_strided(flat, shape=shape, strides=strides)
 
+    def nearest_labels(self, empty=0, not_from=None, voxelsize=(1.0, 1.0, 1.0), max_distance=None):
+        """For every voxel of the resident volume the nearest voxel that is neither `empty` nor `not_from` (None: nothing excluded),
+        the smallest label among several that are equally near: a `NearestLabels` (per label the empty voxels it would gain within
+        `max_distance`, None = no limit) whose rows are those of the current extraction (swept first when there is none), in the ids
+        of the image.  Three passes over the volume on the GPU; `.nearest()`, `.distance()` and `.image()` of the result download the
+        images, `.apply()` is `apply_nearest()`."""
+        import time
+        from .nearest_labels import resident_nearest_labels
+        t0 = time.perf_counter()
+        nl = resident_nearest_labels(self, empty, not_from, voxelsize, max_distance)
+        self.ms["nearest_labels"] = (time.perf_counter() - t0) * 1e3
+        return nl
+
+    def nearest_images(self, first_plane=0, nplanes=None):
+        """(uint32 image of the nearest labels, float64 image of the SQUARED distances) of the last `nearest_labels()`, with the axes
+        and the layout of the image; of `nplanes` planes from `first_plane` along the slowest memory axis only when those are given."""
+        out = []
+        for flat in self.ctx.nearest_image(first_plane, nplanes):
+            shape = list(self.host.shape)
+            strides = [s // self.host.dtype.itemsize * flat.dtype.itemsize for s in self.host.strides]
+            if flat.size != self.host.size:
+                slow = max((d for d in range(3) if shape[d] != 1), key=lambda d: strides[d])
+                shape[slow] = flat.size // (self.host.size // shape[slow])
+            out.append(np.lib.stride_tricks.as_strided(flat, shape=shape, strides=strides))
+        return tuple(out)
+
+    def apply_nearest(self, features=_capi.F_ALL):
+        """Every voxel the last `nearest_labels()` fills takes its nearest label, on the resident volume AND on `self.host` (copied
+        back), then sweep the new volume."""
+        self.ctx.nearest_apply()
+        if not self.host.flags.writeable:
+            self.host = self.host.copy(order="K")
+            self.is_input = False
+        self.ctx.get_volume(self.host)
+        return self.extract(features)
+
     def wall_geometry(self, voxelsize=(1.0, 1.0, 1.0)):
         """The geometry of every wall of the resident volume: a `WallGeometry` (signed face counts, first and second sums of the
         face centres) whose rows are the pairs of the current extraction (swept first when there is none), in the ids of the

@@ -703,6 +703,37 @@ class AbstractSpatialImageAnalysis(object):
         labels = self.label_request(labels)
         return self.convert_return(self.distance_from(real=real).of_labels(labels, "min2"), labels)
 
+    # -- nearest-label maps (include/tissue_scan_nearest.h; three passes over the resident volume on the GPU)
+    def nearest_labels(self, empty=0, max_distance=None, not_from=None, real=True):
+        """For every voxel the nearest voxel that is neither `empty` nor `not_from` (None: nothing excluded), the smallest label
+        among several that are equally near: a `NearestLabels` in the ids of the image, with this analysis' voxel size (ones with
+        real=False, and then `max_distance` is in voxels).  `.gained()` tells what every label would gain from the empty voxels
+        within `max_distance` (None: all of them), `.image()` is the image `fill_erased_voxels()` would leave.  Not cached."""
+        vs = tuple(float(v) for v in self._voxelsize) if real else (1.0, 1.0, 1.0)
+        return self._resident_rows().nearest_labels(int(empty), not_from, vs, max_distance)
+
+    def fill_erased_voxels(self, empty=0, max_distance=None, not_from=None, real=True):
+        """Modify the image so that every voxel of `empty` (what `remove_small_fragments`, `remove_labels_from_image` and
+        `remove_stack_margin_labels_from_image` erase to) takes the label of the nearest voxel that is neither `empty` nor
+        `not_from`, the smallest label among several that are equally near; with `max_distance` only the voxels that far from one
+        at most (inclusive; real units, or voxels with real=False).  Returns {label: voxels gained}."""
+        rv = self._resident_rows()
+        nl = self.nearest_labels(empty, max_distance, not_from, real)
+        gained = nl.gained()
+        if nl.filled:                                      # (no new label value: nothing to check against the image dtype)
+            self._edit_image(rv, np.zeros(0, dtype=np.int64), 0, lambda rv, table: nl.apply())
+        return gained
+
+    def expand_labels(self, distance, into=None, real=True):
+        """Modify the image so that the labels grow by `distance` into the voxels of `into` (default: the background), every
+        voxel going to the label it lies nearest to: skimage.segmentation.expand_labels with a stated rule for ties (the
+        smallest label).  Returns {label: voxels gained}."""
+        if into is None:
+            into = self.background()
+        if into is None:
+            raise ValueError("expand_labels needs a label to grow into (this analysis has no background)")
+        return self.fill_erased_voxels(empty=int(into), max_distance=distance, real=real)
+
     # -- distance-shell profiles (include/tissue_scan_profile.h; one pass over labels, distances and signal on the GPU)
     def _shell_profile(self, edges, signal, from_label, edge_is_wall, real=True):
         dm = self.wall_distance(edge_is_wall, real) if from_label is None else self.distance_from(from_label, edge_is_wall, real)
