@@ -17,6 +17,7 @@ from .spatial_image_analysis import (NPLIST, LIST, DICT, AbstractSpatialImageAna
 from .extraction import Extraction, extract_volume
 from .signal_stats import SignalStats
 from .signal_quantiles import SignalHistogram, SignalQuantiles
+from .signal_moments import SignalMoments
 from .cell_meshes import CellMeshes
 from .label_overlap import LabelOverlap, label_overlap, lineage_from_images
 from .cell_junctions import CellJunctions, cell_junctions
@@ -29,7 +30,7 @@ from .property_graph import PropertyGraph
 from .graph_from_image import graph_from_image, property_graph_to_dataframe
 
 __all__ = ["SpatialImage", "NPLIST", "LIST", "DICT", "AbstractSpatialImageAnalysis",
-           "SpatialImageAnalysis3D", "SpatialImageAnalysis", "Extraction", "extract_volume", "SignalStats", "SignalHistogram", "SignalQuantiles", "CellMeshes",
+           "SpatialImageAnalysis3D", "SpatialImageAnalysis", "Extraction", "extract_volume", "SignalStats", "SignalHistogram", "SignalQuantiles", "SignalMoments", "CellMeshes",
            "LabelOverlap", "label_overlap", "lineage_from_images", "CellJunctions", "cell_junctions", "WallGeometry", "wall_geometry",
            "LabelComponents", "label_components", "DistanceMap", "distance_map", "NearestLabels", "ShellProfile",
            "dilation", "dilation_by", "real_indices", "return_list_of_vectors", "hollow_out_cells", "wall", "contact_surface",

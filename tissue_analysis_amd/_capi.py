@@ -100,6 +100,11 @@ SIGRANK_NONE = 0xFFFFFFFF              # value of a rank >= n
 SIGHIST_SLOTS = 39                     # TA_SH_SLOTS of csrc/ta_sighist.h: rows of 256 counters in a workgroup's LDS table
 SIGHIST_MAX_GROUPS = 65536             # TA_SH_MAX_GROUPS: workgroups of the digit pass at most (the plan: tests/sighist_reference.py)
 
+# every symbol include/tissue_scan_sigmoments.h declares (same library)
+SIGMOM_SYMBOLS = ("ta_sigmom_extract", "ta_sigmom_get", "ta_sigmom_debug", "ta_sigmom_timing")
+SIGMOM_SLOTS = 448                     # SM_SLOTS of csrc/ta_sigmoments.h: rows of a workgroup's LDS table
+SIGMOM_MAX_GROUPS = 1024               # SM_MAX_GROUPS: workgroups of the pass at most (the plan: tests/sigmoment_reference.py)
+
 
 def exchange_words(capacity_pairs):
     """uint64 words of one exchange block (TA_EXCHANGE_WORDS in include/tissue_scan.h)."""
@@ -252,9 +257,13 @@ def load():
         "ta_sigrank_get": (ci, [vp, vp]),
         "ta_sighist_debug": (ci, [vp, P(u32)]),
         "ta_sighist_timing": (ci, [vp, P(ctypes.c_double), P(ctypes.c_double)]),
+        "ta_sigmom_extract": (ci, [vp]),
+        "ta_sigmom_get": (ci, [vp, vp, vp, vp, vp]),
+        "ta_sigmom_debug": (ci, [vp, P(u32)]),
+        "ta_sigmom_timing": (ci, [vp, P(ctypes.c_double)]),
     }
     for name in (SYMBOLS + SIGNAL_SYMBOLS + MESH_SYMBOLS + OVERLAP_SYMBOLS + JUNCTION_SYMBOLS + WALLGEO_SYMBOLS + COMPONENT_SYMBOLS
-                 + DISTANCE_SYMBOLS + NEAREST_SYMBOLS + PROFILE_SYMBOLS + SIGHIST_SYMBOLS):
+                 + DISTANCE_SYMBOLS + NEAREST_SYMBOLS + PROFILE_SYMBOLS + SIGHIST_SYMBOLS + SIGMOM_SYMBOLS):
         fn = getattr(lib, name)      # AttributeError here == the .so does not match the header
         fn.restype, fn.argtypes = sig[name]
     if lib.ta_version() != ABI_VERSION:
@@ -365,6 +374,8 @@ class Context(object):
         _check(self._lib.ta_volume_set(self._h, ctypes.c_void_p(a.ctypes.data), a.dtype.itemsize,
                                        _i64x3(a.shape), _i64x3(a.strides)))
         self._vol_layout = (tuple(a.shape), tuple(s // a.dtype.itemsize for s in a.strides))
+        # the library's order of the axes in memory: by decreasing stride, size-1 axes first
+        self._memory_axes = tuple(sorted(range(3), key=lambda d: -(float("inf") if a.shape[d] == 1 else a.strides[d])))
         self._owned_planes = int(a.shape[int(np.argmax(a.strides))])         # planes of the slowest MEMORY axis
         self._halo_planes = 0
 
@@ -462,6 +473,7 @@ class Context(object):
                                               _i64x3(buf_dims), int(a0_origin), int(bool(has_low_halo))))
         d = [int(x) for x in buf_dims]
         self._vol_layout = (tuple(d), (d[1] * d[2], d[2], 1))
+        self._memory_axes = (0, 1, 2)
         self._keep = [keep]
         self._owned_planes = int(buf_dims[0]) - (1 if has_low_halo else 0)
         self._halo_planes = 1 if has_low_halo else 0
@@ -918,6 +930,37 @@ class Context(object):
         _check(self._lib.ta_sighist_timing(self._h, ctypes.byref(a), ctypes.byref(b)))
         some = lambda v: None if v != v else v
         return some(a.value), some(b.value)
+
+    # -- signal-weighted moments (include/tissue_scan_sigmoments.h)
+    def sigmom_extract(self):
+        """Enqueue the signal-moment pass over the current extraction and the signal image of the context."""
+        _check(self._lib.ta_sigmom_extract(self._h))
+        self._sigmom_rows = self._max_label + 1
+
+    def sigmom_rows(self):
+        """(n u64[R], w u64[R], m1 u64[R, 3], m2 u64[R, 6, 2] (lo, hi words)), rows as labels(); MEMORY-axis order, axis 0 counted
+        from the first owned plane of the buffer (`memory_axes()` has the array axis of each)."""
+        R = getattr(self, "_sigmom_rows", 1)                   # (no pass yet: the library answers TA_EINVAL)
+        n, w = np.zeros(R, dtype=np.uint64), np.zeros(R, dtype=np.uint64)
+        m1, m2 = np.zeros((R, 3), dtype=np.uint64), np.zeros((R, 6, 2), dtype=np.uint64)
+        _check(self._lib.ta_sigmom_get(self._h, n.ctypes.data, w.ctypes.data, m1.ctypes.data, m2.ctypes.data))
+        return n, w, m1, m2
+
+    def sigmom_debug(self):
+        """Diagnostics of the last signal-moment pass: records that missed a workgroup's LDS table (spills) and the launch plan
+        (tiles_per_group, groups)."""
+        out = (ctypes.c_uint32 * 4)()
+        _check(self._lib.ta_sigmom_debug(self._h, out))
+        return dict(spills=int(out[0]), tiles_per_group=int(out[2]), groups=int(out[3]))
+
+    def sigmom_timing(self):
+        ms = ctypes.c_double(0.0)
+        _check(self._lib.ta_sigmom_timing(self._h, ctypes.byref(ms)))
+        return ms.value
+
+    def memory_axes(self):
+        """perm[k] = the array axis of memory axis k of the resident volume (slowest first), as the library orders them."""
+        return self._memory_axes
 
     def max_label(self):
         v = ctypes.c_uint32(0)

@@ -61,14 +61,14 @@ extern "C" {
 TA_API int ta_signal_set(ta_ctx* c, const void* host_ptr, int itemsize, const int64_t dims[3], const int64_t strides_bytes[3]) {
     if (!c) return fail(TA_EINVAL, "ctx is NULL");
     const int rc = companion_set_host(c, c->sig.img, SIGNAL, host_ptr, itemsize, dims, strides_bytes);
-    if (rc == TA_OK) { c->sig.seq = 0; profile_on_new_signal(c); sighist_on_new_signal(c); }     // (the results are stale only once a new signal is in place: deliberate, as inherited)
+    if (rc == TA_OK) { c->sig.seq = 0; profile_on_new_signal(c); sighist_on_new_signal(c); sigmom_on_new_signal(c); }     // (the results are stale only once a new signal is in place: deliberate, as inherited)
     return rc;
 }
 
 TA_API int ta_signal_set_device(ta_ctx* c, const void* dev_ptr, int itemsize) {
     if (!c) return fail(TA_EINVAL, "ctx is NULL");
     const int rc = companion_set_device(c, c->sig.img, SIGNAL, dev_ptr, itemsize);
-    if (rc == TA_OK) { c->sig.seq = 0; profile_on_new_signal(c); sighist_on_new_signal(c); }
+    if (rc == TA_OK) { c->sig.seq = 0; profile_on_new_signal(c); sighist_on_new_signal(c); sigmom_on_new_signal(c); }
     return rc;
 }
 

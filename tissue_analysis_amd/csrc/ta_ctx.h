@@ -225,6 +225,16 @@ struct SigHistState {
     void release() { out.release(); rank.release(); destroy_events(ev); }
 };
 
+// signal-weighted moments (include/tissue_scan_sigmoments.h)
+struct SigMomentState {
+    DevBuf out;                                         // flags u32[4] | n u64[R] | w u64[R] | m1 u64[R][3] | m2 u64[R][6][2]
+    uint64_t seq = 0;                                   // extract_seq of the extraction the rows belong to, 0 = none
+    uint32_t rows = 0;                                  // max_label + 1 of that extraction
+    ta::RangePlan plan;                                 // what the last pass was launched with (ta_sigmom_debug)
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    void release() { out.release(); destroy_events(ev); }
+};
+
 // wall voxels and wall medians (ta_api_walls.hip)
 struct WallVoxelState {
     DevBuf counts;                                      // per-chunk record counts, then offsets
@@ -339,6 +349,7 @@ struct ta_ctx {
     NearestState near;
     ProfileState prof;
     SigHistState sh;
+    SigMomentState sm;
 };
 
 inline int use_device(ta_ctx* c) {
@@ -383,6 +394,8 @@ void profile_on_new_distance(ta_ctx* c);              // a new ta_distance_extra
 void profile_on_new_signal(ta_ctx* c);                // a new signal image: stale when the pass read the old one.  ta_api_profile.hip
 void sighist_on_new_volume(ta_ctx* c);
 void sighist_on_new_signal(ta_ctx* c);                // a new signal image: both tables read the old one.  ta_api_sighist.hip
+void sigmom_on_new_volume(ta_ctx* c);
+void sigmom_on_new_signal(ta_ctx* c);                 // a new signal image: the rows read the old one.  ta_api_sigmoments.hip
 void walls_on_new_labels(ta_ctx* c);                  // new label values in the same volume: the staging buffer is kept.  ta_api_walls.hip
 
 // The two ways the voxels change (ta_api.hip).  volume_replaced: the tail of ta_volume_set / ta_volume_set_device, called once vol,

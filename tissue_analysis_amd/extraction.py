@@ -541,6 +541,17 @@ class ResidentVolume(object):
         self.ms["signal_quantiles"] = (time.perf_counter() - t0) * 1e3
         return sq
 
+    def signal_moments(self, signal, voxelsize=(1.0, 1.0, 1.0)):
+        """Where in every cell an intensity image (uint8 / uint16, the shape of the labels) sits: a `SignalMoments` (signal-weighted
+        centroid, polarity, covariance and inertia axes from exact integer sums) whose rows line up with the last extraction.
+        One upload of the signal and one pass over labels + signal on the GPU."""
+        import time
+        from .signal_moments import resident_signal_moments
+        t0 = time.perf_counter()
+        sm = resident_signal_moments(self, signal, voxelsize)
+        self.ms["signal_moments"] = (time.perf_counter() - t0) * 1e3
+        return sm
+
     def meshes(self, labels=None, sub_factor=1, voxelsize=(1.0, 1.0, 1.0)):
         """The exact voxel-face surface meshes of the cells `labels` (ids; None = every label, background included) of
         host[::s, ::s, ::s]: a `CellMeshes`.  Count, scan and emit on the GPU, over the current extraction (swept first when

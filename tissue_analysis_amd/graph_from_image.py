@@ -128,7 +128,9 @@ def tissue_tables(analysis, labels, background, properties, property_as_real=Tru
     """The vertex / edge tables of the tissue graph from the sweep results held by `analysis`.
     `labels`: the vertex ids (any order, distinct).  Returns a PropertyGraph whose columns are plain numpy arrays.
     With an intensity image `signal`, 'mean_signal' (vertex: cell_signal's mean), 'median_signal' (vertex: signal_median) and
-    'wall_signal' (edge: wall_signal's face-weighted mean) can be asked for too.  'wall_centroid', 'wall_normal' and 'wall_projected_area' (edge: the columns of
+    'wall_signal' (edge: wall_signal's face-weighted mean) can be asked for too, and 'signal_barycenter' and 'signal_polarity'
+    (vertex: signal_center_of_mass and the vector of signal_polarity, which run the signal-moment pass; a property list without
+    them does not).  'wall_centroid', 'wall_normal' and 'wall_projected_area' (edge: the columns of
     `analysis.wall_geometry()`) run the wall-geometry pass; a property list without them does not.  'n_components' (vertex:
     the face-connected blobs the label consists of, `analysis.label_components()`) runs the component pass, likewise; and so do
     'inscribed_radius' (vertex: `analysis.inscribed_radius()`) and 'depth' (vertex: `analysis.cell_depth()`, which needs a
@@ -211,6 +213,12 @@ def tissue_tables(analysis, labels, background, properties, property_as_real=Tru
     if signal is not None and 'median_signal' in properties:
         medians = analysis._resident_rows().signal_quantiles(np.asarray(signal), [0.5], 'midpoint')
         graph.set_vertex_column('median_signal', medians.of_labels(ids)[:, 0], asked)
+    if signal is not None and ('signal_barycenter' in properties or 'signal_polarity' in properties):
+        moments = analysis._signal_moments(signal)
+        if 'signal_barycenter' in properties:
+            graph.set_vertex_column('signal_barycenter', moments.of_labels(ids, 'centroid', real), asked, _show_vector)
+        if 'signal_polarity' in properties:
+            graph.set_vertex_column('signal_polarity', moments.of_labels(ids, 'polarity', real), asked, _show_vector)
     wall_geometry_columns = [p for p in ('wall_centroid', 'wall_normal', 'wall_projected_area') if p in properties]
     if wall_geometry_columns:
         geo = analysis.wall_geometry()
@@ -270,7 +278,8 @@ graph_from_image3D = graph_from_image2D        # (the reference's two entry poin
 def graph_from_image(image, labels=None, background=1, spatio_temporal_properties=None, property_as_real=True,
                      ignore_cells_at_stack_margins=True, min_contact_area=None, signal=None):
     """TGI:260-284.  `image`: a label image or an analysis object of this package.  `signal`: an intensity image (uint8 /
-    uint16) of the same shape, which makes the properties 'mean_signal', 'median_signal' (vertex) and 'wall_signal' (edge) available."""
+    uint16) of the same shape, which makes the properties 'mean_signal', 'median_signal', 'signal_barycenter', 'signal_polarity'
+    (vertex) and 'wall_signal' (edge) available."""
     if isinstance(image, AbstractSpatialImageAnalysis):
         shape = np.shape(image.image)
         if labels is None:

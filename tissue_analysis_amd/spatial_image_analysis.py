@@ -266,6 +266,7 @@ class AbstractSpatialImageAnalysis(object):
         self._walls = None
         self._wall_medians = None
         self._signal_cache = None
+        self._sigmom_cache = None
         self._mesh_cache = {}
         self._junctions = None
         self._wall_geometry = None
@@ -591,6 +592,59 @@ class AbstractSpatialImageAnalysis(object):
             return dict((k, float(col[r]) if r >= 0 else float('nan')) for k, r in zip(keys, rows.tolist()))
         a, b = stats.wall_side_means
         return dict((k, (float(a[r]), float(b[r])) if r >= 0 else (float('nan'), float('nan'))) for k, r in zip(keys, rows.tolist()))
+
+    # -- where in the cell the signal sits (include/tissue_scan_sigmoments.h; one pass on the GPU)
+    def _signal_moments(self, signal):
+        """SignalMoments of `signal` over this image: uploaded and reduced once per array OBJECT, like `_signal_stats`."""
+        cache = getattr(self, "_sigmom_cache", None)
+        if cache is not None and cache[0] is signal:
+            return cache[1]
+        moments = self._resident_rows().signal_moments(np.asarray(signal), self._voxelsize)
+        self._sigmom_cache = (signal, moments)
+        return moments
+
+    def _signal_moment_column(self, signal, labels, column, real):
+        labels = self.label_request(labels)
+        values = self._signal_moments(signal).of_labels(labels, column, real)
+        if len(labels) == 1:
+            return values[0]
+        return self.convert_return(values if self.return_type == NPLIST else list(values), labels)
+
+    def signal_center_of_mass(self, signal, labels=None, real=True):
+        """Per label the centroid of the intensity image `signal` (uint8 / uint16, the image's shape) over the label's voxels,
+        what scipy.ndimage.center_of_mass(signal, image, labels) gives (times the voxel size with `real`); NaN for a label
+        without signal.  Returned like center_of_mass()."""
+        return self._signal_moment_column(signal, labels, "centroid", real)
+
+    def signal_polarity(self, signal, labels=None, real=True, normalised=False):
+        """Per label the vector from the cell's barycentre to its signal centroid; normalised: divided by the cell's radius of
+        gyration (dimensionless, 0 for a uniform signal).  Returned like center_of_mass()."""
+        labels = self.label_request(labels)
+        m = self._signal_moments(signal)
+        rows = m.rows_of(np.asarray(labels, dtype=np.int64).reshape(-1), missing=-1)
+        values = m.polarity(real, normalised)[np.where(rows >= 0, rows, 0)]
+        values[rows < 0] = np.nan
+        if len(labels) == 1:
+            return values[0]
+        return self.convert_return(values if self.return_type == NPLIST else list(values), labels)
+
+    def signal_inertia_axis(self, signal, labels=None, real=True):
+        """Per label the axes along which the signal is spread: (eigenvectors as rows, eigenvalues) of the signal-weighted
+        covariance of the voxel positions, by decreasing eigenvalue; the counterpart of inertia_axis(), returned like it."""
+        labels = self.label_request(labels)
+        m = self._signal_moments(signal)
+        rows = m.rows_of(np.asarray(labels, dtype=np.int64).reshape(-1), missing=-1)
+        vecs, vals = m.inertia_axis(real)
+        at = np.where(rows >= 0, rows, 0)
+        vecs, vals = vecs[at], vals[at]
+        vecs[rows < 0] = np.nan
+        vals[rows < 0] = np.nan
+        if len(labels) == 1:
+            return return_list_of_vectors(vecs[0]), vals[0]
+        if self.return_type == NPLIST:
+            return vecs, vals
+        axes = [list(v) for v in vecs]
+        return self.convert_return(axes, labels), self.convert_return(list(vals), labels)
 
     # -- exact histograms, medians and quantiles of a signal image (include/tissue_scan_sighist.h; radix select on the GPU)
     def signal_quantiles(self, signal, q, labels=None, method='linear'):
