@@ -1,12 +1,13 @@
-"""The launch plans of the component, junction and distance passes, and label volumes that take them past their limits.
+"""The launch plans of the component, junction, distance and nearest-label passes, and label volumes that take them past their limits.
 
-kernels_components.hip, kernels_junctions.hip and kernels_distance.hip cap the grids of the kernels that stride over their work: a
+kernels_components.hip, kernels_junctions.hip, kernels_distance.hip and kernels_nearest.hip cap the grids of the kernels that stride over their work: a
 workgroup then takes a second trip through its loop.  This file restates, in plain Python and without the library, (1) the grid each
 launcher computes for a shape and which loop takes a second trip, (2) where inside a tile, a task or a chunk a voxel or a block lies,
 and (3) label volumes that are cheap to make at the shapes that cross each limit, with the closed forms of their tables where the
 references of tests/ would take too long.  test_launch_limits_cpu.py checks the restatement and the closed forms against the
 references at small shapes; test_gpu_component_limits.py, test_gpu_junction_limits.py and test_gpu_distance_limits.py run the volumes
-through the kernels and compare the plan with what the device reports (ta_components_debug, ta_junctions_debug, ta_distance_debug).
+through the kernels and compare the plan with what the device reports (ta_components_debug, ta_junctions_debug, ta_distance_debug).  The nearest-label pass
+has its plan here and its volumes in tests/nearest_cases.py; test_gpu_nearest_limits.py compares with ta_nearest_debug.
 """
 import collections
 
@@ -27,6 +28,10 @@ JN_KEY_MAX_GROUPS = 8192                                  # key kernel: 256 reco
 # csrc/ta_distance.h, csrc/kernels_distance.hip
 DIST_ROW_MAX_GROUPS, DIST_VOXEL_MAX_GROUPS, DIST_INIT_MAX_GROUPS = 1 << 16, 1 << 14, 1 << 12
 DIST_ROWS_PER_GROUP, DIST_CHUNK = 4, 64                   # row pass: one wave a row, 64 voxels at a time
+# csrc/ta_nearest.h, csrc/kernels_nearest.hip
+NEAR_ROW_MAX_GROUPS, NEAR_VOXEL_MAX_GROUPS = 1 << 16, 1 << 14
+NEAR_ROWS_PER_GROUP = 4                                   # row pass: one wave a row
+NEAR_WORK_CAP, NEAR_STACK_ENTRY = 1 << 30, 28             # bytes of the column passes' stacks, bytes of an entry
 
 
 def _ceil(a, b):
@@ -378,3 +383,39 @@ def far_label(dtype=np.uint32):
     V = np.ones(MANY_TABLE_ROWS_DIMS, dtype=dtype)
     V[1:3, 2:6, 20:40] = MANY_TABLE_ROWS_LABEL
     return V
+
+
+# ---- nearest labels ---------------------------------------------------------------------------------------------------------------
+NearestPlan = collections.namedtuple("NearestPlan", "rows row_groups row_trips voxels voxel_groups voxel_trips")
+
+
+def nearest_plan(dims):
+    """dims in memory order.  The row pass gives a workgroup four rows at a time; the counting and the apply pass 256 voxels."""
+    n0, n1, n2 = (int(d) for d in dims)
+    rows, voxels = n0 * n1, n0 * n1 * n2
+    rg, rt = strided_groups(rows, NEAR_ROW_MAX_GROUPS, NEAR_ROWS_PER_GROUP)
+    vg, vt = strided_groups(voxels, NEAR_VOXEL_MAX_GROUPS)
+    return NearestPlan(rows, rg, rt, voxels, vg, vt)
+
+
+def nearest_second_trip(dims):
+    """(the first row of the row pass's second trip, the first voxel of the streaming kernels' second trip), None where there is none."""
+    p = nearest_plan(dims)
+    return (p.row_groups * NEAR_ROWS_PER_GROUP if p.row_trips > 1 else None, p.voxel_groups * THREADS if p.voxel_trips > 1 else None)
+
+
+def nearest_column_launches(dims):
+    """Launches of the column kernel along memory axis 1 and along memory axis 0 together, with the automatic batch."""
+    n0, n1, n2 = (int(d) for d in dims)
+    total = 0
+    for length, columns in ((n1, n2 * n0), (n0, n2 * n1)):
+        batch = min(max(64, NEAR_WORK_CAP // (length * NEAR_STACK_ENTRY) // 64 * 64), _ceil(columns, 64) * 64)
+        total += _ceil(columns, batch)
+    return total
+
+
+def nearest_stack_bytes(dims):
+    """Bytes of the envelope stacks with the automatic batch: the larger of the two column passes'."""
+    n0, n1, n2 = (int(d) for d in dims)
+    return max(length * min(max(64, NEAR_WORK_CAP // (length * NEAR_STACK_ENTRY) // 64 * 64), _ceil(columns, 64) * 64) * NEAR_STACK_ENTRY
+               for length, columns in ((n1, n2 * n0), (n0, n2 * n1)))

@@ -1,8 +1,11 @@
 """References for the nearest-label maps (include/tissue_scan_nearest.h), host only.
 
-Two of them, which share nothing with the kernels and nothing with each other:
+Three of them, which share nothing with the kernels and no arithmetic with each other:
 
-  brute         every pair of voxels.  For power-of-two spacings in exact integer arithmetic (the spacings are scaled to integers, the
+  brute_sites   every voxel against every site, a few planes at a time: its cost grows with the sites, not with the square of the
+                voxels, so it reaches the volumes that cross the launch caps.  Power-of-two spacings only, in exact integers; beside
+                N and D2 it returns `ways`, the number of distinct labels at exactly the minimal distance.
+  brute         every pair of voxels. For power-of-two spacings in exact integer arithmetic (the spacings are scaled to integers, the
                 result divided by a power of two: no rounding anywhere); for other spacings in float64, ((a0 + a1) + a2).  N is the
                 smallest label among the sites at exactly the minimal distance.  At most 4096 voxels: the pair matrix is N x N.
   by_label_edt  at any size.  For every site label l in ascending order D2_l from scipy.ndimage.distance_transform_edt(V != l,
@@ -10,8 +13,8 @@ Two of them, which share nothing with the kernels and nothing with each other:
                 distance would lose the last bit); then N = ids[argmin over l] -- argmin returns the first minimum, which is the
                 smallest label -- and D2 = min over l.
 
-Both return (N uint32, D2 float64) with the shape of V; N is NONE and D2 +inf where there is no site.  filled() and result() apply
-the definitions of "filled" on top of them."""
+All begin their answer with (N uint32, D2 float64) with the shape of V; N is NONE and D2 +inf where there is no site.  filled() and
+result() apply the definitions of "filled" on top of them."""
 import math
 
 import numpy as np
@@ -62,6 +65,38 @@ def brute(V, empty=0, spacing=(1.0, 1.0, 1.0), not_from=None, ties=False):
     if ties:
         out += ((np.where(at_best, labels[None, :], -1).max(axis=1) != nearest).reshape(V.shape),)
     return out
+
+
+def brute_sites(V, empty=0, spacing=(1.0, 1.0, 1.0), not_from=None, budget=1 << 22):
+    """(N, D2, ways) at any size with few sites: every voxel against every site, whole planes of axis 0 at a time so that no array
+    has more than about `budget` elements.  Power-of-two spacings only, in the exact integers of brute().  ways (int32) is the number
+    of distinct labels among the sites at exactly the minimal distance, 0 where there is no site."""
+    V = np.asarray(V)
+    assert V.ndim == 3 and is_dyadic(spacing), "exact integers need power-of-two spacings"
+    ratios = [float(s).as_integer_ratio() for s in spacing]
+    den = max(d for _, d in ratios)
+    w = [n * (den // d) for n, d in ratios]
+    assert sum((w[a] * V.shape[a]) ** 2 for a in range(3)) < 2 ** 53
+    where = np.argwhere(site_mask(V, empty, not_from))
+    if where.shape[0] == 0:
+        return np.full(V.shape, NONE, dtype=np.uint32), np.full(V.shape, np.inf), np.zeros(V.shape, dtype=np.int32)
+    labels = V[tuple(where.T)].astype(np.int64)
+    order = np.argsort(labels, kind="stable")
+    where, labels = where[order], labels[order]          # ascending labels: the first site at the minimum has the smallest label
+    groups = np.flatnonzero(np.r_[True, labels[1:] != labels[:-1]])
+    along = [(w[a] * (np.arange(V.shape[a], dtype=np.int64)[None, :] - where[:, a, None])) ** 2 for a in range(3)]      # [site][position]
+    N = np.empty(V.shape, dtype=np.uint32)
+    D2 = np.empty(V.shape, dtype=np.float64)
+    ways = np.empty(V.shape, dtype=np.int32)
+    planes = max(1, budget // (labels.size * V.shape[1] * V.shape[2]))
+    for q in range(0, V.shape[0], planes):
+        d = along[0][:, q:q + planes, None, None] + along[1][:, None, :, None] + along[2][:, None, None, :]
+        best = d.min(axis=0)
+        at_best = d == best[None]
+        N[q:q + planes] = labels[at_best.argmax(axis=0)]
+        D2[q:q + planes] = best.astype(np.float64) / float(den * den)
+        ways[q:q + planes] = at_best.sum(axis=0) if groups.size == labels.size else np.logical_or.reduceat(at_best, groups, axis=0).sum(axis=0)
+    return N, D2, ways
 
 
 def label_d2(V, label, spacing):

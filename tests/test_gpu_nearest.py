@@ -5,7 +5,11 @@ power of two, for uint16 and uint32 and every memory layout.
 Few labels on small integer grids make ties common, and every test asserts that its reference has voxels with two labels equally
 near, so the tie rule (the smallest label) cannot go untested.  The shapes are the smallest at which the passes can still go wrong:
 rows across the 64-voxel chunk of the row pass with the site carried over (130, 70), more columns than one 256-lane workgroup, more
-than one batch of columns (the batch is set to one wave of 64 through ta_nearest_set_batch), axes of one voxel, a long axis 0."""
+than one batch of columns (the batch is set to one wave of 64 through ta_nearest_set_batch), axes of one voxel, a long axis 0.
+
+Noise meets two labels equally near, in envelopes two or three entries deep.  Ties of many labels, where parabola after parabola pops
+its predecessor at one and the same boundary, and the carry of the row pass from chunk to chunk are in test_gpu_nearest_ties.py; volumes past the launch
+caps in test_gpu_nearest_limits.py."""
 import ctypes
 import functools
 import itertools

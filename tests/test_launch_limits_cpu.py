@@ -11,6 +11,7 @@ import components_reference as cref
 import distance_reference as dref
 import junction_reference as jref
 import launch_limits as ll
+import nearest_cases
 from tissue_analysis_amd import _capi, synth
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -45,11 +46,18 @@ def test_the_constants_are_those_of_the_kernel_sources():
     assert constant(h, "DIST_INIT_MAX_GROUPS") == ll.DIST_INIT_MAX_GROUPS == 1 << 12
     k = source("kernels_distance.hip")
     assert all(name in k for name in ("DIST_ROW_MAX_GROUPS", "DIST_VOXEL_MAX_GROUPS", "DIST_INIT_MAX_GROUPS")) and "1u << 1" not in k
+    h = source("ta_nearest.h")
+    assert constant(h, "NEAR_ROW_MAX_GROUPS") == ll.NEAR_ROW_MAX_GROUPS == 1 << 16
+    assert constant(h, "NEAR_VOXEL_MAX_GROUPS") == ll.NEAR_VOXEL_MAX_GROUPS == 1 << 14
+    assert constant(h, "NEAR_WORK_CAP") == ll.NEAR_WORK_CAP and constant(h, "NEAR_STACK_ENTRY") == ll.NEAR_STACK_ENTRY
+    k = source("kernels_nearest.hip")
+    assert "NEAR_ROW_MAX_GROUPS" in k and "NEAR_VOXEL_MAX_GROUPS" in k and "1u << 1" not in k
+    assert "blockIdx.x * 4 + (threadIdx.x >> 6)" in k and ll.NEAR_ROWS_PER_GROUP == 4
 
 
 def test_the_debug_calls_refuse_a_null_context_without_a_gpu():
     lib = _capi.load()
-    for name in ("ta_components_debug", "ta_junctions_debug", "ta_distance_debug"):
+    for name in ("ta_components_debug", "ta_junctions_debug", "ta_distance_debug", "ta_nearest_debug"):
         assert getattr(lib, name)(None, None) == _capi.TA_EINVAL, name
         assert b"NULL" in lib.ta_last_error()
 
@@ -252,3 +260,33 @@ def test_half_space_closed_form():
         assert np.array_equal(d2, want)
         for g, t in zip(table, dref.table(V, want, 3)):
             assert g.dtype == t.dtype and np.array_equal(g, t)
+
+
+# ---- nearest labels ---------------------------------------------------------------------------------------------------------------
+def test_nearest_plans_and_the_volume_that_crosses_both_caps():
+    assert ll.nearest_plan((7, 9, 11)) == (63, 16, 1, 693, 3, 1) and ll.nearest_second_trip((7, 9, 11)) == (None, None)
+    assert ll.nearest_plan((1, 1, 1)) == (1, 1, 1, 1, 1, 1) and ll.nearest_plan((65536, 4, 16))[1:3] == (65536, 1)
+    assert ll.nearest_plan((65536, 4, 16))[4:] == (16384, 1) and ll.nearest_plan((65536, 4, 17))[4:] == (16384, 2)
+    assert ll.nearest_plan((1, 262145, 1))[1:3] == (65536, 2) and ll.nearest_column_launches((7, 9, 11)) == 2
+    assert ll.nearest_column_launches((3, 1 << 20, 64)) == 3 + 6  # stacks of 2^20 entries: a wave of 64 columns a launch; of 3: 12 782 592 of 2^26
+    dims = nearest_cases.CAP_DIMS
+    for d in (dims, (dims[0], dims[2], dims[1])):                  # (a layout that swaps the two fast axes crosses the voxel cap only)
+        p = ll.nearest_plan(d)
+        assert p.voxels == 4482594 > ll.NEAR_VOXEL_MAX_GROUPS * ll.THREADS == 4194304 and (p.voxel_groups, p.voxel_trips) == (16384, 2)
+    p = ll.nearest_plan(dims)
+    assert p.rows == 263682 > ll.NEAR_ROW_MAX_GROUPS * ll.NEAR_ROWS_PER_GROUP == 262144 and (p.row_groups, p.row_trips) == (65536, 2)
+    assert p.voxels % 64 == 34                                     # the last wave of the counting kernel is partly past the volume
+    row, voxel = ll.nearest_second_trip(dims)
+    assert divmod(row, dims[1]) == (1020, 4) and np.unravel_index(voxel, dims) == (960, 3, 13)
+    assert nearest_cases.CAP_LATE == 1021 and nearest_cases.CAP_MIDDLE == 960
+    assert ll.nearest_column_launches(dims) == 2 and 120e6 < ll.nearest_stack_bytes(dims) < 130e6 < ll.NEAR_WORK_CAP
+    V = nearest_cases.cap_sites()
+    planes = np.nonzero(V)[0]
+    assert V.shape == dims and V.dtype == np.uint16 and sorted(V[V != 0].tolist()) == list(range(1, 17))
+    assert (planes >= 1021).sum() >= 3 and ((planes >= 960) & (planes <= 1019)).sum() >= 3 and (planes < 960).sum() >= 3
+    # the control: the same sites in a volume under both caps
+    p = ll.nearest_plan(nearest_cases.CAP_CONTROL_DIMS)
+    assert p.row_groups < ll.NEAR_ROW_MAX_GROUPS and p.voxel_groups < ll.NEAR_VOXEL_MAX_GROUPS and (p.row_trips, p.voxel_trips) == (1, 1)
+    assert p.rows > 0.99 * 262144 and p.voxels > 0.99 * 4194304
+    C = nearest_cases.cap_sites(nearest_cases.CAP_CONTROL_DIMS)
+    assert sorted(C[C != 0].tolist()) == list(range(1, 17))

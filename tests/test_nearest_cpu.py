@@ -1,12 +1,14 @@
 """The references of the nearest-label maps against each other, the host side of the feature (NearestLabels on injected arrays), and
 the C ABI of include/tissue_scan_nearest.h as far as it goes without a GPU."""
 import ctypes
+import itertools
 import os
 import re
 
 import numpy as np
 import pytest
 
+import nearest_cases as cases
 import nearest_reference as ref
 from tissue_analysis_amd import NearestLabels, _capi
 
@@ -54,6 +56,121 @@ def test_reference_known_values():
     assert not image.any() and gained.tolist() == [0] and (filled, left) == (0, 24)          # without a site nothing is filled
     n, d2 = ref.brute(V, 9)                                                                 # an empty label the volume does not hold
     assert np.array_equal(n, V) and (d2 == 0).all()
+
+
+# ---- the reference by sites, and the cases of test_gpu_nearest_ties.py ------------------------------------------------------------
+def test_brute_sites_is_brute():
+    tie_volumes = 0
+    for V in volumes():
+        for not_from in (None, 1):
+            for spacing in DYADIC:
+                n, d2, ties = ref.brute(V, 0, spacing, not_from, ties=True)
+                m, e2, ways = ref.brute_sites(V, 0, spacing, not_from, budget=1 << 14)          # several planes, and one, at a time
+                assert m.dtype == np.uint32 and e2.dtype == np.float64 and np.array_equal(n, m) and np.array_equal(d2, e2)
+                assert ways.shape == V.shape and np.array_equal(ways >= 2, ties) and (ways >= 1).all()
+                tie_volumes += bool(ties.any())
+    assert tie_volumes > 20
+    V = np.array([[[3, 0, 0, 0, 2, 0, 1, 0, 3]]])
+    n, d2, ways = ref.brute_sites(V, 0, (1, 1, 0.5))
+    assert n[0, 0].tolist() == [3, 3, 2, 2, 2, 1, 1, 1, 3] and ways[0, 0].tolist() == [1, 1, 2, 1, 1, 2, 1, 2, 1]
+    n, d2, ways = ref.brute_sites(np.array([[[4, 0, 4, 0, 2]]]), 0)                            # two sites of one label are one way
+    assert n[0, 0].tolist() == [4, 4, 4, 2, 2] and ways[0, 0].tolist() == [1, 1, 1, 2, 1]
+    n, d2, ways = ref.brute_sites(np.zeros((2, 3, 4), dtype=np.uint16))
+    assert (n == ref.NONE).all() and np.isinf(d2).all() and not ways.any()
+    with pytest.raises(AssertionError):
+        ref.brute_sites(V, 0, OTHER)
+
+
+# ways >= 3 per shell: of the spheres at least the 100 asked of them; of the ellipsoids what the reference gives, which is all there is
+SHELL_WAYS3 = dict(r9=113, r26=303, r41=387, half20=19, half36=31, mixed80=19, mixed144=23)
+
+
+@pytest.mark.parametrize("name", list(cases.SHELLS))
+def test_shells_hold_the_ties_they_are_built_for_and_the_restated_passes_get_them(name):
+    spacing, weights, c, pad, count = cases.SHELLS[name]
+    sh = cases.shell(name)
+    assert sh.sites.shape == (count, 3) and len(set(map(tuple, sh.sites.tolist()))) == count
+    assert all(sum((w * (x - o)) ** 2 for w, x, o in zip(weights, p, sh.centre)) == c for p in sh.sites.tolist())
+    every = list(cases.assignments(count))
+    assert len(every) == 4 + 2 * count and all(sorted(labels.tolist()) == list(range(1, count + 1)) for _, labels in every)
+    assert all(any(labels[j] == 1 for _, labels in every[4:]) for j in range(count))       # the smallest label visits every site
+    for k, (_, labels) in enumerate(every):
+        V = cases.shell_volume(sh, labels)
+        n, d2, ways = ref.brute_sites(V, 0, spacing)
+        if k == 0:
+            assert ways[sh.centre] == count and d2[sh.centre] == cases.shell_d2(name) and n[sh.centre] == 1
+            assert int((ways >= 3).sum()) == SHELL_WAYS3[name] and (name[0] != "r" or SHELL_WAYS3[name] >= 100)
+        for perm in cases.shell_layouts(name):
+            m, e2 = cases.model(V, perm, spacing)
+            assert np.array_equal(n, m) and np.array_equal(d2, e2), (name, k, perm)
+
+
+def test_off_centre_shells_and_rows_by_the_restated_passes():
+    sh = cases.shell("r9")
+    for column in cases.OFF_CENTRE_COLUMNS:
+        for _, labels in itertools.islice(cases.assignments(30), 4):
+            V = cases.shell_volume(sh, labels, np.uint16, cases.OFF_CENTRE_SHAPE, (5, 5, column))
+            n, d2, ways = ref.brute_sites(V, 0, cases.UNIT)
+            assert ways[5, 5, column] == 30 and (ways[:, :, column - 1:column + 2] >= 2).any(axis=(0, 1)).all()     # ties across a chunk's end
+            for perm in cases.PERMS:
+                m, e2 = cases.model(V, perm, cases.UNIT)
+                assert np.array_equal(n, m) and np.array_equal(d2, e2)
+    V = cases.row_carry_rows()
+    assert V.shape == (1, 11, 200) and [sorted(r) for r in cases.CARRY_ROWS[:6:2]] == [[60, 68], [1, 127], [3, 189]]
+    n, d2, ties = ref.brute(V, 0, cases.ROW_SPACING, ties=True)
+    m, e2, ways = ref.brute_sites(V, 0, cases.ROW_SPACING)
+    assert np.array_equal(n, m) and np.array_equal(d2, e2) and np.array_equal(ways >= 2, ties)
+    assert n[0, :6, 64].tolist() == [2, 2, 3, 3, 4, 8] and ways[0, :6, 64].tolist() == [2, 2, 2, 2, 1, 1]
+    assert n[0, 4:6, 96].tolist() == [4, 4] and ways[0, 4:6, 96].tolist() == [2, 2] and d2[0, 4, 96] == 93.0 ** 2
+    assert n[0, 6].tolist() == [5] * 200 and n[0, 7].tolist() == [6] * 200 and d2[0, 7, 0] == 199.0 ** 2
+    assert n[0, 8, 60:68].tolist() == [11] * 4 + [10] * 4 and n[0, 8, 96] == 10 and n[0, 8, 97] == 12 and ways[0, 8, 96] == 2
+    assert (d2[0, 9] >= 256.0 ** 2).all() and np.array_equal(n[0, 10], V[0, 10]) and not d2[0, 10].any()
+    for perm in cases.PERMS:
+        m, e2 = cases.model(V, perm, cases.ROW_SPACING)
+        assert np.array_equal(n, m) and np.array_equal(d2, e2)
+
+
+RULES = ("chain", "boundary", "previous")
+
+
+def misses(V, spacing, perms, rule):
+    """Voxels at which the restated passes without `rule` give another label than the reference (D2 does not depend on the rules)."""
+    n, d2, _ = ref.brute_sites(V, 0, spacing)
+    total = 0
+    for perm in perms:
+        m, e2 = cases.model(V, perm, spacing, **{rule: False})
+        assert np.array_equal(d2, e2)
+        total += int((n != m).sum())
+    return total
+
+
+@pytest.mark.parametrize("rule", RULES)
+def test_every_dropped_tie_rule_is_caught_by_the_shells(rule):
+    """A kernel that drops one of the three tie rules gives a wrong label on a shell, in the layouts and with the label assignments
+    test_gpu_nearest_ties.py runs.  Measured: every shell catches every rule within its four random assignments."""
+    for name in cases.SHELLS:
+        spacing = cases.SHELLS[name][0]
+        sh = cases.shell(name)
+        caught = sum(misses(cases.shell_volume(sh, labels), spacing, cases.shell_layouts(name), rule) > 0
+                     for _, labels in itertools.islice(cases.assignments(len(sh.sites)), 4))
+        assert caught >= 1, name
+
+
+def test_the_noise_of_the_parity_test_does_not_catch_a_boundary_label_dropped_on_a_chained_pop():
+    """Why the shells exist: `carried = tl` in place of `carried = umin(tl, tb)` in the column kernel passes all five volumes of
+    test_gpu_nearest.py::test_parity_with_brute_force in every layout and with every spacing that test uses.  In noise the envelopes
+    are two or three entries deep and no boundary label that matters has to outlive a second pop.  The two other rules the noise does catch."""
+    import test_gpu_nearest as old
+    marks = [m for m in old.test_parity_with_brute_force.pytestmark if m.name == "parametrize" and m.args[0] == "shape,labels"]
+    assert len(marks) == 1 and len(marks[0].args[1]) == 5
+    caught = dict((rule, 0) for rule in RULES)
+    for shape, labels in marks[0].args[1]:
+        V = old.noise(shape, labels)
+        for spacing in (old.UNIT, old.HALF, old.MIXED):
+            caught["chain"] += misses(V, spacing, cases.PERMS, "chain")
+        for rule in RULES[1:]:
+            caught[rule] += misses(V, old.UNIT, cases.PERMS[:1], rule)
+    assert caught["chain"] == 0 and caught["boundary"] > 0 and caught["previous"] > 0
 
 
 # ---- NearestLabels on host arrays ---------------------------------------------------------------------------------------------
