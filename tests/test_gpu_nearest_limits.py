@@ -3,12 +3,14 @@ voxels than the counting and the apply kernel have threads, in one volume of (10
 so the last wave of the counting kernel's second trip is partly past the volume.  The sites come from nearest_cases.cap_sites (checked
 without a GPU by test_launch_limits_cpu.py), the plan from tests/launch_limits.py; the test asserts from the reference that sites,
 ties, filled and unfilled voxels lie in the second trips, then compares what the device launched (ta_nearest_debug) with the plan and
-N, D2, the counts and the filled volume bit for bit with nearest_reference.brute_sites."""
+N, D2, the counts and the filled volume bit for bit with nearest_reference.brute_sites.  One small volume takes the plan of the
+column batches, which this pass shares with the distance pass (csrc/ta_separable.h), through an explicit batch that is no whole wave."""
 import functools
 
 import numpy as np
 import pytest
 
+import distance_reference as dref
 import launch_limits as ll
 import nearest_cases as cases
 import nearest_reference as ref
@@ -89,6 +91,38 @@ def test_past_both_caps_in_a_permuted_layout_of_32_bit_labels():
     assert W.shape == (257, 1026, 17) and not W.flags.c_contiguous
     p = run(W, (s[1], s[0], s[2]), n.transpose(1, 0, 2), d2.transpose(1, 0, 2), limit, dims)
     assert (p.row_groups, p.row_trips, p.voxel_groups, p.voxel_trips) == (ll.NEAR_ROW_MAX_GROUPS, 2, ll.NEAR_VOXEL_MAX_GROUPS, 2)
+
+
+def test_an_explicit_batch_rounds_up_to_whole_waves_in_both_passes():
+    """ta_distance_set_batch and ta_nearest_set_batch go through one plan: 100 columns a launch are rounded up to two waves, which
+    the 3 * 70 = 210 columns along memory axis 1 take in 2 launches and the 5 * 70 = 350 along axis 0 in 3.  What both passes
+    answer does not depend on the batch, and is the references'."""
+    V = np.random.default_rng(11).integers(0, 5, (3, 5, 70)).astype(np.uint16)
+    assert (V == 0).any() and int(V.max()) == 4
+    spacing = (0.5, 1.0, 2.0)
+    want_d2 = dref.scipy_d2(V, spacing)
+    n, d2 = ref.brute(V, 0, spacing)
+    answers = []
+    rv = ResidentVolume(V)
+    try:
+        for batch, launches in ((100, 2 + 3), (0, 1 + 1)):
+            rv.ctx.distance_set_batch(batch)
+            rv.ctx.nearest_set_batch(batch)
+            near = device(rv, 0, spacing)
+            rv.ctx.distance_extract(_capi.DIST_OWN_WALL, 0, spacing, 0)
+            dist = (np.array(rv.distance_image()),) + rv.ctx.distance_get()
+            assert rv.ctx.distance_debug()["column_launches"] == rv.ctx.nearest_debug()["column_launches"] == launches
+            answers.append((near, dist))
+    finally:
+        rv.close()
+    (near, dist), (near_auto, dist_auto) = answers
+    assert near[3:] == near_auto[3:]
+    for a, b in zip(near[:3] + dist, near_auto[:3] + dist_auto):
+        assert a.dtype == b.dtype and a.shape == b.shape and np.array_equal(a, b)
+    same(near, V, n, d2)
+    assert dist[0].dtype == np.float64 and np.array_equal(dist[0], want_d2)
+    for g, w in zip(dist[1:], dref.table(V, want_d2, 5)):
+        assert g.dtype == w.dtype and g.shape == w.shape and np.array_equal(g, w)
 
 
 def test_just_below_both_caps():

@@ -297,6 +297,13 @@ def _i64x3(v):
     return (ctypes.c_int64 * 3)(*[int(x) for x in v])
 
 
+def _spacing(spacing):
+    sp = [float(v) for v in spacing]
+    if len(sp) != 3:
+        raise ValueError("spacing must have three entries")
+    return (ctypes.c_double * 3)(*sp)
+
+
 def _dense_permuted(a):
     """True when the array is dense in some axis permutation (C, F or transposed layouts)."""
     order = sorted(range(a.ndim), key=lambda d: (a.shape[d] != 1, -a.strides[d]))
@@ -504,6 +511,13 @@ class Context(object):
             view[...] = a
             a = view
         return a
+
+    def _plane_range(self, first_plane, nplanes):
+        """(nplanes, voxels) of `nplanes` buffer planes from `first_plane` along memory axis 0 (None: all that follow)."""
+        planes = self.owned_planes() + self._halo_planes          # (asked of the library: a size-1 axis moves the slowest MEMORY axis)
+        if nplanes is None:
+            nplanes = planes - int(first_plane)
+        return int(nplanes), max(int(nplanes), 0) * (int(np.prod(self._vol_layout[0])) // planes)
 
     # -- signal image (include/tissue_scan_signal.h)
     def set_signal(self, array):
@@ -727,12 +741,9 @@ class Context(object):
     def components_image(self, first_plane=0, nplanes=None):
         """uint32 rows of the voxels of `nplanes` buffer planes from `first_plane` along memory axis 0 (None: all that follow), flat
         and in memory order; COMPONENT_NONE where the voxel's component has no row."""
-        planes = self.owned_planes() + self._halo_planes          # (asked of the library: a size-1 axis moves the slowest MEMORY axis)
-        per_plane = int(np.prod(self._vol_layout[0])) // planes
-        if nplanes is None:
-            nplanes = planes - int(first_plane)
-        out = np.zeros(max(int(nplanes), 0) * per_plane, dtype=np.uint32)
-        _check(self._lib.ta_components_image(self._h, int(first_plane), int(nplanes), out.ctypes.data))
+        nplanes, count = self._plane_range(first_plane, nplanes)
+        out = np.zeros(count, dtype=np.uint32)
+        _check(self._lib.ta_components_image(self._h, int(first_plane), nplanes, out.ctypes.data))
         return out
 
     def components_relabel(self, new_label):
@@ -757,10 +768,7 @@ class Context(object):
     def distance_extract(self, mode=DIST_OWN_WALL, site_label=0, spacing=(1.0, 1.0, 1.0), flags=0):
         """Enqueue the three passes of the exact squared distance transform over the current extraction, and its table.  spacing
         in array-axis order; site_label (an id) is read with DIST_FROM_LABEL only."""
-        sp = [float(v) for v in spacing]
-        if len(sp) != 3:
-            raise ValueError("spacing must have three entries")
-        _check(self._lib.ta_distance_extract(self._h, int(mode), int(site_label) & 0xFFFFFFFF, (ctypes.c_double * 3)(*sp), int(flags)))
+        _check(self._lib.ta_distance_extract(self._h, int(mode), int(site_label) & 0xFFFFFFFF, _spacing(spacing), int(flags)))
 
     def distance_get(self):
         """(min2 f64[R], max2 f64[R], pole i32[R, 3]), rows as labels(); +inf, +inf, (-1, -1, -1) for a row without voxels."""
@@ -773,12 +781,9 @@ class Context(object):
     def distance_image(self, first_plane=0, nplanes=None):
         """float64 squared distances of the voxels of `nplanes` buffer planes from `first_plane` along memory axis 0 (None: all that
         follow), flat and in memory order."""
-        planes = self.owned_planes() + self._halo_planes
-        per_plane = int(np.prod(self._vol_layout[0])) // planes
-        if nplanes is None:
-            nplanes = planes - int(first_plane)
-        out = np.zeros(max(int(nplanes), 0) * per_plane, dtype=np.float64)
-        _check(self._lib.ta_distance_image(self._h, int(first_plane), int(nplanes), out.ctypes.data))
+        nplanes, count = self._plane_range(first_plane, nplanes)
+        out = np.zeros(count, dtype=np.float64)
+        _check(self._lib.ta_distance_image(self._h, int(first_plane), nplanes, out.ctypes.data))
         return out
 
     def distance_timing(self):
@@ -804,12 +809,9 @@ class Context(object):
         every label gains: the voxels of `empty_label` (an id) are filled from all others, those of `not_from_label` (an id, None =
         nothing excluded) are neither sites nor filled; an empty voxel is filled when its squared distance is <= max_d2.  spacing
         in array-axis order."""
-        sp = [float(v) for v in spacing]
-        if len(sp) != 3:
-            raise ValueError("spacing must have three entries")
         flags = 0 if not_from_label is None else NEAREST_NOT_FROM
         _check(self._lib.ta_nearest_extract(self._h, int(empty_label) & 0xFFFFFFFF, int(not_from_label or 0) & 0xFFFFFFFF,
-                                            (ctypes.c_double * 3)(*sp), float(max_d2), flags))
+                                            _spacing(spacing), float(max_d2), flags))
 
     def nearest_get(self):
         """(gained u64[R], filled voxels, empty voxels left unfilled), rows as labels()."""
@@ -822,14 +824,10 @@ class Context(object):
         """(uint32 nearest labels (ids; NEAREST_NONE without a site), float64 squared distances) of the voxels of `nplanes` buffer
         planes from `first_plane` along memory axis 0 (None: all that follow), flat and in memory order; None for the one not asked
         for."""
-        planes = self.owned_planes() + self._halo_planes
-        per_plane = int(np.prod(self._vol_layout[0])) // planes
-        if nplanes is None:
-            nplanes = planes - int(first_plane)
-        count = max(int(nplanes), 0) * per_plane
+        nplanes, count = self._plane_range(first_plane, nplanes)
         n = np.zeros(count, dtype=np.uint32) if nearest else None
         d = np.zeros(count, dtype=np.float64) if d2 else None
-        _check(self._lib.ta_nearest_image(self._h, int(first_plane), int(nplanes), None if n is None else n.ctypes.data,
+        _check(self._lib.ta_nearest_image(self._h, int(first_plane), nplanes, None if n is None else n.ctypes.data,
                                           None if d is None else d.ctypes.data))
         return n, d
 

@@ -195,11 +195,6 @@ __global__ __launch_bounds__(256) void distance_pole_kernel(DistanceArgs a, Dist
     }
 }
 
-uint32_t blocks_for(uint64_t threads, uint32_t cap) {
-    const uint64_t b = (threads + 255) / 256;
-    return (uint32_t)(b < 1 ? 1 : (b > cap ? cap : b));
-}
-
 }  // namespace
 
 uint32_t launch_distance_rows(hipStream_t s, const DistanceArgs& a, int itemsize) {
@@ -210,28 +205,19 @@ uint32_t launch_distance_rows(hipStream_t s, const DistanceArgs& a, int itemsize
     return grid;
 }
 
-uint64_t distance_columns(const DistanceArgs& a, int axis) {
-    return (uint64_t)a.n2 * (uint64_t)(axis == 1 ? a.n0 : a.n1);
-}
-
 void launch_distance_columns(hipStream_t s, const DistanceArgs& a, int itemsize, int axis, uint64_t first, uint64_t columns, void* work,
                              uint64_t stride) {
-    const uint64_t plane = (uint64_t)a.n1 * (uint64_t)a.n2;
-    const int64_t len = axis == 1 ? a.n1 : a.n0;
-    const uint64_t step = axis == 1 ? (uint64_t)a.n2 : plane;
-    const uint64_t inner = axis == 1 ? (uint64_t)a.n2 : plane;     // columns that lie side by side in memory
-    const uint64_t outer_stride = plane;                           // axis 1: one group of them per plane; axis 0: one group
-    char* p = (char*)work;
-    double* sf = (double*)p;
-    double* sz = sf + (uint64_t)len * stride;
-    int32_t* sv = (int32_t*)(sz + (uint64_t)len * stride);
-    const uint32_t grid = (uint32_t)((columns + 255) / 256);
+    const ColumnPass g = column_pass(a.n0, a.n1, a.n2, axis);
+    double* sf = (double*)work;
+    double* sz = sf + (uint64_t)g.len * stride;
+    int32_t* sv = (int32_t*)(sz + (uint64_t)g.len * stride);
+    const uint32_t grid = column_grid(columns);
     if (itemsize == 2)
-        hipLaunchKernelGGL(distance_column_kernel<uint16_t>, dim3(grid), dim3(256), 0, s, a, len, step, inner, outer_stride, a.w[axis], first,
-                           columns, sv, sf, sz, stride);
+        hipLaunchKernelGGL(distance_column_kernel<uint16_t>, dim3(grid), dim3(256), 0, s, a, g.len, g.step, g.inner, g.outer_stride, a.w[axis],
+                           first, columns, sv, sf, sz, stride);
     else
-        hipLaunchKernelGGL(distance_column_kernel<uint32_t>, dim3(grid), dim3(256), 0, s, a, len, step, inner, outer_stride, a.w[axis], first,
-                           columns, sv, sf, sz, stride);
+        hipLaunchKernelGGL(distance_column_kernel<uint32_t>, dim3(grid), dim3(256), 0, s, a, g.len, g.step, g.inner, g.outer_stride, a.w[axis],
+                           first, columns, sv, sf, sz, stride);
 }
 
 void launch_distance_table(hipStream_t s, const DistanceArgs& a, int itemsize, const DistanceTable& t, DistanceLaunch& launched) {

@@ -193,11 +193,6 @@ __global__ __launch_bounds__(256) void nearest_apply_kernel(NearestArgs a, uint6
     }
 }
 
-uint32_t blocks_for(uint64_t threads, uint32_t cap) {
-    const uint64_t b = (threads + 255) / 256;
-    return (uint32_t)(b < 1 ? 1 : (b > cap ? cap : b));
-}
-
 uint64_t voxels_of(const NearestArgs& a) { return (uint64_t)a.n0 * (uint64_t)a.n1 * (uint64_t)a.n2; }
 
 }  // namespace
@@ -210,26 +205,17 @@ uint32_t launch_nearest_rows(hipStream_t s, const NearestArgs& a, int itemsize) 
     return grid;
 }
 
-uint64_t nearest_columns(const NearestArgs& a, int axis) {
-    return (uint64_t)a.n2 * (uint64_t)(axis == 1 ? a.n0 : a.n1);
-}
-
 void launch_nearest_columns(hipStream_t s, const NearestArgs& a, int axis, uint64_t first, uint64_t columns, void* work, uint64_t stride) {
-    const uint64_t plane = (uint64_t)a.n1 * (uint64_t)a.n2;
-    const int64_t len = axis == 1 ? a.n1 : a.n0;
-    const uint64_t step = axis == 1 ? (uint64_t)a.n2 : plane;
-    const uint64_t inner = axis == 1 ? (uint64_t)a.n2 : plane;     // columns that lie side by side in memory
-    const uint64_t outer_stride = plane;                           // axis 1: one group of them per plane; axis 0: one group
+    const ColumnPass g = column_pass(a.n0, a.n1, a.n2, axis);
     static_assert(NEAR_STACK_ENTRY == 2 * sizeof(double) + sizeof(int32_t) + 2 * sizeof(uint32_t), "the five arrays below are what the host reserves");
-    const uint64_t entries = (uint64_t)len * stride;
+    const uint64_t entries = (uint64_t)g.len * stride;
     double* sf = (double*)work;
     double* sz = sf + entries;
     int32_t* sv = (int32_t*)(sz + entries);
     uint32_t* sl = (uint32_t*)(sv + entries);
     uint32_t* sb = sl + entries;
-    const uint32_t grid = (uint32_t)((columns + 255) / 256);
-    hipLaunchKernelGGL(nearest_column_kernel, dim3(grid), dim3(256), 0, s, a, len, step, inner, outer_stride, a.w[axis], first, columns, sf, sz,
-                       sv, sl, sb, stride);
+    hipLaunchKernelGGL(nearest_column_kernel, dim3(column_grid(columns)), dim3(256), 0, s, a, g.len, g.step, g.inner, g.outer_stride, a.w[axis],
+                       first, columns, sf, sz, sv, sl, sb, stride);
 }
 
 uint32_t nearest_voxel_groups(const NearestArgs& a) { return blocks_for(voxels_of(a), NEAR_VOXEL_MAX_GROUPS); }

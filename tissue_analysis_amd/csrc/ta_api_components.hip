@@ -7,8 +7,6 @@ namespace {
 
 const char* const NO_TABLES = "no component tables for the current volume (run ta_components_extract)";
 
-uint64_t voxels(const ta_ctx* c) { return (uint64_t)c->mdims[0] * (uint64_t)c->mdims[1] * (uint64_t)c->mdims[2]; }
-
 // where the parts of ComponentState::work lie, for W waves
 struct ComponentWork {
     uint64_t counts, offsets, scratch, bytes;
@@ -205,10 +203,7 @@ TA_API int ta_components_get(ta_ctx* c, uint32_t* label, uint64_t* n, int32_t* f
 TA_API int ta_components_image(ta_ctx* c, int64_t first_plane, int64_t nplanes, uint32_t* rows) {
     int rc = components_ready(c);
     if (rc != TA_OK) return rc;
-    if (first_plane < 0 || nplanes < 0 || first_plane > c->mdims[0] || nplanes > c->mdims[0] - first_plane)
-        return fail(TA_EINVAL, "planes %lld .. %lld are not inside the buffer's %lld", (long long)first_plane, (long long)(first_plane + nplanes),
-                    (long long)c->mdims[0]);
-    if (!nplanes) return TA_OK;
+    if ((rc = check_planes(c, first_plane, nplanes)) != TA_OK || !nplanes) return rc;
     if (!rows) return fail(TA_EINVAL, "rows is NULL");
     const uint64_t plane = (uint64_t)c->mdims[1] * (uint64_t)c->mdims[2], count = (uint64_t)nplanes * plane;
     if ((rc = c->cc.image.reserve(count * 4)) != TA_OK) return rc;

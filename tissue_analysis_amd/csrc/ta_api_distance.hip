@@ -3,16 +3,11 @@
 #include "ta_ctx.h"
 #include "ta_distance.h"
 
-#include <cmath>
 #include <limits>
 
 namespace {
 
 const char* const NO_RESULTS = "no distance map for the current extraction (run ta_distance_extract)";
-
-bool distance_current(const ta_ctx* c) { return c->dist.seq != 0 && c->extracted && c->dist.seq == c->extract_seq; }
-
-uint64_t voxels(const ta_ctx* c) { return (uint64_t)c->mdims[0] * (uint64_t)c->mdims[1] * (uint64_t)c->mdims[2]; }
 
 // byte offsets of the parts of DistanceState::table for R rows
 struct DistanceLayout {
@@ -20,18 +15,7 @@ struct DistanceLayout {
     explicit DistanceLayout(uint64_t R) { max2 = 8 * R; pole = 16 * R; flags = 24 * R; bytes = flags + 4 * ta::DIST_NFLAGS; }
 };
 
-// columns of a launch along an axis of `len` voxels with `columns` columns: whole waves; what the option says, else what fits the cap
-uint64_t batch_columns(const ta_ctx* c, uint64_t len, uint64_t columns) {
-    const uint64_t b = c->dist.opt_batch > 0 ? ((uint64_t)c->dist.opt_batch + 63) / 64 * 64
-                                             : std::max<uint64_t>(64, ta::DIST_WORK_CAP / (len * ta::DIST_STACK_ENTRY) / 64 * 64);
-    return std::min(b, (columns + 63) / 64 * 64);
-}
-
-int distance_ready(ta_ctx* c) {
-    if (!c) return fail(TA_EINVAL, "ctx is NULL");
-    if (!distance_current(c)) return fail(TA_EINVAL, NO_RESULTS);
-    return use_device(c);
-}
+int distance_ready(ta_ctx* c) { return c ? transform_ready(c, c->dist.seq, NO_RESULTS) : fail(TA_EINVAL, "ctx is NULL"); }
 
 }  // namespace
 
@@ -41,57 +25,32 @@ void distance_on_new_volume(ta_ctx* c) { c->dist.seq = 0; }
 extern "C" {
 
 TA_API int ta_distance_set_batch(ta_ctx* c, int64_t columns) {
-    if (!c) return fail(TA_EINVAL, "ctx is NULL");
-    if (columns < 0 || columns > (1ll << 30)) return fail(TA_EINVAL, "the columns of a batch must be 0 (automatic) or in [1, 2^30]");
-    c->dist.opt_batch = columns;
-    return TA_OK;
+    const int rc = check_batch_option(c, columns);
+    if (rc == TA_OK) c->dist.opt_batch = columns;
+    return rc;
 }
 
 TA_API int ta_distance_extract(ta_ctx* c, int mode, uint32_t site_label, const double spacing[3], uint32_t flags) {
     if (!c) return fail(TA_EINVAL, "ctx is NULL");
     if (mode != TA_DIST_OWN_WALL && mode != TA_DIST_FROM_LABEL) return fail(TA_EINVAL, "bad distance mode %d", mode);
     if (flags & ~TA_DIST_EDGE_IS_SITE) return fail(TA_EINVAL, "bad distance flags 0x%x", flags);
-    if (!spacing) return fail(TA_EINVAL, "spacing is NULL");
-    for (int k = 0; k < 3; ++k)
-        if (!(spacing[k] > 0.0) || !std::isfinite(spacing[k])) return fail(TA_EINVAL, "spacing[%d]=%g is not positive and finite", k, spacing[k]);
-    if (!c->vol) return fail(TA_EINVAL, "no label volume set");
-    if (c->first_owned != 0 || c->a_origin != 0)
-        return fail(TA_EINVAL, "the distance pass does not take a slab (an exact transform needs halos of unbounded depth)");
-    int rc = use_device(c);
-    if (rc != TA_OK) return rc;
-    if (!c->extracted) return fail(TA_EINVAL, "the distance pass needs a ta_extract of the current volume first");
-    if ((rc = finish_extract(c)) != TA_OK) return rc;
+    ta::DistanceArgs a = {};
+    int rc = check_spacing(spacing);
+    if (rc != TA_OK || (rc = transform_preflight(c, "distance", spacing, a.w)) != TA_OK) return rc;
     c->dist.seq = 0;
     profile_on_new_distance(c);
     const uint64_t nvox = voxels(c), R = (uint64_t)c->max_label + 1;
     const DistanceLayout L(R);
 
-    ta::DistanceArgs a = {};
     a.vol = sweep_vol(c);
     a.n0 = c->mdims[0]; a.n1 = c->mdims[1]; a.n2 = c->mdims[2];
-    for (int k = 0; k < 3; ++k) a.w[k] = spacing[c->perm[k]];
     a.mode = mode;
     a.flags = flags & TA_DIST_EDGE_IS_SITE ? ta::DIST_EDGE_IS_SITE : 0u;
-    if (mode == TA_DIST_FROM_LABEL) {
-        a.site = site_label;
-        a.has_site = c->itemsize == 4 || site_label <= 0xFFFFu;
-        if (c->ids.compact) {                       // the pass reads ranks: the id's rank, if the volume holds it
-            const auto& ids = c->ids.h_ids;
-            const auto it = std::lower_bound(ids.begin(), ids.end(), site_label);
-            a.has_site = it != ids.end() && *it == site_label;
-            a.site = (uint32_t)(it - ids.begin());
-        }
-    }
+    if (mode == TA_DIST_FROM_LABEL) a.has_site = stored_label(c, site_label, &a.site);
 
-    uint64_t batch[2], work = 0;                    // [0]: along memory axis 1, [1]: along memory axis 0
-    for (int k = 0; k < 2; ++k) {
-        const int axis = 1 - k;
-        const uint64_t len = (uint64_t)c->mdims[axis];
-        batch[k] = batch_columns(c, len, ta::distance_columns(a, axis));
-        work = std::max(work, len * batch[k] * ta::DIST_STACK_ENTRY);
-    }
+    const ta::BatchPlan plan = ta::plan_batches(c->mdims, c->dist.opt_batch, ta::DIST_STACK_ENTRY, ta::DIST_WORK_CAP);
     if ((rc = c->dist.d2.reserve(nvox * 8)) != TA_OK) return rc;
-    if ((rc = c->dist.work.reserve(work)) != TA_OK) return rc;
+    if ((rc = c->dist.work.reserve(plan.work)) != TA_OK) return rc;
     if ((rc = c->dist.table.reserve(L.bytes)) != TA_OK) return rc;
     if ((rc = ensure_events(c->dist.ev)) != TA_OK) return rc;
     a.d2 = (double*)c->dist.d2.p;
@@ -99,11 +58,10 @@ TA_API int ta_distance_extract(ta_ctx* c, int mode, uint32_t site_label, const d
     TA_HIP(hipEventRecord(c->dist.ev[0], c->stream));
     ta::DistanceLaunch launched;
     launched.row_groups = ta::launch_distance_rows(c->stream, a, c->itemsize);
-    for (int k = 0; k < 2; ++k) {
-        const int axis = 1 - k;
-        const uint64_t columns = ta::distance_columns(a, axis);
-        for (uint64_t first = 0; first < columns; first += batch[k], ++launched.column_launches)
-            ta::launch_distance_columns(c->stream, a, c->itemsize, axis, first, std::min(batch[k], columns - first), c->dist.work.p, batch[k]);
+    for (int k = 0; k < 2; ++k) {                   // along memory axis 1, then 0
+        const uint64_t columns = ta::column_pass(a.n0, a.n1, a.n2, 1 - k).columns, batch = plan.batch[k];
+        for (uint64_t first = 0; first < columns; first += batch, ++launched.column_launches)
+            ta::launch_distance_columns(c->stream, a, c->itemsize, 1 - k, first, std::min(batch, columns - first), c->dist.work.p, batch);
     }
     TA_HIP(hipGetLastError());
     TA_HIP(hipEventRecord(c->dist.ev[1], c->stream));
@@ -161,10 +119,7 @@ TA_API int ta_distance_get(ta_ctx* c, double* min2, double* max2, int32_t* pole)
 TA_API int ta_distance_image(ta_ctx* c, int64_t first_plane, int64_t nplanes, double* d2) {
     int rc = distance_ready(c);
     if (rc != TA_OK) return rc;
-    if (first_plane < 0 || nplanes < 0 || first_plane > c->mdims[0] || nplanes > c->mdims[0] - first_plane)
-        return fail(TA_EINVAL, "planes %lld .. %lld are not inside the buffer's %lld", (long long)first_plane, (long long)(first_plane + nplanes),
-                    (long long)c->mdims[0]);
-    if (!nplanes) return TA_OK;
+    if ((rc = check_planes(c, first_plane, nplanes)) != TA_OK || !nplanes) return rc;
     if (!d2) return fail(TA_EINVAL, "d2 is NULL");
     const uint64_t plane = (uint64_t)c->mdims[1] * (uint64_t)c->mdims[2];
     TA_HIP(hipMemcpyAsync(d2, (const double*)c->dist.d2.p + (uint64_t)first_plane * plane, (uint64_t)nplanes * plane * 8, hipMemcpyDeviceToHost,
@@ -183,13 +138,7 @@ TA_API int ta_distance_debug(ta_ctx* c, uint32_t out[4]) {
 
 TA_API int ta_distance_timing(ta_ctx* c, double* ms_pass, double* ms_after) {
     int rc = distance_ready(c);
-    if (rc != TA_OK) return rc;
-    TA_HIP(hipEventSynchronize(c->dist.ev[2]));
-    double pass = 0.0, after = 0.0;
-    if ((rc = elapsed_ms(c->dist.ev[0], c->dist.ev[1], &pass)) != TA_OK || (rc = elapsed_ms(c->dist.ev[1], c->dist.ev[2], &after)) != TA_OK) return rc;
-    if (ms_pass) *ms_pass = pass;
-    if (ms_after) *ms_after = after;
-    return TA_OK;
+    return rc != TA_OK ? rc : two_intervals_ms(c->dist.ev, ms_pass, ms_after);
 }
 
 }  // extern "C"

@@ -2,15 +2,9 @@
 #include "../../include/tissue_scan_nearest.h"
 #include "ta_ctx.h"
 
-#include <cmath>
-
 namespace {
 
 const char* const NO_RESULTS = "no nearest-label map for the current extraction (run ta_nearest_extract)";
-
-bool nearest_current(const ta_ctx* c) { return c->near.seq != 0 && c->extracted && c->near.seq == c->extract_seq; }
-
-uint64_t voxels(const ta_ctx* c) { return (uint64_t)c->mdims[0] * (uint64_t)c->mdims[1] * (uint64_t)c->mdims[2]; }
 
 // byte offsets of the parts of NearestState::table for R rows
 struct NearestLayout {
@@ -18,28 +12,7 @@ struct NearestLayout {
     explicit NearestLayout(uint64_t R) { totals = 8 * R; flags = totals + 16; bytes = flags + 4 * ta::NEAR_NFLAGS; }
 };
 
-// columns of a launch along an axis of `len` voxels with `columns` columns: whole waves; what the option says, else what fits the cap
-uint64_t batch_columns(const ta_ctx* c, uint64_t len, uint64_t columns) {
-    const uint64_t b = c->near.opt_batch > 0 ? ((uint64_t)c->near.opt_batch + 63) / 64 * 64
-                                             : std::max<uint64_t>(64, ta::NEAR_WORK_CAP / (len * ta::NEAR_STACK_ENTRY) / 64 * 64);
-    return std::min(b, (columns + 63) / 64 * 64);
-}
-
-// an id as the volume the passes read stores it; false when no voxel can hold it
-bool stored_label(const ta_ctx* c, uint32_t id, uint32_t* stored) {
-    *stored = id;
-    if (!c->ids.compact) return c->itemsize == 4 || id <= 0xFFFFu;
-    const auto& ids = c->ids.h_ids;                 // the passes read ranks: the id's rank, if the volume holds it
-    const auto it = std::lower_bound(ids.begin(), ids.end(), id);
-    *stored = (uint32_t)(it - ids.begin());
-    return it != ids.end() && *it == id;
-}
-
-int nearest_ready(ta_ctx* c) {
-    if (!c) return fail(TA_EINVAL, "ctx is NULL");
-    if (!nearest_current(c)) return fail(TA_EINVAL, NO_RESULTS);
-    return use_device(c);
-}
+int nearest_ready(ta_ctx* c) { return c ? transform_ready(c, c->near.seq, NO_RESULTS) : fail(TA_EINVAL, "ctx is NULL"); }
 
 }  // namespace
 
@@ -49,48 +22,33 @@ void nearest_on_new_volume(ta_ctx* c) { c->near.seq = 0; }
 extern "C" {
 
 TA_API int ta_nearest_set_batch(ta_ctx* c, int64_t columns) {
-    if (!c) return fail(TA_EINVAL, "ctx is NULL");
-    if (columns < 0 || columns > (1ll << 30)) return fail(TA_EINVAL, "the columns of a batch must be 0 (automatic) or in [1, 2^30]");
-    c->near.opt_batch = columns;
-    return TA_OK;
+    const int rc = check_batch_option(c, columns);
+    if (rc == TA_OK) c->near.opt_batch = columns;
+    return rc;
 }
 
 TA_API int ta_nearest_extract(ta_ctx* c, uint32_t empty_label, uint32_t not_from_label, const double spacing[3], double max_d2, uint32_t flags) {
     if (!c) return fail(TA_EINVAL, "ctx is NULL");
     if (flags & ~TA_NEAREST_NOT_FROM) return fail(TA_EINVAL, "bad nearest-label flags 0x%x", flags);
-    if (!spacing) return fail(TA_EINVAL, "spacing is NULL");
-    for (int k = 0; k < 3; ++k)
-        if (!(spacing[k] > 0.0) || !std::isfinite(spacing[k])) return fail(TA_EINVAL, "spacing[%d]=%g is not positive and finite", k, spacing[k]);
-    if (!(max_d2 >= 0.0)) return fail(TA_EINVAL, "max_d2=%g is negative or not a number", max_d2);
-    if (!c->vol) return fail(TA_EINVAL, "no label volume set");
-    if (c->first_owned != 0 || c->a_origin != 0)
-        return fail(TA_EINVAL, "the nearest-label pass does not take a slab (an exact transform needs halos of unbounded depth)");
-    int rc = use_device(c);
+    ta::NearestArgs a = {};
+    int rc = check_spacing(spacing);
     if (rc != TA_OK) return rc;
-    if (!c->extracted) return fail(TA_EINVAL, "the nearest-label pass needs a ta_extract of the current volume first");
-    if ((rc = finish_extract(c)) != TA_OK) return rc;
+    if (!(max_d2 >= 0.0)) return fail(TA_EINVAL, "max_d2=%g is negative or not a number", max_d2);
+    if ((rc = transform_preflight(c, "nearest-label", spacing, a.w)) != TA_OK) return rc;
     c->near.seq = 0;
     const uint64_t nvox = voxels(c), R = (uint64_t)c->max_label + 1;
     const NearestLayout L(R);
 
-    ta::NearestArgs a = {};
     a.vol = sweep_vol(c);
     a.n0 = c->mdims[0]; a.n1 = c->mdims[1]; a.n2 = c->mdims[2];
-    for (int k = 0; k < 3; ++k) a.w[k] = spacing[c->perm[k]];
     a.max_d2 = max_d2;
     a.has_empty = stored_label(c, empty_label, &a.empty);
     if (flags & TA_NEAREST_NOT_FROM) a.has_not_from = stored_label(c, not_from_label, &a.not_from);
 
-    uint64_t batch[2], work = 0;                    // [0]: along memory axis 1, [1]: along memory axis 0
-    for (int k = 0; k < 2; ++k) {
-        const int axis = 1 - k;
-        const uint64_t len = (uint64_t)c->mdims[axis];
-        batch[k] = batch_columns(c, len, ta::nearest_columns(a, axis));
-        work = std::max(work, len * batch[k] * ta::NEAR_STACK_ENTRY);
-    }
+    const ta::BatchPlan plan = ta::plan_batches(c->mdims, c->near.opt_batch, ta::NEAR_STACK_ENTRY, ta::NEAR_WORK_CAP);
     if ((rc = c->near.f.reserve(nvox * 8)) != TA_OK) return rc;
     if ((rc = c->near.lab.reserve(nvox * 4)) != TA_OK) return rc;
-    if ((rc = c->near.work.reserve(work)) != TA_OK) return rc;
+    if ((rc = c->near.work.reserve(plan.work)) != TA_OK) return rc;
     if ((rc = c->near.table.reserve(L.bytes)) != TA_OK) return rc;
     if ((rc = ensure_events(c->near.ev)) != TA_OK) return rc;
     a.f = (double*)c->near.f.p;
@@ -99,11 +57,10 @@ TA_API int ta_nearest_extract(ta_ctx* c, uint32_t empty_label, uint32_t not_from
     TA_HIP(hipEventRecord(c->near.ev[0], c->stream));
     uint32_t launched[4] = {0, 0, 0, 0};
     launched[0] = ta::launch_nearest_rows(c->stream, a, c->itemsize);
-    for (int k = 0; k < 2; ++k) {
-        const int axis = 1 - k;
-        const uint64_t columns = ta::nearest_columns(a, axis);
-        for (uint64_t first = 0; first < columns; first += batch[k], ++launched[3])
-            ta::launch_nearest_columns(c->stream, a, axis, first, std::min(batch[k], columns - first), c->near.work.p, batch[k]);
+    for (int k = 0; k < 2; ++k) {                   // along memory axis 1, then 0
+        const uint64_t columns = ta::column_pass(a.n0, a.n1, a.n2, 1 - k).columns, batch = plan.batch[k];
+        for (uint64_t first = 0; first < columns; first += batch, ++launched[3])
+            ta::launch_nearest_columns(c->stream, a, 1 - k, first, std::min(batch, columns - first), c->near.work.p, batch);
     }
     TA_HIP(hipGetLastError());
     TA_HIP(hipEventRecord(c->near.ev[1], c->stream));
@@ -142,10 +99,7 @@ TA_API int ta_nearest_get(ta_ctx* c, uint64_t* gained, uint64_t totals[2]) {
 TA_API int ta_nearest_image(ta_ctx* c, int64_t first_plane, int64_t nplanes, uint32_t* nearest, double* d2) {
     int rc = nearest_ready(c);
     if (rc != TA_OK) return rc;
-    if (first_plane < 0 || nplanes < 0 || first_plane > c->mdims[0] || nplanes > c->mdims[0] - first_plane)
-        return fail(TA_EINVAL, "planes %lld .. %lld are not inside the buffer's %lld", (long long)first_plane, (long long)(first_plane + nplanes),
-                    (long long)c->mdims[0]);
-    if (!nplanes) return TA_OK;
+    if ((rc = check_planes(c, first_plane, nplanes)) != TA_OK || !nplanes) return rc;
     const uint64_t plane = (uint64_t)c->mdims[1] * (uint64_t)c->mdims[2], from = (uint64_t)first_plane * plane, count = (uint64_t)nplanes * plane;
     if (nearest) TA_HIP(hipMemcpyAsync(nearest, (const uint32_t*)c->near.lab.p + from, count * 4, hipMemcpyDeviceToHost, c->stream));
     if (d2) TA_HIP(hipMemcpyAsync(d2, (const double*)c->near.f.p + from, count * 8, hipMemcpyDeviceToHost, c->stream));
@@ -178,13 +132,7 @@ TA_API int ta_nearest_debug(ta_ctx* c, uint32_t out[4]) {
 
 TA_API int ta_nearest_timing(ta_ctx* c, double* ms_pass, double* ms_after) {
     int rc = nearest_ready(c);
-    if (rc != TA_OK) return rc;
-    TA_HIP(hipEventSynchronize(c->near.ev[2]));
-    double pass = 0.0, after = 0.0;
-    if ((rc = elapsed_ms(c->near.ev[0], c->near.ev[1], &pass)) != TA_OK || (rc = elapsed_ms(c->near.ev[1], c->near.ev[2], &after)) != TA_OK) return rc;
-    if (ms_pass) *ms_pass = pass;
-    if (ms_after) *ms_after = after;
-    return TA_OK;
+    return rc != TA_OK ? rc : two_intervals_ms(c->near.ev, ms_pass, ms_after);
 }
 
 }  // extern "C"

@@ -1,13 +1,17 @@
 // ta_ctx.h -- the context behind the C ABI and what the ta_api*.hip files share (host only, private to csrc/).  Every concern has one
 // struct of state below and its entry points in a file of its own: ta_api.hip holds the core (context, volume, sweep, extraction)
 // and the sweep's tile shape; ta_api_walls.hip, ta_api_sparse.hip and ta_api_exchange.hip the wall voxels, the sparse label ids and
-// the rank exchange; ta_api_<feature>.hip a feature.  What crosses files is declared here, with the file that defines it.
+// the rank exchange; ta_api_<feature>.hip a feature.  What crosses files is declared here, with the file that defines it; the small
+// checks that several features repeat are inline below the context (the plane range of a ta_*_image call, an id as the volume
+// stores it, a feature's two timed intervals, and the entry checks of the two separable transforms, whose column-pass geometry and
+// batch plan are in ta_separable.h).
 #pragma once
 #include "../../include/tissue_scan.h"
 #include "ta_kernels.h"
 #include "ta_nearest.h"
 
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -361,6 +365,70 @@ inline int use_device(ta_ctx* c) {
 inline const void* sweep_vol(const ta_ctx* c) { return c->ids.compact ? c->ids.compact_vol.p : c->vol; }
 inline int64_t compact_rows(const ta_ctx* c) { return c->ids.compact ? c->ids.census_n : -1; }      // rows of a compacted context, -1 = dense
 
+// Drain the stream and validate the flags of the last pass; grows the adjacency table and re-runs when it overflowed.  ta_api.hip.
+int finish_extract(ta_ctx* c);
+
+inline uint64_t voxels(const ta_ctx* c) { return (uint64_t)c->mdims[0] * (uint64_t)c->mdims[1] * (uint64_t)c->mdims[2]; }
+
+// an id as the volume the passes read stores it; false when no voxel can hold it
+inline bool stored_label(const ta_ctx* c, uint32_t id, uint32_t* stored) {
+    *stored = id;
+    if (!c->ids.compact) return c->itemsize == 4 || id <= 0xFFFFu;
+    const auto& ids = c->ids.h_ids;                 // the passes read ranks: the id's rank, if the volume holds it
+    const auto it = std::lower_bound(ids.begin(), ids.end(), id);
+    *stored = (uint32_t)(it - ids.begin());
+    return it != ids.end() && *it == id;
+}
+
+// the plane range of a ta_*_image call lies inside the buffer
+inline int check_planes(const ta_ctx* c, int64_t first_plane, int64_t nplanes) {
+    if (first_plane < 0 || nplanes < 0 || first_plane > c->mdims[0] || nplanes > c->mdims[0] - first_plane)
+        return fail(TA_EINVAL, "planes %lld .. %lld are not inside the buffer's %lld", (long long)first_plane, (long long)(first_plane + nplanes),
+                    (long long)c->mdims[0]);
+    return TA_OK;
+}
+
+// the two intervals between three recorded events of a feature, once the last one is complete; either output may be NULL
+inline int two_intervals_ms(hipEvent_t (&ev)[3], double* ms_first, double* ms_second) {
+    TA_HIP(hipEventSynchronize(ev[2]));
+    double first = 0.0, second = 0.0;
+    int rc;
+    if ((rc = elapsed_ms(ev[0], ev[1], &first)) != TA_OK || (rc = elapsed_ms(ev[1], ev[2], &second)) != TA_OK) return rc;
+    if (ms_first) *ms_first = first;
+    if (ms_second) *ms_second = second;
+    return TA_OK;
+}
+
+// The whole-volume separable transforms (ta_api_distance.hip, ta_api_nearest.hip; `noun` is what their messages call the pass).
+// Their entry checks run in this order: check_spacing, then transform_preflight, which settles the extraction the pass reads and
+// fills w, the spacing of memory axis k.  transform_ready: a getter's context holds results of the current extraction (seq).
+inline int check_spacing(const double spacing[3]) {
+    if (!spacing) return fail(TA_EINVAL, "spacing is NULL");
+    for (int k = 0; k < 3; ++k)
+        if (!(spacing[k] > 0.0) || !std::isfinite(spacing[k])) return fail(TA_EINVAL, "spacing[%d]=%g is not positive and finite", k, spacing[k]);
+    return TA_OK;
+}
+inline int transform_preflight(ta_ctx* c, const char* noun, const double spacing[3], double w[3]) {
+    if (!c->vol) return fail(TA_EINVAL, "no label volume set");
+    if (c->first_owned != 0 || c->a_origin != 0)
+        return fail(TA_EINVAL, "the %s pass does not take a slab (an exact transform needs halos of unbounded depth)", noun);
+    int rc = use_device(c);
+    if (rc != TA_OK) return rc;
+    if (!c->extracted) return fail(TA_EINVAL, "the %s pass needs a ta_extract of the current volume first", noun);
+    if ((rc = finish_extract(c)) != TA_OK) return rc;
+    for (int k = 0; k < 3; ++k) w[k] = spacing[c->perm[k]];
+    return TA_OK;
+}
+inline int transform_ready(ta_ctx* c, uint64_t seq, const char* no_results) {
+    if (seq == 0 || !c->extracted || seq != c->extract_seq) return fail(TA_EINVAL, no_results);
+    return use_device(c);
+}
+inline int check_batch_option(const ta_ctx* c, int64_t columns) {
+    if (!c) return fail(TA_EINVAL, "ctx is NULL");
+    if (columns < 0 || columns > (1ll << 30)) return fail(TA_EINVAL, "the columns of a batch must be 0 (automatic) or in [1, 2^30]");
+    return TA_OK;
+}
+
 // ta_ctx::small and its host mirror h_small: flags, cursor, max label, parked hot-row pointer (2 words)
 constexpr int SMALL_WORDS = ta::SMALL_WORDS_DEV;
 inline uint32_t* flags_dev(ta_ctx* c) { return (uint32_t*)c->small.p; }
@@ -373,9 +441,6 @@ inline ta::PairTable pair_table(ta_ctx* c) {
     pt.mask = (uint32_t)((1ull << c->pair_log2) - 1);
     return pt;
 }
-
-// Drain the stream and validate the flags of the last pass; grows the adjacency table and re-runs when it overflowed.  ta_api.hip.
-int finish_extract(ta_ctx* c);
 
 // A new label volume (for the sparse ids, the overlap, the junctions, the components, the distance maps and their profiles, the nearest-label maps also: new label values in it).  Defined by
 // the file of each concern, called by the core's volume_replaced / volume_labels_changed (the junctions' and the components' also by

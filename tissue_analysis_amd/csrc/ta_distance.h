@@ -2,6 +2,7 @@
 // volume to its nearest site (include/tissue_scan_distance.h), one pass per memory axis, and the per-label table of it.
 #pragma once
 #include "ta_device.h"
+#include "ta_separable.h"
 
 namespace ta {
 
@@ -32,8 +33,7 @@ uint32_t launch_distance_rows(hipStream_t s, const DistanceArgs& a, int itemsize
 // Column pass along memory axis `axis` (1 or 0), in place on d2: per run of equal class the lower envelope of the run's own
 // parabolas and of a zero parabola on the voxel behind either end.  One lane per column; `columns` of them from `first` per launch.
 // The stack of a column lies in `work`: f f64[len][stride] | boundaries f64[len][stride] | positions i32[len][stride], len = the
-// axis' length, stride = the columns of a batch (DIST_STACK_ENTRY bytes per entry and column).
-uint64_t distance_columns(const DistanceArgs& a, int axis);
+// axis' length, stride = the columns of a batch (DIST_STACK_ENTRY bytes per entry and column).  Geometry and batches: ta_separable.h.
 void launch_distance_columns(hipStream_t s, const DistanceArgs& a, int itemsize, int axis, uint64_t first, uint64_t columns, void* work,
                              uint64_t stride);
 

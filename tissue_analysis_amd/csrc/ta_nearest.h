@@ -3,6 +3,7 @@
 // axis, then the counts of the empty voxels every label gains and the pass that writes them into the volume.
 #pragma once
 #include "ta_device.h"
+#include "ta_separable.h"
 
 namespace ta {
 
@@ -34,8 +35,7 @@ uint32_t launch_nearest_rows(hipStream_t s, const NearestArgs& a, int itemsize);
 // the column, with the smallest label where several parabolas are lowest.  One lane per column; `columns` of them from `first` per
 // launch.  The stack of a column lies in `work`: f f64[len][stride] | boundaries f64[len][stride] | positions i32[len][stride] |
 // labels u32[len][stride] | boundary labels u32[len][stride], len = the axis' length, stride = the columns of a batch
-// (NEAR_STACK_ENTRY bytes per entry and column).
-uint64_t nearest_columns(const NearestArgs& a, int axis);
+// (NEAR_STACK_ENTRY bytes per entry and column).  Geometry and batches: ta_separable.h.
 void launch_nearest_columns(hipStream_t s, const NearestArgs& a, int axis, uint64_t first, uint64_t columns, void* work, uint64_t stride);
 
 struct NearestTable {
