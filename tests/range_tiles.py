@@ -1,22 +1,25 @@
-"""The tile ranges of the signal, overlap and wall-geometry passes, and label volumes that exercise them.
+"""The tile ranges of the six range passes (csrc/ta_range_plan.h), and label volumes that exercise them.
 
-kernels_signal.hip, kernels_overlap.hip and kernels_wallgeo.hip share one scheme: a tile is WAVES rows x 64 * VPL columns x PLANES
-planes (VPL = 16 / sizeof(label) voxels a lane), a workgroup takes `per` consecutive tiles (column blocks first, then row blocks,
-then plane blocks), keeps open-addressed LDS tables for the whole range, and a record that finds no LDS slot goes to the global
-rows.  This file restates, in plain Python and without the library, (1) the plan launch_signal / launch_overlap / launch_wallgeo
-compute, (2) which workgroup walks which voxel, and from it the spills no hash can avoid, and (3) label volumes that are cheap
-to make at the shapes that reach multi-tile ranges.  test_range_tiles_cpu.py checks the restatement; test_gpu_tile_ranges.py
-and test_gpu_feature_table_spills.py run the volumes through the kernels and compare the plan with the one the device reports.
+kernels_signal, _overlap, _wallgeo, _profile, _sighist and _sigmoments.hip share one scheme: a tile is WAVES rows x 64 * VPL columns
+x PLANES planes (VPL = 16 / sizeof(label) voxels a lane), a workgroup takes `per` consecutive tiles (column blocks first, then row
+blocks, then plane blocks), keeps open-addressed LDS tables for the whole range, and a record that finds no LDS slot goes to the
+global rows.  This file restates, in plain Python and without the library, (1) the plan range_tiles / plan_ranges of
+ta_range_plan.h compute, (2) which workgroup walks which voxel, and from it the spills no hash can avoid, and (3) label volumes
+that are cheap to make at the shapes that reach multi-tile ranges.  test_range_tiles_cpu.py checks the restatement, also against
+the header itself (tests/native/range_plan.cpp); test_gpu_tile_ranges.py and test_gpu_feature_table_spills.py run the volumes
+through the kernels and compare the plan with the one the device reports.
 """
 import collections
 
 import numpy as np
 
-WAVES, PLANES = 4, 16                                     # rows and planes of a tile, all three passes
-MAX_GROUPS = {"signal": 1024, "overlap": 1024, "wallgeo": 4096}
-VOXEL_CAP_LOG2 = {"signal": 31, "overlap": 31, "wallgeo": 30}      # a workgroup's LDS rows count in u32
+WAVES, PLANES = 4, 16                                     # rows and planes of a tile, all six passes
+MAX_GROUPS = {"signal": 1024, "overlap": 1024, "wallgeo": 4096, "profile": 4096, "sighist": 65536, "sigmoments": 1024}
+# a workgroup's LDS rows count in u32
+VOXEL_CAP_LOG2 = {"signal": 31, "overlap": 31, "wallgeo": 30, "profile": 30, "sighist": 31, "sigmoments": 31}
 # LDS slots of a workgroup: a record spills only when the table it goes to is out of reach
-LABEL_SLOTS = {"signal": 512}
+LABEL_SLOTS = {"signal": 512, "sigmoments": 448}
+KEY_SLOTS = {"profile": 1024, "sighist": 39}              # (row, shell) keys; rows of 256 digit counters
 PAIR_SLOTS = {"signal": 2048, "overlap": 2048, "wallgeo": 512}
 
 Plan = collections.namedtuple("Plan", "ncb nrb npb tiles per groups tiles_in_last_group")
@@ -47,10 +50,10 @@ def vector_path(dims, label_itemsize):
     return int(dims[2]) % (16 // int(label_itemsize)) == 0
 
 
-def group_image(dims, first_owned, label_itemsize, which):
-    """int64 image of the buffer: the workgroup that walks each voxel, -1 in the halo plane."""
+def group_image(dims, first_owned, label_itemsize, which, p=None):
+    """int64 image of the buffer: the workgroup that walks each voxel, -1 in the halo plane (p: a plan other than the pass's plain one)."""
     n0, n1, n2 = (int(d) for d in dims)
-    p = plan(dims, first_owned, label_itemsize, which)
+    p = p or plan(dims, first_owned, label_itemsize, which)
     pb = (np.arange(n0) - int(first_owned)) // PLANES
     rb = np.arange(n1) // WAVES
     cb = np.arange(n2) // columns(label_itemsize)

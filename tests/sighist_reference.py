@@ -4,7 +4,7 @@ histogram(V, S, nrows, log2_width)      counts u64[R, B] by np.bincount(row * B 
 order_statistics(V, S, nrows, ranks)    u32[R, n] by sorting each row's values; UINT32_MAX where rank >= n
                                         (order_statistics_by_counting: the same from a full-resolution histogram, for large volumes)
 two_pass_select(V, S, nrows, ranks)     the same through the device's steps: digit histogram, prefix, remainder, selectors, dedupe
-plan(dims, first_owned, itemsize)       the launch plan of the digit kernel, as range_tiles.plan restates the other passes'
+plan(dims, first_owned, itemsize)       the launch plan of the digit kernel: range_tiles.plan(..., "sighist")
 `first_owned` = 1: plane 0 of V / S is a halo plane and adds nothing; `rows`: the row of every voxel (default: the label)."""
 import numpy as np
 
@@ -14,8 +14,7 @@ from tissue_analysis_amd import _capi
 NONE = np.uint32(0xFFFFFFFF)
 NO_RANK = np.uint64(0xFFFFFFFFFFFFFFFF)
 SLOTS = _capi.SIGHIST_SLOTS
-MAX_GROUPS = _capi.SIGHIST_MAX_GROUPS
-VOXEL_CAP_LOG2 = 31                         # a workgroup's LDS counters are u32
+MAX_GROUPS = rt.MAX_GROUPS["sighist"]       # (== _capi.SIGHIST_MAX_GROUPS: test_signal_quantiles_cpu.py)
 
 
 def _flat(V, S, rows, first_owned):
@@ -128,14 +127,7 @@ def quantile(values, q, method):
 def plan(dims, first_owned, label_itemsize):
     """dims: the buffer dims in memory order (the halo plane included when first_owned == 1).  The tile of the signal pass, a
     workgroup for every `per` consecutive tiles, MAX_GROUPS workgroups at most."""
-    n0, n1, n2 = (int(d) for d in dims)
-    cols = rt.columns(label_itemsize)
-    ncb, nrb, npb = rt._ceil(n2, cols), rt._ceil(n1, rt.WAVES), rt._ceil(n0 - int(first_owned), rt.PLANES)
-    tiles = ncb * nrb * npb
-    most = (1 << VOXEL_CAP_LOG2) // (rt.WAVES * cols * rt.PLANES)
-    per = min(rt._ceil(tiles, MAX_GROUPS), most)
-    groups = rt._ceil(tiles, per)
-    return rt.Plan(ncb, nrb, npb, tiles, per, groups, tiles - (groups - 1) * per)
+    return rt.plan(dims, first_owned, label_itemsize, "sighist")
 
 
 def two_tile_dims(label_itemsize, vector):

@@ -9,9 +9,8 @@ import numpy as np
 import range_tiles
 
 PAIR_ORDER = ((0, 0), (0, 1), (0, 2), (1, 1), (1, 2), (2, 2))
-LABEL_SLOTS = 448                      # rows of a workgroup's LDS table (SM_SLOTS of csrc/ta_sigmoments.h): the one place tests read it
-MAX_GROUPS = 1024                      # SM_MAX_GROUPS
-VOXEL_CAP_LOG2 = 31                    # a workgroup's LDS rows count voxels in u32
+LABEL_SLOTS = range_tiles.LABEL_SLOTS["sigmoments"]      # rows of a workgroup's LDS table (SM_SLOTS of csrc/ta_sigmoments.h)
+MAX_GROUPS = range_tiles.MAX_GROUPS["sigmoments"]        # SM_MAX_GROUPS
 
 
 # ---- the integers ---------------------------------------------------------------------------------------------------------------
@@ -116,15 +115,14 @@ def first_moments_fit(dims, signal_itemsize):
 
 
 def plan(dims, first_owned, label_itemsize, signal_itemsize):
-    """dims: the buffer dims in memory order (the halo plane included when first_owned == 1).  range_tiles.plan(..., "signal")
+    """dims: the buffer dims in memory order (the halo plane included when first_owned == 1).  range_tiles.plan(..., "sigmoments")
     with the exactness cap: a workgroup takes no more tiles than keep voxels x g^2 x smax below 2^64, g = the largest buffer dim
     minus one.  most == 0 (then per == groups == 0): the pass refuses the dims.  uncapped: what the plan would be without the cap."""
-    base = range_tiles.plan(dims, first_owned, label_itemsize, "signal")
-    assert MAX_GROUPS == range_tiles.MAX_GROUPS["signal"] and VOXEL_CAP_LOG2 == range_tiles.VOXEL_CAP_LOG2["signal"]
+    base = range_tiles.plan(dims, first_owned, label_itemsize, "sigmoments")
     tile_voxels = range_tiles.WAVES * range_tiles.columns(label_itemsize) * range_tiles.PLANES
     g = max(max(int(d) for d in dims) - 1, 1)
     exact = (1 << 64) // (g * g * smax(signal_itemsize)) // tile_voxels
-    most = min((1 << VOXEL_CAP_LOG2) // tile_voxels, exact)
+    most = min((1 << range_tiles.VOXEL_CAP_LOG2["sigmoments"]) // tile_voxels, exact)
     if most == 0:
         return Plan(base.ncb, base.nrb, base.npb, base.tiles, 0, 0, 0, 0, base.per)
     per = min(base.per, most)
@@ -134,14 +132,7 @@ def plan(dims, first_owned, label_itemsize, signal_itemsize):
 
 def group_image(dims, first_owned, label_itemsize, signal_itemsize):
     """int64 image of the buffer: the workgroup that walks each voxel, -1 in the halo plane."""
-    n0, n1, n2 = (int(d) for d in dims)
-    p = plan(dims, first_owned, label_itemsize, signal_itemsize)
-    pb = (np.arange(n0) - int(first_owned)) // range_tiles.PLANES
-    rb = np.arange(n1) // range_tiles.WAVES
-    cb = np.arange(n2) // range_tiles.columns(label_itemsize)
-    g = ((pb[:, None, None] * p.nrb + rb[None, :, None]) * p.ncb + cb[None, None, :]) // p.per
-    g[:int(first_owned)] = -1
-    return g
+    return range_tiles.group_image(dims, first_owned, label_itemsize, "sigmoments", plan(dims, first_owned, label_itemsize, signal_itemsize))
 
 
 def label_spill_bound(V, first_owned, signal_itemsize):

@@ -25,7 +25,7 @@ OWN, FROM = _capi.DIST_OWN_WALL, _capi.DIST_FROM_LABEL
 UNIT, HALF = (1.0, 1.0, 1.0), (0.5, 0.5, 1.0)
 BG = synth.BACKGROUND
 EDGES = np.array([0.0, 1.0, 1.5, 2.0, 3.0, np.inf])          # distances; the kernels take their squares
-PLAN = "wallgeo"                                             # range_tiles.plan: the tile shape of the signal pass, the ranges (4096 workgroups at most) of the wall-geometry pass
+PLAN = "profile"                                             # range_tiles.plan: 4096 workgroups at most, every plane walked (first_owned = 0)
 
 
 @functools.lru_cache(maxsize=None)

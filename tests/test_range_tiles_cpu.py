@@ -3,12 +3,14 @@ test_gpu_tile_ranges.py and test_gpu_feature_table_spills.py has the property it
 the ones the kernels are compiled with today."""
 import os
 import re
+import subprocess
 
 import numpy as np
 import pytest
 
 import overlap_reference
 import range_tiles as rt
+import sighist_reference
 import signal_reference
 import wall_geometry_reference
 
@@ -21,14 +23,26 @@ def _constant(source, name):
     return int(m.group(1))
 
 
+def _named(text, name):
+    """The integer behind `name` in the sources `text`: a literal, a constexpr, or the default a #define gives."""
+    return int(name) if name.isdigit() else _named(text, re.search(r"(?:constexpr\s+\w+|#define)\s+%s\s*=?\s*(\w+)" % name, text).group(1))
+
+
+def range_shape(which):
+    """(waves, planes, max_groups, voxel_cap_log2) of the one RangeShape line of the pass's kernel file (names: there or in its header)."""
+    text = "".join(open(os.path.join(CSRC, f % which)).read() for f in ("kernels_%s.hip", "ta_%s.h"))
+    (fields,) = re.findall(r"constexpr\s+RangeShape\s+\w+\s*=\s*\{([^}]*)\}", text)
+    return tuple(_named(text, f.strip()) for f in fields.split(","))
+
+
 def test_restated_constants_are_the_sources():
-    """A retuned tile, table or group count must change range_tiles.py (and the shapes below) deliberately."""
-    for which, src, pre in (("signal", "kernels_signal.hip", "SIG"), ("overlap", "kernels_overlap.hip", "OV"),
-                            ("wallgeo", "kernels_wallgeo.hip", "WG")):
-        assert _constant(src, pre + "_WAVES") == rt.WAVES and _constant(src, pre + "_PLANES") == rt.PLANES
-        assert _constant(src, pre + "_MAX_GROUPS") == rt.MAX_GROUPS[which]
-        assert re.search(r"\(int64_t\)1 << %d\) / \(%s_WAVES \* cols \* %s_PLANES\)" % (rt.VOXEL_CAP_LOG2[which], pre, pre),
-                         open(os.path.join(CSRC, src)).read())
+    """A retuned tile, table, group count or voxel cap must change range_tiles.py (and the shapes below) deliberately."""
+    assert sorted(rt.MAX_GROUPS) == sorted(rt.VOXEL_CAP_LOG2) == ["overlap", "profile", "sighist", "sigmoments", "signal", "wallgeo"]
+    for which in rt.MAX_GROUPS:
+        assert range_shape(which) == (rt.WAVES, rt.PLANES, rt.MAX_GROUPS[which], rt.VOXEL_CAP_LOG2[which]), which
+    assert _constant("ta_sigmoments.h", "SM_SLOTS") == rt.LABEL_SLOTS["sigmoments"]
+    assert _constant("ta_profile.h", "PROF_SLOTS") == rt.KEY_SLOTS["profile"]
+    assert _named(open(os.path.join(CSRC, "ta_sighist.h")).read(), "SH_SLOTS") == rt.KEY_SLOTS["sighist"]
     assert _constant("kernels_signal.hip", "SIG_LSLOTS") == rt.LABEL_SLOTS["signal"]
     assert _constant("kernels_signal.hip", "SIG_PSLOTS") == rt.PAIR_SLOTS["signal"]
     assert _constant("kernels_overlap.hip", "OV_SLOTS") == rt.PAIR_SLOTS["overlap"]
@@ -59,6 +73,48 @@ RECORDED = [
 @pytest.mark.parametrize("dims,first_owned,itemsize,which,want", RECORDED)
 def test_plan_gives_the_recorded_numbers(dims, first_owned, itemsize, which, want):
     assert tuple(rt.plan(dims, first_owned, itemsize, which)) == want
+
+
+@pytest.fixture(scope="module")
+def range_plan_exe(tmp_path_factory):
+    """tests/native/range_plan.cpp: csrc/ta_range_plan.h compiled as plain host C++ by the compiler of the build."""
+    from tissue_analysis_amd import build as ta_build
+    exe = str(tmp_path_factory.mktemp("range_plan") / "range_plan")
+    subprocess.check_call([ta_build._hipcc(), "-x", "c++", "-std=c++17", "-O1", "-Wall", "-I", CSRC,
+                           os.path.join(os.path.dirname(os.path.abspath(__file__)), "native", "range_plan.cpp"), "-o", exe])
+    return lambda mode, lines: subprocess.run([exe, mode], input="\n".join(lines) + "\n", stdout=subprocess.PIPE, check=True,
+                                              universal_newlines=True, timeout=60).stdout.split("\n")[:-1]
+
+
+def test_the_header_computes_the_restated_plan(range_plan_exe):
+    """range_tiles + plan_ranges of ta_range_plan.h against rt.plan: the recorded rows, and the passes they do not cover."""
+    rows = [(dims, first_owned, itemsize, which) for dims, first_owned, itemsize, which, _ in RECORDED]
+    rows += [(sighist_reference.two_tile_dims(itemsize, vector), 0, itemsize, "sighist") for itemsize in (2, 4) for vector in (True, False)]
+    rows += [((1 << 14, 1 << 16, 1 << 18), 0, 2, "sighist")]                          # 2^48 voxels: the voxel cap binds
+    rows += [((257, 1025, 9), 0, itemsize, which) for itemsize in (2, 4) for which in ("profile", "sigmoments")]
+    rows += [((1, 5, 7), 1, 2, "signal"), ((0, 5, 7), 0, 4, "wallgeo")]               # nothing owned: no tile, no group
+    out = range_plan_exe("plan", ["%d %d %d %d %d %d %d %d %d" % (tuple(dims) + (first_owned, itemsize, rt.WAVES, rt.PLANES, rt.MAX_GROUPS[which],
+                                                                                  rt.VOXEL_CAP_LOG2[which])) for dims, first_owned, itemsize, which in rows])
+    assert len(out) == len(rows)
+    for (dims, first_owned, itemsize, which), line in zip(rows, out):
+        want = tuple(rt.plan(dims, first_owned, itemsize, which))[:6] if dims[0] > first_owned else (0,) * 6
+        assert tuple(int(v) for v in line.split()) == want, (dims, first_owned, itemsize, which)
+    assert out[len(RECORDED) + 4].split()[4:] == ["65536", "131072"]                # the capped plan, by hand: 2^31 / 2^15 tiles a group
+
+
+def test_the_header_takes_the_vector_loads_where_expected(range_plan_exe):
+    """strips_vectorize: rows of whole strips, and every buffer aligned to min(strip, 16) bytes.  Expected by hand."""
+    whole = {2: (8, 24), 4: (8, 24)}                                   # n2 of 8, 9, 23, 24 that are whole strips of 8 / 4 labels
+    aligned = {(2, 1): (0, 8, 16), (4, 1): (0, 4, 8, 16),              # uint8 signal: strips of 8 / 4 bytes
+               (2, 2): (0, 16), (4, 2): (0, 8, 16),                    # uint16 signal: 16 / 8 bytes
+               (2, 8): (0, 16), (4, 8): (0, 16)}                       # f64: 64 / 32 bytes, loaded 16 at a time
+    cases = [(n2, lw, size, off) for n2 in (8, 9, 23, 24) for lw in (2, 4)
+             for size, offs in ((1, (0, 2, 4, 8, 16)), (2, (0, 2, 4, 8, 16)), (8, (0, 8, 16))) for off in offs]
+    out = range_plan_exe("vec", ["%d %d 2 4096 %d %d %d" % (n2, lw, lw, 4096 + off, size) for n2, lw, size, off in cases])
+    assert [int(v) for v in out] == [int(n2 in whole[lw] and off in aligned[lw, size]) for n2, lw, size, off in cases]
+    assert sum(int(v) for v in out) == 2 * (3 + 4 + 2 + 3 + 2 + 2)
+    # the labels' own buffer needs 16 bytes; a buffer of item size 0 is not read
+    assert range_plan_exe("vec", ["8 2 1 4104 2", "8 2 1 4112 2", "8 2 2 4096 2 4099 0"]) == ["0", "1", "1"]
 
 
 def test_the_voxel_cap_limits_a_range():

@@ -29,6 +29,8 @@ constexpr int OV_SLOTS = 2048;                     // LDS table slots (24 KB: a 
 constexpr int OV_PROBE = 32;                       // LDS probes before a record goes to the global table directly
 constexpr uint32_t OV_GLOBAL_PROBE = 512u;         // global probes before the table counts as full
 constexpr int64_t OV_MAX_GROUPS = 1024;            // four workgroups a CU
+// a lane's record and a workgroup's LDS slots count voxels in u32: fewer than 2^31 voxels a workgroup
+constexpr RangeShape OV_RANGE = {OV_WAVES, OV_PLANES, OV_MAX_GROUPS, 31};
 
 struct OvTable {
     unsigned long long key[OV_SLOTS];
@@ -245,25 +247,15 @@ void launch_types(hipStream_t s, const OverlapArgs& a, bool vec, int64_t groups)
 }  // namespace
 
 RangePlan launch_overlap(hipStream_t s, OverlapArgs a, int itemsize_a, int itemsize_b) {
-    const int vpl = 16 / itemsize_a;
-    const int64_t cols = 64 * vpl;
-    const int64_t owned = a.n0 - a.first_owned;
-    RangePlan plan;
-    if (owned <= 0 || a.n1 <= 0 || a.n2 <= 0) return plan;
-    const int64_t tiles = ((a.n2 + cols - 1) / cols) * ((a.n1 + OV_WAVES - 1) / OV_WAVES) * ((owned + OV_PLANES - 1) / OV_PLANES);
-    // a lane's record and a workgroup's LDS slots count voxels in u32: fewer than 2^31 voxels a workgroup
-    const int64_t most = ((int64_t)1 << 31) / (OV_WAVES * cols * OV_PLANES);
-    int64_t per = (tiles + OV_MAX_GROUPS - 1) / OV_MAX_GROUPS;
-    if (per > most) per = most;
-    a.tiles_per_group = (uint32_t)per;
-    const int64_t groups = (tiles + per - 1) / per;
-    const int b_strip = vpl * itemsize_b;                          // bytes of a lane's strip of B: 8, 16 or 32
-    const bool vec = a.n2 % vpl == 0 && ((uintptr_t)a.a % 16) == 0 && ((uintptr_t)a.b % (uintptr_t)(b_strip < 16 ? b_strip : 16)) == 0;
-    if (itemsize_a == 2 && itemsize_b == 2) launch_types<uint16_t, uint16_t>(s, a, vec, groups);
-    else if (itemsize_a == 2) launch_types<uint16_t, uint32_t>(s, a, vec, groups);
-    else if (itemsize_b == 2) launch_types<uint32_t, uint16_t>(s, a, vec, groups);
-    else launch_types<uint32_t, uint32_t>(s, a, vec, groups);
-    plan.tiles_per_group = (uint32_t)per; plan.groups = (uint32_t)groups;
+    const RangeTiles t = range_tiles(a.n0, a.n1, a.n2, a.first_owned, itemsize_a, OV_RANGE);
+    const RangePlan plan = plan_ranges(t.tiles, t.tile_voxels, OV_RANGE);
+    if (!plan.groups) return plan;
+    a.tiles_per_group = plan.tiles_per_group;
+    const bool vec = strips_vectorize(a.n2, itemsize_a, {{a.a, itemsize_a}, {a.b, itemsize_b}});      // (a lane's strip of B: 8, 16 or 32 bytes)
+    if (itemsize_a == 2 && itemsize_b == 2) launch_types<uint16_t, uint16_t>(s, a, vec, plan.groups);
+    else if (itemsize_a == 2) launch_types<uint16_t, uint32_t>(s, a, vec, plan.groups);
+    else if (itemsize_b == 2) launch_types<uint32_t, uint16_t>(s, a, vec, plan.groups);
+    else launch_types<uint32_t, uint32_t>(s, a, vec, plan.groups);
     return plan;
 }
 

@@ -32,6 +32,8 @@ constexpr int PRF_THREADS = PRF_WAVES * 64;
 constexpr int PRF_PLANES = 16;                     // planes of a tile
 constexpr int PRF_PROBE = 32;                      // probes before a record goes to the global rows directly
 constexpr int64_t PRF_MAX_GROUPS = 4096;           // 16 a CU, four of them resident: a range short enough for its keys to fit the table
+// a workgroup's LDS rows count voxels in u32: 2^30 voxels a workgroup at most
+constexpr RangeShape PRF_RANGE = {PRF_WAVES, PRF_PLANES, PRF_MAX_GROUPS, 30};
 constexpr uint32_t NO_KEY = 0xffffffffu;           // rows * K <= 2^31: never a key
 constexpr uint32_t NO_SIGNAL_MIN = 0xffffffffu;
 
@@ -266,22 +268,14 @@ void launch_types(hipStream_t s, const ProfileArgs& a, int signal_itemsize, bool
 }  // namespace
 
 RangePlan launch_profile(hipStream_t s, ProfileArgs a, int label_itemsize, int signal_itemsize) {
-    const int vpl = 16 / label_itemsize;
-    const int64_t cols = 64 * vpl;
-    RangePlan plan;
-    if (a.n0 <= 0 || a.n1 <= 0 || a.n2 <= 0) return plan;
-    const int64_t tiles = ((a.n2 + cols - 1) / cols) * ((a.n1 + PRF_WAVES - 1) / PRF_WAVES) * ((a.n0 + PRF_PLANES - 1) / PRF_PLANES);
-    // a workgroup's LDS rows count voxels in u32: 2^30 voxels a workgroup at most
-    const int64_t most = ((int64_t)1 << 30) / (PRF_WAVES * cols * PRF_PLANES);
-    int64_t per = (tiles + PRF_MAX_GROUPS - 1) / PRF_MAX_GROUPS;
-    if (per > most) per = most;
-    a.tiles_per_group = (uint32_t)per;
-    const int64_t groups = (tiles + per - 1) / per;
-    const bool vec = a.n2 % vpl == 0 && ((uintptr_t)a.vol % 16) == 0 && ((uintptr_t)a.d2 % 16) == 0 &&
-                     (!signal_itemsize || ((uintptr_t)a.sig % (uintptr_t)(vpl * signal_itemsize)) == 0);
-    if (label_itemsize == 2) launch_types<uint16_t>(s, a, signal_itemsize, vec, groups);
-    else launch_types<uint32_t>(s, a, signal_itemsize, vec, groups);
-    plan.tiles_per_group = (uint32_t)per; plan.groups = (uint32_t)groups;
+    const RangeTiles t = range_tiles(a.n0, a.n1, a.n2, 0, label_itemsize, PRF_RANGE);      // (the pass walks every plane: it takes no slab)
+    const RangePlan plan = plan_ranges(t.tiles, t.tile_voxels, PRF_RANGE);
+    if (!plan.groups) return plan;
+    a.tiles_per_group = plan.tiles_per_group;
+    // (without a signal a.sig is NULL and its item size 0: not a buffer of the pass)
+    const bool vec = strips_vectorize(a.n2, label_itemsize, {{a.vol, label_itemsize}, {a.d2, 8}, {a.sig, signal_itemsize}});
+    if (label_itemsize == 2) launch_types<uint16_t>(s, a, signal_itemsize, vec, plan.groups);
+    else launch_types<uint32_t>(s, a, signal_itemsize, vec, plan.groups);
     return plan;
 }
 

@@ -32,6 +32,8 @@ constexpr int SH_WAVES = 4;                        // rows of a tile = waves of 
 constexpr int SH_THREADS = SH_WAVES * 64;
 constexpr int SH_PLANES = 16;                      // planes of a tile
 constexpr int SH_PROBE = SH_SLOTS < 16 ? SH_SLOTS : 16;      // probes before a key goes without a slot
+// a workgroup's LDS counters are u32: fewer than 2^31 voxels a workgroup
+constexpr RangeShape SH_RANGE = {SH_WAVES, SH_PLANES, SH_MAX_GROUPS, 31};
 constexpr uint32_t NO_KEY = 0xffffffffu;           // keys are below 2^23: never a key
 constexpr uint32_t SLOT_GLOBAL = 0xfffffffeu;      // the key found no slot: its voxels go to the global counters
 constexpr uint32_t SLOT_SKIP = 0xffffffffu;        // nothing to count (no selector, or a label out of range)
@@ -304,24 +306,15 @@ void launch_kind(hipStream_t s, const DigitArgs& a, bool vec, int64_t groups) {
 }  // namespace
 
 RangePlan launch_sighist_digits(hipStream_t s, DigitArgs a, int label_itemsize, int signal_itemsize) {
-    const int vpl = 16 / label_itemsize;
-    const int64_t cols = 64 * vpl;
-    const int64_t owned = a.n0 - a.first_owned;
-    RangePlan plan;
-    if (owned <= 0 || a.n1 <= 0 || a.n2 <= 0) return plan;
-    const int64_t tiles = ((a.n2 + cols - 1) / cols) * ((a.n1 + SH_WAVES - 1) / SH_WAVES) * ((owned + SH_PLANES - 1) / SH_PLANES);
-    // a workgroup's LDS counters are u32: fewer than 2^31 voxels a workgroup
-    const int64_t most = ((int64_t)1 << 31) / (SH_WAVES * cols * SH_PLANES);
-    int64_t per = (tiles + SH_MAX_GROUPS - 1) / SH_MAX_GROUPS;
-    if (per > most) per = most;
-    a.tiles_per_group = (uint32_t)per;
-    const int64_t groups = (tiles + per - 1) / per;
-    const bool vec = a.n2 % vpl == 0 && ((uintptr_t)a.vol % 16) == 0 && ((uintptr_t)a.sig % (uintptr_t)(vpl * signal_itemsize)) == 0;
-    if (label_itemsize == 2 && signal_itemsize == 1) launch_kind<uint16_t, uint8_t>(s, a, vec, groups);
-    else if (label_itemsize == 2) launch_kind<uint16_t, uint16_t>(s, a, vec, groups);
-    else if (signal_itemsize == 1) launch_kind<uint32_t, uint8_t>(s, a, vec, groups);
-    else launch_kind<uint32_t, uint16_t>(s, a, vec, groups);
-    plan.tiles_per_group = (uint32_t)per; plan.groups = (uint32_t)groups;
+    const RangeTiles t = range_tiles(a.n0, a.n1, a.n2, a.first_owned, label_itemsize, SH_RANGE);
+    const RangePlan plan = plan_ranges(t.tiles, t.tile_voxels, SH_RANGE);
+    if (!plan.groups) return plan;
+    a.tiles_per_group = plan.tiles_per_group;
+    const bool vec = strips_vectorize(a.n2, label_itemsize, {{a.vol, label_itemsize}, {a.sig, signal_itemsize}});
+    if (label_itemsize == 2 && signal_itemsize == 1) launch_kind<uint16_t, uint8_t>(s, a, vec, plan.groups);
+    else if (label_itemsize == 2) launch_kind<uint16_t, uint16_t>(s, a, vec, plan.groups);
+    else if (signal_itemsize == 1) launch_kind<uint32_t, uint8_t>(s, a, vec, plan.groups);
+    else launch_kind<uint32_t, uint16_t>(s, a, vec, plan.groups);
     return plan;
 }
 

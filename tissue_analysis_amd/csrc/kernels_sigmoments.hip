@@ -31,6 +31,8 @@ constexpr int SM_WAVES = 4;                        // rows of a tile = waves of 
 constexpr int SM_THREADS = SM_WAVES * 64;
 constexpr int SM_PLANES = 16;                      // planes of a tile
 constexpr int SM_PROBE = 32;                       // probes before a record goes to the global rows directly
+// n is u32 in a workgroup's LDS row: fewer than 2^31 voxels a workgroup (sigmoments_plan adds the cap that keeps the 64-bit sums exact)
+constexpr RangeShape SM_RANGE = {SM_WAVES, SM_PLANES, SM_MAX_GROUPS, 31};
 
 // the 32-bit tile record at its largest: 8 voxels of 65535 a plane step, q <= 15, j <= 7
 static_assert(65535ull * 8 * (SM_PLANES - 1) * (SM_PLANES - 1) * SM_PLANES < (1ull << 32), "QQ wraps");
@@ -266,10 +268,9 @@ void launch_types(hipStream_t s, const SigMomArgs& a, bool vec, uint32_t groups)
 
 int sigmoments_plan(const int64_t dims[3], int first_owned, int label_itemsize, int signal_itemsize, RangePlan* plan) {
     typedef unsigned __int128 u128;
-    const int64_t cols = 64 * (16 / label_itemsize);
-    const int64_t owned = dims[0] - first_owned;
     *plan = RangePlan();
-    if (owned <= 0 || dims[1] <= 0 || dims[2] <= 0) return 0;
+    const RangeTiles t = range_tiles(dims[0], dims[1], dims[2], first_owned, label_itemsize, SM_RANGE);
+    if (!t.tiles) return 0;
     const uint64_t gmax = (uint64_t)std::max(dims[0], std::max(dims[1], dims[2]));
     const uint64_t g = std::max<uint64_t>(gmax - 1, 1), smax = signal_itemsize == 1 ? 255u : 65535u;
     const u128 two64 = (u128)1 << 64;
@@ -277,24 +278,15 @@ int sigmoments_plan(const int64_t dims[3], int first_owned, int label_itemsize, 
     const u128 nvox = (u128)((uint64_t)dims[0] * (uint64_t)dims[1]) * (uint64_t)dims[2];       // (every dim <= 2^30)
     if (nvox > (two64 - 1) / (u128)(g * smax)) return 1;
     // a workgroup's 64-bit rows: voxels g^2 smax <= 2^64 (never equal: smax is odd), beside the u32 n
-    const int64_t tile_voxels = SM_WAVES * cols * SM_PLANES;
-    const u128 exact = two64 / ((u128)g * g * smax) / (u128)tile_voxels;
-    const int64_t tiles = ((dims[2] + cols - 1) / cols) * ((dims[1] + SM_WAVES - 1) / SM_WAVES) * ((owned + SM_PLANES - 1) / SM_PLANES);
-    int64_t most = ((int64_t)1 << 31) / tile_voxels;
-    if (exact < (u128)most) most = (int64_t)exact;
-    if (most == 0) return 2;
-    int64_t per = (tiles + SM_MAX_GROUPS - 1) / SM_MAX_GROUPS;
-    if (per > most) per = most;
-    plan->tiles_per_group = (uint32_t)per;
-    plan->groups = (uint32_t)((tiles + per - 1) / per);
-    return 0;
+    const u128 exact = two64 / ((u128)g * g * smax) / (u128)t.tile_voxels;
+    *plan = plan_ranges(t.tiles, t.tile_voxels, SM_RANGE, (int64_t)std::min<u128>(exact, (u128)INT64_MAX));
+    return plan->groups ? 0 : 2;                               // (no group: not one tile fits)
 }
 
 void launch_sigmoments(hipStream_t s, SigMomArgs a, int label_itemsize, int signal_itemsize, const RangePlan& plan) {
     if (!plan.groups) return;
-    const int vpl = 16 / label_itemsize;
     a.tiles_per_group = plan.tiles_per_group;
-    const bool vec = a.n2 % vpl == 0 && ((uintptr_t)a.vol % 16) == 0 && ((uintptr_t)a.sig % (uintptr_t)(vpl * signal_itemsize)) == 0;
+    const bool vec = strips_vectorize(a.n2, label_itemsize, {{a.vol, label_itemsize}, {a.sig, signal_itemsize}});
     if (label_itemsize == 2 && signal_itemsize == 1) launch_types<uint16_t, uint8_t>(s, a, vec, plan.groups);
     else if (label_itemsize == 2) launch_types<uint16_t, uint16_t>(s, a, vec, plan.groups);
     else if (signal_itemsize == 1) launch_types<uint32_t, uint8_t>(s, a, vec, plan.groups);

@@ -31,6 +31,8 @@ constexpr int SIG_PLANES = 16;                     // planes of a tile
 constexpr int SIG_LSLOTS = 512, SIG_PSLOTS = 2048; // LDS table slots (16 + 48 KB: a workgroup's tiles of C4 touch ~750 pairs)
 constexpr int SIG_LPROBE = 32, SIG_PPROBE = 32;    // probes before a record goes to the global rows directly
 constexpr int64_t SIG_MAX_GROUPS = 1024;           // four workgroups a CU
+// a workgroup's LDS rows count voxels in u32: fewer than 2^31 voxels a workgroup
+constexpr RangeShape SIG_RANGE = {SIG_WAVES, SIG_PLANES, SIG_MAX_GROUPS, 31};
 constexpr uint32_t NO_SIGNAL_MIN = 0xffffffffu;
 
 // (a pass without walls has no pair table: 16 KB of LDS instead of 64, more workgroups a CU)
@@ -349,24 +351,16 @@ void launch_signal_hash(hipStream_t s, const uint64_t* keys, uint64_t n, uint64_
 }
 
 RangePlan launch_signal(hipStream_t s, SignalArgs a, int label_itemsize, int signal_itemsize, uint32_t what) {
-    const int vpl = 16 / label_itemsize;
-    const int64_t cols = 64 * vpl;
-    const int64_t owned = a.n0 - a.first_owned;
-    RangePlan plan;
-    if (owned <= 0 || a.n1 <= 0 || a.n2 <= 0 || !(what & (SIG_LABELS | SIG_WALLS))) return plan;
-    const int64_t tiles = ((a.n2 + cols - 1) / cols) * ((a.n1 + SIG_WAVES - 1) / SIG_WAVES) * ((owned + SIG_PLANES - 1) / SIG_PLANES);
-    // a workgroup's LDS rows count voxels in u32: fewer than 2^31 voxels a workgroup
-    const int64_t most = ((int64_t)1 << 31) / (SIG_WAVES * cols * SIG_PLANES);
-    int64_t per = (tiles + SIG_MAX_GROUPS - 1) / SIG_MAX_GROUPS;
-    if (per > most) per = most;
-    a.tiles_per_group = (uint32_t)per;
-    const int64_t groups = (tiles + per - 1) / per;
-    const bool vec = a.n2 % vpl == 0 && ((uintptr_t)a.vol % 16) == 0 && ((uintptr_t)a.sig % (uintptr_t)(vpl * signal_itemsize)) == 0;
-    if (label_itemsize == 2 && signal_itemsize == 1) launch_types<uint16_t, uint8_t>(s, a, what, vec, groups);
-    else if (label_itemsize == 2) launch_types<uint16_t, uint16_t>(s, a, what, vec, groups);
-    else if (signal_itemsize == 1) launch_types<uint32_t, uint8_t>(s, a, what, vec, groups);
-    else launch_types<uint32_t, uint16_t>(s, a, what, vec, groups);
-    plan.tiles_per_group = (uint32_t)per; plan.groups = (uint32_t)groups;
+    if (!(what & (SIG_LABELS | SIG_WALLS))) return RangePlan();
+    const RangeTiles t = range_tiles(a.n0, a.n1, a.n2, a.first_owned, label_itemsize, SIG_RANGE);
+    const RangePlan plan = plan_ranges(t.tiles, t.tile_voxels, SIG_RANGE);
+    if (!plan.groups) return plan;
+    a.tiles_per_group = plan.tiles_per_group;
+    const bool vec = strips_vectorize(a.n2, label_itemsize, {{a.vol, label_itemsize}, {a.sig, signal_itemsize}});
+    if (label_itemsize == 2 && signal_itemsize == 1) launch_types<uint16_t, uint8_t>(s, a, what, vec, plan.groups);
+    else if (label_itemsize == 2) launch_types<uint16_t, uint16_t>(s, a, what, vec, plan.groups);
+    else if (signal_itemsize == 1) launch_types<uint32_t, uint8_t>(s, a, what, vec, plan.groups);
+    else launch_types<uint32_t, uint16_t>(s, a, what, vec, plan.groups);
     return plan;
 }
 

@@ -36,6 +36,8 @@ constexpr int WG_PLANES = 16;                      // planes of a tile
 constexpr int WG_SLOTS = 512;                      // LDS rows: 512 x 104 bytes = 52 KB, three workgroups a CU
 constexpr int WG_PROBE = 32;                       // probes before a record goes to the global rows directly
 constexpr int64_t WG_MAX_GROUPS = 4096;            // (ranges a quarter of the signal pass's: a table a quarter of its slots)
+// a workgroup's LDS rows count faces in u32: fewer than 2^30 voxels (three faces each) a workgroup
+constexpr RangeShape WG_RANGE = {WG_WAVES, WG_PLANES, WG_MAX_GROUPS, 30};
 
 struct WgTable {
     unsigned long long key[WG_SLOTS];
@@ -288,27 +290,18 @@ __global__ __launch_bounds__(WG_THREADS) void wallgeo_kernel(const WallGeoArgs A
 }  // namespace
 
 RangePlan launch_wallgeo(hipStream_t s, WallGeoArgs a, int label_itemsize) {
-    const int vpl = 16 / label_itemsize;
-    const int64_t cols = 64 * vpl;
-    const int64_t owned = a.n0 - a.first_owned;
-    RangePlan plan;
-    if (owned <= 0 || a.n1 <= 0 || a.n2 <= 0) return plan;
-    const int64_t tiles = ((a.n2 + cols - 1) / cols) * ((a.n1 + WG_WAVES - 1) / WG_WAVES) * ((owned + WG_PLANES - 1) / WG_PLANES);
-    // a workgroup's LDS rows count faces in u32: fewer than 2^30 voxels (three faces each) a workgroup
-    const int64_t most = ((int64_t)1 << 30) / (WG_WAVES * cols * WG_PLANES);
-    int64_t per = (tiles + WG_MAX_GROUPS - 1) / WG_MAX_GROUPS;
-    if (per > most) per = most;
-    a.tiles_per_group = (uint32_t)per;
-    const int64_t groups = (tiles + per - 1) / per;
-    const bool vec = a.n2 % vpl == 0 && ((uintptr_t)a.vol % 16) == 0;
+    const RangeTiles t = range_tiles(a.n0, a.n1, a.n2, a.first_owned, label_itemsize, WG_RANGE);
+    const RangePlan plan = plan_ranges(t.tiles, t.tile_voxels, WG_RANGE);
+    if (!plan.groups) return plan;
+    a.tiles_per_group = plan.tiles_per_group;
+    const bool vec = strips_vectorize(a.n2, label_itemsize, {{a.vol, label_itemsize}});
     if (label_itemsize == 2) {
-        if (vec) hipLaunchKernelGGL((wallgeo_kernel<uint16_t, true>), dim3((unsigned)groups), dim3(WG_THREADS), 0, s, a);
-        else hipLaunchKernelGGL((wallgeo_kernel<uint16_t, false>), dim3((unsigned)groups), dim3(WG_THREADS), 0, s, a);
+        if (vec) hipLaunchKernelGGL((wallgeo_kernel<uint16_t, true>), dim3(plan.groups), dim3(WG_THREADS), 0, s, a);
+        else hipLaunchKernelGGL((wallgeo_kernel<uint16_t, false>), dim3(plan.groups), dim3(WG_THREADS), 0, s, a);
     } else {
-        if (vec) hipLaunchKernelGGL((wallgeo_kernel<uint32_t, true>), dim3((unsigned)groups), dim3(WG_THREADS), 0, s, a);
-        else hipLaunchKernelGGL((wallgeo_kernel<uint32_t, false>), dim3((unsigned)groups), dim3(WG_THREADS), 0, s, a);
+        if (vec) hipLaunchKernelGGL((wallgeo_kernel<uint32_t, true>), dim3(plan.groups), dim3(WG_THREADS), 0, s, a);
+        else hipLaunchKernelGGL((wallgeo_kernel<uint32_t, false>), dim3(plan.groups), dim3(WG_THREADS), 0, s, a);
     }
-    plan.tiles_per_group = (uint32_t)per; plan.groups = (uint32_t)groups;
     return plan;
 }
 

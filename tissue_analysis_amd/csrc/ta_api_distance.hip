@@ -36,7 +36,7 @@ TA_API int ta_distance_extract(ta_ctx* c, int mode, uint32_t site_label, const d
     if (flags & ~TA_DIST_EDGE_IS_SITE) return fail(TA_EINVAL, "bad distance flags 0x%x", flags);
     ta::DistanceArgs a = {};
     int rc = check_spacing(spacing);
-    if (rc != TA_OK || (rc = transform_preflight(c, "distance", spacing, a.w)) != TA_OK) return rc;
+    if (rc != TA_OK || (rc = transform_preflight(c, "distance pass", spacing, a.w)) != TA_OK) return rc;
     c->dist.seq = 0;
     profile_on_new_distance(c);
     const uint64_t nvox = voxels(c), R = (uint64_t)c->max_label + 1;

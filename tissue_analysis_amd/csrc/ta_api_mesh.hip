@@ -5,7 +5,7 @@
 
 namespace {
 
-bool mesh_current(const ta_ctx* c) { return c->mesh.seq != 0 && c->extracted && c->mesh.seq == c->extract_seq; }
+bool mesh_current(const ta_ctx* c) { return pass_current(c, c->mesh.seq); }
 
 // byte offsets of the parts of MeshState::small for R rows and wf / wc waves of the face / corner kernels
 struct MeshSmall {
@@ -70,10 +70,8 @@ TA_API int ta_mesh_extract(ta_ctx* c, int sub_factor, const uint8_t* wanted_rows
     if (sub_factor < 1) return fail(TA_EINVAL, "sub_factor must be >= 1, not %d", sub_factor);
     if (!c->vol) return fail(TA_EINVAL, "no volume set");
     if (c->first_owned) return fail(TA_EINVAL, "cell meshes are not available on a slab that carries a halo plane");
-    int rc = use_device(c);
+    int rc = extraction_preflight(c, "mesh pass");
     if (rc != TA_OK) return rc;
-    if (!c->extracted) return fail(TA_EINVAL, "the mesh pass needs a ta_extract of the current volume first");
-    if ((rc = finish_extract(c)) != TA_OK) return rc;
     c->mesh.seq = 0;
     c->mesh.host_ready = false;
     const uint64_t R = (uint64_t)c->max_label + 1;

@@ -34,7 +34,7 @@ TA_API int ta_nearest_extract(ta_ctx* c, uint32_t empty_label, uint32_t not_from
     int rc = check_spacing(spacing);
     if (rc != TA_OK) return rc;
     if (!(max_d2 >= 0.0)) return fail(TA_EINVAL, "max_d2=%g is negative or not a number", max_d2);
-    if ((rc = transform_preflight(c, "nearest-label", spacing, a.w)) != TA_OK) return rc;
+    if ((rc = transform_preflight(c, "nearest-label pass", spacing, a.w)) != TA_OK) return rc;
     c->near.seq = 0;
     const uint64_t nvox = voxels(c), R = (uint64_t)c->max_label + 1;
     const NearestLayout L(R);

@@ -204,8 +204,7 @@ TA_API int ta_overlap_timing(ta_ctx* c, double* ms) {
     if (c->ov.state == 0 || !c->ov.ev[1]) return fail(TA_EINVAL, "no overlap pass has been run");
     int rc = use_device(c);
     if (rc != TA_OK) return rc;
-    TA_HIP(hipEventSynchronize(c->ov.ev[1]));
-    return elapsed_ms(c->ov.ev[0], c->ov.ev[1], ms);
+    return interval_ms(c->ov.ev[0], c->ov.ev[1], ms);
 }
 
 TA_API int ta_overlap_timing_compaction(ta_ctx* c, double* ms, int* passes) {

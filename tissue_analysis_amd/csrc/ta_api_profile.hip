@@ -14,9 +14,7 @@ static_assert(sizeof(ProfileState::edges) == 8 * (ta::PROF_MAX_BINS + 1), "Profi
 const char* const NO_RESULTS = "no distance-shell profile of the current distance map (run ta_profile_extract)";
 
 // the table belongs to the current extraction AND to the distance map the context holds (a new one ends it: profile_on_new_distance)
-bool profile_current(const ta_ctx* c) {
-    return c->prof.seq != 0 && c->extracted && c->prof.seq == c->extract_seq && c->dist.seq == c->extract_seq;
-}
+bool profile_current(const ta_ctx* c) { return pass_current(c, c->prof.seq) && c->dist.seq == c->extract_seq; }
 
 // byte offsets of the parts of ProfileState::out for N = rows x bins entries; the signal columns only in a pass with signal
 struct ProfileLayout {
@@ -36,8 +34,7 @@ int profile_ready(ta_ctx* c) {
 // drain the stream and look at the pass's flag words
 int profile_finish(ta_ctx* c, uint32_t* spills = nullptr) {
     uint32_t flags[ta::PROF_NFLAGS] = {0, 0, 0, 0};
-    TA_HIP(hipMemcpyAsync(flags, c->prof.out.p, sizeof(flags), hipMemcpyDeviceToHost, c->stream));
-    TA_HIP(hipStreamSynchronize(c->stream));
+    if (const int rc = read_pass_flags<ta::PROF_NFLAGS>(c, c->prof.out.p, flags); rc != TA_OK) return rc;
     if (flags[ta::PROF_FLAG_RANGE])
         return fail(TA_ERANGE, "the profile pass met a label above max_label=%u (the volume changed since ta_extract)", c->max_label);
     if (spills) *spills = flags[ta::PROF_FLAG_SPILL];
@@ -62,7 +59,7 @@ TA_API int ta_profile_extract(ta_ctx* c, int nbins, const double* edges2, uint32
     for (int k = 0; k < nbins; ++k)
         if (!(edges2[k + 1] > edges2[k])) return fail(TA_EINVAL, "edges2[%d]=%g does not lie above edges2[%d]=%g", k + 1, edges2[k + 1], k, edges2[k]);
     const bool signal = what & TA_PROF_SIGNAL;
-    if (!c->vol || c->dist.seq == 0 || !c->extracted || c->dist.seq != c->extract_seq)
+    if (!c->vol || !pass_current(c, c->dist.seq))
         return fail(TA_EINVAL, "the profile pass needs a ta_distance_extract of the current extraction first");
     if (signal && !c->sig.img.p) return fail(TA_EINVAL, "TA_PROF_SIGNAL without a signal set");
     if (signal && !companion_matches(c, c->sig.img)) return fail(TA_EINVAL, "the signal does not match the label volume");
@@ -137,8 +134,7 @@ TA_API int ta_profile_timing(ta_ctx* c, double* ms) {
     if (!ms) return fail(TA_EINVAL, "NULL argument");
     int rc = profile_ready(c);
     if (rc != TA_OK) return rc;
-    TA_HIP(hipEventSynchronize(c->prof.ev[1]));
-    return elapsed_ms(c->prof.ev[0], c->prof.ev[1], ms);
+    return interval_ms(c->prof.ev[0], c->prof.ev[1], ms);
 }
 
 }  // extern "C"

@@ -12,8 +12,6 @@ static_assert(TA_SIGRANK_MAX_RANKS == ta::SH_MAX_RANKS, "the public header and t
 const char* const NO_HIST = "no signal histogram of the current extraction (run ta_sighist_extract)";
 const char* const NO_RANK = "no order statistics of the current extraction (run ta_sigrank_extract)";
 
-bool current(const ta_ctx* c, uint64_t seq) { return seq != 0 && c->extracted && seq == c->extract_seq; }
-
 // byte offsets of the parts of SigHistState::rank for R rows of n ranks; counts2 only for a uint16 signal
 struct RankLayout {
     uint64_t flags = 0, ranks, rem, hi, sel, map, values, counts1, counts2, bytes;
@@ -24,16 +22,6 @@ struct RankLayout {
         bytes = two ? counts2 + 8 * 256 * N : counts2;
     }
 };
-
-// what both entry points ask of the context before a pass; leaves the stream's extraction settled
-int pass_ready(ta_ctx* c) {
-    if (!c->sig.img.p) return fail(TA_EINVAL, "no signal set");
-    if (!c->vol || !companion_matches(c, c->sig.img)) return fail(TA_EINVAL, "the signal does not match the label volume");
-    int rc = use_device(c);
-    if (rc != TA_OK) return rc;
-    if (!c->extracted) return fail(TA_EINVAL, "the pass needs a ta_extract of the current volume first");
-    return finish_extract(c);
-}
 
 ta::DigitArgs digit_args(const ta_ctx* c) {
     ta::DigitArgs a = {};
@@ -48,8 +36,8 @@ ta::DigitArgs digit_args(const ta_ctx* c) {
 // drain the stream and look at the flag words of `passes` digit passes at `flags`; spills: those of the last of them
 int digits_finish(ta_ctx* c, const void* flags, int passes, uint32_t* spills = nullptr) {
     uint32_t f[2 * ta::SH_NFLAGS] = {0, 0, 0, 0, 0, 0, 0, 0};
-    TA_HIP(hipMemcpyAsync(f, flags, sizeof(uint32_t) * ta::SH_NFLAGS * passes, hipMemcpyDeviceToHost, c->stream));
-    TA_HIP(hipStreamSynchronize(c->stream));
+    const int rc = passes == 2 ? read_pass_flags<2 * ta::SH_NFLAGS>(c, flags, f) : read_pass_flags<ta::SH_NFLAGS>(c, flags, f);
+    if (rc != TA_OK) return rc;
     if (f[ta::SH_FLAG_RANGE] || f[ta::SH_NFLAGS + ta::SH_FLAG_RANGE])
         return fail(TA_ERANGE, "the pass met a label above max_label=%u (the volume changed since ta_extract)", c->max_label);
     if (spills) *spills = f[(passes - 1) * ta::SH_NFLAGS + ta::SH_FLAG_SPILL];
@@ -66,7 +54,7 @@ extern "C" {
 
 TA_API int ta_sighist_extract(ta_ctx* c, int log2_width) {
     if (!c) return fail(TA_EINVAL, "ctx is NULL");
-    int rc = pass_ready(c);
+    int rc = signal_pass_preflight(c, "pass");
     if (rc != TA_OK) return rc;
     const int bits = 8 * c->sig.img.itemsize;
     if (log2_width < bits - 8 || log2_width > bits)
@@ -98,7 +86,7 @@ TA_API int ta_sighist_extract(ta_ctx* c, int log2_width) {
 
 TA_API int ta_sighist_get(ta_ctx* c, uint64_t* counts) {
     if (!c) return fail(TA_EINVAL, "ctx is NULL");
-    if (!current(c, c->sh.hist_seq)) return fail(TA_EINVAL, NO_HIST);
+    if (!pass_current(c, c->sh.hist_seq)) return fail(TA_EINVAL, NO_HIST);
     int rc = use_device(c);
     if (rc != TA_OK) return rc;
     if ((rc = digits_finish(c, c->sh.out.p, 1)) != TA_OK) return rc;
@@ -113,7 +101,7 @@ TA_API int ta_sigrank_extract(ta_ctx* c, int nranks, const uint64_t* ranks) {
     if (!c) return fail(TA_EINVAL, "ctx is NULL");
     if (nranks < 1 || nranks > TA_SIGRANK_MAX_RANKS) return fail(TA_EINVAL, "nranks=%d is not in [1, %d]", nranks, TA_SIGRANK_MAX_RANKS);
     if (!ranks) return fail(TA_EINVAL, "ranks is NULL");
-    int rc = pass_ready(c);
+    int rc = signal_pass_preflight(c, "pass");
     if (rc != TA_OK) return rc;
     if (c->first_owned || c->a_origin)
         return fail(TA_EINVAL, "order statistics of a slab are not those of the volume: ta_sigrank_extract takes whole volumes only");
@@ -164,7 +152,7 @@ TA_API int ta_sigrank_extract(ta_ctx* c, int nranks, const uint64_t* ranks) {
 
 TA_API int ta_sigrank_get(ta_ctx* c, uint32_t* values) {
     if (!c) return fail(TA_EINVAL, "ctx is NULL");
-    if (!current(c, c->sh.rank_seq)) return fail(TA_EINVAL, NO_RANK);
+    if (!pass_current(c, c->sh.rank_seq)) return fail(TA_EINVAL, NO_RANK);
     int rc = use_device(c);
     if (rc != TA_OK) return rc;
     if ((rc = digits_finish(c, c->sh.rank.p, c->sh.rank_passes)) != TA_OK) return rc;
@@ -178,7 +166,7 @@ TA_API int ta_sigrank_get(ta_ctx* c, uint32_t* values) {
 
 TA_API int ta_sighist_debug(ta_ctx* c, uint32_t out[4]) {
     if (!c) return fail(TA_EINVAL, "ctx is NULL");
-    const bool hist = c->sh.last == 1 && current(c, c->sh.hist_seq), rank = c->sh.last == 2 && current(c, c->sh.rank_seq);
+    const bool hist = c->sh.last == 1 && pass_current(c, c->sh.hist_seq), rank = c->sh.last == 2 && pass_current(c, c->sh.rank_seq);
     if (!hist && !rank) return fail(TA_EINVAL, NO_HIST);
     int rc = use_device(c);
     if (rc != TA_OK) return rc;
@@ -190,20 +178,14 @@ TA_API int ta_sighist_debug(ta_ctx* c, uint32_t out[4]) {
 
 TA_API int ta_sighist_timing(ta_ctx* c, double* ms_hist, double* ms_rank) {
     if (!c) return fail(TA_EINVAL, "ctx is NULL");
-    const bool hist = current(c, c->sh.hist_seq), rank = current(c, c->sh.rank_seq);
+    const bool hist = pass_current(c, c->sh.hist_seq), rank = pass_current(c, c->sh.rank_seq);
     if (!hist && !rank) return fail(TA_EINVAL, NO_HIST);
     int rc = use_device(c);
     if (rc != TA_OK) return rc;
     const double nan = std::numeric_limits<double>::quiet_NaN();
     double h = nan, r = nan;
-    if (hist) {
-        TA_HIP(hipEventSynchronize(c->sh.ev[1]));
-        if ((rc = elapsed_ms(c->sh.ev[0], c->sh.ev[1], &h)) != TA_OK) return rc;
-    }
-    if (rank) {
-        TA_HIP(hipEventSynchronize(c->sh.ev[3]));
-        if ((rc = elapsed_ms(c->sh.ev[2], c->sh.ev[3], &r)) != TA_OK) return rc;
-    }
+    if (hist && (rc = interval_ms(c->sh.ev[0], c->sh.ev[1], &h)) != TA_OK) return rc;
+    if (rank && (rc = interval_ms(c->sh.ev[2], c->sh.ev[3], &r)) != TA_OK) return rc;
     if (ms_hist) *ms_hist = h;
     if (ms_rank) *ms_rank = r;
     return TA_OK;

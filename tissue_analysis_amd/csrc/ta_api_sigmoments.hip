@@ -7,8 +7,6 @@ namespace {
 
 const char* const NO_ROWS = "no signal moments of the current extraction (run ta_sigmom_extract)";
 
-bool sigmom_current(const ta_ctx* c) { return c->sm.seq != 0 && c->extracted && c->sm.seq == c->extract_seq; }
-
 // byte offsets of the parts of SigMomentState::out for R rows
 struct SigMomLayout {
     uint64_t flags = 0, n, w, m1, m2, bytes;
@@ -18,8 +16,7 @@ struct SigMomLayout {
 // drain the stream and look at the pass's flag words; spills: records that missed a workgroup's LDS table
 int sigmom_finish(ta_ctx* c, uint32_t* spills = nullptr) {
     uint32_t flags[ta::SM_NFLAGS] = {0, 0, 0, 0};
-    TA_HIP(hipMemcpyAsync(flags, c->sm.out.p, sizeof(flags), hipMemcpyDeviceToHost, c->stream));
-    TA_HIP(hipStreamSynchronize(c->stream));
+    if (const int rc = read_pass_flags<ta::SM_NFLAGS>(c, c->sm.out.p, flags); rc != TA_OK) return rc;
     if (flags[ta::SM_FLAG_RANGE]) return fail(TA_ERANGE, "the signal-moment pass met a label above max_label=%u (the volume changed since ta_extract)", c->max_label);
     if (spills) *spills = flags[ta::SM_FLAG_SPILL];
     return TA_OK;
@@ -35,12 +32,8 @@ extern "C" {
 
 TA_API int ta_sigmom_extract(ta_ctx* c) {
     if (!c) return fail(TA_EINVAL, "ctx is NULL");
-    if (!c->sig.img.p) return fail(TA_EINVAL, "no signal set");
-    if (!c->vol || !companion_matches(c, c->sig.img)) return fail(TA_EINVAL, "the signal does not match the label volume");
-    int rc = use_device(c);
+    int rc = signal_pass_preflight(c, "signal-moment pass");
     if (rc != TA_OK) return rc;
-    if (!c->extracted) return fail(TA_EINVAL, "the signal-moment pass needs a ta_extract of the current volume first");
-    if ((rc = finish_extract(c)) != TA_OK) return rc;
     c->sm.seq = 0;
     ta::RangePlan plan;
     const int verdict = ta::sigmoments_plan(c->mdims, c->first_owned, c->itemsize, c->sig.img.itemsize, &plan);
@@ -80,7 +73,7 @@ TA_API int ta_sigmom_extract(ta_ctx* c) {
 
 TA_API int ta_sigmom_get(ta_ctx* c, uint64_t* n, uint64_t* w, uint64_t* m1, uint64_t* m2) {
     if (!c) return fail(TA_EINVAL, "ctx is NULL");
-    if (!sigmom_current(c)) return fail(TA_EINVAL, NO_ROWS);
+    if (!pass_current(c, c->sm.seq)) return fail(TA_EINVAL, NO_ROWS);
     int rc = use_device(c);
     if (rc != TA_OK) return rc;
     if ((rc = sigmom_finish(c)) != TA_OK) return rc;
@@ -97,7 +90,7 @@ TA_API int ta_sigmom_get(ta_ctx* c, uint64_t* n, uint64_t* w, uint64_t* m1, uint
 
 TA_API int ta_sigmom_debug(ta_ctx* c, uint32_t out[4]) {
     if (!c) return fail(TA_EINVAL, "ctx is NULL");
-    if (!sigmom_current(c)) return fail(TA_EINVAL, NO_ROWS);
+    if (!pass_current(c, c->sm.seq)) return fail(TA_EINVAL, NO_ROWS);
     int rc = use_device(c);
     if (rc != TA_OK) return rc;
     uint32_t spills = 0;
@@ -112,8 +105,7 @@ TA_API int ta_sigmom_timing(ta_ctx* c, double* ms) {
     if (c->sm.seq == 0 || !c->sm.ev[1]) return fail(TA_EINVAL, "no signal-moment pass has been run");
     int rc = use_device(c);
     if (rc != TA_OK) return rc;
-    TA_HIP(hipEventSynchronize(c->sm.ev[1]));
-    return elapsed_ms(c->sm.ev[0], c->sm.ev[1], ms);
+    return interval_ms(c->sm.ev[0], c->sm.ev[1], ms);
 }
 
 }  // extern "C"

@@ -7,8 +7,6 @@ namespace {
 
 constexpr CompanionKind SIGNAL = {"the signal", 1, 2};      // uint8 or uint16
 
-bool signal_current(const ta_ctx* c) { return c->sig.seq != 0 && c->extracted && c->sig.seq == c->extract_seq; }
-
 // byte offsets of the parts of SignalState::out for R rows and P pairs
 struct SignalLayout {
     uint64_t flags = 0, n, sum, sumsq, vmin, vmax, side_lo, side_hi, bytes;
@@ -21,8 +19,7 @@ struct SignalLayout {
 // drain the stream and look at the pass's flag words; spills: label records, pair records that missed a workgroup's LDS tables
 int signal_finish(ta_ctx* c, uint32_t* spills = nullptr) {
     uint32_t flags[ta::SIG_NFLAGS] = {0, 0, 0, 0};
-    TA_HIP(hipMemcpyAsync(flags, c->sig.out.p, sizeof(flags), hipMemcpyDeviceToHost, c->stream));
-    TA_HIP(hipStreamSynchronize(c->stream));
+    if (const int rc = read_pass_flags<ta::SIG_NFLAGS>(c, c->sig.out.p, flags); rc != TA_OK) return rc;
     if (flags[ta::SIG_FLAG_RANGE]) return fail(TA_ERANGE, "the signal pass met a label above max_label=%u (the volume changed since ta_extract)", c->max_label);
     if (flags[ta::SIG_FLAG_PAIR_MISS]) return fail(TA_ERANGE, "the signal pass met a pair the extraction does not hold (the volume changed since ta_extract)");
     if (spills) { spills[0] = flags[ta::SIG_FLAG_LABEL_SPILL]; spills[1] = flags[ta::SIG_FLAG_PAIR_SPILL]; }
@@ -75,12 +72,8 @@ TA_API int ta_signal_set_device(ta_ctx* c, const void* dev_ptr, int itemsize) {
 TA_API int ta_signal_extract(ta_ctx* c, uint32_t what) {
     if (!c) return fail(TA_EINVAL, "ctx is NULL");
     if (what == 0 || (what & ~(TA_SIG_LABELS | TA_SIG_WALLS))) return fail(TA_EINVAL, "bad signal mask 0x%x", what);
-    if (!c->sig.img.p) return fail(TA_EINVAL, "no signal set");
-    if (!c->vol || !companion_matches(c, c->sig.img)) return fail(TA_EINVAL, "the signal does not match the label volume");
-    int rc = use_device(c);
+    int rc = signal_pass_preflight(c, "signal pass");
     if (rc != TA_OK) return rc;
-    if (!c->extracted) return fail(TA_EINVAL, "the signal pass needs a ta_extract of the current volume first");
-    if ((rc = finish_extract(c)) != TA_OK) return rc;
     const bool walls = what & TA_SIG_WALLS;
     if (walls && !(c->feature_mask & TA_F_ADJACENCY)) return fail(TA_EINVAL, "TA_SIG_WALLS needs an extraction with TA_F_ADJACENCY");
     if (walls && c->exchanged) return fail(TA_EINVAL, "TA_SIG_WALLS needs this context's own pair list (not a merged one)");
@@ -123,7 +116,7 @@ TA_API int ta_signal_extract(ta_ctx* c, uint32_t what) {
 
 TA_API int ta_signal_get_labels(ta_ctx* c, uint64_t* n, uint64_t* sum, uint64_t* sumsq, uint32_t* vmin, uint32_t* vmax) {
     if (!c) return fail(TA_EINVAL, "ctx is NULL");
-    if (!signal_current(c) || !(c->sig.what & TA_SIG_LABELS))
+    if (!pass_current(c, c->sig.seq) || !(c->sig.what & TA_SIG_LABELS))
         return fail(TA_EINVAL, "no per-label signal results for the current extraction (run ta_signal_extract with TA_SIG_LABELS)");
     int rc = use_device(c);
     if (rc != TA_OK) return rc;
@@ -142,7 +135,7 @@ TA_API int ta_signal_get_labels(ta_ctx* c, uint64_t* n, uint64_t* sum, uint64_t*
 
 TA_API int ta_signal_get_walls(ta_ctx* c, uint64_t* side_lo, uint64_t* side_hi) {
     if (!c) return fail(TA_EINVAL, "ctx is NULL");
-    if (!signal_current(c) || !(c->sig.what & TA_SIG_WALLS) || c->exchanged)
+    if (!pass_current(c, c->sig.seq) || !(c->sig.what & TA_SIG_WALLS) || c->exchanged)
         return fail(TA_EINVAL, "no per-wall signal results for the current extraction (run ta_signal_extract with TA_SIG_WALLS)");
     int rc = use_device(c);
     if (rc != TA_OK) return rc;
@@ -158,7 +151,7 @@ TA_API int ta_signal_get_walls(ta_ctx* c, uint64_t* side_lo, uint64_t* side_hi) 
 
 TA_API int ta_signal_debug(ta_ctx* c, uint32_t out[4]) {
     if (!c) return fail(TA_EINVAL, "ctx is NULL");
-    if (!signal_current(c)) return fail(TA_EINVAL, "no signal results for the current extraction (run ta_signal_extract)");
+    if (!pass_current(c, c->sig.seq)) return fail(TA_EINVAL, "no signal results for the current extraction (run ta_signal_extract)");
     int rc = use_device(c);
     if (rc != TA_OK) return rc;
     uint32_t spills[2] = {0, 0};
@@ -173,8 +166,7 @@ TA_API int ta_signal_timing(ta_ctx* c, double* ms) {
     if (c->sig.seq == 0 || !c->sig.ev[1]) return fail(TA_EINVAL, "no signal pass has been run");
     int rc = use_device(c);
     if (rc != TA_OK) return rc;
-    TA_HIP(hipEventSynchronize(c->sig.ev[1]));
-    return elapsed_ms(c->sig.ev[0], c->sig.ev[1], ms);
+    return interval_ms(c->sig.ev[0], c->sig.ev[1], ms);
 }
 
 }  // extern "C"

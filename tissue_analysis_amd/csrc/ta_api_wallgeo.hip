@@ -5,13 +5,12 @@
 
 namespace {
 
-bool wallgeo_current(const ta_ctx* c) { return c->wg.seq != 0 && c->extracted && !c->exchanged && c->wg.seq == c->extract_seq; }
+bool wallgeo_current(const ta_ctx* c) { return pass_current(c, c->wg.seq) && !c->exchanged; }
 
 // drain the stream and look at the pass's flag words
 int wallgeo_finish(ta_ctx* c, uint32_t* spills) {
     uint32_t flags[ta::WG_NFLAGS] = {0, 0, 0, 0};
-    TA_HIP(hipMemcpyAsync(flags, c->wg.out.p, sizeof(flags), hipMemcpyDeviceToHost, c->stream));
-    TA_HIP(hipStreamSynchronize(c->stream));
+    if (const int rc = read_pass_flags<ta::WG_NFLAGS>(c, c->wg.out.p, flags); rc != TA_OK) return rc;
     if (flags[ta::WG_FLAG_PAIR_MISS]) return fail(TA_ERANGE, "the wall-geometry pass met a pair the extraction does not hold (the volume changed since ta_extract)");
     if (spills) *spills = flags[ta::WG_FLAG_SPILL];
     return TA_OK;
@@ -27,10 +26,8 @@ extern "C" {
 TA_API int ta_wallgeo_extract(ta_ctx* c) {
     if (!c) return fail(TA_EINVAL, "ctx is NULL");
     if (!c->vol) return fail(TA_EINVAL, "no label volume set");
-    int rc = use_device(c);
+    int rc = extraction_preflight(c, "wall-geometry pass");
     if (rc != TA_OK) return rc;
-    if (!c->extracted) return fail(TA_EINVAL, "the wall-geometry pass needs a ta_extract of the current volume first");
-    if ((rc = finish_extract(c)) != TA_OK) return rc;
     if (!(c->feature_mask & TA_F_ADJACENCY)) return fail(TA_EINVAL, "the wall-geometry pass needs an extraction with TA_F_ADJACENCY");
     if (c->exchanged) return fail(TA_EINVAL, "the wall-geometry pass needs this context's own pair list (not a merged one)");
     c->wg.seq = 0;
@@ -120,8 +117,7 @@ TA_API int ta_wallgeo_timing(ta_ctx* c, double* ms) {
     if (c->wg.seq == 0 || !c->wg.ev[1]) return fail(TA_EINVAL, "no wall-geometry pass has been run");
     int rc = use_device(c);
     if (rc != TA_OK) return rc;
-    TA_HIP(hipEventSynchronize(c->wg.ev[1]));
-    return elapsed_ms(c->wg.ev[0], c->wg.ev[1], ms);
+    return interval_ms(c->wg.ev[0], c->wg.ev[1], ms);
 }
 
 }  // extern "C"

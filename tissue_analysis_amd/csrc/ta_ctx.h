@@ -3,8 +3,9 @@
 // and the sweep's tile shape; ta_api_walls.hip, ta_api_sparse.hip and ta_api_exchange.hip the wall voxels, the sparse label ids and
 // the rank exchange; ta_api_<feature>.hip a feature.  What crosses files is declared here, with the file that defines it; the small
 // checks that several features repeat are inline below the context (the plane range of a ta_*_image call, an id as the volume
-// stores it, a feature's two timed intervals, and the entry checks of the two separable transforms, whose column-pass geometry and
-// batch plan are in ta_separable.h).
+// stores it, a feature's timed intervals, what the passes over a settled extraction share -- the "current" predicate, the entry
+// checks, the read of a pass's flag words -- and the entry checks of the two separable transforms, whose column-pass geometry and
+// batch plan are in ta_separable.h; the launch plan of the range passes is in ta_range_plan.h).
 #pragma once
 #include "../../include/tissue_scan.h"
 #include "ta_kernels.h"
@@ -61,6 +62,10 @@ inline int elapsed_ms(hipEvent_t a, hipEvent_t b, double* ms) {       // (both r
     TA_HIP(hipEventElapsedTime(&t, a, b));
     *ms = (double)t;
     return TA_OK;
+}
+inline int interval_ms(hipEvent_t a, hipEvent_t b, double* ms) {      // (both recorded: waits for b)
+    TA_HIP(hipEventSynchronize(b));
+    return elapsed_ms(a, b, ms);
 }
 
 // the workspace of launch_radix_sort_u32 / _u64 for n records, as byte offsets from `at`: keys (of key_bytes) x 2 | index u32 x 2 | temp
@@ -368,6 +373,22 @@ inline int64_t compact_rows(const ta_ctx* c) { return c->ids.compact ? c->ids.ce
 // Drain the stream and validate the flags of the last pass; grows the adjacency table and re-runs when it overflowed.  ta_api.hip.
 int finish_extract(ta_ctx* c);
 
+// What the passes over a settled extraction share.  pass_current: results tagged `seq` belong to the extraction the context holds.
+inline bool pass_current(const ta_ctx* c, uint64_t seq) { return seq != 0 && c->extracted && seq == c->extract_seq; }
+// the entry checks behind a pass's own (`noun` is what its messages call it, "signal pass"): the device, an extraction, its flags settled
+inline int extraction_preflight(ta_ctx* c, const char* noun) {
+    int rc = use_device(c);
+    if (rc != TA_OK) return rc;
+    if (!c->extracted) return fail(TA_EINVAL, "the %s needs a ta_extract of the current volume first", noun);
+    return finish_extract(c);
+}
+// the N flag words a pass left at `dev`, once the stream has drained; each feature reads its own meaning into them
+template <int N> int read_pass_flags(ta_ctx* c, const void* dev, uint32_t* flags) {
+    TA_HIP(hipMemcpyAsync(flags, dev, N * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    TA_HIP(hipStreamSynchronize(c->stream));
+    return TA_OK;
+}
+
 inline uint64_t voxels(const ta_ctx* c) { return (uint64_t)c->mdims[0] * (uint64_t)c->mdims[1] * (uint64_t)c->mdims[2]; }
 
 // an id as the volume the passes read stores it; false when no voxel can hold it
@@ -399,7 +420,7 @@ inline int two_intervals_ms(hipEvent_t (&ev)[3], double* ms_first, double* ms_se
     return TA_OK;
 }
 
-// The whole-volume separable transforms (ta_api_distance.hip, ta_api_nearest.hip; `noun` is what their messages call the pass).
+// The whole-volume separable transforms (ta_api_distance.hip, ta_api_nearest.hip; `noun` is what their messages call the pass, "distance pass").
 // Their entry checks run in this order: check_spacing, then transform_preflight, which settles the extraction the pass reads and
 // fills w, the spacing of memory axis k.  transform_ready: a getter's context holds results of the current extraction (seq).
 inline int check_spacing(const double spacing[3]) {
@@ -411,16 +432,14 @@ inline int check_spacing(const double spacing[3]) {
 inline int transform_preflight(ta_ctx* c, const char* noun, const double spacing[3], double w[3]) {
     if (!c->vol) return fail(TA_EINVAL, "no label volume set");
     if (c->first_owned != 0 || c->a_origin != 0)
-        return fail(TA_EINVAL, "the %s pass does not take a slab (an exact transform needs halos of unbounded depth)", noun);
-    int rc = use_device(c);
+        return fail(TA_EINVAL, "the %s does not take a slab (an exact transform needs halos of unbounded depth)", noun);
+    const int rc = extraction_preflight(c, noun);
     if (rc != TA_OK) return rc;
-    if (!c->extracted) return fail(TA_EINVAL, "the %s pass needs a ta_extract of the current volume first", noun);
-    if ((rc = finish_extract(c)) != TA_OK) return rc;
     for (int k = 0; k < 3; ++k) w[k] = spacing[c->perm[k]];
     return TA_OK;
 }
 inline int transform_ready(ta_ctx* c, uint64_t seq, const char* no_results) {
-    if (seq == 0 || !c->extracted || seq != c->extract_seq) return fail(TA_EINVAL, no_results);
+    if (!pass_current(c, seq)) return fail(TA_EINVAL, no_results);
     return use_device(c);
 }
 inline int check_batch_option(const ta_ctx* c, int64_t columns) {
@@ -486,3 +505,10 @@ int companion_set_host(ta_ctx* c, Companion& v, const CompanionKind& kind, const
 int companion_set_device(ta_ctx* c, Companion& v, const CompanionKind& kind, const void* dev_ptr, int itemsize);
 inline bool companion_matches(const ta_ctx* c, const Companion& v) { return std::equal(v.mdims, v.mdims + 3, c->mdims); }   // set for these dims
 void companion_on_new_volume(const ta_ctx* c, Companion& v);      // ... or dropped
+
+// the entry checks of a pass over labels + signal: a signal set for this volume, then extraction_preflight
+inline int signal_pass_preflight(ta_ctx* c, const char* noun) {
+    if (!c->sig.img.p) return fail(TA_EINVAL, "no signal set");
+    if (!c->vol || !companion_matches(c, c->sig.img)) return fail(TA_EINVAL, "the signal does not match the label volume");
+    return extraction_preflight(c, noun);
+}

@@ -6,6 +6,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "ta_range_plan.h"
+
 namespace ta {
 
 constexpr uint32_t INVALID_LABEL = 0xFFFFFFFFu;     // "outside the volume" sentinel (never a label)
@@ -23,9 +25,6 @@ enum { FLAG_RANGE = 0, FLAG_PAIR_OVERFLOW = 1, FLAG_LDS_LABEL_SPILL = 2, FLAG_LD
 constexpr int XHDR = 2;
 constexpr uint64_t XSTATUS_RANGE = 1, XSTATUS_PAIR_OVERFLOW = 2;
 
-// What launch_signal, launch_overlap and launch_wallgeo launched: every workgroup takes `tiles_per_group` consecutive tiles (the
-// last one what is left); 0, 0 when there was nothing to launch.  The host layer keeps it for the ta_*_debug getters.
-struct RangePlan { uint32_t tiles_per_group = 0, groups = 0; };
 // What the distance pass launched, kept for ta_distance_debug: the workgroups of the row pass, of the extremes and pole kernels and
 // of the table initialisation (ta_distance.h), and the launches of the column kernel along both axes together.
 struct DistanceLaunch { uint32_t row_groups = 0, voxel_groups = 0, init_groups = 0, column_launches = 0; };
