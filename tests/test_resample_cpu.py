@@ -1,0 +1,216 @@
+"""Resampling onto the label grid without a GPU: the C ABI of include/tissue_scan_resample.h (declarations, exports, NULL-context
+checks), index_matrix and transform_points against hand-worked cases, the NumPy restatement (tests/resample_reference.py) against
+scipy.ndimage.affine_transform where the two definitions agree, and a voxel whose answer a fused multiply-add would change."""
+import ctypes
+import fractions
+import os
+import re
+
+import numpy as np
+import pytest
+
+import resample_reference as ref
+from tissue_analysis_amd import _capi, index_matrix, transform_points
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def declared_symbols(header):
+    text = open(os.path.join(ROOT, "include", header)).read()
+    return sorted(set(re.findall(r"TA_API\s+(?:const\s+char\s*\*|int)\s+(ta_\w+)\s*\(", text)))
+
+
+def test_resample_header_and_binding_agree():
+    assert declared_symbols("tissue_scan_resample.h") == sorted(_capi.RESAMPLE_SYMBOLS)
+    needed = {"ta_resample_set_source", "ta_resample_set_source_device", "ta_resample_extract", "ta_resample_get", "ta_resample_device",
+              "ta_resample_outside", "ta_resample_timing", "ta_resample_debug", "ta_resample_as_overlap", "ta_resample_as_signal"}
+    assert needed <= set(_capi.RESAMPLE_SYMBOLS)
+    others = (set(_capi.SYMBOLS) | set(_capi.SIGNAL_SYMBOLS) | set(_capi.OVERLAP_SYMBOLS) | set(_capi.MESH_SYMBOLS))
+    assert not set(_capi.RESAMPLE_SYMBOLS) & others
+    assert declared_symbols("tissue_scan.h") == sorted(_capi.SYMBOLS)          # the core header is unchanged
+    text = open(os.path.join(ROOT, "include", "tissue_scan_resample.h")).read()
+    assert re.search(r"TA_API\s+int\s+ta_resample_debug\s*\(ta_ctx\*\s*ctx,\s*uint32_t\s+out\[4\]\)", text)
+    assert "#define TA_RS_NEAREST %d" % _capi.RS_NEAREST in text and "#define TA_RS_LINEAR %d" % _capi.RS_LINEAR in text
+
+
+def test_library_exports_the_resample_symbols_and_they_reject_a_null_context():
+    lib = _capi.load()
+    i64 = (ctypes.c_int64 * 3)(4, 4, 4)
+    buf = (ctypes.c_uint64 * 64)()
+    A = (ctypes.c_double * 12)(1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0)
+    dbl, u64, vp, ci = ctypes.c_double(0), ctypes.c_uint64(0), ctypes.c_void_p(), ctypes.c_int(0)
+    calls = {
+        "ta_resample_set_source": (None, buf, 2, i64, None),
+        "ta_resample_set_source_device": (None, buf, 2, i64),
+        "ta_resample_extract": (None, A, 0, 0),
+        "ta_resample_get": (None, buf, 0, 1),
+        "ta_resample_device": (None, ctypes.byref(vp), ctypes.byref(ci)),
+        "ta_resample_outside": (None, ctypes.byref(u64)),
+        "ta_resample_timing": (None, ctypes.byref(dbl)),
+        "ta_resample_debug": (None, (ctypes.c_uint32 * 4)()),
+        "ta_resample_as_overlap": (None,),
+        "ta_resample_as_signal": (None,),
+    }
+    assert sorted(calls) == sorted(_capi.RESAMPLE_SYMBOLS)
+    for name in declared_symbols("tissue_scan_resample.h"):
+        assert hasattr(lib, name), name
+        assert getattr(lib, name)(*calls[name]) == _capi.TA_EINVAL, name
+        err = lib.ta_last_error()
+        assert b"NULL" in err or b"ctx" in err, (name, err)
+
+
+def test_build_recipe_lists_the_new_files():
+    from tissue_analysis_amd import build
+    assert "kernels_resample.hip" in build.SOURCES and "ta_api_resample.hip" in build.SOURCES
+    assert "ta_resample.h" in build.HEADERS and any(h.endswith("tissue_scan_resample.h") for h in build.HEADERS)
+    assert "-ffp-contract=off" in build.EXTRA_FLAGS["kernels_resample.hip"]
+    assert "#pragma clang fp contract(off)" in open(os.path.join(build.CSRC, "kernels_resample.hip")).read()
+
+
+# ---- index_matrix, transform_points: hand-worked cases
+
+def test_index_matrix_identity_and_voxel_sizes():
+    assert np.array_equal(index_matrix(), np.eye(4)[:3])
+    assert np.array_equal(index_matrix(np.eye(4)), np.eye(4)[:3])
+    # target voxels of (0.5, 0.5, 2.0) um, source voxels of (0.25, 1.0, 1.0) um, no motion: target index (2, 3, 4) lies at
+    # (1.0, 1.5, 8.0) um, which is source index (4.0, 1.5, 8.0)
+    m = index_matrix(None, (0.5, 0.5, 2.0), (0.25, 1.0, 1.0))
+    assert np.array_equal(m, np.array([[2.0, 0, 0, 0], [0, 0.5, 0, 0], [0, 0, 2.0, 0]]))
+    assert np.array_equal(m @ np.array([2.0, 3.0, 4.0, 1.0]), np.array([4.0, 1.5, 8.0]))
+
+
+def test_index_matrix_composes_a_translation_with_anisotropic_voxels():
+    # physical source = physical target + (1.0, -3.0, 0.5) um; target voxels (0.5, 0.5, 2.0), source voxels (0.25, 1.0, 1.0):
+    # target index (2, 3, 4) -> (1.0, 1.5, 8.0) um -> (2.0, -1.5, 8.5) um -> source index (8.0, -1.5, 8.5)
+    T = np.eye(4)
+    T[:3, 3] = (1.0, -3.0, 0.5)
+    m = index_matrix(T, (0.5, 0.5, 2.0), (0.25, 1.0, 1.0))
+    assert m.shape == (3, 4) and m.dtype == np.float64
+    assert np.array_equal(m[:, 3], np.array([4.0, -3.0, 0.5]))
+    assert np.array_equal(m @ np.array([2.0, 3.0, 4.0, 1.0]), np.array([8.0, -1.5, 8.5]))
+    # a swap of axes 0 and 1 on top of it: the scales follow their axes (column: target size, row: source size)
+    P = np.eye(4)[[1, 0, 2, 3]]
+    m = index_matrix(T @ P, (0.5, 0.5, 2.0), (0.25, 1.0, 1.0))
+    assert np.array_equal(m, np.array([[0, 2.0, 0, 4.0], [0.5, 0, 0, -3.0], [0, 0, 2.0, 0.5]]))
+
+
+def test_index_matrix_of_a_2d_transform():
+    # a quarter turn in the plane plus a shift of (5, 1), pixels of 2 x 2 (target) and 1 x 4 (source)
+    T = np.array([[0.0, -1.0, 5.0], [1.0, 0.0, 1.0], [0.0, 0.0, 1.0]])
+    m = index_matrix(T, (2.0, 2.0), (1.0, 4.0))
+    assert np.array_equal(m, np.array([[0, -2.0, 0, 5.0], [0.5, 0, 0, 0.25], [0, 0, 1.0, 0]]))
+    # pixel (1, 2) lies at (2, 4) -> (-4 + 5, 2 + 1) = (1, 3) -> source pixel (1, 0.75); axis 2 is left alone
+    assert np.array_equal(m @ np.array([1.0, 2.0, 0.0, 1.0]), np.array([1.0, 0.75, 0.0]))
+    with pytest.raises(ValueError):
+        index_matrix(np.ones((3, 3)))
+    with pytest.raises(ValueError):
+        index_matrix(np.eye(5))
+    with pytest.raises(ValueError):
+        index_matrix(None, (1.0, 0.0, 1.0))
+
+
+def test_transform_points():
+    T = np.eye(4)
+    T[:3, :3] = np.array([[0.0, -1.0, 0.0], [1.0, 0.0, 0.0], [0.0, 0.0, 2.0]])
+    T[:3, 3] = (10.0, 20.0, 30.0)
+    pts = np.array([[1.0, 2.0, 3.0], [0.0, 0.0, 0.0]])
+    assert np.array_equal(transform_points(pts, T), np.array([[8.0, 21.0, 36.0], [10.0, 20.0, 30.0]]))
+    assert np.array_equal(transform_points(pts[0], T), np.array([8.0, 21.0, 36.0]))
+    assert np.array_equal(transform_points(pts, None), pts)
+    T2 = np.array([[0.0, -1.0, 5.0], [1.0, 0.0, 1.0], [0.0, 0.0, 1.0]])
+    assert np.array_equal(transform_points(np.array([[2.0, 4.0]]), T2), np.array([[1.0, 3.0]]))
+    # two translations compose by adding
+    A, B = np.eye(4), np.eye(4)
+    A[:3, 3], B[:3, 3] = (1.0, 2.0, 3.0), (-4.0, 0.5, 0.0)
+    assert np.array_equal(transform_points(transform_points(pts, A), B), transform_points(pts, B @ A))
+
+
+# ---- the restatement itself
+
+def test_restatement_on_maps_with_known_answers():
+    S = ref.random_source((4, 5, 6), np.uint16)
+    eye = np.eye(4)[:3]
+    for mode in (ref.NEAREST, ref.LINEAR):
+        out, filled = ref.resample(S, eye, S.shape, mode)
+        assert np.array_equal(out, S) and not filled.any()
+    shift = eye.copy()
+    shift[:, 3] = (1, -2, 3)
+    out, filled = ref.resample(S, shift, S.shape, ref.NEAREST, fill=7)
+    want = np.full(S.shape, 7, dtype=S.dtype)
+    want[:3, 2:, :3] = S[1:, :3, 3:]
+    assert np.array_equal(out, want) and ref.outside(filled) == S.size - 3 * 3 * 3
+    # a half-voxel shift: every voxel is a tie and ties go up; linear gives the mean of two neighbours, rounded half to even
+    half = eye.copy()
+    half[2, 3] = 0.5
+    out, filled = ref.resample(S, half, S.shape, ref.NEAREST)
+    assert np.array_equal(out[:, :, :-1], S[:, :, 1:]) and filled[:, :, -1].all() and not filled[:, :, :-1].any()
+    out, filled = ref.resample(S, half, S.shape, ref.LINEAR)
+    mean = np.rint((S[:, :, :-1].astype(np.float64) + S[:, :, 1:]) / 2)
+    assert np.array_equal(out[:, :, :-1], mean.astype(S.dtype)) and filled[:, :, -1].all()
+    # the border band of linear mode: s in [-0.5, 0) reads the clamped corner, s < -0.5 is outside
+    band = eye.copy()
+    band[0, 3] = -0.25
+    out, filled = ref.resample(S, band, S.shape, ref.LINEAR)
+    assert np.array_equal(out[0], S[0]) and not filled.any()
+    band[0, 3] = -0.75
+    assert ref.resample(S, band, S.shape, ref.LINEAR)[1][0].all()
+
+
+def test_restatement_against_scipy_where_the_definitions_agree():
+    """Target 5 x 7 x 70 from source 6 x 9 x 24 (uint16) under the rotation with scales.  SciPy's tie and border rules are its own:
+    compared are the voxels with 0 <= s_x <= m_x - 1 on all axes and s_x + 0.5 farther than 1e-6 from an integer; the near ties
+    must be under 5 % of the volume and the compared voxels over half of it.  Order 0 must match exactly, order 1 within one
+    grey level."""
+    from scipy import ndimage
+    shape, S, A = (5, 7, 70), ref.random_source((6, 9, 24), np.uint16), ref.rotation_with_scales()
+    s = ref.source_index(A, shape)
+    interior = np.ones(shape, dtype=bool)
+    near_tie = np.zeros(shape, dtype=bool)
+    for x in range(3):
+        interior &= (s[x] >= 0.0) & (s[x] <= S.shape[x] - 1.0)
+        t = s[x] + 0.5
+        near_tie |= np.abs(t - np.rint(t)) <= 1e-6
+    compared = interior & ~near_tie
+    print("near ties %.2f %%, compared %.2f %%" % (100.0 * near_tie.mean(), 100.0 * compared.mean()))
+    assert near_tie.mean() < 0.05 and compared.mean() > 0.5
+    for order, mode, bound in ((0, ref.NEAREST, 0), (1, ref.LINEAR, 1)):
+        sp = ndimage.affine_transform(S, A[:, :3], offset=A[:, 3], output_shape=shape, order=order, mode="constant", cval=0)
+        ours, _ = ref.resample(S, A, shape, mode)
+        worst = int(np.abs(sp.astype(np.int64) - ours.astype(np.int64))[compared].max())
+        print("order %d: largest difference %d" % (order, worst))
+        assert worst <= bound
+
+
+def test_a_fused_multiply_add_changes_a_voxel():
+    """Along one axis A = 0.3, offset 0.1: at index 18 the product and the sum rounded one after the other give
+    5.499999999999999 and q = 5; rounded once (a fused multiply-add) they give 5.5 and q = 6.  Index 48 behaves the same way.
+    test_gpu_resample.py builds this axis into a case, so a contracted kernel fails there (it does: a build of the kernel without
+    the contraction pragma and flag fails that case in nearest mode, and linear cases through their lerps)."""
+    a, b = 0.3, 0.1
+    for i, q_separate in ((18, 5), (48, 14)):
+        separate = a * float(i) + b                       # two roundings: Python floats never fuse
+        product = float(fractions.Fraction(a) * i)        # the product alone, rounded once: what the first step must give
+        assert product == a * float(i)
+        fused = ref.exact_axis(a, i, b)                   # one rounding of the exact a * i + b
+        assert separate < q_separate + 0.5 == fused
+        assert np.floor(separate + 0.5) == q_separate and np.floor(fused + 0.5) == q_separate + 1
+    # and the restatement takes the separate roundings.  In the three-term order a compiler fuses a product with the sum BEFORE it,
+    # so the case carries the 0.1 as A[2][0] * i0 in plane i0 = 1 (the matrix of test_gpu_resample.contraction_axis): the stated
+    # order gives (0.1 + 0) + 0.3 * 18 = 5.499999999999999, the fused one fma(0.3, 18, 0.1) = 5.5
+    A = np.eye(4)[:3].copy()
+    A[2, 0], A[2, 2] = b, a
+    S = np.arange(40, dtype=np.uint16).reshape(2, 1, 20)
+    out, _ = ref.resample(S, A, (2, 1, 60), ref.NEAREST)
+    assert out[1, 0, 18] == 20 + 5 and out[1, 0, 48] == 20 + 14
+    assert out[0, 0, 18] == 5 and out[0, 0, 48] == 14           # plane 0: 0.3 i2 alone, 5.3999... and 14.399...
+    s2 = ref.source_index(A, (2, 1, 60))[2]
+    assert s2[1, 0, 18] == 0.1 + 0.3 * 18.0 < 5.5 == ref.exact_axis(a, 18, b)
+
+
+def test_launch_plan_restatement_covers_every_tile_once():
+    for dims, itemsize in (((5, 7, 70), 2), ((200, 400, 4), 2), ((3, 5, 1100), 2), ((9, 3, 2), 1), ((67, 515, 300), 4)):
+        ncb, nrb, npb, tiles, per, groups = ref.plan(dims, itemsize)
+        assert tiles == ncb * nrb * npb and per >= 1 and groups <= ref.RS_MAX_GROUPS
+        assert (groups - 1) * per < tiles <= groups * per
+    assert ref.plan((200, 400, 4), 2)[3:] == (5000, 2, 2500)
+    assert ref.plan((67, 515, 300), 4)[3:] == (17 * 129 * 2, 2, 2193)

@@ -20,6 +20,7 @@ from .signal_quantiles import SignalHistogram, SignalQuantiles
 from .signal_moments import SignalMoments
 from .cell_meshes import CellMeshes
 from .label_overlap import LabelOverlap, label_overlap, lineage_from_images
+from .resample import Resampled, index_matrix, transform_points
 from .cell_junctions import CellJunctions, cell_junctions
 from .wall_geometry import WallGeometry, wall_geometry
 from .components import LabelComponents, label_components
@@ -31,7 +32,7 @@ from .graph_from_image import graph_from_image, property_graph_to_dataframe
 
 __all__ = ["SpatialImage", "NPLIST", "LIST", "DICT", "AbstractSpatialImageAnalysis",
            "SpatialImageAnalysis3D", "SpatialImageAnalysis", "Extraction", "extract_volume", "SignalStats", "SignalHistogram", "SignalQuantiles", "SignalMoments", "CellMeshes",
-           "LabelOverlap", "label_overlap", "lineage_from_images", "CellJunctions", "cell_junctions", "WallGeometry", "wall_geometry",
+           "LabelOverlap", "label_overlap", "lineage_from_images", "Resampled", "index_matrix", "transform_points", "CellJunctions", "cell_junctions", "WallGeometry", "wall_geometry",
            "LabelComponents", "label_components", "DistanceMap", "distance_map", "NearestLabels", "ShellProfile",
            "dilation", "dilation_by", "real_indices", "return_list_of_vectors", "hollow_out_cells", "wall", "contact_surface",
            "coordinates_centering3D", "compute_covariance_matrix", "eigen_values_vectors", "distance",

@@ -105,6 +105,13 @@ SIGMOM_SYMBOLS = ("ta_sigmom_extract", "ta_sigmom_get", "ta_sigmom_debug", "ta_s
 SIGMOM_SLOTS = 448                     # SM_SLOTS of csrc/ta_sigmoments.h: rows of a workgroup's LDS table
 SIGMOM_MAX_GROUPS = 1024               # SM_MAX_GROUPS: workgroups of the pass at most (the plan: tests/sigmoment_reference.py)
 
+# every symbol include/tissue_scan_resample.h declares (same library)
+RESAMPLE_SYMBOLS = ("ta_resample_set_source", "ta_resample_set_source_device", "ta_resample_extract", "ta_resample_get",
+                    "ta_resample_device", "ta_resample_outside", "ta_resample_timing", "ta_resample_debug", "ta_resample_as_overlap",
+                    "ta_resample_as_signal")
+RS_NEAREST, RS_LINEAR = 0, 1           # TA_RS_NEAREST / TA_RS_LINEAR
+RESAMPLE_DTYPES = (np.uint8, np.uint16, np.uint32)
+
 
 def exchange_words(capacity_pairs):
     """uint64 words of one exchange block (TA_EXCHANGE_WORDS in include/tissue_scan.h)."""
@@ -261,9 +268,19 @@ def load():
         "ta_sigmom_get": (ci, [vp, vp, vp, vp, vp]),
         "ta_sigmom_debug": (ci, [vp, P(u32)]),
         "ta_sigmom_timing": (ci, [vp, P(ctypes.c_double)]),
+        "ta_resample_set_source": (ci, [vp, vp, ci, P(i64), P(i64)]),
+        "ta_resample_set_source_device": (ci, [vp, vp, ci, P(i64)]),
+        "ta_resample_extract": (ci, [vp, P(ctypes.c_double), ci, u32]),
+        "ta_resample_get": (ci, [vp, vp, i64, i64]),
+        "ta_resample_device": (ci, [vp, P(vp), P(ci)]),
+        "ta_resample_outside": (ci, [vp, P(u64)]),
+        "ta_resample_timing": (ci, [vp, P(ctypes.c_double)]),
+        "ta_resample_debug": (ci, [vp, P(u32)]),
+        "ta_resample_as_overlap": (ci, [vp]),
+        "ta_resample_as_signal": (ci, [vp]),
     }
     for name in (SYMBOLS + SIGNAL_SYMBOLS + MESH_SYMBOLS + OVERLAP_SYMBOLS + JUNCTION_SYMBOLS + WALLGEO_SYMBOLS + COMPONENT_SYMBOLS
-                 + DISTANCE_SYMBOLS + NEAREST_SYMBOLS + PROFILE_SYMBOLS + SIGHIST_SYMBOLS + SIGMOM_SYMBOLS):
+                 + DISTANCE_SYMBOLS + NEAREST_SYMBOLS + PROFILE_SYMBOLS + SIGHIST_SYMBOLS + SIGMOM_SYMBOLS + RESAMPLE_SYMBOLS):
         fn = getattr(lib, name)      # AttributeError here == the .so does not match the header
         fn.restype, fn.argtypes = sig[name]
     if lib.ta_version() != ABI_VERSION:
@@ -523,6 +540,9 @@ class Context(object):
     def set_signal(self, array):
         """Upload a uint8 / uint16 intensity image of the label volume's shape.  One stored in another axis permutation than
         the labels is copied into the labels' layout first."""
+        if hasattr(array, "adopt_as_signal"):          # an image on another grid: resampled onto the labels' on the device (resample.OnGrid)
+            self._signal_itemsize = array.adopt_as_signal(self)
+            return
         a = np.asarray(array)
         if a.dtype not in SIGNAL_DTYPES:
             raise TypeError("signal images must be uint8 or uint16, not %s" % a.dtype)
@@ -955,6 +975,76 @@ class Context(object):
         ms = ctypes.c_double(0.0)
         _check(self._lib.ta_sigmom_timing(self._h, ctypes.byref(ms)))
         return ms.value
+
+    # -- resampling a second volume onto the label grid (include/tissue_scan_resample.h)
+    def set_resample_source(self, array):
+        """Upload the source volume (uint8 / uint16 / uint32, any 3-D shape, any dense axis permutation)."""
+        a = np.asarray(array)
+        if a.ndim != 3:
+            raise ValueError("a 3D source volume is required")
+        if a.dtype not in RESAMPLE_DTYPES:
+            raise TypeError("source volumes must be uint8, uint16 or uint32, not %s" % a.dtype)
+        if not _dense_permuted(a):
+            a = np.ascontiguousarray(a)
+        _check(self._lib.ta_resample_set_source(self._h, ctypes.c_void_p(a.ctypes.data), a.dtype.itemsize, _i64x3(a.shape), _i64x3(a.strides)))
+        self._keep_resample_source = None
+        self._resample_itemsize = a.dtype.itemsize
+
+    def set_resample_source_device(self, dev_ptr, itemsize, dims, keep=None):
+        """Adopt a device-resident source: dense C order with `dims`."""
+        _check(self._lib.ta_resample_set_source_device(self._h, ctypes.c_void_p(int(dev_ptr)), int(itemsize), _i64x3(dims)))
+        self._keep_resample_source = keep
+        self._resample_itemsize = int(itemsize)
+
+    def resample_extract(self, matrix, mode=RS_NEAREST, fill=0):
+        """Enqueue the gather pass: `matrix` is the 3 x 4 index matrix (target voxel index -> continuous source index)."""
+        m = np.ascontiguousarray(matrix, dtype=np.float64)
+        if m.shape != (3, 4):
+            raise ValueError("the index matrix must be 3 x 4, not %s" % (m.shape,))
+        _check(self._lib.ta_resample_extract(self._h, m.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), int(mode), int(fill) & 0xFFFFFFFF))
+
+    def resample_get(self, first_plane=0, nplanes=None):
+        """The voxels of `nplanes` buffer planes of the result from `first_plane` along memory axis 0 (None: all that follow), flat
+        and in memory order, in the source's dtype."""
+        nplanes, count = self._plane_range(first_plane, nplanes)
+        _, itemsize = self.resample_device()
+        out = np.zeros(count, dtype={1: np.uint8, 2: np.uint16, 4: np.uint32}[itemsize])
+        _check(self._lib.ta_resample_get(self._h, out.ctypes.data, int(first_plane), nplanes))
+        return out
+
+    def resample_device(self):
+        """(device pointer, itemsize) of the result; the context owns the buffer."""
+        p, n = ctypes.c_void_p(), ctypes.c_int(0)
+        _check(self._lib.ta_resample_device(self._h, ctypes.byref(p), ctypes.byref(n)))
+        return p.value, int(n.value)
+
+    def resample_outside(self):
+        """Owned target voxels of the last pass that received `fill`."""
+        n = ctypes.c_uint64(0)
+        _check(self._lib.ta_resample_outside(self._h, ctypes.byref(n)))
+        return int(n.value)
+
+    def resample_timing(self):
+        ms = ctypes.c_double(0.0)
+        _check(self._lib.ta_resample_timing(self._h, ctypes.byref(ms)))
+        return ms.value
+
+    def resample_debug(self):
+        """What the last pass launched: whole 16-byte strips or scalar stores (vector), the mode, the launch plan."""
+        out = (ctypes.c_uint32 * 4)()
+        _check(self._lib.ta_resample_debug(self._h, out))
+        return dict(vector=bool(out[0]), mode=int(out[1]), tiles_per_group=int(out[2]), groups=int(out[3]))
+
+    def resample_as_overlap(self):
+        """Hand the result to the overlap pass as its B (a nearest-neighbour result of uint16 / uint32)."""
+        _check(self._lib.ta_resample_as_overlap(self._h))
+        self._keep_overlap = None
+
+    def resample_as_signal(self):
+        """Hand the result to the signal passes (uint8 / uint16)."""
+        _check(self._lib.ta_resample_as_signal(self._h))
+        self._keep_sig = None
+        self._signal_itemsize = self.resample_device()[1]
 
     def memory_axes(self):
         """perm[k] = the array axis of memory axis k of the resident volume (slowest first), as the library orders them."""

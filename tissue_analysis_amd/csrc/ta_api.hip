@@ -342,6 +342,7 @@ void volume_replaced(ta_ctx* c) {
     walls_on_new_volume(c);
     signal_on_new_volume(c);         // (these two are keyed by the extraction, which is gone; a signal of other dims is dropped)
     wallgeo_on_new_volume(c);
+    resample_on_new_volume(c);       // (reads the grid only: new label values leave it alone)
 }
 
 extern "C" {
@@ -409,7 +410,7 @@ TA_API int ta_ctx_destroy(ta_ctx* c) {
     c->small.release();
     c->hot_rows.release(); c->sort_buf.release(); c->h_pairs.release();
     c->walls.release(); c->ids.release(); c->shape.release();
-    c->sig.release(); c->mesh.release(); c->ov.release(); c->jn.release(); c->wg.release(); c->cc.release(); c->dist.release(); c->near.release(); c->prof.release(); c->sh.release(); c->sm.release();
+    c->sig.release(); c->mesh.release(); c->ov.release(); c->jn.release(); c->wg.release(); c->cc.release(); c->dist.release(); c->near.release(); c->prof.release(); c->sh.release(); c->sm.release(); c->rs.release();
     if (c->h_small) (void)hipHostFree(c->h_small);
     destroy_events(c->ev);
     for (auto& e : c->ring) if (e) (void)hipEventDestroy(e);

@@ -121,6 +121,13 @@ void overlap_on_new_volume(ta_ctx* c) {
     companion_on_new_volume(c, c->ov.b);
 }
 
+// the resample pass rewrites (or has moved) the buffer B was adopted from: the table is stale, a B that is gone is dropped
+void overlap_on_resampled(ta_ctx* c, const void* buf, const void* now, int itemsize) {
+    if (!buf || c->ov.b.p != buf || c->ov.b.owned.p) return;
+    c->ov.state = 0;
+    if (now != buf || itemsize != c->ov.b.itemsize) { c->ov.b.p = nullptr; c->ov.b.itemsize = 0; }
+}
+
 extern "C" {
 
 TA_API int ta_overlap_set(ta_ctx* c, const void* host_ptr, int itemsize, const int64_t dims[3], const int64_t strides_bytes[3]) {

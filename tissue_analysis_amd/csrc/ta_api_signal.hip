@@ -53,6 +53,13 @@ void signal_on_new_volume(ta_ctx* c) {
     companion_on_new_volume(c, c->sig.img);
 }
 
+// the resample pass rewrites (or has moved) the buffer the signal was adopted from: its results are stale, a signal that is gone is dropped
+void signal_on_resampled(ta_ctx* c, const void* buf, const void* now, int itemsize) {
+    if (!buf || c->sig.img.p != buf || c->sig.img.owned.p) return;
+    c->sig.seq = 0; profile_on_new_signal(c); sighist_on_new_signal(c); sigmom_on_new_signal(c);
+    if (now != buf || itemsize != c->sig.img.itemsize) { c->sig.img.p = nullptr; c->sig.img.itemsize = 0; }
+}
+
 extern "C" {
 
 TA_API int ta_signal_set(ta_ctx* c, const void* host_ptr, int itemsize, const int64_t dims[3], const int64_t strides_bytes[3]) {

@@ -244,6 +244,24 @@ struct SigMomentState {
     void release() { out.release(); destroy_events(ev); }
 };
 
+// resampling a second volume onto the label grid (include/tissue_scan_resample.h)
+struct ResampleState {
+    const void* src = nullptr;                          // device pointer (owned_src.p or adopted), NULL = none
+    DevBuf owned_src;
+    int src_itemsize = 0;
+    int64_t sdims[3] = {0, 0, 0}, sel[3] = {0, 0, 0};   // source dims and element strides, array-axis order
+    DevBuf out;                                         // the result: the label volume's buffer dims and layout, the source's type
+    DevBuf small;                                       // outside u64
+    bool valid = false;                                 // out holds the result of a pass over the current grid
+    int itemsize = 0, mode = 0;                         // of that result
+    bool vec = false;                                   // that pass wrote whole strips (ta_resample_debug)
+    int64_t mdims[3] = {0, 0, 0}, a_origin = 0;         // the grid it was computed for
+    int first_owned = 0;
+    ta::RangePlan plan;                                 // what the last pass was launched with (ta_resample_debug)
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    void release() { owned_src.release(); out.release(); small.release(); destroy_events(ev); }
+};
+
 // wall voxels and wall medians (ta_api_walls.hip)
 struct WallVoxelState {
     DevBuf counts;                                      // per-chunk record counts, then offsets
@@ -359,6 +377,7 @@ struct ta_ctx {
     ProfileState prof;
     SigHistState sh;
     SigMomentState sm;
+    ResampleState rs;
 };
 
 inline int use_device(ta_ctx* c) {
@@ -480,6 +499,12 @@ void sighist_on_new_volume(ta_ctx* c);
 void sighist_on_new_signal(ta_ctx* c);                // a new signal image: both tables read the old one.  ta_api_sighist.hip
 void sigmom_on_new_volume(ta_ctx* c);
 void sigmom_on_new_signal(ta_ctx* c);                 // a new signal image: the rows read the old one.  ta_api_sigmoments.hip
+void resample_on_new_volume(ta_ctx* c);               // a grid of other dims drops source and result.  ta_api_resample.hip
+// ta_resample_extract is about to write into `buf` (or, now == NULL, has let go of it): a B / a signal adopted from it by
+// ta_resample_as_overlap / _as_signal holds new contents -- its tables are stale -- and is dropped when the buffer moved to `now`
+// or changed its item size.  ta_api_overlap.hip, ta_api_signal.hip.
+void overlap_on_resampled(ta_ctx* c, const void* buf, const void* now, int itemsize);
+void signal_on_resampled(ta_ctx* c, const void* buf, const void* now, int itemsize);
 void walls_on_new_labels(ta_ctx* c);                  // new label values in the same volume: the staging buffer is kept.  ta_api_walls.hip
 
 // The two ways the voxels change (ta_api.hip).  volume_replaced: the tail of ta_volume_set / ta_volume_set_device, called once vol,

@@ -508,45 +508,70 @@ class ResidentVolume(object):
         self.last = x
         return x
 
-    def signal(self, signal, walls=True):
+    def resample(self, source, matrix, order=0, fill=0):
+        """`source` (a NumPy array or CUDA tensor of uint8 / uint16 / uint32, ANY shape) sampled onto the grid of the resident
+        volume through `matrix`, the 3 x 4 index matrix of `resample.index_matrix` (target voxel index -> continuous source
+        index): order 0 nearest neighbour (labels), 1 trilinear (uint8 / uint16 signals); voxels that fall outside the source
+        take `fill`.  A `Resampled`: .image(), .tensor(), .outside, .ms.  One gather pass on the GPU; the result stays there."""
+        import time
+        from .resample import resident_resample
+        t0 = time.perf_counter()
+        r = resident_resample(self, source, matrix, order, fill)
+        self.ms["resample"] = (time.perf_counter() - t0) * 1e3
+        return r
+
+    def _signal_on_grid(self, signal, matrix, order, fill):
+        """`signal` itself, or with an index matrix what the signal passes take in its place: resampled on the device, adopted there."""
+        if matrix is None:
+            return signal
+        from .resample import OnGrid
+        return OnGrid(self, signal, matrix, order, fill)
+
+    def signal(self, signal, walls=True, matrix=None, order=1, fill=0):
         """Statistics of an intensity image (uint8 / uint16, the shape of the labels; a 2-D one for a 2-D label image) per
         label and, with `walls`, per wall: a `SignalStats` whose rows line up with the last extraction (`.ids` when sparse,
-        `.lo` / `.hi` for walls).  One upload of the signal and one pass over labels + signal on the GPU."""
+        `.lo` / `.hi` for walls).  One upload of the signal and one pass over labels + signal on the GPU.  With `matrix` (a
+        3 x 4 index matrix, `resample.index_matrix`) the image may have any shape: it is resampled onto the labels' grid on the
+        device (`order`, `fill` as for `resample`) and read from there -- so for the three signal passes below."""
         import time
         from .signal_stats import resident_signal
+        signal = self._signal_on_grid(signal, matrix, order, fill)
         t0 = time.perf_counter()
         st = resident_signal(self, signal, walls)
         self.ms["signal"] = (time.perf_counter() - t0) * 1e3
         return st
 
-    def signal_histogram(self, signal, bin_width=None):
+    def signal_histogram(self, signal, bin_width=None, matrix=None, order=1, fill=0):
         """Per-label histogram of an intensity image (uint8 / uint16, the shape of the labels): a `SignalHistogram` whose rows
         line up with the last extraction.  bin_width: a power of two leaving at most 256 bins (default 1 for uint8, 256 for
         uint16).  One upload of the signal and one pass over labels + signal on the GPU."""
         import time
         from .signal_quantiles import resident_signal_histogram
+        signal = self._signal_on_grid(signal, matrix, order, fill)
         t0 = time.perf_counter()
         h = resident_signal_histogram(self, signal, bin_width)
         self.ms["signal_histogram"] = (time.perf_counter() - t0) * 1e3
         return h
 
-    def signal_quantiles(self, signal, q, method='linear'):
+    def signal_quantiles(self, signal, q, method='linear', matrix=None, order=1, fill=0):
         """Per-label quantiles `q` (in [0, 1]) of an intensity image by numpy's rule for `method` ('linear', 'lower', 'higher',
         'midpoint'), from exact order statistics selected on the GPU: a `SignalQuantiles` whose rows line up with the last
         extraction.  One or two passes over labels + signal (uint8 / uint16) for every eight ranks a row."""
         import time
         from .signal_quantiles import resident_signal_quantiles
+        signal = self._signal_on_grid(signal, matrix, order, fill)
         t0 = time.perf_counter()
         sq = resident_signal_quantiles(self, signal, q, method)
         self.ms["signal_quantiles"] = (time.perf_counter() - t0) * 1e3
         return sq
 
-    def signal_moments(self, signal, voxelsize=(1.0, 1.0, 1.0)):
+    def signal_moments(self, signal, voxelsize=(1.0, 1.0, 1.0), matrix=None, order=1, fill=0):
         """Where in every cell an intensity image (uint8 / uint16, the shape of the labels) sits: a `SignalMoments` (signal-weighted
         centroid, polarity, covariance and inertia axes from exact integer sums) whose rows line up with the last extraction.
         One upload of the signal and one pass over labels + signal on the GPU."""
         import time
         from .signal_moments import resident_signal_moments
+        signal = self._signal_on_grid(signal, matrix, order, fill)
         t0 = time.perf_counter()
         sm = resident_signal_moments(self, signal, voxelsize)
         self.ms["signal_moments"] = (time.perf_counter() - t0) * 1e3
@@ -563,14 +588,16 @@ class ResidentVolume(object):
         self.ms["meshes"] = (time.perf_counter() - t0) * 1e3
         return m
 
-    def overlap(self, other):
+    def overlap(self, other, matrix=None, fill=0):
         """The overlap table of the resident volume with `other`, a second label image of the same shape (an integer array, or a
         CUDA tensor of it): a `LabelOverlap` of rows (a, b, n) in the ids of the two images.  One upload of `other` (none for a
-        tensor) and one pass over both volumes on the GPU; no sweep is needed."""
+        tensor) and one pass over both volumes on the GPU; no sweep is needed.  With `matrix` (a 3 x 4 index matrix,
+        `resample.index_matrix`) `other` may have any shape: it is resampled onto this grid by nearest neighbour on the device
+        (voxels outside it read as the label `fill`) and compared there."""
         import time
         from .label_overlap import resident_overlap
         t0 = time.perf_counter()
-        ov = resident_overlap(self, other)
+        ov = resident_overlap(self, other, matrix, fill)
         self.ms["overlap"] = (time.perf_counter() - t0) * 1e3
         return ov
 

@@ -20,6 +20,7 @@ class LabelOverlap(object):
         n               uint64
         size_a, size_b  (ids int64 ascending, voxels uint64) of every label of one side: the table's margins, exact
         ms              milliseconds of the pass kernel on the device (None for a table built on the host)
+        outside         voxels of A where a B resampled from another grid had no voxel and reads as its fill label (None otherwise)
     """
 
     def __init__(self, a, b, n, ms=None):
@@ -29,6 +30,7 @@ class LabelOverlap(object):
         if not (self.a.shape == self.b.shape == self.n.shape and self.a.ndim == 1):
             raise ValueError("a, b and n must be 1-D arrays of one length")
         self.ms = ms
+        self.outside = None
         self._margins = {}
 
     def __len__(self):
@@ -114,13 +116,24 @@ def _cuda_tensor(x):
     return hasattr(x, "data_ptr") and hasattr(x, "is_cuda") and bool(x.is_cuda)
 
 
-def resident_overlap(resident, other):
+def resident_overlap(resident, other, matrix=None, fill=0):
     """The overlap pass over the volume resident in `resident` (a ResidentVolume) and `other`: an integer array of the same
     shape (a 2-D one for a 2-D label image), or a CUDA tensor of it (int16 / int32 storage holding uint16 / uint32 labels,
-    contiguous, on the volume's GPU)."""
+    contiguous, on the volume's GPU).  With `matrix` (a 3 x 4 index matrix) `other` has any shape and is resampled onto the
+    grid of the volume by nearest neighbour first, on the device, where the pass then reads it; the table's `.outside` is the
+    number of voxels that fell outside `other` and count as its label `fill`."""
     from .extraction import _as_label_volume
     ctx = resident.ctx
-    if _cuda_tensor(other):
+    outside = None
+    if matrix is not None:
+        from .resample import resident_resample
+        if not _cuda_tensor(other):
+            other, _ = _as_label_volume(other)          # (uint16 / uint32: what the overlap pass takes)
+        elif other.element_size() not in (2, 4):
+            raise TypeError("label tensors must hold 2- or 4-byte integers")
+        outside = resident_resample(resident, other, matrix, 0, fill).outside
+        ctx.resample_as_overlap()
+    elif _cuda_tensor(other):
         shape = tuple(int(d) for d in other.shape)
         if len(shape) == 2:
             shape = shape + (1,)
@@ -134,21 +147,32 @@ def resident_overlap(resident, other):
         ctx.set_overlap(b)
     ctx.overlap_extract()
     a, b, n = ctx.overlap_get()
-    return LabelOverlap(a, b, n, ms=ctx.overlap_timing())
+    ov = LabelOverlap(a, b, n, ms=ctx.overlap_timing())
+    ov.outside = outside
+    return ov
 
 
-def label_overlap(image_a, image_b, device=0):
-    """The overlap table of two label images of one shape (2-D or 3-D integer arrays): a `LabelOverlap`."""
+def label_overlap(image_a, image_b, device=0, matrix=None, fill=0):
+    """The overlap table of two label images (2-D or 3-D integer arrays): a `LabelOverlap`.  They share one shape, or `matrix` (a
+    3 x 4 index matrix, `resample.index_matrix`) takes a voxel index of image_a to the continuous index in image_b."""
     from .extraction import ResidentVolume
     rv = ResidentVolume(image_a, device=device)
     try:
-        return rv.overlap(image_b)
+        return rv.overlap(image_b, matrix, fill)
     finally:
         rv.close()
 
 
-def lineage_from_images(image_t0, image_t1, min_fraction=0.5, background=1, device=0):
-    """{mother in image_t0: [daughters in image_t1]} of two frames on one grid; 0 and `background` are nobody's mother or
-    daughter."""
+def lineage_from_images(image_t0, image_t1, min_fraction=0.5, background=1, device=0, transform=None, voxelsize_t0=None,
+                        voxelsize_t1=None):
+    """{mother in image_t0: [daughters in image_t1]} of two frames; 0 and `background` are nobody's mother or daughter.  The
+    frames share one grid, or `transform` (a homogeneous matrix from physical coordinates of frame t0 to those of frame t1; with
+    only the voxel sizes given, the identity) registers them: frame t1 is then resampled onto the grid of frame t0 on the
+    device, and its voxels that fall outside count as the background."""
     exclude = (0,) if background is None else (0, int(background))
-    return label_overlap(image_t0, image_t1, device=device).lineage(min_fraction=min_fraction, exclude=exclude)
+    matrix = None
+    if transform is not None or voxelsize_t0 is not None or voxelsize_t1 is not None:
+        from .resample import index_matrix
+        matrix = index_matrix(transform, voxelsize_t0, voxelsize_t1)
+    ov = label_overlap(image_t0, image_t1, device=device, matrix=matrix, fill=0 if background is None else int(background))
+    return ov.lineage(min_fraction=min_fraction, exclude=exclude)

@@ -145,6 +145,8 @@ def _with_extraction(resident, signal, enqueue):
 
 
 def _bits(signal):
+    if hasattr(signal, "adopt_as_signal"):           # an image on another grid with its index matrix (resample.OnGrid)
+        return signal, 8 * signal.dtype.itemsize
     a = np.asarray(signal)
     if a.dtype not in _capi.SIGNAL_DTYPES:
         raise TypeError("signal images must be uint8 or uint16, not %s" % a.dtype)

@@ -553,27 +553,53 @@ class AbstractSpatialImageAnalysis(object):
                     areas[key] = areas.get(key, 0.0) + val
         return areas
 
+    # -- a second image on another grid (include/tissue_scan_resample.h; one gather pass on the GPU)
+    def _index_matrix(self, image, transform, voxelsize):
+        """None when `image` is taken as lying on this grid (no transform and no voxel size named): today's path.  Else the 3 x 4
+        index matrix from this grid into `image`'s: `transform` maps physical coordinates of this image to those of `image`
+        (None = identity), whose voxel size is `voxelsize`, or its own (a SpatialImage), or this image's."""
+        if transform is None and voxelsize is None:
+            return None
+        from .resample import index_matrix
+        if voxelsize is None:
+            voxelsize = getattr(image, "voxelsize", self._voxelsize)
+        return index_matrix(transform, self._voxelsize, voxelsize)
+
+    def resample_onto_grid(self, image, transform=None, order=0, fill=0, voxelsize=None):
+        """`image` (any shape; uint8 / uint16 / uint32) resampled onto this analysis' grid on the GPU: a SpatialImage with this
+        image's shape and voxel size.  `transform`: the homogeneous matrix (4 x 4, 3 x 3 for 2-D images) from physical
+        coordinates of this image to those of `image`, None = identity, so that only the voxel sizes differ; order 0 nearest
+        neighbour (labels), 1 trilinear (signals); `fill` where `image` has no voxel."""
+        from .resample import index_matrix
+        vs = getattr(image, "voxelsize", self._voxelsize) if voxelsize is None else voxelsize
+        out = self._resident().resample(np.asarray(image), index_matrix(transform, self._voxelsize, vs), order, fill).image()
+        return SpatialImage(out, voxelsize=tuple(self._voxelsize))
+
     # -- intensity statistics of a signal image over the labels (include/tissue_scan_signal.h; one pass on the GPU)
-    def _signal_stats(self, signal):
+    def _signal_stats(self, signal, matrix=None):
         """SignalStats of `signal` over this image: uploaded and reduced once per array OBJECT (a signal modified in place
-        needs a new array, or refresh()), on the resident label volume."""
+        needs a new array, or refresh()) and index matrix, on the resident label volume."""
         cache = getattr(self, "_signal_cache", None)
-        if cache is not None and cache[0] is signal:
+        key = None if matrix is None else matrix.tobytes()
+        if cache is not None and cache[0] is signal and cache[2] == key:
             return cache[1]
-        stats = self._resident_rows().signal(np.asarray(signal), walls=True)
-        self._signal_cache = (signal, stats)
+        stats = self._resident_rows().signal(np.asarray(signal), walls=True, matrix=matrix)
+        self._signal_cache = (signal, stats, key)
         return stats
 
-    def cell_signal(self, signal, labels=None, statistic='mean'):
+    def cell_signal(self, signal, labels=None, statistic='mean', transform=None, voxelsize=None):
         """Per-label `statistic` of the intensity image `signal` (uint8 / uint16, the image's shape): 'mean', 'std'
-        (population), 'min', 'max' (float64) or 'sum' (integer); returned like volume()."""
+        (population), 'min', 'max' (float64) or 'sum' (integer); returned like volume().  With `transform` (physical coordinates
+        of this image -> those of `signal`) and / or `voxelsize` (of `signal`; a SpatialImage brings its own) the signal may lie
+        on any grid: it is resampled onto this one on the GPU, trilinearly -- so for wall_signal, signal_quantiles,
+        signal_median and signal_histogram."""
         if statistic not in STATISTICS:
             raise ValueError("statistic must be one of %s, not %r" % ("|".join(STATISTICS), statistic))
         labels = self.label_request(labels)
-        values = self._signal_stats(signal).of_labels(labels, statistic)
+        values = self._signal_stats(signal, self._index_matrix(signal, transform, voxelsize)).of_labels(labels, statistic)
         return self.convert_return(values, labels)
 
-    def wall_signal(self, signal, neighbors=None, statistic='mean'):
+    def wall_signal(self, signal, neighbors=None, statistic='mean', transform=None, voxelsize=None):
         """{(l1, l2): value} for the walls wall_areas(neighbors) returns: 'mean' = the signal averaged over both sides of every
         face of the wall (face-weighted, like the wall area), 'sides' = (mean on l1's side, mean on l2's side), l1 < l2."""
         if statistic not in WALL_STATISTICS:
@@ -583,7 +609,7 @@ class AbstractSpatialImageAnalysis(object):
             keys = [tuple(k) for k in np.asarray(walls[0]).tolist()]
         else:
             keys = list(walls.keys())
-        stats = self._signal_stats(signal)
+        stats = self._signal_stats(signal, self._index_matrix(signal, transform, voxelsize))
         lo = np.array([k[0] for k in keys], dtype=np.int64)
         hi = np.array([k[1] for k in keys], dtype=np.int64)
         rows = stats.wall_rows(lo, hi)
@@ -647,27 +673,27 @@ class AbstractSpatialImageAnalysis(object):
         return self.convert_return(axes, labels), self.convert_return(list(vals), labels)
 
     # -- exact histograms, medians and quantiles of a signal image (include/tissue_scan_sighist.h; radix select on the GPU)
-    def signal_quantiles(self, signal, q, labels=None, method='linear'):
+    def signal_quantiles(self, signal, q, labels=None, method='linear', transform=None, voxelsize=None):
         """Per label the quantiles `q` (a sequence in [0, 1]) of the intensity image `signal` (uint8 / uint16, the image's shape),
         by numpy.quantile's rule for `method` ('linear', 'lower', 'higher' or 'midpoint') over the exact order statistics of the
         label's voxels.  One array of len(q) per label, returned like volume() (NPLIST: an array [labels, len(q)])."""
         labels = self.label_request(labels)
-        sq = self._resident_rows().signal_quantiles(np.asarray(signal), q, method)
+        sq = self._resident_rows().signal_quantiles(np.asarray(signal), q, method, matrix=self._index_matrix(signal, transform, voxelsize))
         return self.convert_return(sq.of_labels(labels), labels)
 
-    def signal_median(self, signal, labels=None):
+    def signal_median(self, signal, labels=None, transform=None, voxelsize=None):
         """Per label the median of the intensity image `signal` over the label's voxels (float64, what numpy.median of them
         gives, NaN for a label without voxels); returned like volume()."""
         labels = self.label_request(labels)
-        sq = self._resident_rows().signal_quantiles(np.asarray(signal), [0.5], 'midpoint')
+        sq = self._resident_rows().signal_quantiles(np.asarray(signal), [0.5], 'midpoint', matrix=self._index_matrix(signal, transform, voxelsize))
         return self.convert_return(sq.of_labels(labels)[:, 0], labels)
 
-    def signal_histogram(self, signal, labels=None, bin_width=None):
+    def signal_histogram(self, signal, labels=None, bin_width=None, transform=None, voxelsize=None):
         """Per label the histogram of the intensity image `signal`: uint64 counts of the bins [b * bin_width, (b + 1) * bin_width),
         `bin_width` a power of two that leaves at most 256 bins (default 1 for uint8, 256 for uint16).  One array per label,
         returned like volume() (NPLIST: an array [labels, bins])."""
         labels = self.label_request(labels)
-        h = self._resident_rows().signal_histogram(np.asarray(signal), bin_width)
+        h = self._resident_rows().signal_histogram(np.asarray(signal), bin_width, matrix=self._index_matrix(signal, transform, voxelsize))
         return self.convert_return(h.of_labels(labels), labels)
 
     # -- cell surface meshes (include/tissue_scan_mesh.h; count, scan and emit on the GPU)
@@ -687,11 +713,14 @@ class AbstractSpatialImageAnalysis(object):
         return cache[key]
 
     # -- overlap with a second label image of the same grid (include/tissue_scan_overlap.h; one pass on the GPU)
-    def overlap(self, other_image):
-        """The overlap table of this image with `other_image` (the next frame resampled onto this grid, or another segmentation
-        of the same image): a `LabelOverlap` of rows (a, b, n) in the ids of the two images.  Nothing is excluded here:
-        `overlap(next).lineage(exclude=(0, analysis.background()))` leaves the background out."""
-        return self._resident().overlap(np.asarray(other_image))
+    def overlap(self, other_image, transform=None, voxelsize=None, fill=0):
+        """The overlap table of this image with `other_image` (the next frame, or another segmentation of the same image): a
+        `LabelOverlap` of rows (a, b, n) in the ids of the two images.  Nothing is excluded here:
+        `overlap(next).lineage(exclude=(0, analysis.background()))` leaves the background out.  The two share a grid, or
+        `transform` (physical coordinates of this image -> those of `other_image`, None = identity) and / or `voxelsize` (of
+        `other_image`; a SpatialImage brings its own) place the other image, of any shape: it is resampled onto this grid on
+        the GPU by nearest neighbour, voxels where it has none reading as the label `fill`."""
+        return self._resident().overlap(np.asarray(other_image), self._index_matrix(other_image, transform, voxelsize), fill)
 
     # -- cell junctions (include/tissue_scan_junctions.h; two walks over the resident volume on the GPU)
     def cell_junctions(self):
