@@ -105,6 +105,11 @@ SIGMOM_SYMBOLS = ("ta_sigmom_extract", "ta_sigmom_get", "ta_sigmom_debug", "ta_s
 SIGMOM_SLOTS = 448                     # SM_SLOTS of csrc/ta_sigmoments.h: rows of a workgroup's LDS table
 SIGMOM_MAX_GROUPS = 1024               # SM_MAX_GROUPS: workgroups of the pass at most (the plan: tests/sigmoment_reference.py)
 
+# every symbol include/tissue_scan_topology.h declares (same library)
+TOPOLOGY_SYMBOLS = ("ta_topology_extract", "ta_topology_get", "ta_topology_debug", "ta_topology_timing")
+TOPOLOGY_SLOTS = 768                   # TP_SLOTS of csrc/ta_topology.h: rows of a workgroup's LDS table
+TOPOLOGY_MAX_GROUPS = 1024             # TP_MAX_GROUPS: workgroups of the pass at most (the plan: tests/topology_reference.py)
+
 # every symbol include/tissue_scan_resample.h declares (same library)
 RESAMPLE_SYMBOLS = ("ta_resample_set_source", "ta_resample_set_source_device", "ta_resample_extract", "ta_resample_get",
                     "ta_resample_device", "ta_resample_outside", "ta_resample_timing", "ta_resample_debug", "ta_resample_as_overlap",
@@ -268,6 +273,10 @@ def load():
         "ta_sigmom_get": (ci, [vp, vp, vp, vp, vp]),
         "ta_sigmom_debug": (ci, [vp, P(u32)]),
         "ta_sigmom_timing": (ci, [vp, P(ctypes.c_double)]),
+        "ta_topology_extract": (ci, [vp]),
+        "ta_topology_get": (ci, [vp, vp, vp, vp, vp, vp, vp]),
+        "ta_topology_debug": (ci, [vp, P(u32)]),
+        "ta_topology_timing": (ci, [vp, P(ctypes.c_double)]),
         "ta_resample_set_source": (ci, [vp, vp, ci, P(i64), P(i64)]),
         "ta_resample_set_source_device": (ci, [vp, vp, ci, P(i64)]),
         "ta_resample_extract": (ci, [vp, P(ctypes.c_double), ci, u32]),
@@ -280,7 +289,7 @@ def load():
         "ta_resample_as_signal": (ci, [vp]),
     }
     for name in (SYMBOLS + SIGNAL_SYMBOLS + MESH_SYMBOLS + OVERLAP_SYMBOLS + JUNCTION_SYMBOLS + WALLGEO_SYMBOLS + COMPONENT_SYMBOLS
-                 + DISTANCE_SYMBOLS + NEAREST_SYMBOLS + PROFILE_SYMBOLS + SIGHIST_SYMBOLS + SIGMOM_SYMBOLS + RESAMPLE_SYMBOLS):
+                 + DISTANCE_SYMBOLS + NEAREST_SYMBOLS + PROFILE_SYMBOLS + SIGHIST_SYMBOLS + SIGMOM_SYMBOLS + TOPOLOGY_SYMBOLS + RESAMPLE_SYMBOLS):
         fn = getattr(lib, name)      # AttributeError here == the .so does not match the header
         fn.restype, fn.argtypes = sig[name]
     if lib.ta_version() != ABI_VERSION:
@@ -974,6 +983,34 @@ class Context(object):
     def sigmom_timing(self):
         ms = ctypes.c_double(0.0)
         _check(self._lib.ta_sigmom_timing(self._h, ctypes.byref(ms)))
+        return ms.value
+
+    # -- Euler numbers (include/tissue_scan_topology.h)
+    def topology_extract(self):
+        """Enqueue the pass over the 2 x 2 x 2 blocks of the resident volume, for the rows of the current extraction."""
+        _check(self._lib.ta_topology_extract(self._h))
+        self._topology_rows = self._max_label + 1
+
+    def topology_rows(self):
+        """(n0 u64[R], n1 u64[R, 3], n2 u64[R, 3], n3 u64[R], v u64[R], e u64[R, 3]), rows as labels(); the per-axis columns in
+        MEMORY-axis order (`memory_axes()` has the array axis of each)."""
+        R = getattr(self, "_topology_rows", 1)                 # (no pass yet: the library answers TA_EINVAL)
+        one, three = (lambda: np.zeros(R, dtype=np.uint64)), (lambda: np.zeros((R, 3), dtype=np.uint64))
+        n0, n1, n2, n3, v, e = one(), three(), three(), one(), one(), three()
+        _check(self._lib.ta_topology_get(self._h, n0.ctypes.data, n1.ctypes.data, n2.ctypes.data, n3.ctypes.data, v.ctypes.data,
+                                         e.ctypes.data))
+        return n0, n1, n2, n3, v, e
+
+    def topology_debug(self):
+        """Diagnostics of the last pass: records that missed a workgroup's LDS table (spills), blocks of more than one label
+        (mixed, saturating) and the launch plan (tiles_per_group, groups)."""
+        out = (ctypes.c_uint32 * 4)()
+        _check(self._lib.ta_topology_debug(self._h, out))
+        return dict(spills=int(out[0]), mixed=int(out[1]), tiles_per_group=int(out[2]), groups=int(out[3]))
+
+    def topology_timing(self):
+        ms = ctypes.c_double(0.0)
+        _check(self._lib.ta_topology_timing(self._h, ctypes.byref(ms)))
         return ms.value
 
     # -- resampling a second volume onto the label grid (include/tissue_scan_resample.h)

@@ -244,6 +244,16 @@ struct SigMomentState {
     void release() { out.release(); destroy_events(ev); }
 };
 
+// Euler numbers (include/tissue_scan_topology.h)
+struct TopologyState {
+    DevBuf out;                                         // flags u32[4] | mixed blocks u64 | n0 u64[R] | n1 u64[R][3] | n2 u64[R][3] | n3 u64[R] | v u64[R] | e u64[R][3]
+    uint64_t seq = 0;                                   // extract_seq of the extraction the rows belong to, 0 = none
+    uint32_t rows = 0;                                  // max_label + 1 of that extraction
+    ta::RangePlan plan;                                 // what the last pass was launched with (ta_topology_debug)
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    void release() { out.release(); destroy_events(ev); }
+};
+
 // resampling a second volume onto the label grid (include/tissue_scan_resample.h)
 struct ResampleState {
     const void* src = nullptr;                          // device pointer (owned_src.p or adopted), NULL = none
@@ -377,6 +387,7 @@ struct ta_ctx {
     ProfileState prof;
     SigHistState sh;
     SigMomentState sm;
+    TopologyState tp;
     ResampleState rs;
 };
 
@@ -499,6 +510,7 @@ void sighist_on_new_volume(ta_ctx* c);
 void sighist_on_new_signal(ta_ctx* c);                // a new signal image: both tables read the old one.  ta_api_sighist.hip
 void sigmom_on_new_volume(ta_ctx* c);
 void sigmom_on_new_signal(ta_ctx* c);                 // a new signal image: the rows read the old one.  ta_api_sigmoments.hip
+void topology_on_new_volume(ta_ctx* c);
 void resample_on_new_volume(ta_ctx* c);               // a grid of other dims drops source and result.  ta_api_resample.hip
 // ta_resample_extract is about to write into `buf` (or, now == NULL, has let go of it): a B / a signal adopted from it by
 // ta_resample_as_overlap / _as_signal holds new contents -- its tables are stale -- and is dropped when the buffer moved to `now`

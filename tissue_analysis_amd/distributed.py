@@ -323,6 +323,10 @@ class SlabJob(object):
         raise NotImplementedError("the nearest-label maps (tissue_scan_nearest.h) do not run on a slab: an exact Euclidean "
                                   "transform needs halos of unbounded depth")
 
+    def topology(self, *args, **kwargs):
+        raise NotImplementedError("the Euler numbers (tissue_scan_topology.h) do not run on a slab: a 2 x 2 x 2 block at a seam "
+                                  "belongs to two buffers")
+
     def owned_view(self):
         return self.vol[1:] if self.has_low_halo else self.vol
 
@@ -606,6 +610,10 @@ class PipelinedSlabJob(object):
     def nearest_labels(self, *args, **kwargs):
         raise NotImplementedError("the nearest-label maps (tissue_scan_nearest.h) do not run on a slab: an exact Euclidean "
                                   "transform needs halos of unbounded depth")
+
+    def topology(self, *args, **kwargs):
+        raise NotImplementedError("the Euler numbers (tissue_scan_topology.h) do not run on a slab: a 2 x 2 x 2 block at a seam "
+                                  "belongs to two buffers")
 
     def owned_view(self):
         return self.jobs[0].owned_view()

@@ -132,7 +132,8 @@ def tissue_tables(analysis, labels, background, properties, property_as_real=Tru
     (vertex: signal_center_of_mass and the vector of signal_polarity, which run the signal-moment pass; a property list without
     them does not).  'wall_centroid', 'wall_normal' and 'wall_projected_area' (edge: the columns of
     `analysis.wall_geometry()`) run the wall-geometry pass; a property list without them does not.  'n_components' (vertex:
-    the face-connected blobs the label consists of, `analysis.label_components()`) runs the component pass, likewise; and so do
+    the face-connected blobs the label consists of, `analysis.label_components()`) runs the component pass, likewise;
+    'euler_number' (vertex: `analysis.euler_number()`, 6-connectivity) the Euler-number pass; and so do
     'inscribed_radius' (vertex: `analysis.inscribed_radius()`) and 'depth' (vertex: `analysis.cell_depth()`, which needs a
     background) with the distance pass, in real units with `property_as_real`."""
     x = analysis.extraction
@@ -234,6 +235,8 @@ def tissue_tables(analysis, labels, background, properties, property_as_real=Tru
     if 'n_components' in properties:
         blobs = analysis.label_components().per_label()
         graph.set_vertex_column('n_components', np.array([blobs.get(l, 0) for l in ids.tolist()], dtype=np.int64), present)
+    if 'euler_number' in properties:
+        graph.set_vertex_column('euler_number', analysis.cell_topology().of_labels(ids, 'euler_number', 6), present)
     if 'inscribed_radius' in properties:
         graph.set_vertex_column('inscribed_radius', analysis.wall_distance(real=real).of_labels(ids, 'max2'), asked)
     if 'depth' in properties:

@@ -207,6 +207,7 @@ class AbstractSpatialImageAnalysis(object):
         self._junctions = None
         self._wall_geometry = None
         self._components = None
+        self._topology = None
         self._distance_cache = {}
         try:
             self.filepath, self.filename = split(image.info["Filename"])
@@ -271,6 +272,7 @@ class AbstractSpatialImageAnalysis(object):
         self._junctions = None
         self._wall_geometry = None
         self._components = None
+        self._topology = None
         self._distance_cache = {}
         self._voxel_layer1 = None
         self._voxel_layer18 = None
@@ -747,6 +749,36 @@ class AbstractSpatialImageAnalysis(object):
     def disconnected_labels(self):
         """{label: k} of the labels whose voxels form k > 1 separate blobs, without the ignored labels."""
         return self.label_components().fragmented(exclude=self._ignoredlabels)
+
+    # -- Euler numbers: tunnels and cavities (include/tissue_scan_topology.h; one pass over the resident volume on the GPU)
+    def cell_topology(self):
+        """The twelve exact block counts of every label and what follows from them: a `CellTopology` (Euler numbers for 6- and
+        26-connectivity, intrinsic volumes) in the ids of the image and with this analysis' voxel size.  Nothing is excluded
+        here.  Cached until `refresh()` or an edit of the image."""
+        if getattr(self, "_topology", None) is None:
+            self._topology = self._resident_rows().topology(tuple(float(v) for v in self._voxelsize))
+        return self._topology
+
+    def euler_number(self, labels=None, connectivity=6):
+        """Per label the Euler number of its voxels, joined across faces (connectivity 6) or across faces, edges and corners
+        (26): blobs - tunnels + cavities.  A ball gives 1, a cell with a tunnel through it 0, one that encloses a cavity 2.
+        Returned like volume()."""
+        labels = self.label_request(labels)
+        return self.convert_return(self.cell_topology().of_labels(labels, "euler_number", connectivity), labels)
+
+    def mean_breadth(self, labels=None, real=True):
+        """Per label the mean breadth of its voxel solid (half the intrinsic volume V1; a box of a x b x c voxels gives
+        (a s0 + b s1 + c s2) / 2), in real units or in voxels; returned like volume()."""
+        labels = self.label_request(labels)
+        vs = None if real else (1.0, 1.0, 1.0)
+        return self.convert_return(self.cell_topology().of_labels(labels, "mean_breadth", voxelsize=vs), labels)
+
+    def topological_defects(self, exclude=()):
+        """{label: {'blobs': b0, 'euler': chi6, 'tunnels_minus_cavities': b0 - chi6}} of the labels that are not unions of balls:
+        those whose face-connected Euler number differs from the number of their face-connected blobs (`label_components()`),
+        without those in `exclude`.  For 6-connectivity only: the components are face-connected."""
+        from .cell_topology import topological_defects
+        return topological_defects(self.cell_topology(), self.label_components(), exclude)
 
     # -- exact Euclidean distance maps (include/tissue_scan_distance.h; three passes over the resident volume on the GPU)
     def _distance_map(self, mode, label, edge, real):
