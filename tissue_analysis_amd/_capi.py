@@ -24,96 +24,222 @@ OPT_IMPL, OPT_TILE_PLANES, OPT_PAIR_SLOTS, OPT_TIMING, OPT_TIMING_RING, OPT_VOLU
 OPT_TILE_PLANES_USED = 9         # read only: the tile height the last sweep was launched with (0 before any sweep)
 STREAM_LEGACY_DEFAULT = 1          # TA_STREAM_LEGACY_DEFAULT of include/tissue_scan.h
 
-# every symbol include/tissue_scan.h declares
-SYMBOLS = (
-    "ta_version", "ta_adjacency_scope", "ta_last_error", "ta_device_count", "ta_ctx_create", "ta_ctx_destroy",
-    "ta_ctx_set_stream", "ta_ctx_set_option", "ta_ctx_get_option", "ta_ctx_synchronize", "ta_volume_set",
-    "ta_volume_set_device", "ta_volume_max_label", "ta_volume_label_census", "ta_label_census_get", "ta_volume_compact_labels",
-    "ta_volume_is_compact", "ta_volume_rerank", "ta_volume_uncompact", "ta_volume_owned_planes", "ta_volume_plane_events", "ta_volume_relabel", "ta_volume_get", "ta_volume_map",
-    "ta_volume_first_layer", "ta_volume_hollow", "ta_volume_layer18", "ta_wall_voxels_count", "ta_wall_voxels_get", "ta_wall_voxels_get_by_pair",
-    "ta_wall_medians", "ta_wall_medians_get",
-    "ta_extract", "ta_get_labels",
-    "ta_adjacency_size", "ta_adjacency_get", "ta_timing", "ta_timing_series", "ta_read_probe", "ta_debug_counters", "ta_bind_accumulators",
-    "ta_accumulators_device", "ta_accumulators_reduced", "ta_adjacency_device", "ta_adjacency_export", "ta_adjacency_merge",
-    "ta_adjacency_pack", "ta_adjacency_pack_shared", "ta_adjacency_merge_blocks", "ta_synth_voronoi",
-    "ta_device_malloc", "ta_device_free", "ta_memcpy_d2h", "ta_memcpy_h2d",
-)
+_vp, _i64, _u32, _u64, _ci, _f64 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_int, ctypes.c_double
+_P = ctypes.POINTER
 
-# every symbol include/tissue_scan_signal.h declares (same library; kept apart from SYMBOLS, which is tissue_scan.h's list)
-SIGNAL_SYMBOLS = (
-    "ta_signal_set", "ta_signal_set_device", "ta_signal_extract", "ta_signal_get_labels", "ta_signal_get_walls",
-    "ta_signal_timing", "ta_signal_debug",
-)
+# Every symbol every header under include/ declares, with its (restype, argtypes): the one list of them.  All live in the same
+# library; `load()` walks this table, and the *_SYMBOLS tuples below are its keys, header by header.
+DECLARED = {
+    "tissue_scan.h": {
+        "ta_version": (_ci, []),
+        "ta_adjacency_scope": (_ci, [_vp, _P(_ci)]),
+        "ta_last_error": (ctypes.c_char_p, []),
+        "ta_device_count": (_ci, [_P(_ci)]),
+        "ta_ctx_create": (_ci, [_ci, _P(_vp)]),
+        "ta_ctx_destroy": (_ci, [_vp]),
+        "ta_ctx_set_stream": (_ci, [_vp, _vp]),
+        "ta_ctx_set_option": (_ci, [_vp, _ci, _i64]),
+        "ta_ctx_get_option": (_ci, [_vp, _ci, _P(_i64)]),
+        "ta_ctx_synchronize": (_ci, [_vp]),
+        "ta_volume_set": (_ci, [_vp, _vp, _ci, _P(_i64), _P(_i64)]),
+        "ta_volume_set_device": (_ci, [_vp, _vp, _ci, _P(_i64), _i64, _ci]),
+        "ta_volume_max_label": (_ci, [_vp, _P(_u32)]),
+        "ta_volume_label_census": (_ci, [_vp, _P(_u32), _P(_u32)]),
+        "ta_label_census_get": (_ci, [_vp, _vp]),
+        "ta_volume_compact_labels": (_ci, [_vp, _vp, _u32, _P(_u32)]),
+        "ta_volume_is_compact": (_ci, [_vp, _P(_ci), _P(_u32)]),
+        "ta_volume_rerank": (_ci, [_vp]),
+        "ta_volume_uncompact": (_ci, [_vp]),
+        "ta_volume_owned_planes": (_ci, [_vp, _P(_i64)]),
+        "ta_volume_plane_events": (_ci, [_vp, _vp]),
+        "ta_volume_relabel": (_ci, [_vp, _vp, _u32]),
+        "ta_volume_get": (_ci, [_vp, _vp]),
+        "ta_volume_map": (_ci, [_vp, _vp, _u32, _vp, _ci, _vp]),
+        "ta_volume_first_layer": (_ci, [_vp, _u32, _ci, _vp]),
+        "ta_volume_hollow": (_ci, [_vp, _u32, _ci, _ci, _vp]),
+        "ta_volume_layer18": (_ci, [_vp, _vp]),
+        "ta_wall_voxels_count": (_ci, [_vp, _P(_i64)]),
+        "ta_wall_voxels_get": (_ci, [_vp, _vp, _vp, _P(_f64)]),
+        "ta_wall_medians": (_ci, [_vp, _ci, _P(_i64), _P(_f64)]),
+        "ta_wall_medians_get": (_ci, [_vp, _vp, _vp, _vp]),
+        "ta_wall_voxels_get_by_pair": (_ci, [_vp, _vp, _vp, _P(_f64)]),
+        "ta_extract": (_ci, [_vp, _u32, _u32]),
+        "ta_get_labels": (_ci, [_vp, _vp, _vp, _vp, _vp]),
+        "ta_adjacency_size": (_ci, [_vp, _P(_i64)]),
+        "ta_adjacency_get": (_ci, [_vp, _vp, _vp, _vp]),
+        "ta_timing": (_ci, [_vp, _P(_f64), _P(_f64), _P(_f64), _P(_u64)]),
+        "ta_timing_series": (_ci, [_vp, _P(_f64), _ci, _P(_ci)]),
+        "ta_read_probe": (_ci, [_vp, _vp, _u64, _ci, _P(_f64)]),
+        "ta_debug_counters": (_ci, [_vp, _P(_u32)]),
+        "ta_bind_accumulators": (_ci, [_vp, _vp, _vp, _u32]),
+        "ta_accumulators_device": (_ci, [_vp, _P(_vp), _P(_vp), _P(_u32)]),
+        "ta_accumulators_reduced": (_ci, [_vp]),
+        "ta_adjacency_device": (_ci, [_vp, _P(_vp), _P(_vp), _P(_i64)]),
+        "ta_adjacency_export": (_ci, [_vp, _vp, _vp, _i64]),
+        "ta_adjacency_merge": (_ci, [_vp, _vp, _vp, _i64]),
+        "ta_adjacency_pack": (_ci, [_vp, _vp, _i64]),
+        "ta_adjacency_pack_shared": (_ci, [_vp, _vp, _i64]),
+        "ta_adjacency_merge_blocks": (_ci, [_vp, _vp, _ci, _i64]),
+        "ta_synth_voronoi": (_ci, [_vp, _vp, _ci, _P(_i64), _i64, _i64, _vp, _P(ctypes.c_int32), _vp]),
+        "ta_device_malloc": (_ci, [_vp, _u64, _P(_vp)]),
+        "ta_device_free": (_ci, [_vp, _vp]),
+        "ta_memcpy_d2h": (_ci, [_vp, _vp, _vp, _u64]),
+        "ta_memcpy_h2d": (_ci, [_vp, _vp, _vp, _u64]),
+    },
+    "tissue_scan_signal.h": {
+        "ta_signal_set": (_ci, [_vp, _vp, _ci, _P(_i64), _P(_i64)]),
+        "ta_signal_set_device": (_ci, [_vp, _vp, _ci]),
+        "ta_signal_extract": (_ci, [_vp, _u32]),
+        "ta_signal_get_labels": (_ci, [_vp, _vp, _vp, _vp, _vp, _vp]),
+        "ta_signal_get_walls": (_ci, [_vp, _vp, _vp]),
+        "ta_signal_timing": (_ci, [_vp, _P(_f64)]),
+        "ta_signal_debug": (_ci, [_vp, _P(_u32)]),
+    },
+    "tissue_scan_mesh.h": {
+        "ta_mesh_extract": (_ci, [_vp, _ci, _vp]),
+        "ta_mesh_size": (_ci, [_vp, _P(_u64), _P(_u64), _P(_u64)]),
+        "ta_mesh_get": (_ci, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+        "ta_mesh_timing": (_ci, [_vp, _P(_f64)]),
+    },
+    "tissue_scan_overlap.h": {
+        "ta_overlap_set": (_ci, [_vp, _vp, _ci, _P(_i64), _P(_i64)]),
+        "ta_overlap_set_device": (_ci, [_vp, _vp, _ci]),
+        "ta_overlap_set_capacity": (_ci, [_vp, _ci]),
+        "ta_overlap_extract": (_ci, [_vp]),
+        "ta_overlap_size": (_ci, [_vp, _P(_u64)]),
+        "ta_overlap_get": (_ci, [_vp, _vp, _vp, _vp]),
+        "ta_overlap_timing": (_ci, [_vp, _P(_f64)]),
+        "ta_overlap_timing_compaction": (_ci, [_vp, _P(_f64), _P(_ci)]),
+        "ta_overlap_debug": (_ci, [_vp, _P(_u32)]),
+    },
+    "tissue_scan_junctions.h": {
+        "ta_junctions_extract": (_ci, [_vp]),
+        "ta_junctions_size": (_ci, [_vp, _P(_u64), _P(_u64), _P(_u64)]),
+        "ta_junctions_get_edges": (_ci, [_vp, _vp, _vp, _vp]),
+        "ta_junctions_get_vertices": (_ci, [_vp, _vp, _vp, _vp]),
+        "ta_junctions_timing": (_ci, [_vp, _P(_f64), _P(_f64)]),
+        "ta_junctions_debug": (_ci, [_vp, _P(_u32)]),
+    },
+    "tissue_scan_wallgeo.h": {
+        "ta_wallgeo_extract": (_ci, [_vp]),
+        "ta_wallgeo_get": (_ci, [_vp, _vp, _vp, _vp, _vp]),
+        "ta_wallgeo_spills": (_ci, [_vp, _P(_u32)]),
+        "ta_wallgeo_debug": (_ci, [_vp, _P(_u32)]),
+        "ta_wallgeo_timing": (_ci, [_vp, _P(_f64)]),
+    },
+    "tissue_scan_components.h": {
+        "ta_components_extract": (_ci, [_vp]),
+        "ta_components_size": (_ci, [_vp, _P(_u64)]),
+        "ta_components_get": (_ci, [_vp, _vp, _vp, _vp, _vp, _vp]),
+        "ta_components_image": (_ci, [_vp, _i64, _i64, _vp]),
+        "ta_components_relabel": (_ci, [_vp, _vp, _u64]),
+        "ta_components_timing": (_ci, [_vp, _P(_f64), _P(_f64)]),
+        "ta_components_debug": (_ci, [_vp, _P(_u32)]),
+    },
+    "tissue_scan_distance.h": {
+        "ta_distance_extract": (_ci, [_vp, _ci, _u32, _P(_f64), _u32]),
+        "ta_distance_get": (_ci, [_vp, _vp, _vp, _vp]),
+        "ta_distance_image": (_ci, [_vp, _i64, _i64, _vp]),
+        "ta_distance_timing": (_ci, [_vp, _P(_f64), _P(_f64)]),
+        "ta_distance_set_batch": (_ci, [_vp, _i64]),
+        "ta_distance_debug": (_ci, [_vp, _P(_u32)]),
+    },
+    "tissue_scan_nearest.h": {
+        "ta_nearest_extract": (_ci, [_vp, _u32, _u32, _P(_f64), _f64, _u32]),
+        "ta_nearest_get": (_ci, [_vp, _vp, _vp]),
+        "ta_nearest_image": (_ci, [_vp, _i64, _i64, _vp, _vp]),
+        "ta_nearest_apply": (_ci, [_vp]),
+        "ta_nearest_timing": (_ci, [_vp, _P(_f64), _P(_f64)]),
+        "ta_nearest_debug": (_ci, [_vp, _P(_u32)]),
+        "ta_nearest_set_batch": (_ci, [_vp, _i64]),
+    },
+    "tissue_scan_profile.h": {
+        "ta_profile_extract": (_ci, [_vp, _ci, _P(_f64), _u32]),
+        "ta_profile_get": (_ci, [_vp, _vp, _vp, _vp, _vp, _vp]),
+        "ta_profile_debug": (_ci, [_vp, _P(_u32)]),
+        "ta_profile_timing": (_ci, [_vp, _P(_f64)]),
+    },
+    "tissue_scan_sighist.h": {
+        "ta_sighist_extract": (_ci, [_vp, _ci]),
+        "ta_sighist_get": (_ci, [_vp, _vp]),
+        "ta_sigrank_extract": (_ci, [_vp, _ci, _vp]),
+        "ta_sigrank_get": (_ci, [_vp, _vp]),
+        "ta_sighist_debug": (_ci, [_vp, _P(_u32)]),
+        "ta_sighist_timing": (_ci, [_vp, _P(_f64), _P(_f64)]),
+    },
+    "tissue_scan_sigmoments.h": {
+        "ta_sigmom_extract": (_ci, [_vp]),
+        "ta_sigmom_get": (_ci, [_vp, _vp, _vp, _vp, _vp]),
+        "ta_sigmom_debug": (_ci, [_vp, _P(_u32)]),
+        "ta_sigmom_timing": (_ci, [_vp, _P(_f64)]),
+    },
+    "tissue_scan_topology.h": {
+        "ta_topology_extract": (_ci, [_vp]),
+        "ta_topology_get": (_ci, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+        "ta_topology_debug": (_ci, [_vp, _P(_u32)]),
+        "ta_topology_timing": (_ci, [_vp, _P(_f64)]),
+    },
+    "tissue_scan_resample.h": {
+        "ta_resample_set_source": (_ci, [_vp, _vp, _ci, _P(_i64), _P(_i64)]),
+        "ta_resample_set_source_device": (_ci, [_vp, _vp, _ci, _P(_i64)]),
+        "ta_resample_extract": (_ci, [_vp, _P(_f64), _ci, _u32]),
+        "ta_resample_get": (_ci, [_vp, _vp, _i64, _i64]),
+        "ta_resample_device": (_ci, [_vp, _P(_vp), _P(_ci)]),
+        "ta_resample_outside": (_ci, [_vp, _P(_u64)]),
+        "ta_resample_timing": (_ci, [_vp, _P(_f64)]),
+        "ta_resample_debug": (_ci, [_vp, _P(_u32)]),
+        "ta_resample_as_overlap": (_ci, [_vp]),
+        "ta_resample_as_signal": (_ci, [_vp]),
+    },
+}
+
+SYMBOLS = tuple(DECLARED["tissue_scan.h"])          # (kept apart from the feature headers' lists: this is tissue_scan.h's)
+
+SIGNAL_SYMBOLS = tuple(DECLARED["tissue_scan_signal.h"])
 SIG_LABELS, SIG_WALLS = 1, 2           # TA_SIG_LABELS / TA_SIG_WALLS
-
-# every symbol include/tissue_scan_mesh.h declares (same library)
-MESH_SYMBOLS = ("ta_mesh_extract", "ta_mesh_size", "ta_mesh_get", "ta_mesh_timing")
-MESH_OUTSIDE = 0xFFFFFFFF              # TA_MESH_OUTSIDE
 SIGNAL_DTYPES = (np.uint8, np.uint16)
 
-# every symbol include/tissue_scan_overlap.h declares (same library)
-OVERLAP_SYMBOLS = (
-    "ta_overlap_set", "ta_overlap_set_device", "ta_overlap_set_capacity", "ta_overlap_extract", "ta_overlap_size", "ta_overlap_get",
-    "ta_overlap_timing", "ta_overlap_timing_compaction", "ta_overlap_debug",
-)
+MESH_SYMBOLS = tuple(DECLARED["tissue_scan_mesh.h"])
+MESH_OUTSIDE = 0xFFFFFFFF              # TA_MESH_OUTSIDE
 
-# every symbol include/tissue_scan_junctions.h declares (same library)
-JUNCTION_SYMBOLS = (
-    "ta_junctions_extract", "ta_junctions_size", "ta_junctions_get_edges", "ta_junctions_get_vertices", "ta_junctions_timing",
-    "ta_junctions_debug",
-)
+OVERLAP_SYMBOLS = tuple(DECLARED["tissue_scan_overlap.h"])
 
-# every symbol include/tissue_scan_wallgeo.h declares (same library)
-WALLGEO_SYMBOLS = ("ta_wallgeo_extract", "ta_wallgeo_get", "ta_wallgeo_spills", "ta_wallgeo_debug", "ta_wallgeo_timing")
+JUNCTION_SYMBOLS = tuple(DECLARED["tissue_scan_junctions.h"])
 
-# every symbol include/tissue_scan_components.h declares (same library)
-COMPONENT_SYMBOLS = (
-    "ta_components_extract", "ta_components_size", "ta_components_get", "ta_components_image", "ta_components_relabel",
-    "ta_components_timing", "ta_components_debug",
-)
+WALLGEO_SYMBOLS = tuple(DECLARED["tissue_scan_wallgeo.h"])
+
+COMPONENT_SYMBOLS = tuple(DECLARED["tissue_scan_components.h"])
 COMPONENT_NONE = 0xFFFFFFFF            # TA_COMPONENT_NONE
 COMPONENT_MAX_VOXELS = 1 << 31         # voxels of a buffer the component pass takes
 
-# every symbol include/tissue_scan_distance.h declares (same library)
-DISTANCE_SYMBOLS = ("ta_distance_extract", "ta_distance_get", "ta_distance_image", "ta_distance_timing", "ta_distance_set_batch",
-                    "ta_distance_debug")
+DISTANCE_SYMBOLS = tuple(DECLARED["tissue_scan_distance.h"])
 DIST_OWN_WALL, DIST_FROM_LABEL = 0, 1  # TA_DIST_OWN_WALL / TA_DIST_FROM_LABEL
 DIST_EDGE_IS_SITE = 1                  # TA_DIST_EDGE_IS_SITE
 
-# every symbol include/tissue_scan_nearest.h declares (same library)
-NEAREST_SYMBOLS = ("ta_nearest_extract", "ta_nearest_get", "ta_nearest_image", "ta_nearest_apply", "ta_nearest_timing",
-                   "ta_nearest_debug", "ta_nearest_set_batch")
+NEAREST_SYMBOLS = tuple(DECLARED["tissue_scan_nearest.h"])
 NEAREST_NOT_FROM = 1                   # TA_NEAREST_NOT_FROM
 NEAREST_NONE = 0xFFFFFFFF              # TA_NEAREST_NONE
 
-# every symbol include/tissue_scan_profile.h declares (same library)
-PROFILE_SYMBOLS = ("ta_profile_extract", "ta_profile_get", "ta_profile_debug", "ta_profile_timing")
+PROFILE_SYMBOLS = tuple(DECLARED["tissue_scan_profile.h"])
 PROF_SIGNAL = 1                        # TA_PROF_SIGNAL
 PROFILE_MAX_BINS = 64                  # TA_PROF_MAX_BINS
 PROFILE_SLOTS = 1024                   # PROF_SLOTS of csrc/ta_profile.h: slots of a workgroup's LDS table
 
-# every symbol include/tissue_scan_sighist.h declares (same library)
-SIGHIST_SYMBOLS = ("ta_sighist_extract", "ta_sighist_get", "ta_sigrank_extract", "ta_sigrank_get", "ta_sighist_debug",
-                   "ta_sighist_timing")
+SIGHIST_SYMBOLS = tuple(DECLARED["tissue_scan_sighist.h"])
 SIGRANK_MAX_RANKS = 8                  # TA_SIGRANK_MAX_RANKS
 SIGRANK_NONE = 0xFFFFFFFF              # value of a rank >= n
 SIGHIST_SLOTS = 39                     # TA_SH_SLOTS of csrc/ta_sighist.h: rows of 256 counters in a workgroup's LDS table
 SIGHIST_MAX_GROUPS = 65536             # TA_SH_MAX_GROUPS: workgroups of the digit pass at most (the plan: tests/sighist_reference.py)
 
-# every symbol include/tissue_scan_sigmoments.h declares (same library)
-SIGMOM_SYMBOLS = ("ta_sigmom_extract", "ta_sigmom_get", "ta_sigmom_debug", "ta_sigmom_timing")
+SIGMOM_SYMBOLS = tuple(DECLARED["tissue_scan_sigmoments.h"])
 SIGMOM_SLOTS = 448                     # SM_SLOTS of csrc/ta_sigmoments.h: rows of a workgroup's LDS table
 SIGMOM_MAX_GROUPS = 1024               # SM_MAX_GROUPS: workgroups of the pass at most (the plan: tests/sigmoment_reference.py)
 
-# every symbol include/tissue_scan_topology.h declares (same library)
-TOPOLOGY_SYMBOLS = ("ta_topology_extract", "ta_topology_get", "ta_topology_debug", "ta_topology_timing")
+TOPOLOGY_SYMBOLS = tuple(DECLARED["tissue_scan_topology.h"])
 TOPOLOGY_SLOTS = 768                   # TP_SLOTS of csrc/ta_topology.h: rows of a workgroup's LDS table
 TOPOLOGY_MAX_GROUPS = 1024             # TP_MAX_GROUPS: workgroups of the pass at most (the plan: tests/topology_reference.py)
 
-# every symbol include/tissue_scan_resample.h declares (same library)
-RESAMPLE_SYMBOLS = ("ta_resample_set_source", "ta_resample_set_source_device", "ta_resample_extract", "ta_resample_get",
-                    "ta_resample_device", "ta_resample_outside", "ta_resample_timing", "ta_resample_debug", "ta_resample_as_overlap",
-                    "ta_resample_as_signal")
+RESAMPLE_SYMBOLS = tuple(DECLARED["tissue_scan_resample.h"])
 RS_NEAREST, RS_LINEAR = 0, 1           # TA_RS_NEAREST / TA_RS_LINEAR
 RESAMPLE_DTYPES = (np.uint8, np.uint16, np.uint32)
 
@@ -150,148 +276,10 @@ def load():
     except ImportError:
         pass
     lib = ctypes.CDLL(LIB_PATH)
-    vp, i64, u32, u64, ci = (ctypes.c_void_p, ctypes.c_int64, ctypes.c_uint32, ctypes.c_uint64,
-                             ctypes.c_int)
-    P = ctypes.POINTER
-    sig = {
-        "ta_version": (ci, []),
-        "ta_adjacency_scope": (ci, [vp, P(ci)]),
-        "ta_last_error": (ctypes.c_char_p, []),
-        "ta_device_count": (ci, [P(ci)]),
-        "ta_ctx_create": (ci, [ci, P(vp)]),
-        "ta_ctx_destroy": (ci, [vp]),
-        "ta_ctx_set_stream": (ci, [vp, vp]),
-        "ta_ctx_set_option": (ci, [vp, ci, i64]),
-        "ta_ctx_get_option": (ci, [vp, ci, P(i64)]),
-        "ta_ctx_synchronize": (ci, [vp]),
-        "ta_volume_set": (ci, [vp, vp, ci, P(i64), P(i64)]),
-        "ta_volume_set_device": (ci, [vp, vp, ci, P(i64), i64, ci]),
-        "ta_volume_max_label": (ci, [vp, P(u32)]),
-        "ta_volume_label_census": (ci, [vp, P(u32), P(u32)]),
-        "ta_label_census_get": (ci, [vp, vp]),
-        "ta_volume_compact_labels": (ci, [vp, vp, u32, P(u32)]),
-        "ta_volume_is_compact": (ci, [vp, P(ci), P(u32)]),
-        "ta_volume_rerank": (ci, [vp]),
-        "ta_volume_uncompact": (ci, [vp]),
-        "ta_volume_owned_planes": (ci, [vp, P(i64)]),
-        "ta_volume_plane_events": (ci, [vp, vp]),
-        "ta_volume_relabel": (ci, [vp, vp, u32]),
-        "ta_volume_get": (ci, [vp, vp]),
-        "ta_volume_map": (ci, [vp, vp, u32, vp, ci, vp]),
-        "ta_volume_first_layer": (ci, [vp, u32, ci, vp]),
-        "ta_volume_hollow": (ci, [vp, u32, ci, ci, vp]),
-        "ta_volume_layer18": (ci, [vp, vp]),
-        "ta_wall_voxels_count": (ci, [vp, P(i64)]),
-        "ta_wall_voxels_get": (ci, [vp, vp, vp, P(ctypes.c_double)]),
-        "ta_wall_medians": (ci, [vp, ci, P(i64), P(ctypes.c_double)]),
-        "ta_wall_medians_get": (ci, [vp, vp, vp, vp]),
-        "ta_wall_voxels_get_by_pair": (ci, [vp, vp, vp, P(ctypes.c_double)]),
-        "ta_extract": (ci, [vp, u32, u32]),
-        "ta_get_labels": (ci, [vp, vp, vp, vp, vp]),
-        "ta_adjacency_size": (ci, [vp, P(i64)]),
-        "ta_adjacency_get": (ci, [vp, vp, vp, vp]),
-        "ta_timing": (ci, [vp, P(ctypes.c_double), P(ctypes.c_double), P(ctypes.c_double), P(u64)]),
-        "ta_timing_series": (ci, [vp, P(ctypes.c_double), ci, P(ci)]),
-        "ta_read_probe": (ci, [vp, vp, u64, ci, P(ctypes.c_double)]),
-        "ta_debug_counters": (ci, [vp, P(u32)]),
-        "ta_bind_accumulators": (ci, [vp, vp, vp, u32]),
-        "ta_accumulators_device": (ci, [vp, P(vp), P(vp), P(u32)]),
-        "ta_accumulators_reduced": (ci, [vp]),
-        "ta_adjacency_device": (ci, [vp, P(vp), P(vp), P(i64)]),
-        "ta_adjacency_export": (ci, [vp, vp, vp, i64]),
-        "ta_adjacency_merge": (ci, [vp, vp, vp, i64]),
-        "ta_adjacency_pack": (ci, [vp, vp, i64]),
-        "ta_adjacency_pack_shared": (ci, [vp, vp, i64]),
-        "ta_adjacency_merge_blocks": (ci, [vp, vp, ci, i64]),
-        "ta_synth_voronoi": (ci, [vp, vp, ci, P(i64), i64, i64, vp, P(ctypes.c_int32), vp]),
-        "ta_device_malloc": (ci, [vp, u64, P(vp)]),
-        "ta_device_free": (ci, [vp, vp]),
-        "ta_memcpy_d2h": (ci, [vp, vp, vp, u64]),
-        "ta_memcpy_h2d": (ci, [vp, vp, vp, u64]),
-        "ta_signal_set": (ci, [vp, vp, ci, P(i64), P(i64)]),
-        "ta_signal_set_device": (ci, [vp, vp, ci]),
-        "ta_signal_extract": (ci, [vp, u32]),
-        "ta_signal_get_labels": (ci, [vp, vp, vp, vp, vp, vp]),
-        "ta_signal_get_walls": (ci, [vp, vp, vp]),
-        "ta_signal_timing": (ci, [vp, P(ctypes.c_double)]),
-        "ta_signal_debug": (ci, [vp, P(u32)]),
-        "ta_mesh_extract": (ci, [vp, ci, vp]),
-        "ta_mesh_size": (ci, [vp, P(u64), P(u64), P(u64)]),
-        "ta_mesh_get": (ci, [vp, vp, vp, vp, vp, vp, vp, vp]),
-        "ta_mesh_timing": (ci, [vp, P(ctypes.c_double)]),
-        "ta_overlap_set": (ci, [vp, vp, ci, P(i64), P(i64)]),
-        "ta_overlap_set_device": (ci, [vp, vp, ci]),
-        "ta_overlap_set_capacity": (ci, [vp, ci]),
-        "ta_overlap_extract": (ci, [vp]),
-        "ta_overlap_size": (ci, [vp, P(u64)]),
-        "ta_overlap_get": (ci, [vp, vp, vp, vp]),
-        "ta_overlap_timing": (ci, [vp, P(ctypes.c_double)]),
-        "ta_overlap_timing_compaction": (ci, [vp, P(ctypes.c_double), P(ci)]),
-        "ta_overlap_debug": (ci, [vp, P(u32)]),
-        "ta_junctions_extract": (ci, [vp]),
-        "ta_junctions_size": (ci, [vp, P(u64), P(u64), P(u64)]),
-        "ta_junctions_get_edges": (ci, [vp, vp, vp, vp]),
-        "ta_junctions_get_vertices": (ci, [vp, vp, vp, vp]),
-        "ta_junctions_timing": (ci, [vp, P(ctypes.c_double), P(ctypes.c_double)]),
-        "ta_junctions_debug": (ci, [vp, P(u32)]),
-        "ta_wallgeo_extract": (ci, [vp]),
-        "ta_wallgeo_get": (ci, [vp, vp, vp, vp, vp]),
-        "ta_wallgeo_spills": (ci, [vp, P(u32)]),
-        "ta_wallgeo_debug": (ci, [vp, P(u32)]),
-        "ta_wallgeo_timing": (ci, [vp, P(ctypes.c_double)]),
-        "ta_components_extract": (ci, [vp]),
-        "ta_components_size": (ci, [vp, P(u64)]),
-        "ta_components_get": (ci, [vp, vp, vp, vp, vp, vp]),
-        "ta_components_image": (ci, [vp, i64, i64, vp]),
-        "ta_components_relabel": (ci, [vp, vp, u64]),
-        "ta_components_timing": (ci, [vp, P(ctypes.c_double), P(ctypes.c_double)]),
-        "ta_components_debug": (ci, [vp, P(u32)]),
-        "ta_distance_extract": (ci, [vp, ci, u32, P(ctypes.c_double), u32]),
-        "ta_distance_get": (ci, [vp, vp, vp, vp]),
-        "ta_distance_image": (ci, [vp, i64, i64, vp]),
-        "ta_distance_timing": (ci, [vp, P(ctypes.c_double), P(ctypes.c_double)]),
-        "ta_distance_set_batch": (ci, [vp, i64]),
-        "ta_distance_debug": (ci, [vp, P(u32)]),
-        "ta_nearest_extract": (ci, [vp, u32, u32, P(ctypes.c_double), ctypes.c_double, u32]),
-        "ta_nearest_get": (ci, [vp, vp, vp]),
-        "ta_nearest_image": (ci, [vp, i64, i64, vp, vp]),
-        "ta_nearest_apply": (ci, [vp]),
-        "ta_nearest_timing": (ci, [vp, P(ctypes.c_double), P(ctypes.c_double)]),
-        "ta_nearest_debug": (ci, [vp, P(u32)]),
-        "ta_nearest_set_batch": (ci, [vp, i64]),
-        "ta_profile_extract": (ci, [vp, ci, P(ctypes.c_double), u32]),
-        "ta_profile_get": (ci, [vp, vp, vp, vp, vp, vp]),
-        "ta_profile_debug": (ci, [vp, P(u32)]),
-        "ta_profile_timing": (ci, [vp, P(ctypes.c_double)]),
-        "ta_sighist_extract": (ci, [vp, ci]),
-        "ta_sighist_get": (ci, [vp, vp]),
-        "ta_sigrank_extract": (ci, [vp, ci, vp]),
-        "ta_sigrank_get": (ci, [vp, vp]),
-        "ta_sighist_debug": (ci, [vp, P(u32)]),
-        "ta_sighist_timing": (ci, [vp, P(ctypes.c_double), P(ctypes.c_double)]),
-        "ta_sigmom_extract": (ci, [vp]),
-        "ta_sigmom_get": (ci, [vp, vp, vp, vp, vp]),
-        "ta_sigmom_debug": (ci, [vp, P(u32)]),
-        "ta_sigmom_timing": (ci, [vp, P(ctypes.c_double)]),
-        "ta_topology_extract": (ci, [vp]),
-        "ta_topology_get": (ci, [vp, vp, vp, vp, vp, vp, vp]),
-        "ta_topology_debug": (ci, [vp, P(u32)]),
-        "ta_topology_timing": (ci, [vp, P(ctypes.c_double)]),
-        "ta_resample_set_source": (ci, [vp, vp, ci, P(i64), P(i64)]),
-        "ta_resample_set_source_device": (ci, [vp, vp, ci, P(i64)]),
-        "ta_resample_extract": (ci, [vp, P(ctypes.c_double), ci, u32]),
-        "ta_resample_get": (ci, [vp, vp, i64, i64]),
-        "ta_resample_device": (ci, [vp, P(vp), P(ci)]),
-        "ta_resample_outside": (ci, [vp, P(u64)]),
-        "ta_resample_timing": (ci, [vp, P(ctypes.c_double)]),
-        "ta_resample_debug": (ci, [vp, P(u32)]),
-        "ta_resample_as_overlap": (ci, [vp]),
-        "ta_resample_as_signal": (ci, [vp]),
-    }
-    for name in (SYMBOLS + SIGNAL_SYMBOLS + MESH_SYMBOLS + OVERLAP_SYMBOLS + JUNCTION_SYMBOLS + WALLGEO_SYMBOLS + COMPONENT_SYMBOLS
-                 + DISTANCE_SYMBOLS + NEAREST_SYMBOLS + PROFILE_SYMBOLS + SIGHIST_SYMBOLS + SIGMOM_SYMBOLS + TOPOLOGY_SYMBOLS + RESAMPLE_SYMBOLS):
-        fn = getattr(lib, name)      # AttributeError here == the .so does not match the header
-        fn.restype, fn.argtypes = sig[name]
+    for symbols in DECLARED.values():
+        for name, (restype, argtypes) in symbols.items():
+            fn = getattr(lib, name)      # AttributeError here == the .so does not match the header
+            fn.restype, fn.argtypes = restype, argtypes
     if lib.ta_version() != ABI_VERSION:
         raise ImportError("%s speaks ABI version %d, this binding %d: rebuild it (python -m tissue_analysis_amd.build --force)"
                           % (LIB_PATH, lib.ta_version(), ABI_VERSION))
@@ -341,6 +329,14 @@ def _dense_permuted(a):
     return True
 
 
+def _empty_like(like, what, dtype=None):
+    """An array for the pass `what` to fill: the shape and the memory order of `like` (the array given to set_volume)."""
+    out = np.empty_like(like, dtype=dtype)
+    if not _dense_permuted(out):
+        raise ValueError("%s needs a dense (possibly axis-permuted) volume" % what)
+    return out
+
+
 class Context(object):
     """One ta_ctx == one GPU.  Thin, explicit wrapper: every method is one C call."""
 
@@ -370,6 +366,25 @@ class Context(object):
 
     def __exit__(self, *exc):
         self.close()
+
+    def _doubles(self, fn, n, *more):
+        """The n doubles that fn(ctx, &d[0], .., &d[n - 1], *more) writes -- the shape of every ta_*_timing."""
+        out = [ctypes.c_double(0.0) for _ in range(n)]
+        _check(fn(self._h, *([ctypes.byref(v) for v in out] + list(more))))
+        return tuple(v.value for v in out)
+
+    def _debug_words(self, fn):
+        """The four uint32 words that fn(ctx, out[4]) writes -- the shape of every ta_*_debug."""
+        out = (ctypes.c_uint32 * 4)()
+        _check(fn(self._h, out))
+        return [int(v) for v in out]
+
+    def _census_ids(self, n):
+        """The n ascending ids (uint32) of the census the context holds."""
+        ids = np.zeros(n, dtype=np.uint32)
+        if n:
+            _check(self._lib.ta_label_census_get(self._h, ids.ctypes.data_as(ctypes.c_void_p)))
+        return ids
 
     # -- plumbing
     def set_stream(self, stream_handle):
@@ -431,9 +446,7 @@ class Context(object):
         lut = np.ascontiguousarray(lut)
         if lut.dtype.itemsize not in (1, 2, 4, 8):
             raise TypeError("lookup tables of %s are not supported" % lut.dtype)
-        out = np.empty_like(like, dtype=lut.dtype)            # keeps the memory order of `like`
-        if not _dense_permuted(out):
-            raise ValueError("map_labels needs a dense (possibly axis-permuted) volume")
+        out = _empty_like(like, "map_labels", lut.dtype)
         fillv = np.array([fill]).astype(lut.dtype)
         _check(self._lib.ta_volume_map(self._h, ctypes.c_void_p(lut.ctypes.data), int(lut.size),
                                        ctypes.c_void_p(fillv.ctypes.data), int(lut.dtype.itemsize),
@@ -443,9 +456,7 @@ class Context(object):
     def first_layer(self, background, keep_background, like):
         """voxel_first_layer of the resident volume (SIA:1024-1046) as a host image shaped and laid out like `like`
         (the array given to set_volume)."""
-        out = np.empty_like(like)
-        if not _dense_permuted(out):
-            raise ValueError("first_layer needs a dense (possibly axis-permuted) volume")
+        out = _empty_like(like, "first_layer")
         _check(self._lib.ta_volume_first_layer(self._h, int(background), int(bool(keep_background)),
                                                ctypes.c_void_p(out.ctypes.data)))
         return out
@@ -454,9 +465,7 @@ class Context(object):
         """hollow_out_cells of the resident volume (SIA:74-95): the labels where their integer Laplacian (modulo
         2^label_bits, 0 = the volume's own width) is not zero (and, with remove_background, where they are not the
         background), 0 elsewhere; shaped and laid out like `like`."""
-        out = np.empty_like(like)
-        if not _dense_permuted(out):
-            raise ValueError("hollow needs a dense (possibly axis-permuted) volume")
+        out = _empty_like(like, "hollow")
         _check(self._lib.ta_volume_hollow(self._h, int(background) & 0xFFFFFFFF, int(bool(remove_background)), int(label_bits),
                                           ctypes.c_void_p(out.ctypes.data)))
         return out
@@ -464,9 +473,7 @@ class Context(object):
     def layer18(self, like):
         """uint8 image, 1 where a voxel has one of its 18 neighbours in another label (cells_voxel_layer, SIA:1399-1448,
         for every label at once); shaped and laid out like `like`."""
-        out = np.empty_like(like, dtype=np.uint8)
-        if not _dense_permuted(out):
-            raise ValueError("layer18 needs a dense (possibly axis-permuted) volume")
+        out = _empty_like(like, "layer18", np.uint8)
         _check(self._lib.ta_volume_layer18(self._h, ctypes.c_void_p(out.ctypes.data)))
         return out
 
@@ -588,14 +595,11 @@ class Context(object):
     def signal_debug(self):
         """Diagnostics of the last signal pass: records that missed a workgroup's LDS tables (label_spills, pair_spills) and the
         launch plan (tiles_per_group, groups)."""
-        out = (ctypes.c_uint32 * 4)()
-        _check(self._lib.ta_signal_debug(self._h, out))
-        return dict(label_spills=int(out[0]), pair_spills=int(out[1]), tiles_per_group=int(out[2]), groups=int(out[3]))
+        out = self._debug_words(self._lib.ta_signal_debug)
+        return dict(label_spills=out[0], pair_spills=out[1], tiles_per_group=out[2], groups=out[3])
 
     def signal_timing(self):
-        ms = ctypes.c_double(0.0)
-        _check(self._lib.ta_signal_timing(self._h, ctypes.byref(ms)))
-        return ms.value
+        return self._doubles(self._lib.ta_signal_timing, 1)[0]
 
     # -- cell meshes (include/tissue_scan_mesh.h)
     def mesh(self, sub_factor=1, wanted_rows=None):
@@ -622,9 +626,7 @@ class Context(object):
         return cells, voff, toff, corners, tri, tcell, tnb, self.mesh_timing()
 
     def mesh_timing(self):
-        ms = ctypes.c_double(0.0)
-        _check(self._lib.ta_mesh_timing(self._h, ctypes.byref(ms)))
-        return ms.value
+        return self._doubles(self._lib.ta_mesh_timing, 1)[0]
 
     # -- label overlap with a second label volume (include/tissue_scan_overlap.h)
     def set_overlap(self, array):
@@ -666,21 +668,18 @@ class Context(object):
     def overlap_debug(self):
         """Diagnostics of the last run of the overlap pass kernel: records that missed a workgroup's LDS table (spills), the runs
         it took (passes) and the launch plan (tiles_per_group, groups).  Settles the table."""
-        out = (ctypes.c_uint32 * 4)()
-        _check(self._lib.ta_overlap_debug(self._h, out))
-        return dict(spills=int(out[0]), passes=int(out[1]), tiles_per_group=int(out[2]), groups=int(out[3]))
+        out = self._debug_words(self._lib.ta_overlap_debug)
+        return dict(spills=out[0], passes=out[1], tiles_per_group=out[2], groups=out[3])
 
     def overlap_timing(self):
         """Milliseconds of the pass kernel of the last overlap_extract."""
-        ms = ctypes.c_double(0.0)
-        _check(self._lib.ta_overlap_timing(self._h, ctypes.byref(ms)))
-        return ms.value
+        return self._doubles(self._lib.ta_overlap_timing, 1)[0]
 
     def overlap_timing_compaction(self):
         """(milliseconds of compaction + sort of the settled table, runs of the pass kernel it took)."""
-        ms, passes = ctypes.c_double(0.0), ctypes.c_int(0)
-        _check(self._lib.ta_overlap_timing_compaction(self._h, ctypes.byref(ms), ctypes.byref(passes)))
-        return ms.value, int(passes.value)
+        passes = ctypes.c_int(0)
+        ms, = self._doubles(self._lib.ta_overlap_timing_compaction, 1, ctypes.byref(passes))
+        return ms, int(passes.value)
 
     # -- cell junctions (include/tissue_scan_junctions.h)
     def junctions_extract(self):
@@ -705,16 +704,13 @@ class Context(object):
 
     def junctions_timing(self):
         """(milliseconds of the two walks over the volume, milliseconds of everything after them) of settled tables."""
-        a, b = ctypes.c_double(0.0), ctypes.c_double(0.0)
-        _check(self._lib.ta_junctions_timing(self._h, ctypes.byref(a), ctypes.byref(b)))
-        return a.value, b.value
+        return self._doubles(self._lib.ta_junctions_timing, 2)
 
     def junctions_debug(self):
         """What the last pass launched: the tasks of a walk, and the workgroups of the kernel that writes the sort keys of the edge
         and of the vertex records (0 without records).  Settles the tables."""
-        out = (ctypes.c_uint32 * 4)()
-        _check(self._lib.ta_junctions_debug(self._h, out))
-        return dict(tasks=int(out[0]), edge_key_groups=int(out[1]), vertex_key_groups=int(out[2]))
+        out = self._debug_words(self._lib.ta_junctions_debug)
+        return dict(tasks=out[0], edge_key_groups=out[1], vertex_key_groups=out[2])
 
     # -- wall geometry (include/tissue_scan_wallgeo.h)
     def wallgeo_extract(self):
@@ -737,14 +733,11 @@ class Context(object):
 
     def wallgeo_debug(self):
         """wallgeo_spills() and the launch plan (tiles_per_group, groups; 0 and 0 when there was no pair and no launch)."""
-        out = (ctypes.c_uint32 * 4)()
-        _check(self._lib.ta_wallgeo_debug(self._h, out))
-        return dict(spills=int(out[0]), tiles_per_group=int(out[2]), groups=int(out[3]))
+        out = self._debug_words(self._lib.ta_wallgeo_debug)
+        return dict(spills=out[0], tiles_per_group=out[2], groups=out[3])
 
     def wallgeo_timing(self):
-        ms = ctypes.c_double(0.0)
-        _check(self._lib.ta_wallgeo_timing(self._h, ctypes.byref(ms)))
-        return ms.value
+        return self._doubles(self._lib.ta_wallgeo_timing, 1)[0]
 
     # -- connected components of the labels (include/tissue_scan_components.h)
     def components_extract(self):
@@ -782,16 +775,13 @@ class Context(object):
 
     def components_timing(self):
         """(milliseconds of the kernels that walk the volume, milliseconds of everything after them) of a settled table."""
-        a, b = ctypes.c_double(0.0), ctypes.c_double(0.0)
-        _check(self._lib.ta_components_timing(self._h, ctypes.byref(a), ctypes.byref(b)))
-        return a.value, b.value
+        return self._doubles(self._lib.ta_components_timing, 2)
 
     def components_debug(self):
         """What the last pass launched: the tiles of the local pass, the workgroups of the seam pass, of the last image or relabel
         launch since the extract (0 if none) and of the key kernel.  Settles the table."""
-        out = (ctypes.c_uint32 * 4)()
-        _check(self._lib.ta_components_debug(self._h, out))
-        return dict(tiles=int(out[0]), seam_groups=int(out[1]), stream_groups=int(out[2]), key_groups=int(out[3]))
+        out = self._debug_words(self._lib.ta_components_debug)
+        return dict(tiles=out[0], seam_groups=out[1], stream_groups=out[2], key_groups=out[3])
 
     # -- distance maps (include/tissue_scan_distance.h)
     def distance_extract(self, mode=DIST_OWN_WALL, site_label=0, spacing=(1.0, 1.0, 1.0), flags=0):
@@ -817,9 +807,7 @@ class Context(object):
 
     def distance_timing(self):
         """(milliseconds of the row pass and the two column passes, milliseconds of the table passes)."""
-        a, b = ctypes.c_double(0.0), ctypes.c_double(0.0)
-        _check(self._lib.ta_distance_timing(self._h, ctypes.byref(a), ctypes.byref(b)))
-        return a.value, b.value
+        return self._doubles(self._lib.ta_distance_timing, 2)
 
     def distance_set_batch(self, columns=0):
         """Columns a launch of a column pass takes (0 = automatic); the results do not depend on it."""
@@ -828,9 +816,8 @@ class Context(object):
     def distance_debug(self):
         """What the last distance_extract launched: the workgroups of the row pass, of the extremes and pole kernels and of the
         table initialisation, and the launches of the column kernel along both axes together."""
-        out = (ctypes.c_uint32 * 4)()
-        _check(self._lib.ta_distance_debug(self._h, out))
-        return dict(row_groups=int(out[0]), voxel_groups=int(out[1]), init_groups=int(out[2]), column_launches=int(out[3]))
+        out = self._debug_words(self._lib.ta_distance_debug)
+        return dict(row_groups=out[0], voxel_groups=out[1], init_groups=out[2], column_launches=out[3])
 
     # -- nearest-label maps (include/tissue_scan_nearest.h)
     def nearest_extract(self, empty_label=0, not_from_label=None, spacing=(1.0, 1.0, 1.0), max_d2=float("inf")):
@@ -866,9 +853,7 @@ class Context(object):
 
     def nearest_timing(self):
         """(milliseconds of the row pass and the two column passes, milliseconds of the counting pass)."""
-        a, b = ctypes.c_double(0.0), ctypes.c_double(0.0)
-        _check(self._lib.ta_nearest_timing(self._h, ctypes.byref(a), ctypes.byref(b)))
-        return a.value, b.value
+        return self._doubles(self._lib.ta_nearest_timing, 2)
 
     def nearest_set_batch(self, columns=0):
         """Columns a launch of a column pass takes (0 = automatic); the results do not depend on it."""
@@ -877,9 +862,8 @@ class Context(object):
     def nearest_debug(self):
         """What the last nearest_extract launched: the workgroups of the row pass, of the counting pass and of the apply pass, and
         the launches of the column kernel along both axes together."""
-        out = (ctypes.c_uint32 * 4)()
-        _check(self._lib.ta_nearest_debug(self._h, out))
-        return dict(row_groups=int(out[0]), count_groups=int(out[1]), apply_groups=int(out[2]), column_launches=int(out[3]))
+        out = self._debug_words(self._lib.ta_nearest_debug)
+        return dict(row_groups=out[0], count_groups=out[1], apply_groups=out[2], column_launches=out[3])
 
     # -- distance-shell profiles (include/tissue_scan_profile.h)
     def profile_extract(self, edges2, signal=False):
@@ -906,14 +890,11 @@ class Context(object):
     def profile_debug(self):
         """Diagnostics of the last profile pass: records that missed a workgroup's LDS table (spills) and the launch plan
         (tiles_per_group, groups)."""
-        out = (ctypes.c_uint32 * 4)()
-        _check(self._lib.ta_profile_debug(self._h, out))
-        return dict(spills=int(out[0]), tiles_per_group=int(out[2]), groups=int(out[3]))
+        out = self._debug_words(self._lib.ta_profile_debug)
+        return dict(spills=out[0], tiles_per_group=out[2], groups=out[3])
 
     def profile_timing(self):
-        ms = ctypes.c_double(0.0)
-        _check(self._lib.ta_profile_timing(self._h, ctypes.byref(ms)))
-        return ms.value
+        return self._doubles(self._lib.ta_profile_timing, 1)[0]
 
     # -- signal histograms and order statistics (include/tissue_scan_sighist.h)
     def sighist_extract(self, log2_width):
@@ -946,17 +927,15 @@ class Context(object):
     def sighist_debug(self):
         """Diagnostics of the last digit-kernel launch of either pass: counts that missed a workgroup's LDS table (spills) and the
         launch plan (tiles_per_group, groups)."""
-        out = (ctypes.c_uint32 * 4)()
-        _check(self._lib.ta_sighist_debug(self._h, out))
-        return dict(spills=int(out[0]), tiles_per_group=int(out[2]), groups=int(out[3]))
+        out = self._debug_words(self._lib.ta_sighist_debug)
+        return dict(spills=out[0], tiles_per_group=out[2], groups=out[3])
 
     def sighist_timing(self):
         """(ms_hist, ms_rank): HIP-event milliseconds of the last histogram pass and of all kernels of the last select; None for
         one without valid results."""
-        a, b = ctypes.c_double(0.0), ctypes.c_double(0.0)
-        _check(self._lib.ta_sighist_timing(self._h, ctypes.byref(a), ctypes.byref(b)))
+        a, b = self._doubles(self._lib.ta_sighist_timing, 2)
         some = lambda v: None if v != v else v
-        return some(a.value), some(b.value)
+        return some(a), some(b)
 
     # -- signal-weighted moments (include/tissue_scan_sigmoments.h)
     def sigmom_extract(self):
@@ -976,14 +955,11 @@ class Context(object):
     def sigmom_debug(self):
         """Diagnostics of the last signal-moment pass: records that missed a workgroup's LDS table (spills) and the launch plan
         (tiles_per_group, groups)."""
-        out = (ctypes.c_uint32 * 4)()
-        _check(self._lib.ta_sigmom_debug(self._h, out))
-        return dict(spills=int(out[0]), tiles_per_group=int(out[2]), groups=int(out[3]))
+        out = self._debug_words(self._lib.ta_sigmom_debug)
+        return dict(spills=out[0], tiles_per_group=out[2], groups=out[3])
 
     def sigmom_timing(self):
-        ms = ctypes.c_double(0.0)
-        _check(self._lib.ta_sigmom_timing(self._h, ctypes.byref(ms)))
-        return ms.value
+        return self._doubles(self._lib.ta_sigmom_timing, 1)[0]
 
     # -- Euler numbers (include/tissue_scan_topology.h)
     def topology_extract(self):
@@ -1004,14 +980,11 @@ class Context(object):
     def topology_debug(self):
         """Diagnostics of the last pass: records that missed a workgroup's LDS table (spills), blocks of more than one label
         (mixed, saturating) and the launch plan (tiles_per_group, groups)."""
-        out = (ctypes.c_uint32 * 4)()
-        _check(self._lib.ta_topology_debug(self._h, out))
-        return dict(spills=int(out[0]), mixed=int(out[1]), tiles_per_group=int(out[2]), groups=int(out[3]))
+        out = self._debug_words(self._lib.ta_topology_debug)
+        return dict(spills=out[0], mixed=out[1], tiles_per_group=out[2], groups=out[3])
 
     def topology_timing(self):
-        ms = ctypes.c_double(0.0)
-        _check(self._lib.ta_topology_timing(self._h, ctypes.byref(ms)))
-        return ms.value
+        return self._doubles(self._lib.ta_topology_timing, 1)[0]
 
     # -- resampling a second volume onto the label grid (include/tissue_scan_resample.h)
     def set_resample_source(self, array):
@@ -1062,15 +1035,12 @@ class Context(object):
         return int(n.value)
 
     def resample_timing(self):
-        ms = ctypes.c_double(0.0)
-        _check(self._lib.ta_resample_timing(self._h, ctypes.byref(ms)))
-        return ms.value
+        return self._doubles(self._lib.ta_resample_timing, 1)[0]
 
     def resample_debug(self):
         """What the last pass launched: whole 16-byte strips or scalar stores (vector), the mode, the launch plan."""
-        out = (ctypes.c_uint32 * 4)()
-        _check(self._lib.ta_resample_debug(self._h, out))
-        return dict(vector=bool(out[0]), mode=int(out[1]), tiles_per_group=int(out[2]), groups=int(out[3]))
+        out = self._debug_words(self._lib.ta_resample_debug)
+        return dict(vector=bool(out[0]), mode=out[1], tiles_per_group=out[2], groups=out[3])
 
     def resample_as_overlap(self):
         """Hand the result to the overlap pass as its B (a nearest-neighbour result of uint16 / uint32)."""
@@ -1097,10 +1067,7 @@ class Context(object):
         """(max id, ascending uint32 ids present in the resident volume): np.unique on the device."""
         top, n = ctypes.c_uint32(0), ctypes.c_uint32(0)
         _check(self._lib.ta_volume_label_census(self._h, ctypes.byref(top), ctypes.byref(n)))
-        ids = np.zeros(n.value, dtype=np.uint32)
-        if n.value:
-            _check(self._lib.ta_label_census_get(self._h, ids.ctypes.data_as(ctypes.c_void_p)))
-        return top.value, ids
+        return top.value, self._census_ids(n.value)
 
     def compact_labels(self, ids=None):
         """From now on the sweep reads a copy of the volume written in the RANKS of its ids (`ids`: an ascending unique list
@@ -1112,10 +1079,7 @@ class Context(object):
         else:
             ids = np.ascontiguousarray(ids, dtype=np.uint32)
             _check(self._lib.ta_volume_compact_labels(self._h, ids.ctypes.data_as(ctypes.c_void_p), ids.size, ctypes.byref(n)))
-        out = np.zeros(n.value, dtype=np.uint32)
-        if n.value:
-            _check(self._lib.ta_label_census_get(self._h, out.ctypes.data_as(ctypes.c_void_p)))
-        return out
+        return self._census_ids(n.value)
 
     def is_compact(self):
         flag, n = ctypes.c_int(0), ctypes.c_uint32(0)
@@ -1128,10 +1092,7 @@ class Context(object):
         _check(self._lib.ta_volume_is_compact(self._h, ctypes.byref(flag), ctypes.byref(n)))
         if not flag.value:
             raise TissueScanError(TA_EINVAL, "the context is not compacted")
-        out = np.zeros(n.value, dtype=np.uint32)
-        if n.value:
-            _check(self._lib.ta_label_census_get(self._h, out.ctypes.data_as(ctypes.c_void_p)))
-        return out
+        return self._census_ids(n.value)
 
     # -- hot path
     def rerank(self):
@@ -1198,14 +1159,12 @@ class Context(object):
         return lo, hi, faces
 
     def timing(self):
-        a, b, t = ctypes.c_double(0), ctypes.c_double(0), ctypes.c_double(0)
         nbytes = ctypes.c_uint64(0)
-        _check(self._lib.ta_timing(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(t),
-                                   ctypes.byref(nbytes)))
+        a, b, t = self._doubles(self._lib.ta_timing, 3, ctypes.byref(nbytes))
         # (a duration no event recorded comes back as NaN -- TA_OPT_TIMING 0, or 1 for what only mode 2 brackets -- and is
         #  handed on as None: "not measured" must never read as "took no time" in a bandwidth figure)
         some = lambda v: None if v != v else v
-        return dict(ms_sweep=some(a.value), ms_adjacency=some(b.value), ms_total=some(t.value), bytes_read=nbytes.value)
+        return dict(ms_sweep=some(a), ms_adjacency=some(b), ms_total=some(t), bytes_read=nbytes.value)
 
     def timing_series(self, capacity=4096):
         """Sweep-kernel milliseconds of the last extractions (oldest first; OPT_TIMING_RING of them at most)."""

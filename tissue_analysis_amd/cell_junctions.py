@@ -11,6 +11,8 @@ from __future__ import annotations
 
 import numpy as np
 
+from ._tables import voxelsize3
+
 
 def _member(values, chosen):
     chosen = np.asarray(list(chosen), dtype=np.int64).reshape(-1)
@@ -77,12 +79,7 @@ class CellJunctions(object):
         self.edge_labels, self.edge_n, self.edge_sum = _table(edge_labels, edge_n, edge_sum, 3, "edge")
         self.vertex_labels, self.vertex_n, self.vertex_sum = _table(vertex_labels, vertex_n, vertex_sum, 4, "vertex")
         self.degenerate = int(degenerate)
-        vs = tuple(float(v) for v in voxelsize)
-        if len(vs) == 2:
-            vs = vs + (1.0,)
-        if len(vs) != 3:
-            raise ValueError("voxelsize must have two or three entries")
-        self.voxelsize = vs
+        self.voxelsize = voxelsize3(voxelsize)
         self.ms = ms
 
     # -- positions

@@ -136,9 +136,6 @@ def resident_meshes(resident, labels=None, sub_factor=1, voxelsize=(1.0, 1.0, 1.
     s = int(sub_factor)
     if s < 1:
         raise ValueError("sub_factor must be >= 1, not %r" % (sub_factor,))
-    x = resident.last
-    if x is None:
-        x = resident.extract(_capi.F_ALL)
 
     def wanted(x):
         if labels is None:
@@ -148,13 +145,7 @@ def resident_meshes(resident, labels=None, sub_factor=1, voxelsize=(1.0, 1.0, 1.
         w[rows[rows >= 0]] = 1
         return w
 
-    try:
-        out = ctx.mesh(s, wanted(x))
-    except _capi.TissueScanError as e:
-        if e.code != _capi.TA_EINVAL:
-            raise
-        x = resident.extract(_capi.F_ALL, sparse=x.sparse)
-        out = ctx.mesh(s, wanted(x))
+    x, out = resident.over_extraction(lambda x: ctx.mesh(s, wanted(x)))
     cells, voff, toff, corners, tri, tcell, tnb, ms = out
     ids = (lambda r: r.astype(np.int64)) if x.ids is None else (lambda r: x.ids[r.astype(np.int64)])
     nb = np.full(tnb.shape, OUTSIDE, dtype=np.int64)

@@ -6,21 +6,12 @@ from __future__ import annotations
 
 import numpy as np
 
-from . import _capi
+from ._tables import _ByLabel, to_array_axes, voxelsize3
 
 COLUMNS = ("euler_number", "mean_breadth", "half_surface")
 
 
-def _voxelsize(voxelsize):
-    vs = tuple(float(v) for v in voxelsize)
-    if len(vs) == 2:
-        vs = vs + (1.0,)
-    if len(vs) != 3:
-        raise ValueError("voxelsize must have two or three entries")
-    return vs
-
-
-class CellTopology(object):
+class CellTopology(_ByLabel):
     """Block counts whose rows line up with an `Extraction`: rows 0..max_label, or one per id of `.ids` when the ids are sparse.
     Twelve int64 columns as the pass gives them; the per-axis ones in MEMORY-axis order k = 0, 1, 2 (`perm[k]` is the array axis
     of k):
@@ -53,30 +44,23 @@ class CellTopology(object):
         self.perm = tuple(int(p) for p in perm)
         if sorted(self.perm) != [0, 1, 2]:
             raise ValueError("perm must be a permutation of (0, 1, 2), not %r" % (perm,))
-        self.voxelsize = _voxelsize(voxelsize)
+        self.voxelsize = voxelsize3(voxelsize)
         self.ms = ms
 
     def __len__(self):
         return int(self.n0.size)
 
     # ------------------------------------------------------------------ exact integers
-    def _to_array_axes(self, mem):
-        """Columns of a [R, 3] array from memory-axis to array-axis order."""
-        out = np.empty_like(mem)
-        for k in range(3):
-            out[:, self.perm[k]] = mem[:, k]
-        return out
-
     def _faces_memory(self):
         return 2 * self.n0[:, None] - self.n1
 
     def faces(self):
         """int64 [R, 3]: the lattice faces normal to each ARRAY axis that every label touches, each counted once: 2 n0 - n1."""
-        return self._to_array_axes(self._faces_memory())
+        return to_array_axes(self._faces_memory(), self.perm)
 
     def face_pairs(self):
         """int64 [R, 3]: n1 in ARRAY-axis order."""
-        return self._to_array_axes(self.n1)
+        return to_array_axes(self.n1, self.perm)
 
     def euler_number(self, connectivity=6):
         """int64 [R]: the Euler number of every row's voxels, joined across faces (6) or across faces, edges and corners (26)."""
@@ -91,7 +75,7 @@ class CellTopology(object):
         """(chi26 int64 [R], V1, V2, volume float64 [R]) of the closed voxel solid of every row, with `voxelsize` per ARRAY axis
         (default: this object's).  V1 is twice the mean breadth -- a box of a x b x c voxels gives a s0 + b s1 + c s2 --, V2 half
         the surface, the faces on the image border included."""
-        vs = self.voxelsize if voxelsize is None else _voxelsize(voxelsize)
+        vs = self.voxelsize if voxelsize is None else voxelsize3(voxelsize)
         s = [vs[self.perm[k]] for k in range(3)]                  # per memory axis
         area = [s[1] * s[2], s[0] * s[2], s[0] * s[1]]
         F = self._faces_memory()
@@ -108,12 +92,6 @@ class CellTopology(object):
         return 0.5 * self.intrinsic_volumes(voxelsize)[1]
 
     # ------------------------------------------------------------------ lookups by label id
-    def rows_of(self, labels, missing=None):
-        if self.extraction is None:
-            idx = np.asarray(labels, dtype=np.int64)
-            return idx if missing is None else np.where((idx >= 0) & (idx < len(self)), idx, missing)
-        return self.extraction.rows_of(labels, missing)
-
     def of_labels(self, labels, column="euler_number", connectivity=6, voxelsize=None):
         """`column` of every label id in `labels`: 'euler_number' (int64, for `connectivity`), 'mean_breadth' or 'half_surface'
         (float64, with `voxelsize`).  An id without a row has no voxels: 0, as for a row without voxels."""
@@ -125,11 +103,7 @@ class CellTopology(object):
             col = self.intrinsic_volumes(voxelsize)[1 if column == "mean_breadth" else 2]
             if column == "mean_breadth":
                 col = 0.5 * col
-        rows = self.rows_of(np.asarray(labels, dtype=np.int64).reshape(-1), missing=-1)
-        known = rows >= 0
-        out = col[np.where(known, rows, 0)].copy()
-        out[~known] = 0
-        return out
+        return self._pick(col, labels, 0)
 
 
 def topological_defects(topology, components, exclude=()):
@@ -151,15 +125,6 @@ def resident_topology(resident, voxelsize=(1.0, 1.0, 1.0)):
     """The Euler-number pass over the volume resident in `resident` (a ResidentVolume), with the rows of its current extraction --
     swept first when the context holds none that fits."""
     ctx = resident.ctx
-    x = resident.last
-    try:
-        if x is None:
-            raise _capi.TissueScanError(_capi.TA_EINVAL, "no extraction")
-        ctx.topology_extract()
-    except _capi.TissueScanError as err:
-        if err.code != _capi.TA_EINVAL:
-            raise
-        x = resident.extract(_capi.F_ALL, sparse=None if x is None else x.sparse)
-        ctx.topology_extract()
+    x, _ = resident.over_extraction(lambda x: ctx.topology_extract())
     n0, n1, n2, n3, v, e = ctx.topology_rows()
     return CellTopology(x, n0, n1, n2, n3, v, e, ctx.memory_axes(), voxelsize, ms=ctx.topology_timing())

@@ -9,6 +9,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import _capi
+from ._tables import voxelsize3
 
 NONE = _capi.COMPONENT_NONE            # row image: a voxel whose component has no row (a slab's halo plane only)
 TILE = (4, 4, 256)                     # voxels of the local pass's tile per memory axis (csrc/ta_components.h)
@@ -46,12 +47,7 @@ class LabelComponents(object):
             raise ValueError("the columns of a component table have one entry per row")
         if R and (self.label.min() < 0 or self.label.max() > 0xFFFFFFFF):
             raise ValueError("labels must fit in uint32")
-        vs = tuple(float(v) for v in voxelsize)
-        if len(vs) == 2:
-            vs = vs + (1.0,)
-        if len(vs) != 3:
-            raise ValueError("voxelsize must have two or three entries")
-        self.voxelsize = vs
+        self.voxelsize = voxelsize3(voxelsize)
         self.ms = ms
 
     def __len__(self):

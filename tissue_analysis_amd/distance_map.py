@@ -11,6 +11,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import _capi
+from ._tables import voxelsize3
 
 OWN_WALL, FROM_LABEL = _capi.DIST_OWN_WALL, _capi.DIST_FROM_LABEL
 
@@ -44,11 +45,7 @@ class DistanceMap(object):
             raise ValueError("the columns of a distance table have one entry per row")
         if R > 1 and not (np.diff(self.labels) > 0).all():
             raise ValueError("the labels of a distance table ascend")
-        vs = tuple(float(v) for v in voxelsize)
-        if len(vs) == 2:
-            vs = vs + (1.0,)
-        if len(vs) != 3:
-            raise ValueError("voxelsize must have two or three entries")
+        vs = voxelsize3(voxelsize)
         if mode not in (OWN_WALL, FROM_LABEL):
             raise ValueError("mode must be OWN_WALL (0) or FROM_LABEL (1), not %r" % (mode,))
         self.voxelsize = vs
@@ -141,9 +138,7 @@ def resident_distance_map(resident, mode=OWN_WALL, site_label=None, voxelsize=(1
     """The distance pass over the volume resident in `resident` (a ResidentVolume), with the rows of its current extraction --
     swept first when the context holds none."""
     ctx = resident.ctx
-    vs = tuple(float(v) for v in voxelsize)
-    if len(vs) == 2:
-        vs = vs + (1.0,)
+    vs = voxelsize3(voxelsize)
     if mode not in (OWN_WALL, FROM_LABEL):
         raise ValueError("mode must be OWN_WALL (0) or FROM_LABEL (1), not %r" % (mode,))
     if mode == FROM_LABEL and site_label is None:
@@ -152,16 +147,7 @@ def resident_distance_map(resident, mode=OWN_WALL, site_label=None, voxelsize=(1
     if not 0 <= site <= 0xFFFFFFFF:
         raise ValueError("site_label must fit in uint32")
     flags = _capi.DIST_EDGE_IS_SITE if edge else 0
-    x = resident.last
-    try:
-        if x is None:
-            raise _capi.TissueScanError(_capi.TA_EINVAL, "no extraction")
-        ctx.distance_extract(mode, site, vs, flags)
-    except _capi.TissueScanError as e:
-        if e.code != _capi.TA_EINVAL:
-            raise
-        x = resident.extract(_capi.F_ALL, sparse=None if x is None else x.sparse)
-        ctx.distance_extract(mode, site, vs, flags)
+    x, _ = resident.over_extraction(lambda x: ctx.distance_extract(mode, site, vs, flags))
     min2, max2, pole = ctx.distance_get()
     labels = x.ids if x.sparse else np.arange(x.nrows, dtype=np.int64)
     run = [_next_run(resident)]

@@ -13,6 +13,7 @@ scans voxels.  Formulas (SURVEY.md §8 "Semantics"):
 from __future__ import annotations
 
 from collections.abc import Mapping
+from time import perf_counter as _now
 
 import numpy as np
 
@@ -487,38 +488,68 @@ class ResidentVolume(object):
         except Exception:
             pass
 
+    def _timed(self, key, fn, *args):
+        """fn(*args), its wall-clock milliseconds (host side) left in ms[key]."""
+        t0 = _now()
+        out = fn(*args)
+        self.ms[key] = (_now() - t0) * 1e3
+        return out
+
     def upload(self, array=None):
         """(Re-)upload: after construction, or after the host image was modified in place."""
-        import time
         if array is not None:
             self.host, self.is_input = _as_label_volume(array)
-        t0 = time.perf_counter()
-        self.ctx.set_volume(self.host)
-        self.ms["upload"] = (time.perf_counter() - t0) * 1e3
+        self._timed("upload", self.ctx.set_volume, self.host)
         self.uploads += 1
         self.last = None
 
     def extract(self, features=_capi.F_ALL, max_label=None, sparse=None):
         """One sweep of the resident volume.  Ids that are sparse (`wants_compaction`) are swept in their ranks: the
         Extraction then has one row per id present (`.ids`) instead of rows 0..max_label; sparse=False insists on dense rows."""
-        import time
-        t0 = time.perf_counter()
-        x = extract_resident(self.ctx, self.host.shape, features, max_label, sparse)
-        self.ms["extract"] = (time.perf_counter() - t0) * 1e3
-        self.last = x
-        return x
+        self.last = self._timed("extract", extract_resident, self.ctx, self.host.shape, features, max_label, sparse)
+        return self.last
+
+    def over_extraction(self, enqueue):
+        """The one rule of the passes that run over an extraction: enqueue(x) over the current one, `last`; when there is none,
+        or the context answers TA_EINVAL (an edit since made it stale, or it lacks what the pass needs), sweep -- with the
+        `sparse` the last one had -- and enqueue once more.  Returns (x, what enqueue(x) returned), x the Extraction the pass
+        ran over; every other error, and one after the sweep, is the caller's."""
+        x = self.last
+        if x is not None:
+            try:
+                return x, enqueue(x)
+            except _capi.TissueScanError as e:
+                if e.code != _capi.TA_EINVAL:
+                    raise
+        x = self.extract(_capi.F_ALL, sparse=None if x is None else x.sparse)
+        return x, enqueue(x)
+
+    def _with_host_axes(self, flat):
+        """A flat array in the device's memory order -- the whole volume, or a range of planes along its slowest memory axis -- as
+        an array with the axes and the layout of the image."""
+        shape = list(self.host.shape)
+        strides = [s // self.host.dtype.itemsize * flat.dtype.itemsize for s in self.host.strides]
+        if flat.size != self.host.size:
+            slow = max((d for d in range(3) if shape[d] != 1), key=lambda d: strides[d])
+            shape[slow] = flat.size // (self.host.size // shape[slow])
+        return np.lib.stride_tricks.as_strided(flat, shape=shape, strides=strides)
+
+    def _sweep_edited(self, features):
+        """After an edit on the device: copy the volume back into `host` -- a copy of its own IN THE IMAGE'S LAYOUT when the image
+        is read-only, for the bytes come in the device's memory order -- and sweep the new volume."""
+        if not self.host.flags.writeable:
+            self.host = self.host.copy(order="K")
+            self.is_input = False
+        self.ctx.get_volume(self.host)
+        return self.extract(features)
 
     def resample(self, source, matrix, order=0, fill=0):
         """`source` (a NumPy array or CUDA tensor of uint8 / uint16 / uint32, ANY shape) sampled onto the grid of the resident
         volume through `matrix`, the 3 x 4 index matrix of `resample.index_matrix` (target voxel index -> continuous source
         index): order 0 nearest neighbour (labels), 1 trilinear (uint8 / uint16 signals); voxels that fall outside the source
         take `fill`.  A `Resampled`: .image(), .tensor(), .outside, .ms.  One gather pass on the GPU; the result stays there."""
-        import time
         from .resample import resident_resample
-        t0 = time.perf_counter()
-        r = resident_resample(self, source, matrix, order, fill)
-        self.ms["resample"] = (time.perf_counter() - t0) * 1e3
-        return r
+        return self._timed("resample", resident_resample, self, source, matrix, order, fill)
 
     def _signal_on_grid(self, signal, matrix, order, fill):
         """`signal` itself, or with an index matrix what the signal passes take in its place: resampled on the device, adopted there."""
@@ -533,71 +564,47 @@ class ResidentVolume(object):
         `.lo` / `.hi` for walls).  One upload of the signal and one pass over labels + signal on the GPU.  With `matrix` (a
         3 x 4 index matrix, `resample.index_matrix`) the image may have any shape: it is resampled onto the labels' grid on the
         device (`order`, `fill` as for `resample`) and read from there -- so for the three signal passes below."""
-        import time
         from .signal_stats import resident_signal
         signal = self._signal_on_grid(signal, matrix, order, fill)
-        t0 = time.perf_counter()
-        st = resident_signal(self, signal, walls)
-        self.ms["signal"] = (time.perf_counter() - t0) * 1e3
-        return st
+        return self._timed("signal", resident_signal, self, signal, walls)
 
     def signal_histogram(self, signal, bin_width=None, matrix=None, order=1, fill=0):
         """Per-label histogram of an intensity image (uint8 / uint16, the shape of the labels): a `SignalHistogram` whose rows
         line up with the last extraction.  bin_width: a power of two leaving at most 256 bins (default 1 for uint8, 256 for
         uint16).  One upload of the signal and one pass over labels + signal on the GPU."""
-        import time
         from .signal_quantiles import resident_signal_histogram
         signal = self._signal_on_grid(signal, matrix, order, fill)
-        t0 = time.perf_counter()
-        h = resident_signal_histogram(self, signal, bin_width)
-        self.ms["signal_histogram"] = (time.perf_counter() - t0) * 1e3
-        return h
+        return self._timed("signal_histogram", resident_signal_histogram, self, signal, bin_width)
 
     def signal_quantiles(self, signal, q, method='linear', matrix=None, order=1, fill=0):
         """Per-label quantiles `q` (in [0, 1]) of an intensity image by numpy's rule for `method` ('linear', 'lower', 'higher',
         'midpoint'), from exact order statistics selected on the GPU: a `SignalQuantiles` whose rows line up with the last
         extraction.  One or two passes over labels + signal (uint8 / uint16) for every eight ranks a row."""
-        import time
         from .signal_quantiles import resident_signal_quantiles
         signal = self._signal_on_grid(signal, matrix, order, fill)
-        t0 = time.perf_counter()
-        sq = resident_signal_quantiles(self, signal, q, method)
-        self.ms["signal_quantiles"] = (time.perf_counter() - t0) * 1e3
-        return sq
+        return self._timed("signal_quantiles", resident_signal_quantiles, self, signal, q, method)
 
     def signal_moments(self, signal, voxelsize=(1.0, 1.0, 1.0), matrix=None, order=1, fill=0):
         """Where in every cell an intensity image (uint8 / uint16, the shape of the labels) sits: a `SignalMoments` (signal-weighted
         centroid, polarity, covariance and inertia axes from exact integer sums) whose rows line up with the last extraction.
         One upload of the signal and one pass over labels + signal on the GPU."""
-        import time
         from .signal_moments import resident_signal_moments
         signal = self._signal_on_grid(signal, matrix, order, fill)
-        t0 = time.perf_counter()
-        sm = resident_signal_moments(self, signal, voxelsize)
-        self.ms["signal_moments"] = (time.perf_counter() - t0) * 1e3
-        return sm
+        return self._timed("signal_moments", resident_signal_moments, self, signal, voxelsize)
 
     def topology(self, voxelsize=(1.0, 1.0, 1.0)):
         """The Euler numbers of the labels of the resident volume, for 6- and for 26-connectivity, and the intrinsic volumes of
         their voxel solids: a `CellTopology` (twelve exact block counts per label) whose rows line up with the last extraction
         (swept first when there is none).  One pass over the 2 x 2 x 2 blocks of the volume on the GPU."""
-        import time
         from .cell_topology import resident_topology
-        t0 = time.perf_counter()
-        tp = resident_topology(self, voxelsize)
-        self.ms["topology"] = (time.perf_counter() - t0) * 1e3
-        return tp
+        return self._timed("topology", resident_topology, self, voxelsize)
 
     def meshes(self, labels=None, sub_factor=1, voxelsize=(1.0, 1.0, 1.0)):
         """The exact voxel-face surface meshes of the cells `labels` (ids; None = every label, background included) of
         host[::s, ::s, ::s]: a `CellMeshes`.  Count, scan and emit on the GPU, over the current extraction (swept first when
         there is none)."""
-        import time
         from .cell_meshes import resident_meshes
-        t0 = time.perf_counter()
-        m = resident_meshes(self, labels, sub_factor, voxelsize)
-        self.ms["meshes"] = (time.perf_counter() - t0) * 1e3
-        return m
+        return self._timed("meshes", resident_meshes, self, labels, sub_factor, voxelsize)
 
     def overlap(self, other, matrix=None, fill=0):
         """The overlap table of the resident volume with `other`, a second label image of the same shape (an integer array, or a
@@ -605,45 +612,27 @@ class ResidentVolume(object):
         tensor) and one pass over both volumes on the GPU; no sweep is needed.  With `matrix` (a 3 x 4 index matrix,
         `resample.index_matrix`) `other` may have any shape: it is resampled onto this grid by nearest neighbour on the device
         (voxels outside it read as the label `fill`) and compared there."""
-        import time
         from .label_overlap import resident_overlap
-        t0 = time.perf_counter()
-        ov = resident_overlap(self, other, matrix, fill)
-        self.ms["overlap"] = (time.perf_counter() - t0) * 1e3
-        return ov
+        return self._timed("overlap", resident_overlap, self, other, matrix, fill)
 
     def junctions(self, voxelsize=(1.0, 1.0, 1.0)):
         """The cell junctions of the resident volume: a `CellJunctions` with the edge table (three labels in a 2 x 2 x 2 block) and
         the vertex table (four), in the ids of the image and with positions in array axes.  Two walks over the volume on the
         GPU, a sort and a segmented reduce; no sweep is needed."""
-        import time
         from .cell_junctions import context_junctions
-        t0 = time.perf_counter()
-        j = context_junctions(self.ctx, voxelsize)
-        self.ms["junctions"] = (time.perf_counter() - t0) * 1e3
-        return j
+        return self._timed("junctions", context_junctions, self.ctx, voxelsize)
 
     def components(self, voxelsize=(1.0, 1.0, 1.0)):
         """The connected components of the labels of the resident volume: a `LabelComponents` with one row per face-connected
         blob of equal label, in the ids of the image and with coordinates in array axes.  A block-based union-find on the GPU;
         no sweep is needed."""
-        import time
         from .components import context_components
-        t0 = time.perf_counter()
-        cc = context_components(self.ctx, voxelsize)
-        self.ms["components"] = (time.perf_counter() - t0) * 1e3
-        return cc
+        return self._timed("components", context_components, self.ctx, voxelsize)
 
     def components_image(self, first_plane=0, nplanes=None):
         """uint32 image of the row of `components()` every voxel belongs to, with the axes and the layout of the image; of
         `nplanes` planes from `first_plane` along the slowest memory axis only when those are given."""
-        flat = self.ctx.components_image(first_plane, nplanes)
-        shape = list(self.host.shape)
-        strides = [s // self.host.dtype.itemsize * 4 for s in self.host.strides]
-        if flat.size != self.host.size:
-            slow = max((d for d in range(3) if shape[d] != 1), key=lambda d: strides[d])
-            shape[slow] = flat.size // (self.host.size // shape[slow])
-        return np.lib.stride_tricks.as_strided(flat, shape=shape, strides=strides)
+        return self._with_host_axes(self.ctx.components_image(first_plane, nplanes))
 
     def relabel_components(self, new_label, features=_capi.F_ALL):
         """Every voxel of row r of `components()` becomes new_label[r], on the resident volume AND on `self.host` (copied back),
@@ -652,34 +641,20 @@ class ResidentVolume(object):
         if new_label.size and (int(new_label.min()) < 0 or int(new_label.max()) > np.iinfo(self.host.dtype).max):
             raise ValueError("a new label does not fit the image dtype %s" % self.host.dtype)
         self.ctx.components_relabel(new_label)
-        if not self.host.flags.writeable:
-            self.host = self.host.copy()
-            self.is_input = False
-        self.ctx.get_volume(self.host)
-        return self.extract(features)
+        return self._sweep_edited(features)
 
     def distance_map(self, mode=0, site_label=None, voxelsize=(1.0, 1.0, 1.0), edge=False):
         """The exact Euclidean distance of every voxel of the resident volume to the nearest voxel of another label (mode 0) or of
         `site_label` (mode 1), with `edge` also to the image margin: a `DistanceMap` (per label the smallest and the largest squared
         distance and the voxel of the largest) whose rows are those of the current extraction (swept first when there is none), in
         the ids of the image.  Three passes over the volume on the GPU; `.image()` of the result downloads the distances."""
-        import time
         from .distance_map import resident_distance_map
-        t0 = time.perf_counter()
-        dm = resident_distance_map(self, mode, site_label, voxelsize, edge)
-        self.ms["distance_map"] = (time.perf_counter() - t0) * 1e3
-        return dm
+        return self._timed("distance_map", resident_distance_map, self, mode, site_label, voxelsize, edge)
 
     def distance_image(self, first_plane=0, nplanes=None):
         """float64 image of the SQUARED distances of the last `distance_map()`, with the axes and the layout of the image; of
         `nplanes` planes from `first_plane` along the slowest memory axis only when those are given."""
-        flat = self.ctx.distance_image(first_plane, nplanes)
-        shape = list(self.host.shape)
-        strides = [s // self.host.dtype.itemsize * 8 for s in self.host.strides]
-        if flat.size != self.host.size:
-            slow = max((d for d in range(3) if shape[d] != 1), key=lambda d: strides[d])
-            shape[slow] = flat.size // (self.host.size // shape[slow])
-        return np.lib.stride_tricks.as_strided(flat, shape=shape, strides=strides)
+        return self._with_host_axes(self.ctx.distance_image(first_plane, nplanes))
 
     def nearest_labels(self, empty=0, not_from=None, voxelsize=(1.0, 1.0, 1.0), max_distance=None):
         """For every voxel of the resident volume the nearest voxel that is neither `empty` nor `not_from` (None: nothing excluded),
@@ -687,46 +662,26 @@ class ResidentVolume(object):
         `max_distance`, None = no limit) whose rows are those of the current extraction (swept first when there is none), in the ids
         of the image.  Three passes over the volume on the GPU; `.nearest()`, `.distance()` and `.image()` of the result download the
         images, `.apply()` is `apply_nearest()`."""
-        import time
         from .nearest_labels import resident_nearest_labels
-        t0 = time.perf_counter()
-        nl = resident_nearest_labels(self, empty, not_from, voxelsize, max_distance)
-        self.ms["nearest_labels"] = (time.perf_counter() - t0) * 1e3
-        return nl
+        return self._timed("nearest_labels", resident_nearest_labels, self, empty, not_from, voxelsize, max_distance)
 
     def nearest_images(self, first_plane=0, nplanes=None):
         """(uint32 image of the nearest labels, float64 image of the SQUARED distances) of the last `nearest_labels()`, with the axes
         and the layout of the image; of `nplanes` planes from `first_plane` along the slowest memory axis only when those are given."""
-        out = []
-        for flat in self.ctx.nearest_image(first_plane, nplanes):
-            shape = list(self.host.shape)
-            strides = [s // self.host.dtype.itemsize * flat.dtype.itemsize for s in self.host.strides]
-            if flat.size != self.host.size:
-                slow = max((d for d in range(3) if shape[d] != 1), key=lambda d: strides[d])
-                shape[slow] = flat.size // (self.host.size // shape[slow])
-            out.append(np.lib.stride_tricks.as_strided(flat, shape=shape, strides=strides))
-        return tuple(out)
+        return tuple(self._with_host_axes(flat) for flat in self.ctx.nearest_image(first_plane, nplanes))
 
     def apply_nearest(self, features=_capi.F_ALL):
         """Every voxel the last `nearest_labels()` fills takes its nearest label, on the resident volume AND on `self.host` (copied
         back), then sweep the new volume."""
         self.ctx.nearest_apply()
-        if not self.host.flags.writeable:
-            self.host = self.host.copy(order="K")
-            self.is_input = False
-        self.ctx.get_volume(self.host)
-        return self.extract(features)
+        return self._sweep_edited(features)
 
     def wall_geometry(self, voxelsize=(1.0, 1.0, 1.0)):
         """The geometry of every wall of the resident volume: a `WallGeometry` (signed face counts, first and second sums of the
         face centres) whose rows are the pairs of the current extraction (swept first when there is none), in the ids of the
         image.  One pass over the labels on the GPU."""
-        import time
         from .wall_geometry import resident_wall_geometry
-        t0 = time.perf_counter()
-        g = resident_wall_geometry(self, voxelsize)
-        self.ms["wall_geometry"] = (time.perf_counter() - t0) * 1e3
-        return g
+        return self._timed("wall_geometry", resident_wall_geometry, self, voxelsize)
 
     def wall_table(self):
         if self.host.flags.c_contiguous:       # memory order IS np.where order: the device groups the records by pair
@@ -751,11 +706,7 @@ class ResidentVolume(object):
     def relabel(self, lut, features=_capi.F_ALL):
         """v -> lut[v] on the resident volume AND on `self.host` (copied back), then sweep the new volume."""
         self.ctx.relabel(lut)
-        if not self.host.flags.writeable:
-            self.host = self.host.copy()
-            self.is_input = False
-        self.ctx.get_volume(self.host)
-        return self.extract(features)
+        return self._sweep_edited(features)
 
     def map(self, lut, fill):
         return self.ctx.map_labels(lut, fill, self.host)

@@ -10,6 +10,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import _capi
+from ._tables import voxelsize3
 
 NONE = _capi.NEAREST_NONE
 
@@ -35,11 +36,7 @@ class NearestLabels(object):
             raise ValueError("gained has one entry per row")
         if self.labels.size > 1 and not (np.diff(self.labels) > 0).all():
             raise ValueError("the labels of a nearest-label table ascend")
-        vs = tuple(float(v) for v in voxelsize)
-        if len(vs) == 2:
-            vs = vs + (1.0,)
-        if len(vs) != 3:
-            raise ValueError("voxelsize must have two or three entries")
+        vs = voxelsize3(voxelsize)
         self.filled, self.remaining = int(filled), int(remaining)
         if int(self.gained_voxels.sum()) != self.filled:
             raise ValueError("the gained voxels of the labels sum to the filled voxels")
@@ -113,23 +110,12 @@ def resident_nearest_labels(resident, empty=0, not_from=None, voxelsize=(1.0, 1.
     """The nearest-label pass over the volume resident in `resident` (a ResidentVolume), with the rows of its current extraction --
     swept first when the context holds none."""
     ctx = resident.ctx
-    vs = tuple(float(v) for v in voxelsize)
-    if len(vs) == 2:
-        vs = vs + (1.0,)
+    vs = voxelsize3(voxelsize)
     for name, v in (("empty", empty), ("not_from", not_from)):
         if v is not None and not 0 <= int(v) <= 0xFFFFFFFF:
             raise ValueError("%s must fit in uint32" % name)
     args = (int(empty), None if not_from is None else int(not_from), vs, max_d2_of(max_distance))
-    x = resident.last
-    try:
-        if x is None:
-            raise _capi.TissueScanError(_capi.TA_EINVAL, "no extraction")
-        ctx.nearest_extract(*args)
-    except _capi.TissueScanError as e:
-        if e.code != _capi.TA_EINVAL:
-            raise
-        x = resident.extract(_capi.F_ALL, sparse=None if x is None else x.sparse)
-        ctx.nearest_extract(*args)
+    x, _ = resident.over_extraction(lambda x: ctx.nearest_extract(*args))
     gained, filled, remaining = ctx.nearest_get()
     labels = x.ids if x.sparse else np.arange(x.nrows, dtype=np.int64)
 

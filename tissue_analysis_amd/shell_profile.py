@@ -9,6 +9,8 @@ from __future__ import annotations
 
 import numpy as np
 
+from ._tables import voxelsize3
+
 
 class ShellProfile(object):
     """The profile table of one label image over K shells of distance.
@@ -61,12 +63,7 @@ class ShellProfile(object):
             for name in ("sum", "min", "max"):
                 if getattr(self, name).shape != (R, K):
                     raise ValueError("%s must have shape (labels, shells)" % name)
-        vs = tuple(float(v) for v in voxelsize)
-        if len(vs) == 2:
-            vs = vs + (1.0,)
-        if len(vs) != 3:
-            raise ValueError("voxelsize must have two or three entries")
-        self.voxelsize = vs
+        self.voxelsize = voxelsize3(voxelsize)
         self.present = (self.n.sum(axis=1) > 0) if present is None else np.asarray(present, dtype=bool).reshape(-1)
         if self.present.shape != (R,):
             raise ValueError("present has one entry per label")

@@ -6,7 +6,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from . import _capi
+from ._tables import _ByLabel, to_array_axes, voxelsize3
 
 PAIR_ORDER = ((0, 0), (0, 1), (0, 2), (1, 1), (1, 2), (2, 2))
 COLUMNS = ("centroid", "polarity", "polarity_index", "covariance")
@@ -20,7 +20,7 @@ def _words(value):
     return value & _MASK, value >> 64
 
 
-class SignalMoments(object):
+class SignalMoments(_ByLabel):
     """Signal-weighted moments whose rows line up with an `Extraction`: rows 0..max_label, or one per id of `.ids` when the ids
     are sparse.  Integer columns as the pass gives them, in MEMORY-axis order k = 0, 1, 2 (`perm[k]` is the array axis of k):
 
@@ -51,12 +51,7 @@ class SignalMoments(object):
         self.perm = tuple(int(p) for p in perm)
         if sorted(self.perm) != [0, 1, 2]:
             raise ValueError("perm must be a permutation of (0, 1, 2), not %r" % (perm,))
-        vs = tuple(float(v) for v in voxelsize)
-        if len(vs) == 2:
-            vs = vs + (1.0,)
-        if len(vs) != 3:
-            raise ValueError("voxelsize must have two or three entries")
-        self.voxelsize = vs
+        self.voxelsize = voxelsize3(voxelsize)
         self.origin0 = int(origin0)
         self.ms = ms
 
@@ -116,13 +111,6 @@ class SignalMoments(object):
         return SignalMoments(extraction, n, w, m1, m2, parts[0].perm, parts[0].voxelsize, 0)
 
     # ------------------------------------------------------------------ floats, array axes
-    def _to_array_axes(self, mem):
-        """Columns of a [R, 3] array from memory-axis to array-axis order."""
-        out = np.empty_like(mem)
-        for k in range(3):
-            out[:, self.perm[k]] = mem[:, k]
-        return out
-
     def _scale(self):
         return np.asarray(self.voxelsize, dtype=np.float64)
 
@@ -133,7 +121,7 @@ class SignalMoments(object):
         with np.errstate(invalid="ignore", divide="ignore"):
             c = self.m1.astype(np.float64) / wf[:, None]
         c[:, 0] += float(self.origin0)
-        c = np.where(wf[:, None] > 0, self._to_array_axes(c), np.nan)
+        c = np.where(wf[:, None] > 0, to_array_axes(c, self.perm), np.nan)
         return c * self._scale() if real else c
 
     def _geometry(self):
@@ -218,12 +206,6 @@ class SignalMoments(object):
         return vecs, vals
 
     # ------------------------------------------------------------------ lookups by label id
-    def rows_of(self, labels, missing=None):
-        if self.extraction is None:
-            idx = np.asarray(labels, dtype=np.int64)
-            return idx if missing is None else np.where((idx >= 0) & (idx < len(self)), idx, missing)
-        return self.extraction.rows_of(labels, missing)
-
     def of_labels(self, labels, column="centroid", real=True):
         """`column` ('centroid', 'polarity', 'polarity_index' or 'covariance') of every label id in `labels`, NaN for ids without
         a row."""
@@ -235,11 +217,7 @@ class SignalMoments(object):
             col = self.polarity(real)
         else:
             col = getattr(self, column)(real)
-        rows = self.rows_of(np.asarray(labels, dtype=np.int64).reshape(-1), missing=-1)
-        known = rows >= 0
-        out = col[np.where(known, rows, 0)].copy()
-        out[~known] = np.nan
-        return out
+        return self._pick(col, labels, np.nan)
 
 
 def resident_signal_moments(resident, signal, voxelsize=(1.0, 1.0, 1.0)):
@@ -247,15 +225,6 @@ def resident_signal_moments(resident, signal, voxelsize=(1.0, 1.0, 1.0)):
     -- swept first when the context holds none that fits."""
     ctx = resident.ctx
     ctx.set_signal(signal)
-    x = resident.last
-    try:
-        if x is None:
-            raise _capi.TissueScanError(_capi.TA_EINVAL, "no extraction")
-        ctx.sigmom_extract()
-    except _capi.TissueScanError as e:
-        if e.code != _capi.TA_EINVAL:
-            raise
-        x = resident.extract(_capi.F_ALL, sparse=None if x is None else x.sparse)
-        ctx.sigmom_extract()
+    x, _ = resident.over_extraction(lambda x: ctx.sigmom_extract())
     n, w, m1, m2 = ctx.sigmom_rows()
     return SignalMoments(x, n, w, m1, m2, ctx.memory_axes(), voxelsize, ms=ctx.sigmom_timing())

@@ -6,6 +6,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import _capi
+from ._tables import _ByLabel
 
 METHODS = ("linear", "lower", "higher", "midpoint")
 NO_RANK = np.uint64(0xFFFFFFFFFFFFFFFF)
@@ -45,20 +46,6 @@ def interpolate(s_lo, s_hi, h, method="linear"):
     else:
         out = a + (b - a) * (h - np.floor(h))
     return np.where(none, np.nan, out)
-
-
-class _ByLabel(object):
-    """Rows that line up with an `Extraction`: rows 0..max_label, or one per id of `.ids` when the ids are sparse."""
-
-    def rows_of(self, labels, missing=None):
-        return self.extraction.rows_of(labels, missing)
-
-    def _pick(self, table, labels, fill):
-        rows = self.rows_of(np.asarray(labels, dtype=np.int64).reshape(-1), missing=-1)
-        known = rows >= 0
-        out = table[np.where(known, rows, 0)].copy()
-        out[~known] = fill
-        return out
 
 
 class SignalHistogram(_ByLabel):
@@ -127,23 +114,6 @@ class SignalQuantiles(_ByLabel):
         return self._pick(table, labels, np.nan)
 
 
-def _with_extraction(resident, signal, enqueue):
-    """Set the signal and run enqueue() over the current extraction of `resident` -- swept first when the context holds none."""
-    ctx = resident.ctx
-    ctx.set_signal(signal)
-    x = resident.last
-    try:
-        if x is None:
-            raise _capi.TissueScanError(_capi.TA_EINVAL, "no extraction")
-        enqueue(x)
-    except _capi.TissueScanError as e:
-        if e.code != _capi.TA_EINVAL:
-            raise
-        x = resident.extract(_capi.F_ALL, sparse=None if x is None else x.sparse)
-        enqueue(x)
-    return x
-
-
 def _bits(signal):
     if hasattr(signal, "adopt_as_signal"):           # an image on another grid with its index matrix (resample.OnGrid)
         return signal, 8 * signal.dtype.itemsize
@@ -162,7 +132,8 @@ def resident_signal_histogram(resident, signal, bin_width=None):
     if width < 1 or width != 1 << log2 or not bits - 8 <= log2 <= bits:
         raise ValueError("bin_width must be a power of two from %d to %d for a %d-bit signal, not %r" % (1 << (bits - 8), 1 << bits, bits, bin_width))
     ctx = resident.ctx
-    x = _with_extraction(resident, a, lambda x: ctx.sighist_extract(log2))
+    ctx.set_signal(a)
+    x, _ = resident.over_extraction(lambda x: ctx.sighist_extract(log2))
     counts = ctx.sighist_get()
     return SignalHistogram(x, counts, width, ms=ctx.sighist_timing()[0])
 
@@ -183,7 +154,8 @@ def resident_signal_quantiles(resident, signal, q, method="linear"):
         lo, hi, _ = quantile_ranks(x.count, q)
         return np.concatenate([lo, hi], axis=1)                    # [R, 2 Q]
 
-    x = _with_extraction(resident, a, lambda x: ctx.sigrank_extract(ranks_of(x)[:, :step]) if q.size else None)
+    ctx.set_signal(a)
+    x, _ = resident.over_extraction(lambda x: ctx.sigrank_extract(ranks_of(x)[:, :step]) if q.size else None)
     n = np.asarray(x.count, dtype=np.uint64)
     ranks = ranks_of(x)
     values = np.zeros(ranks.shape, dtype=np.uint32)

@@ -6,12 +6,13 @@ from __future__ import annotations
 import numpy as np
 
 from . import _capi
+from ._tables import _ByLabel
 
 STATISTICS = ("mean", "std", "min", "max", "sum")
 WALL_STATISTICS = ("mean", "sides")
 
 
-class SignalStats(object):
+class SignalStats(_ByLabel):
     """Signal statistics whose rows line up with an `Extraction`: per label, rows 0..max_label (or one per id of `.ids` when
     the ids are sparse); per wall, the pairs `.lo` < `.hi` of its pair list.
 
@@ -88,18 +89,11 @@ class SignalStats(object):
             return self.side_lo.astype(np.float64) / f, self.side_hi.astype(np.float64) / f
 
     # ------------------------------------------------------------------ lookups by label id
-    def rows_of(self, labels, missing=None):
-        return self.extraction.rows_of(labels, missing)
-
     def of_labels(self, labels, statistic="mean"):
         """`statistic` ('mean', 'std', 'min', 'max' or 'sum') of every label id in `labels` (NaN / 0 for ids without voxels)."""
         if statistic not in STATISTICS:
             raise ValueError("statistic must be one of %s, not %r" % ("|".join(STATISTICS), statistic))
-        col = getattr(self, statistic)
-        rows = self.rows_of(np.asarray(labels, dtype=np.int64).reshape(-1), missing=-1)
-        known = rows >= 0
-        out = np.where(known, col[np.where(known, rows, 0)], 0 if statistic == "sum" else np.nan)
-        return out.astype(col.dtype)
+        return self._pick(getattr(self, statistic), labels, 0 if statistic == "sum" else np.nan)
 
     def wall_rows(self, lo, hi):
         """Row of every pair (lo < hi) in the pair list, -1 for a pair it does not hold."""
@@ -117,16 +111,7 @@ def resident_signal(resident, signal, walls=True):
     ctx = resident.ctx
     ctx.set_signal(signal)
     what = _capi.SIG_LABELS | (_capi.SIG_WALLS if walls else 0)
-    x = resident.last
-    try:
-        if x is None:
-            raise _capi.TissueScanError(_capi.TA_EINVAL, "no extraction")
-        ctx.signal_extract(what)
-    except _capi.TissueScanError as e:
-        if e.code != _capi.TA_EINVAL:
-            raise
-        x = resident.extract(_capi.F_ALL, sparse=None if x is None else x.sparse)
-        ctx.signal_extract(what)
+    x, _ = resident.over_extraction(lambda x: ctx.signal_extract(what))
     n, s, q, mn, mx = ctx.signal_labels()
     side_lo = side_hi = None
     if walls:

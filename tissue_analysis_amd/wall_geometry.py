@@ -11,7 +11,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from . import _capi
+from ._tables import voxelsize3
 
 PAIR_ORDER = ((0, 0), (0, 1), (0, 2), (1, 1), (1, 2), (2, 2))
 
@@ -48,12 +48,7 @@ class WallGeometry(object):
         for name in ("fwd", "rev", "sum1", "sum2"):
             if getattr(self, name).shape[0] != P:
                 raise ValueError("%s must have one row per pair" % name)
-        vs = tuple(float(v) for v in voxelsize)
-        if len(vs) == 2:
-            vs = vs + (1.0,)
-        if len(vs) != 3:
-            raise ValueError("voxelsize must have two or three entries")
-        self.voxelsize = vs
+        self.voxelsize = voxelsize3(voxelsize)
         self.ms = ms
 
     def __len__(self):
@@ -195,16 +190,7 @@ def resident_wall_geometry(resident, voxelsize=(1.0, 1.0, 1.0)):
     """The wall-geometry pass over the volume resident in `resident` (a ResidentVolume), with the pairs of its current
     extraction -- swept first when the context holds none that fits (the pass needs the pair list)."""
     ctx = resident.ctx
-    x = resident.last
-    try:
-        if x is None:
-            raise _capi.TissueScanError(_capi.TA_EINVAL, "no extraction")
-        ctx.wallgeo_extract()
-    except _capi.TissueScanError as e:
-        if e.code != _capi.TA_EINVAL:
-            raise
-        x = resident.extract(_capi.F_ALL, sparse=None if x is None else x.sparse)
-        ctx.wallgeo_extract()
+    x, _ = resident.over_extraction(lambda x: ctx.wallgeo_extract())
     fwd, rev, sum1, sum2 = ctx.wallgeo_get()
     return WallGeometry(x.lo, x.hi, fwd, rev, sum1, sum2, voxelsize, ms=ctx.wallgeo_timing())
 
