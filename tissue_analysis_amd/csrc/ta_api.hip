@@ -346,6 +346,21 @@ void volume_replaced(ta_ctx* c) {
     resample_on_new_volume(c);       // (reads the grid only: new label values leave it alone)
 }
 
+// A result of `bytes` that lives on the device only while it is read back: `enqueue(dev)` launches what writes it and answers
+// with hipGetLastError (or an upload's error before it); then the copy to `host_dst` and one drain.  The scratch is released on
+// every path; `what` names the result in the TA_EHIP message.
+template <class Enqueue> static int run_and_read_back(ta_ctx* c, const char* what, uint64_t bytes, void* host_dst, Enqueue enqueue) {
+    DevBuf out;
+    const int rc = out.reserve(bytes);
+    if (rc != TA_OK) return rc;
+    hipError_t e = enqueue(out.p);
+    if (e == hipSuccess) e = hipMemcpyAsync(host_dst, out.p, bytes, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    out.release();
+    if (e != hipSuccess) return fail(TA_EHIP, "%s: %s", what, hipGetErrorString(e));
+    return TA_OK;
+}
+
 extern "C" {
 
 TA_API int ta_version(void) { return TA_ABI_VERSION; }
@@ -624,20 +639,16 @@ TA_API int ta_volume_map(ta_ctx* c, const void* lut, uint32_t lut_len, const voi
     const uint64_t n = (uint64_t)c->mdims[0] * c->mdims[1] * c->mdims[2];
     uint64_t fillw = 0;
     memcpy(&fillw, fill, (size_t)out_itemsize);
-    DevBuf dl, dout;
+    DevBuf dl;
     if ((rc = dl.reserve((uint64_t)lut_len * out_itemsize + 8)) != TA_OK) return rc;
-    if ((rc = dout.reserve(n * out_itemsize)) != TA_OK) { dl.release(); return rc; }
-    hipError_t e = hipSuccess;
-    if (lut_len) e = hipMemcpyAsync(dl.p, lut, (uint64_t)lut_len * out_itemsize, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) {
-        ta::launch_map(c->stream, sweep_vol(c), c->itemsize, dout.p, out_itemsize, n, dl.p, lut_len, fillw);     // (compacted: lut[rank])
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(host_dst, dout.p, n * out_itemsize, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    dl.release(); dout.release();
-    if (e != hipSuccess) return fail(TA_EHIP, "map: %s", hipGetErrorString(e));
-    return TA_OK;
+    rc = run_and_read_back(c, "map", n * out_itemsize, host_dst, [&](void* dout) {
+        if (lut_len)
+            if (const hipError_t e = hipMemcpyAsync(dl.p, lut, (uint64_t)lut_len * out_itemsize, hipMemcpyHostToDevice, c->stream); e != hipSuccess) return e;
+        ta::launch_map(c->stream, sweep_vol(c), c->itemsize, dout, out_itemsize, n, dl.p, lut_len, fillw);     // (compacted: lut[rank])
+        return hipGetLastError();
+    });
+    dl.release();
+    return rc;
 }
 
 TA_API int ta_volume_first_layer(ta_ctx* c, uint32_t background, int keep_background, void* host_dst) {
@@ -647,16 +658,10 @@ TA_API int ta_volume_first_layer(ta_ctx* c, uint32_t background, int keep_backgr
     int rc = use_device(c);
     if (rc != TA_OK) return rc;
     const uint64_t bytes = (uint64_t)c->mdims[0] * c->mdims[1] * c->mdims[2] * c->itemsize;
-    DevBuf dout;
-    if ((rc = dout.reserve(bytes)) != TA_OK) return rc;
-    ta::launch_first_layer(c->stream, c->vol, c->itemsize, dout.p, c->mdims[0], c->mdims[1], c->mdims[2], background,
-                           keep_background ? 1 : 0);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(host_dst, dout.p, bytes, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    dout.release();
-    if (e != hipSuccess) return fail(TA_EHIP, "first voxel layer: %s", hipGetErrorString(e));
-    return TA_OK;
+    return run_and_read_back(c, "first voxel layer", bytes, host_dst, [&](void* dout) {
+        ta::launch_first_layer(c->stream, c->vol, c->itemsize, dout, c->mdims[0], c->mdims[1], c->mdims[2], background, keep_background ? 1 : 0);
+        return hipGetLastError();
+    });
 }
 
 TA_API int ta_volume_hollow(ta_ctx* c, uint32_t background, int remove_background, int label_bits, void* host_dst) {
@@ -668,15 +673,10 @@ TA_API int ta_volume_hollow(ta_ctx* c, uint32_t background, int remove_backgroun
     int rc = use_device(c);
     if (rc != TA_OK) return rc;
     const uint64_t bytes = (uint64_t)c->mdims[0] * c->mdims[1] * c->mdims[2] * c->itemsize;
-    DevBuf dout;
-    if ((rc = dout.reserve(bytes)) != TA_OK) return rc;
-    ta::launch_hollow(c->stream, c->vol, c->itemsize, dout.p, c->mdims[0], c->mdims[1], c->mdims[2], background, remove_background ? 1 : 0, label_bits);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(host_dst, dout.p, bytes, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    dout.release();
-    if (e != hipSuccess) return fail(TA_EHIP, "hollowed-out cells: %s", hipGetErrorString(e));
-    return TA_OK;
+    return run_and_read_back(c, "hollowed-out cells", bytes, host_dst, [&](void* dout) {
+        ta::launch_hollow(c->stream, c->vol, c->itemsize, dout, c->mdims[0], c->mdims[1], c->mdims[2], background, remove_background ? 1 : 0, label_bits);
+        return hipGetLastError();
+    });
 }
 
 TA_API int ta_volume_layer18(ta_ctx* c, uint8_t* host_dst) {
@@ -686,15 +686,10 @@ TA_API int ta_volume_layer18(ta_ctx* c, uint8_t* host_dst) {
     int rc = use_device(c);
     if (rc != TA_OK) return rc;
     const uint64_t bytes = (uint64_t)c->mdims[0] * c->mdims[1] * c->mdims[2];
-    DevBuf dout;
-    if ((rc = dout.reserve(bytes)) != TA_OK) return rc;
-    ta::launch_layer18(c->stream, c->vol, c->itemsize, (uint8_t*)dout.p, c->mdims[0], c->mdims[1], c->mdims[2]);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(host_dst, dout.p, bytes, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    dout.release();
-    if (e != hipSuccess) return fail(TA_EHIP, "voxel layers: %s", hipGetErrorString(e));
-    return TA_OK;
+    return run_and_read_back(c, "voxel layers", bytes, host_dst, [&](void* dout) {
+        ta::launch_layer18(c->stream, c->vol, c->itemsize, (uint8_t*)dout, c->mdims[0], c->mdims[1], c->mdims[2]);
+        return hipGetLastError();
+    });
 }
 
 TA_API int ta_volume_owned_planes(ta_ctx* c, int64_t* planes) {
@@ -710,16 +705,11 @@ TA_API int ta_volume_plane_events(ta_ctx* c, uint64_t* events) {
     if (rc != TA_OK) return rc;
     const int64_t owned = c->mdims[0] - c->first_owned;
     if (owned <= 0) return TA_OK;
-    DevBuf d;
-    if ((rc = d.reserve((uint64_t)owned * sizeof(uint64_t))) != TA_OK) return rc;
     const char* first = (const char*)c->vol + (size_t)c->first_owned * c->mdims[1] * c->mdims[2] * c->itemsize;
-    ta::launch_plane_events(c->stream, first, c->itemsize, owned, c->mdims[1], c->mdims[2], (uint64_t*)d.p);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(events, d.p, (size_t)owned * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    d.release();
-    if (e != hipSuccess) return fail(TA_EHIP, "plane events: %s", hipGetErrorString(e));
-    return TA_OK;
+    return run_and_read_back(c, "plane events", (uint64_t)owned * sizeof(uint64_t), events, [&](void* d) {
+        ta::launch_plane_events(c->stream, first, c->itemsize, owned, c->mdims[1], c->mdims[2], (uint64_t*)d);
+        return hipGetLastError();
+    });
 }
 
 TA_API int ta_bind_accumulators(ta_ctx* c, void* sums_dev, void* boxes_dev, uint32_t max_label) {
@@ -790,9 +780,8 @@ TA_API int ta_get_labels(ta_ctx* c, uint64_t* count, int32_t* bbox, uint64_t* su
     if (!hs.empty()) TA_HIP(hipMemcpyAsync(hs.data(), c->sums, hs.size() * 8, hipMemcpyDeviceToHost, c->stream));
     if (!hb.empty()) TA_HIP(hipMemcpyAsync(hb.data(), c->boxes, hb.size() * 4, hipMemcpyDeviceToHost, c->stream));
     TA_HIP(hipStreamSynchronize(c->stream));
-    // second-moment slot of an (array axis, array axis) pair
-    auto pair_slot = [](int x, int y) { if (x > y) std::swap(x, y); return x == 0 ? y : (x == 1 ? 2 + y : 5); };
-    static const int mem_pair[6][2] = {{0, 0}, {0, 1}, {0, 2}, {1, 1}, {1, 2}, {2, 2}};
+    int slot[6];
+    moment_slots(c, slot);
     const bool mom2 = c->feature_mask & TA_F_MOMENT2;
     if (c->perm[0] == 0 && c->perm[1] == 1 && c->perm[2] == 2) {
         // C-ordered input (array axes = memory axes): no permutation, one tight loop per output
@@ -813,8 +802,7 @@ TA_API int ta_get_labels(ta_ctx* c, uint64_t* count, int32_t* bbox, uint64_t* su
         if (sum1) for (int k = 0; k < 3; ++k) sum1[l * 3 + c->perm[k]] = hs[l * ta::NSUM + 1 + k];
         // (without TA_F_MOMENT2 the device columns are not defined -- the rare table-spill path writes cross terms there --
         //  and the getter answers zero)
-        if (sum2) for (int q = 0; q < 6; ++q)
-            sum2[l * 6 + pair_slot(c->perm[mem_pair[q][0]], c->perm[mem_pair[q][1]])] = mom2 ? hs[l * ta::NSUM + 4 + q] : 0ull;
+        if (sum2) for (int q = 0; q < 6; ++q) sum2[l * 6 + slot[q]] = mom2 ? hs[l * ta::NSUM + 4 + q] : 0ull;
         if (bbox) {
             const bool present = hb[l * 6] != INT32_MAX;
             for (int k = 0; k < 3; ++k) {

@@ -11,11 +11,11 @@ const char* const NO_TABLES = "no component tables for the current volume (run t
 struct ComponentWork {
     uint64_t counts, offsets, scratch, bytes;
     explicit ComponentWork(uint64_t W) {
-        uint64_t at = 0;
-        counts = at; at += align16(W * 4);
-        offsets = at; at += align16(W * 8);
-        scratch = at; at += align16(ta::scan_u32_scratch_bytes(W));
-        bytes = at + 16;
+        PartCursor at;
+        counts = at.take(W * 4, 16).at;
+        offsets = at.take(W * 8, 16).at;
+        scratch = at.take(ta::scan_u32_scratch_bytes(W), 16).at;
+        bytes = at.end(16) + 16;
     }
 };
 
@@ -23,14 +23,14 @@ struct ComponentWork {
 struct ComponentSlots {
     uint64_t root, row, zero, n, sum1, fill, first, box, bytes;
     explicit ComponentSlots(uint64_t S) {
-        uint64_t at = 0;
-        root = at; at += align16(S * 4);
-        row = at; at += align16(S * 4);
-        zero = n = at; at += align16(S * 8);
-        sum1 = at; at += align16(S * 24);
-        fill = first = at; at += align16(S * 8);
-        box = at; at += align16(S * 24);
-        bytes = at + 16;
+        PartCursor at;
+        root = at.take(S * 4, 16).at;
+        row = at.take(S * 4, 16).at;
+        zero = n = at.take(S * 8, 16).at;
+        sum1 = at.take(S * 24, 16).at;
+        fill = first = at.take(S * 8, 16).at;
+        box = at.take(S * 24, 16).at;
+        bytes = at.end(16) + 16;
     }
     ta::ComponentStats stats(char* p) const {
         ta::ComponentStats t;
@@ -40,19 +40,19 @@ struct ComponentSlots {
     }
 };
 
-// where the columns of ComponentState::rows lie, for S rows of room
+// the columns of ComponentState::rows, each from a multiple of 16 with S rows of room; the parts are the first R rows of each
 struct ComponentTable {
-    uint64_t label, n, first, bbox, sum1, bytes;
-    explicit ComponentTable(uint64_t S) {
-        uint64_t at = 0;
-        label = at; at += align16(S * 4);
-        n = at; at += align16(S * 8);
-        first = at; at += align16(S * 12);
-        bbox = at; at += align16(S * 24);
-        sum1 = at; at += align16(S * 24);
-        bytes = at + 16;
+    Part label, n, first, bbox, sum1;
+    uint64_t bytes = 0;
+    constexpr ComponentTable(uint64_t S, uint64_t R) {
+        PartCursor at;
+        const auto column = [&](uint64_t row_bytes) { return Part{at.take(S * row_bytes, 16).at, R * row_bytes}; };
+        label = column(4); n = column(8); first = column(12); bbox = column(24); sum1 = column(24);
+        bytes = at.end(16) + 16;
     }
 };
+static_assert(ComponentTable(3, 2).n.at == 16 && ComponentTable(3, 2).first.at == 48 && ComponentTable(3, 2).bbox.at == 96 && ComponentTable(3, 2).sum1.at == 176 &&
+              ComponentTable(3, 2).bytes == 272 && ComponentTable(3, 2).first.bytes == 24, "label u32 | n u64 | first i32[3] | bbox i32[6] | sum1 u64[3]");
 
 ta::ComponentArgs component_args(ta_ctx* c) {
     ta::ComponentArgs a = {};
@@ -76,7 +76,7 @@ int components_settle(ta_ctx* c) {
     TA_HIP(hipStreamSynchronize(c->stream));
     const ComponentSlots q(S);
     const SortLayout sl(S, 8);
-    const ComponentTable tb(S);
+    const ComponentTable tb(S, S);
     if ((rc = c->cc.slots.reserve(q.bytes)) != TA_OK) return rc;
     if ((rc = c->cc.sort.reserve(sl.end + 16)) != TA_OK) return rc;
     if ((rc = c->cc.rows.reserve(tb.bytes)) != TA_OK) return rc;
@@ -97,8 +97,7 @@ int components_settle(ta_ctx* c) {
     g.n1 = (uint32_t)c->mdims[1]; g.n2 = (uint32_t)c->mdims[2];
     ta::ComponentRows rows = {};
     for (int k = 0; k < 3; ++k) { rows.axis[k] = c->perm[k]; rows.dims[c->perm[k]] = c->mdims[k]; }
-    const uint64_t array_stride[3] = {(uint64_t)rows.dims[1] * (uint64_t)rows.dims[2], (uint64_t)rows.dims[2], 1ull};
-    for (int k = 0; k < 3; ++k) g.key_stride[k] = array_stride[c->perm[k]];
+    array_key_strides(c, g.key_stride);
     ta::launch_component_stats(c->stream, parent, g, stats);
     TA_HIP(hipGetLastError());
     TA_HIP(hipEventRecord(c->cc.ev[4], c->stream));
@@ -110,8 +109,8 @@ int components_settle(ta_ctx* c) {
     uint64_t* ks = k0; uint32_t* is = i0;
     TA_HIP(ta::launch_radix_sort_u64(c->stream, S, k0, k1, i0, i1, op + sl.temp, 64, &ks, &is));
     char* tp = (char*)c->cc.rows.p;
-    rows.label = (uint32_t*)(tp + tb.label); rows.n = (unsigned long long*)(tp + tb.n);
-    rows.first = (int32_t*)(tp + tb.first); rows.bbox = (int32_t*)(tp + tb.bbox); rows.sum1 = (unsigned long long*)(tp + tb.sum1);
+    rows.label = (uint32_t*)(tp + tb.label.at); rows.n = (unsigned long long*)(tp + tb.n.at);
+    rows.first = (int32_t*)(tp + tb.first.at); rows.bbox = (int32_t*)(tp + tb.bbox.at); rows.sum1 = (unsigned long long*)(tp + tb.sum1.at);
     rows.origin0 = c->a_origin - c->first_owned;
     ta::launch_component_rows(c->stream, c->vol, c->itemsize, root_of_slot, stats, is, S, nonempty, (uint32_t*)(sp + q.row), rows);
     TA_HIP(hipGetLastError());
@@ -127,11 +126,8 @@ int components_settle(ta_ctx* c) {
 
 // the checks every function behind the extract shares; settles
 int components_ready(ta_ctx* c) {
-    if (!c) return fail(TA_EINVAL, "ctx is NULL");
-    if (c->cc.state == 0) return fail(TA_EINVAL, NO_TABLES);
-    int rc = use_device(c);
-    if (rc != TA_OK) return rc;
-    return components_settle(c);
+    const int rc = results_ready(c, [](const ta_ctx* c) { return c->cc.state != 0; }, NO_TABLES);
+    return rc != TA_OK ? rc : components_settle(c);
 }
 
 }  // namespace
@@ -187,17 +183,9 @@ TA_API int ta_components_size(ta_ctx* c, uint64_t* nrows) {
 TA_API int ta_components_get(ta_ctx* c, uint32_t* label, uint64_t* n, int32_t* first, int32_t* bbox, uint64_t* sum1) {
     int rc = components_ready(c);
     if (rc != TA_OK) return rc;
-    const uint64_t R = c->cc.nrows;
-    if (!R) return TA_OK;
-    const ComponentTable tb(c->cc.nslots);
-    const char* tp = (const char*)c->cc.rows.p;
-    if (label) TA_HIP(hipMemcpyAsync(label, tp + tb.label, R * 4, hipMemcpyDeviceToHost, c->stream));
-    if (n) TA_HIP(hipMemcpyAsync(n, tp + tb.n, R * 8, hipMemcpyDeviceToHost, c->stream));
-    if (first) TA_HIP(hipMemcpyAsync(first, tp + tb.first, R * 12, hipMemcpyDeviceToHost, c->stream));
-    if (bbox) TA_HIP(hipMemcpyAsync(bbox, tp + tb.bbox, R * 24, hipMemcpyDeviceToHost, c->stream));
-    if (sum1) TA_HIP(hipMemcpyAsync(sum1, tp + tb.sum1, R * 24, hipMemcpyDeviceToHost, c->stream));
-    TA_HIP(hipStreamSynchronize(c->stream));
-    return TA_OK;
+    if (!c->cc.nrows) return TA_OK;
+    const ComponentTable tb(c->cc.nslots, c->cc.nrows);
+    return read_columns(c, c->cc.rows.p, {{label, tb.label}, {n, tb.n}, {first, tb.first}, {bbox, tb.bbox}, {sum1, tb.sum1}});
 }
 
 TA_API int ta_components_image(ta_ctx* c, int64_t first_plane, int64_t nplanes, uint32_t* rows) {

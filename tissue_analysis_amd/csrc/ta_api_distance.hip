@@ -9,13 +9,20 @@ namespace {
 
 const char* const NO_RESULTS = "no distance map for the current extraction (run ta_distance_extract)";
 
-// byte offsets of the parts of DistanceState::table for R rows
+// the parts of DistanceState::table for R rows
 struct DistanceLayout {
-    uint64_t min2 = 0, max2, pole, flags, bytes;
-    explicit DistanceLayout(uint64_t R) { max2 = 8 * R; pole = 16 * R; flags = 24 * R; bytes = flags + 4 * ta::DIST_NFLAGS; }
+    Part min2, max2, pole, flags;
+    uint64_t bytes = 0;
+    constexpr explicit DistanceLayout(uint64_t R) {
+        PartCursor at;
+        min2 = at.take(8 * R); max2 = at.take(8 * R); pole = at.take(8 * R); flags = at.take(4 * ta::DIST_NFLAGS);
+        bytes = at.end();
+    }
 };
+static_assert(DistanceLayout(3).max2.at == 24 && DistanceLayout(3).pole.at == 48 && DistanceLayout(3).flags.at == 72 && DistanceLayout(3).bytes == 88,
+              "min2 [R] | max2 [R] | pole [R] | flags u32[4]");
 
-int distance_ready(ta_ctx* c) { return c ? transform_ready(c, c->dist.seq, NO_RESULTS) : fail(TA_EINVAL, "ctx is NULL"); }
+bool distance_current(const ta_ctx* c) { return pass_current(c, c->dist.seq); }
 
 }  // namespace
 
@@ -67,13 +74,10 @@ TA_API int ta_distance_extract(ta_ctx* c, int mode, uint32_t site_label, const d
     TA_HIP(hipEventRecord(c->dist.ev[1], c->stream));
     char* tp = (char*)c->dist.table.p;
     ta::DistanceTable t = {};
-    t.min2 = (unsigned long long*)(tp + L.min2); t.max2 = (unsigned long long*)(tp + L.max2); t.pole = (unsigned long long*)(tp + L.pole);
-    t.flags = (uint32_t*)(tp + L.flags);
+    t.min2 = (unsigned long long*)(tp + L.min2.at); t.max2 = (unsigned long long*)(tp + L.max2.at); t.pole = (unsigned long long*)(tp + L.pole.at);
+    t.flags = (uint32_t*)(tp + L.flags.at);
     t.max_label = c->max_label;
-    int64_t dims[3];
-    for (int k = 0; k < 3; ++k) dims[c->perm[k]] = c->mdims[k];
-    const uint64_t array_stride[3] = {(uint64_t)dims[1] * (uint64_t)dims[2], (uint64_t)dims[2], 1ull};
-    for (int k = 0; k < 3; ++k) t.key_stride[k] = array_stride[c->perm[k]];
+    array_key_strides(c, t.key_stride);
     ta::launch_distance_table(c->stream, a, c->itemsize, t, launched);
     TA_HIP(hipGetLastError());
     TA_HIP(hipEventRecord(c->dist.ev[2], c->stream));
@@ -84,25 +88,21 @@ TA_API int ta_distance_extract(ta_ctx* c, int mode, uint32_t site_label, const d
 }
 
 TA_API int ta_distance_get(ta_ctx* c, double* min2, double* max2, int32_t* pole) {
-    int rc = distance_ready(c);
+    int rc = results_ready(c, distance_current, NO_RESULTS);
     if (rc != TA_OK) return rc;
     const uint64_t R = c->dist.rows;
     const DistanceLayout L(R);
-    const char* tp = (const char*)c->dist.table.p;
-    std::vector<uint64_t> key(R);
-    std::vector<double> lo(min2 ? 0 : R), hi(max2 ? 0 : R);
+    std::vector<uint64_t> key;
+    std::vector<double> lo, hi;
+    if ((rc = host_alloc([&] { key.resize(R); lo.resize(min2 ? 0 : R); hi.resize(max2 ? 0 : R); })) != TA_OK) return rc;
     if (!min2) min2 = lo.data();
     if (!max2) max2 = hi.data();
     uint32_t flags[ta::DIST_NFLAGS] = {0, 0, 0, 0};
-    TA_HIP(hipMemcpyAsync(flags, tp + L.flags, sizeof(flags), hipMemcpyDeviceToHost, c->stream));
-    TA_HIP(hipMemcpyAsync(min2, tp + L.min2, 8 * R, hipMemcpyDeviceToHost, c->stream));
-    TA_HIP(hipMemcpyAsync(max2, tp + L.max2, 8 * R, hipMemcpyDeviceToHost, c->stream));
-    TA_HIP(hipMemcpyAsync(key.data(), tp + L.pole, 8 * R, hipMemcpyDeviceToHost, c->stream));
-    TA_HIP(hipStreamSynchronize(c->stream));
+    if ((rc = read_columns(c, c->dist.table.p, {{flags, L.flags}, {min2, L.min2}, {max2, L.max2}, {key.data(), L.pole}})) != TA_OK) return rc;
     if (flags[ta::DIST_FLAG_RANGE])
         return fail(TA_ERANGE, "the distance pass met a label above max_label=%u (the volume changed since ta_extract)", c->max_label);
     int64_t dims[3];
-    for (int k = 0; k < 3; ++k) dims[c->perm[k]] = c->mdims[k];
+    array_dims(c, dims);
     const uint64_t d1 = (uint64_t)dims[1], d2 = (uint64_t)dims[2];
     for (uint64_t r = 0; r < R; ++r) {
         const bool absent = key[r] == ta::DIST_NO_POLE;
@@ -117,19 +117,16 @@ TA_API int ta_distance_get(ta_ctx* c, double* min2, double* max2, int32_t* pole)
 }
 
 TA_API int ta_distance_image(ta_ctx* c, int64_t first_plane, int64_t nplanes, double* d2) {
-    int rc = distance_ready(c);
+    int rc = results_ready(c, distance_current, NO_RESULTS);
     if (rc != TA_OK) return rc;
     if ((rc = check_planes(c, first_plane, nplanes)) != TA_OK || !nplanes) return rc;
     if (!d2) return fail(TA_EINVAL, "d2 is NULL");
     const uint64_t plane = (uint64_t)c->mdims[1] * (uint64_t)c->mdims[2];
-    TA_HIP(hipMemcpyAsync(d2, (const double*)c->dist.d2.p + (uint64_t)first_plane * plane, (uint64_t)nplanes * plane * 8, hipMemcpyDeviceToHost,
-                          c->stream));
-    TA_HIP(hipStreamSynchronize(c->stream));
-    return TA_OK;
+    return read_columns(c, c->dist.d2.p, {{d2, Part{(uint64_t)first_plane * plane * 8, (uint64_t)nplanes * plane * 8}}});
 }
 
 TA_API int ta_distance_debug(ta_ctx* c, uint32_t out[4]) {
-    int rc = distance_ready(c);
+    int rc = results_ready(c, distance_current, NO_RESULTS);
     if (rc != TA_OK) return rc;
     const ta::DistanceLaunch& l = c->dist.launched;
     if (out) { out[0] = l.row_groups; out[1] = l.voxel_groups; out[2] = l.init_groups; out[3] = l.column_launches; }
@@ -137,7 +134,7 @@ TA_API int ta_distance_debug(ta_ctx* c, uint32_t out[4]) {
 }
 
 TA_API int ta_distance_timing(ta_ctx* c, double* ms_pass, double* ms_after) {
-    int rc = distance_ready(c);
+    int rc = results_ready(c, distance_current, NO_RESULTS);
     return rc != TA_OK ? rc : two_intervals_ms(c->dist.ev, ms_pass, ms_after);
 }
 

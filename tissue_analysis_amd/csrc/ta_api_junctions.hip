@@ -9,11 +9,11 @@ namespace {
 struct JunctionWork {
     uint64_t counts[2], offsets[2], scratch[2], bytes;
     explicit JunctionWork(uint64_t W) {
-        uint64_t at = 0;
-        for (int k = 0; k < 2; ++k) { counts[k] = at; at += align16(W * 4); }
-        for (int k = 0; k < 2; ++k) { offsets[k] = at; at += align16(W * 8); }
-        for (int k = 0; k < 2; ++k) { scratch[k] = at; at += align16(ta::scan_u32_scratch_bytes(W)); }
-        bytes = at + 16;
+        PartCursor at;
+        for (auto& p : counts) p = at.take(W * 4, 16).at;
+        for (auto& p : offsets) p = at.take(W * 8, 16).at;
+        for (auto& p : scratch) p = at.take(ta::scan_u32_scratch_bytes(W), 16).at;
+        bytes = at.end(16) + 16;
     }
 };
 
@@ -23,13 +23,27 @@ struct JunctionSort {
     uint64_t counts, offsets, scratch, bytes;
     explicit JunctionSort(uint64_t N) : sort(N, 8) {
         const uint64_t B = ta::junction_row_blocks(N);
-        uint64_t at = sort.end;
-        counts = at; at += align16(B * 4);
-        offsets = at; at += align16(B * 8);
-        scratch = at; at += align16(ta::scan_u32_scratch_bytes(B));
-        bytes = at + 16;
+        PartCursor at(sort.end);
+        counts = at.take(B * 4, 16).at;
+        offsets = at.take(B * 8, 16).at;
+        scratch = at.take(ta::scan_u32_scratch_bytes(B), 16).at;
+        bytes = at.end(16) + 16;
     }
 };
+
+// the parts of JunctionState::rows[k], for R rows of K labels
+struct JunctionTable {
+    Part n, sums, labels;
+    uint64_t bytes = 0;
+    constexpr JunctionTable(uint64_t R, uint64_t K) {
+        PartCursor at;
+        n = at.take(R * 8); sums = at.take(R * 24); labels = at.take(R * 4 * K);
+        bytes = at.end() + 16;
+    }
+};
+static_assert(JunctionTable(5, 3).sums.at == 40 && JunctionTable(5, 3).labels.at == 160 && JunctionTable(5, 3).bytes == 236, "n [R] | sums [R][3] | labels u32[R][K]");
+
+const char* const NO_TABLES = "no junction tables for the current volume (run ta_junctions_extract)";
 
 ta::JunctionArgs junction_args(ta_ctx* c) {
     ta::JunctionArgs a = {};
@@ -48,7 +62,7 @@ ta::JunctionArgs junction_args(ta_ctx* c) {
 // drain the stream, read the record counts, allocate, run the emitting walk, sort and reduce the records into the tables
 int junctions_settle(ta_ctx* c) {
     if (c->jn.state == 2) return TA_OK;
-    if (c->jn.state != 1) return fail(TA_EINVAL, "no junction tables for the current volume (run ta_junctions_extract)");
+    if (c->jn.state != 1) return fail(TA_EINVAL, NO_TABLES);
     c->jn.state = 0;                               // (whatever fails below: no tables)
     int rc;
     ta::JunctionArgs a = junction_args(c);
@@ -62,12 +76,14 @@ int junctions_settle(ta_ctx* c) {
     for (int k = 0; k < 2; ++k)
         if (N[k] >= (1ull << 32)) return fail(TA_ENOMEM, "%llu junction records: the sort takes fewer than 2^32", (unsigned long long)N[k]);
     const int K[2] = {3, 4};
-    const uint64_t lab_at[2] = {align16(N[0] * 8) + align16(N[1] * 8), align16(N[0] * 8) + align16(N[1] * 8) + align16(N[0] * 12)};
-    if ((rc = c->jn.rec.reserve(lab_at[1] + align16(N[1] * 16) + 16)) != TA_OK) return rc;
+    PartCursor rec;                                // JunctionState::rec, each part from a multiple of 16
+    const uint64_t org_at[2] = {rec.take(N[0] * 8, 16).at, rec.take(N[1] * 8, 16).at};
+    const uint64_t lab_at[2] = {rec.take(N[0] * 12, 16).at, rec.take(N[1] * 16, 16).at};
+    if ((rc = c->jn.rec.reserve(rec.end(16) + 16)) != TA_OK) return rc;
     for (int k = 0; k < 2; ++k)
         if ((rc = c->jn.sort[k].reserve(JunctionSort(N[k]).bytes)) != TA_OK) return rc;
     char* rp = (char*)c->jn.rec.p;
-    uint64_t* origins[2] = {(uint64_t*)rp, (uint64_t*)(rp + align16(N[0] * 8))};
+    uint64_t* origins[2] = {(uint64_t*)(rp + org_at[0]), (uint64_t*)(rp + org_at[1])};
     uint32_t* labels[2] = {(uint32_t*)(rp + lab_at[0]), (uint32_t*)(rp + lab_at[1])};
     a.origin3 = origins[0]; a.origin4 = origins[1];
     a.labels3 = labels[0]; a.labels4 = labels[1];
@@ -104,17 +120,18 @@ int junctions_settle(ta_ctx* c) {
     }
     TA_HIP(hipStreamSynchronize(c->stream));
     for (int k = 0; k < 2; ++k)
-        if ((rc = c->jn.rows[k].reserve(R[k] * 32 + R[k] * 4 * K[k] + 16)) != TA_OK) return rc;
+        if ((rc = c->jn.rows[k].reserve(JunctionTable(R[k], K[k]).bytes)) != TA_OK) return rc;
     for (int k = 0; k < 2; ++k) {
         if (!N[k]) continue;
         const JunctionSort q(N[k]);
+        const JunctionTable tb(R[k], K[k]);
         char* sp = (char*)c->jn.sort[k].p;
         char* op = (char*)c->jn.rows[k].p;
-        TA_HIP(hipMemsetAsync(op, 0, R[k] * 32, c->stream));
+        TA_HIP(hipMemsetAsync(op, 0, tb.labels.at, c->stream));
         ta::JunctionRows rows;
-        rows.n = (unsigned long long*)op;
-        rows.sums = rows.n + R[k];
-        rows.labels = (uint32_t*)(op + R[k] * 32);
+        rows.n = (unsigned long long*)(op + tb.n.at);
+        rows.sums = (unsigned long long*)(op + tb.sums.at);
+        rows.labels = (uint32_t*)(op + tb.labels.at);
         rows.n0 = c->mdims[0]; rows.n1 = c->mdims[1]; rows.n2 = c->mdims[2];
         rows.origin0 = c->a_origin - c->first_owned;
         for (int d = 0; d < 3; ++d) { rows.flat[d] = c->mdims[d] == 1 ? 1 : 0; rows.axis[d] = c->perm[d]; }
@@ -129,20 +146,17 @@ int junctions_settle(ta_ctx* c) {
     return TA_OK;
 }
 
+// the checks every function behind the extract shares; settles
+int junctions_ready(ta_ctx* c) {
+    const int rc = results_ready(c, [](const ta_ctx* c) { return c->jn.state != 0; }, NO_TABLES);
+    return rc != TA_OK ? rc : junctions_settle(c);
+}
+
 int junctions_get(ta_ctx* c, int k, uint32_t* labels, uint64_t* n, uint64_t* sums) {
-    if (!c) return fail(TA_EINVAL, "ctx is NULL");
-    if (c->jn.state == 0) return fail(TA_EINVAL, "no junction tables for the current volume (run ta_junctions_extract)");
-    int rc = use_device(c);
-    if (rc != TA_OK) return rc;
-    if ((rc = junctions_settle(c)) != TA_OK) return rc;
-    const uint64_t R = c->jn.nrows[k], K = k ? 4 : 3;
-    if (!R) return TA_OK;
-    const char* op = (const char*)c->jn.rows[k].p;
-    if (n) TA_HIP(hipMemcpyAsync(n, op, R * 8, hipMemcpyDeviceToHost, c->stream));
-    if (sums) TA_HIP(hipMemcpyAsync(sums, op + R * 8, R * 24, hipMemcpyDeviceToHost, c->stream));
-    if (labels) TA_HIP(hipMemcpyAsync(labels, op + R * 32, R * 4 * K, hipMemcpyDeviceToHost, c->stream));
-    TA_HIP(hipStreamSynchronize(c->stream));
-    return TA_OK;
+    const int rc = junctions_ready(c);
+    if (rc != TA_OK || !c->jn.nrows[k]) return rc;
+    const JunctionTable tb(c->jn.nrows[k], k ? 4 : 3);
+    return read_columns(c, c->jn.rows[k].p, {{n, tb.n}, {sums, tb.sums}, {labels, tb.labels}});
 }
 
 }  // namespace
@@ -182,11 +196,8 @@ TA_API int ta_junctions_extract(ta_ctx* c) {
 }
 
 TA_API int ta_junctions_size(ta_ctx* c, uint64_t* nedges, uint64_t* nvertices, uint64_t* degenerate) {
-    if (!c) return fail(TA_EINVAL, "ctx is NULL");
-    if (c->jn.state == 0) return fail(TA_EINVAL, "no junction tables for the current volume (run ta_junctions_extract)");
-    int rc = use_device(c);
+    const int rc = junctions_ready(c);
     if (rc != TA_OK) return rc;
-    if ((rc = junctions_settle(c)) != TA_OK) return rc;
     if (nedges) *nedges = c->jn.nrows[0];
     if (nvertices) *nvertices = c->jn.nrows[1];
     if (degenerate) *degenerate = c->jn.degenerate;
@@ -198,11 +209,8 @@ TA_API int ta_junctions_get_edges(ta_ctx* c, uint32_t* labels, uint64_t* n, uint
 TA_API int ta_junctions_get_vertices(ta_ctx* c, uint32_t* labels, uint64_t* n, uint64_t* sums) { return junctions_get(c, 1, labels, n, sums); }
 
 TA_API int ta_junctions_debug(ta_ctx* c, uint32_t out[4]) {
-    if (!c) return fail(TA_EINVAL, "ctx is NULL");
-    if (c->jn.state == 0) return fail(TA_EINVAL, "no junction tables for the current volume (run ta_junctions_extract)");
-    int rc = use_device(c);
+    const int rc = junctions_ready(c);
     if (rc != TA_OK) return rc;
-    if ((rc = junctions_settle(c)) != TA_OK) return rc;
     if (out) {
         out[0] = (uint32_t)std::min<uint64_t>(c->jn.waves, 0xFFFFFFFFull);
         out[1] = c->jn.key_groups[0]; out[2] = c->jn.key_groups[1]; out[3] = 0u;

@@ -5,15 +5,19 @@
 
 namespace {
 
+const char* const NO_MESH = "no mesh of the current extraction (run ta_mesh_extract)";
+
 bool mesh_current(const ta_ctx* c) { return pass_current(c, c->mesh.seq); }
 
-// byte offsets of the parts of MeshState::small for R rows and wf / wc waves of the face / corner kernels
+// byte offsets of the parts of MeshState::small for R rows and wf / wc waves of the face / corner kernels, each a multiple of 16
 struct MeshSmall {
-    uint64_t flags = 0, wanted, fcounts, ccounts, foffs, coffs, fscan, cscan, bytes;
+    uint64_t flags, wanted, fcounts, ccounts, foffs, coffs, fscan, cscan, bytes;
     MeshSmall(uint64_t R, uint64_t wf, uint64_t wc) {
-        wanted = 16; fcounts = wanted + align16(R); ccounts = fcounts + align16(4 * wf); foffs = ccounts + align16(4 * wc);
-        coffs = foffs + align16(8 * wf); fscan = coffs + align16(8 * wc); cscan = fscan + align16(ta::scan_u32_scratch_bytes(wf));
-        bytes = cscan + align16(ta::scan_u32_scratch_bytes(wc));
+        PartCursor at;
+        flags = at.take(16).at; wanted = at.take(R, 16).at; fcounts = at.take(4 * wf, 16).at; ccounts = at.take(4 * wc, 16).at;
+        foffs = at.take(8 * wf, 16).at; coffs = at.take(8 * wc, 16).at;
+        fscan = at.take(ta::scan_u32_scratch_bytes(wf), 16).at; cscan = at.take(ta::scan_u32_scratch_bytes(wc), 16).at;
+        bytes = at.end(16);
     }
 };
 // ... of MeshState::work for F faces and V vertex records
@@ -23,14 +27,21 @@ struct MeshWork {
     MeshWork(uint64_t F, uint64_t V)
         : fnb(align16(8 * F)), corner(fnb + align16(4 * F)), sort(F > V ? F : V, 4, corner + align16(8 * V)) {}
 };
-// ... of MeshState::out
+// the parts of MeshState::out; bounds: vbeg .. fend, the four columns the host reads (and the pass clears) as one
 struct MeshOut {
-    uint64_t vcorner = 0, vbeg, vend, fbeg, fend, tri, tcell, tnb, bytes;
-    MeshOut(uint64_t R, uint64_t F, uint64_t V) {
-        vbeg = align16(8 * V); vend = vbeg + 8 * R; fbeg = vend + 8 * R; fend = fbeg + 8 * R; tri = align16(fend + 8 * R);
-        tcell = tri + align16(24 * F); tnb = tcell + align16(8 * F); bytes = tnb + align16(8 * F);
+    Part vcorner, vbeg, vend, fbeg, fend, tri, tcell, tnb, bounds;
+    uint64_t bytes = 0;
+    constexpr MeshOut(uint64_t R, uint64_t F, uint64_t V) {
+        PartCursor at;
+        vcorner = at.take(8 * V); vbeg = at.take(8 * R, 16); vend = at.take(8 * R); fbeg = at.take(8 * R); fend = at.take(8 * R);
+        bounds = {vbeg.at, at.end() - vbeg.at};
+        tri = at.take(24 * F, 16); tcell = at.take(8 * F, 16); tnb = at.take(8 * F, 16);
+        bytes = at.end(16);
     }
 };
+static_assert(MeshOut(3, 2, 5).vbeg.at == 48 && MeshOut(3, 2, 5).fend.at == 120 && MeshOut(3, 2, 5).bounds.bytes == 96 && MeshOut(3, 2, 5).tri.at == 144 &&
+              MeshOut(3, 2, 5).tcell.at == 192 && MeshOut(3, 2, 5).tnb.at == 208 && MeshOut(3, 2, 5).bytes == 224,
+              "corners u64[V] | vbeg, vend, fbeg, fend u64[R] | triangles u32[2F][3] | cell u32[2F] | neighbour u32[2F], the groups from multiples of 16");
 
 // drain the stream, look at the flags of the emit / resolve kernels, and read the cells and their CSR offsets back once
 int mesh_finish(ta_ctx* c) {
@@ -41,13 +52,12 @@ int mesh_finish(ta_ctx* c) {
         return fail(TA_ERANGE, "the mesh pass found the volume changed since ta_extract (flags %u %u %u)", flags[0], flags[1], flags[2]);
     if (c->mesh.host_ready) return TA_OK;
     const uint64_t R = c->mesh.rows;
-    const MeshOut O(R, c->mesh.faces, c->mesh.verts);
-    std::vector<uint64_t> t(4 * R);
-    const char* o = (const char*)c->mesh.out.p;
-    if (R) TA_HIP(hipMemcpyAsync(t.data(), o + O.vbeg, 32 * R, hipMemcpyDeviceToHost, c->stream));
-    TA_HIP(hipStreamSynchronize(c->stream));
-    const uint64_t *vbeg = t.data(), *vend = vbeg + R, *fbeg = vend + R, *fend = fbeg + R;
+    std::vector<uint64_t> t;
     c->mesh.cells.clear(); c->mesh.voff.clear(); c->mesh.toff.clear();
+    // (room for every row now: no push_back below allocates)
+    int rc = host_alloc([&] { t.resize(4 * R); c->mesh.cells.reserve(R); c->mesh.voff.reserve(R + 1); c->mesh.toff.reserve(R + 1); });
+    if (rc != TA_OK || (rc = read_columns(c, c->mesh.out.p, {{t.data(), MeshOut(R, c->mesh.faces, c->mesh.verts).bounds}})) != TA_OK) return rc;
+    const uint64_t *vbeg = t.data(), *vend = vbeg + R, *fbeg = vend + R, *fend = fbeg + R;
     for (uint64_t r = 0; r < R; ++r) {
         if (vend[r] <= vbeg[r]) continue;
         if (fend[r] <= fbeg[r]) return fail(TA_ERANGE, "mesh: row %llu has vertices and no faces", (unsigned long long)r);
@@ -127,14 +137,14 @@ TA_API int ta_mesh_extract(ta_ctx* c, int sub_factor, const uint8_t* wanted_rows
     uint32_t *keys0 = (uint32_t*)(w + Wk.sort.keys[0]), *keys1 = (uint32_t*)(w + Wk.sort.keys[1]);
     uint32_t *idx0 = (uint32_t*)(w + Wk.sort.idx[0]), *idx1 = (uint32_t*)(w + Wk.sort.idx[1]);
     void* temp = w + Wk.sort.temp;
-    uint64_t* vcorner = (uint64_t*)(o + O.vcorner);
-    uint64_t *vbeg = (uint64_t*)(o + O.vbeg), *vend = (uint64_t*)(o + O.vend);
-    uint64_t *fbeg = (uint64_t*)(o + O.fbeg), *fend = (uint64_t*)(o + O.fend);
+    uint64_t* vcorner = (uint64_t*)(o + O.vcorner.at);
+    uint64_t *vbeg = (uint64_t*)(o + O.vbeg.at), *vend = (uint64_t*)(o + O.vend.at);
+    uint64_t *fbeg = (uint64_t*)(o + O.fbeg.at), *fend = (uint64_t*)(o + O.fend.at);
     const int key_bits = c->max_label ? 32 - __builtin_clz(c->max_label) : 1;
     uint32_t *skeys = nullptr, *sidx = nullptr;
     // emit -> group by cell -> resolve
     TA_HIP(hipEventRecord(c->mesh.ev[2], c->stream));
-    TA_HIP(hipMemsetAsync(vbeg, 0, 32 * R, c->stream));
+    TA_HIP(hipMemsetAsync(o + O.bounds.at, 0, O.bounds.bytes, c->stream));
     ta::launch_mesh_corner_emit(c->stream, a, c->itemsize, coffs, V, corner, keys0, idx0);
     TA_HIP(ta::launch_radix_sort_u32(c->stream, V, keys0, keys1, idx0, idx1, temp, key_bits, &skeys, &sidx));
     ta::launch_mesh_bounds(c->stream, skeys, V, vbeg, vend);
@@ -142,8 +152,8 @@ TA_API int ta_mesh_extract(ta_ctx* c, int sub_factor, const uint8_t* wanted_rows
     ta::launch_mesh_face_emit(c->stream, a, c->itemsize, foffs, F, frec, fnb, keys0, idx0);
     TA_HIP(ta::launch_radix_sort_u32(c->stream, F, keys0, keys1, idx0, idx1, temp, key_bits, &skeys, &sidx));
     ta::launch_mesh_bounds(c->stream, skeys, F, fbeg, fend);
-    ta::launch_mesh_resolve(c->stream, a, skeys, sidx, frec, fnb, F, vcorner, vbeg, vend, (uint32_t*)(o + O.tri),
-                            (uint32_t*)(o + O.tcell), (uint32_t*)(o + O.tnb));
+    ta::launch_mesh_resolve(c->stream, a, skeys, sidx, frec, fnb, F, vcorner, vbeg, vend, (uint32_t*)(o + O.tri.at),
+                            (uint32_t*)(o + O.tcell.at), (uint32_t*)(o + O.tnb.at));
     TA_HIP(hipGetLastError());
     TA_HIP(hipEventRecord(c->mesh.ev[3], c->stream));
     c->mesh.faces = F;
@@ -155,11 +165,8 @@ TA_API int ta_mesh_extract(ta_ctx* c, int sub_factor, const uint8_t* wanted_rows
 }
 
 TA_API int ta_mesh_size(ta_ctx* c, uint64_t* n_cells, uint64_t* n_vertices, uint64_t* n_triangles) {
-    if (!c) return fail(TA_EINVAL, "ctx is NULL");
-    if (!mesh_current(c)) return fail(TA_EINVAL, "no mesh of the current extraction (run ta_mesh_extract)");
-    int rc = use_device(c);
-    if (rc != TA_OK) return rc;
-    if ((rc = mesh_finish(c)) != TA_OK) return rc;
+    int rc = results_ready(c, mesh_current, NO_MESH);
+    if (rc != TA_OK || (rc = mesh_finish(c)) != TA_OK) return rc;
     if (n_cells) *n_cells = (uint64_t)c->mesh.cells.size();
     if (n_vertices) *n_vertices = c->mesh.verts;
     if (n_triangles) *n_triangles = 2 * c->mesh.faces;
@@ -168,29 +175,20 @@ TA_API int ta_mesh_size(ta_ctx* c, uint64_t* n_cells, uint64_t* n_vertices, uint
 
 TA_API int ta_mesh_get(ta_ctx* c, uint32_t* cells, uint64_t* vertex_offsets, uint64_t* triangle_offsets, uint64_t* corners,
                        uint32_t* triangles, uint32_t* triangle_cell, uint32_t* triangle_neighbor) {
-    if (!c) return fail(TA_EINVAL, "ctx is NULL");
-    if (!mesh_current(c)) return fail(TA_EINVAL, "no mesh of the current extraction (run ta_mesh_extract)");
-    int rc = use_device(c);
-    if (rc != TA_OK) return rc;
-    if ((rc = mesh_finish(c)) != TA_OK) return rc;
+    int rc = results_ready(c, mesh_current, NO_MESH);
+    if (rc != TA_OK || (rc = mesh_finish(c)) != TA_OK) return rc;
     const uint64_t F = c->mesh.faces, V = c->mesh.verts;
     const MeshOut O(c->mesh.rows, F, V);
-    const char* o = (const char*)c->mesh.out.p;
     if (cells && !c->mesh.cells.empty()) std::memcpy(cells, c->mesh.cells.data(), 4 * c->mesh.cells.size());
     if (vertex_offsets) std::memcpy(vertex_offsets, c->mesh.voff.data(), 8 * c->mesh.voff.size());
     if (triangle_offsets) std::memcpy(triangle_offsets, c->mesh.toff.data(), 8 * c->mesh.toff.size());
     const bool c_order = c->perm[0] == 0 && c->perm[1] == 1 && c->perm[2] == 2;
-    std::vector<uint64_t> k;                     // (another layout: the corners, converted to array-axis indices, then re-sorted)
-    if (!c_order && V) {
-        k.resize(V);
-        TA_HIP(hipMemcpyAsync(k.data(), o + O.vcorner, 8 * V, hipMemcpyDeviceToHost, c->stream));
-    } else if (corners && V) {
-        TA_HIP(hipMemcpyAsync(corners, o + O.vcorner, 8 * V, hipMemcpyDeviceToHost, c->stream));
-    }
-    if (triangles && F) TA_HIP(hipMemcpyAsync(triangles, o + O.tri, 24 * F, hipMemcpyDeviceToHost, c->stream));
-    if (triangle_cell && F) TA_HIP(hipMemcpyAsync(triangle_cell, o + O.tcell, 8 * F, hipMemcpyDeviceToHost, c->stream));
-    if (triangle_neighbor && F) TA_HIP(hipMemcpyAsync(triangle_neighbor, o + O.tnb, 8 * F, hipMemcpyDeviceToHost, c->stream));
-    TA_HIP(hipStreamSynchronize(c->stream));
+    // (another layout: the corners, converted to array-axis indices, then each cell's re-sorted: ord, and where each went: newpos)
+    std::vector<uint64_t> k;
+    std::vector<uint32_t> ord, newpos;
+    if (!c_order && V && (rc = host_alloc([&] { k.resize(V); ord.resize(V); newpos.resize(V); })) != TA_OK) return rc;
+    if ((rc = read_columns(c, c->mesh.out.p, {{k.empty() ? (void*)corners : k.data(), O.vcorner}, {triangles, O.tri}, {triangle_cell, O.tcell},
+                                               {triangle_neighbor, O.tnb}})) != TA_OK) return rc;
     if (!c_order && V) {
         // the device sorted each cell's corners by their index in MEMORY order: convert them to C-order indices of the array
         // axes and sort each cell's vertices by those (a 2-D image, stored (n0, n1, 1), is such a layout too)
@@ -203,7 +201,6 @@ TA_API int ta_mesh_get(ta_ctx* c, uint32_t* cells, uint64_t* vertex_offsets, uin
             ka[c->perm[0]] = r / g[1]; ka[c->perm[1]] = r % g[1]; ka[c->perm[2]] = k2;
             k[i] = (uint64_t)((ka[0] * ga[1] + ka[1]) * ga[2] + ka[2]);
         }
-        std::vector<uint32_t> ord(V), newpos(V);
         for (size_t ci = 0; ci + 1 < c->mesh.voff.size(); ++ci) {
             const uint64_t v0 = c->mesh.voff[ci], v1 = c->mesh.voff[ci + 1];
             for (uint64_t i = v0; i < v1; ++i) ord[i] = (uint32_t)i;
@@ -217,7 +214,7 @@ TA_API int ta_mesh_get(ta_ctx* c, uint32_t* cells, uint64_t* vertex_offsets, uin
 }
 
 TA_API int ta_mesh_timing(ta_ctx* c, double* ms) {
-    if (!c) return fail(TA_EINVAL, "ctx is NULL");
+    if (!c) return fail(TA_EINVAL, "ctx is NULL");      // (two intervals with a gap between them: not pass_timing's shape)
     if (!ms) return fail(TA_EINVAL, "NULL argument");
     if (c->mesh.seq == 0 || !c->mesh.ev[3]) return fail(TA_EINVAL, "no mesh pass has been run");
     int rc = use_device(c);

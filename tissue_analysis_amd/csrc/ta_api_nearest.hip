@@ -6,13 +6,19 @@ namespace {
 
 const char* const NO_RESULTS = "no nearest-label map for the current extraction (run ta_nearest_extract)";
 
-// byte offsets of the parts of NearestState::table for R rows
+// the parts of NearestState::table for R rows
 struct NearestLayout {
-    uint64_t gained = 0, totals, flags, bytes;
-    explicit NearestLayout(uint64_t R) { totals = 8 * R; flags = totals + 16; bytes = flags + 4 * ta::NEAR_NFLAGS; }
+    Part gained, totals, flags;
+    uint64_t bytes = 0;
+    constexpr explicit NearestLayout(uint64_t R) {
+        PartCursor at;
+        gained = at.take(8 * R); totals = at.take(16); flags = at.take(4 * ta::NEAR_NFLAGS);
+        bytes = at.end();
+    }
 };
+static_assert(NearestLayout(3).totals.at == 24 && NearestLayout(3).flags.at == 40 && NearestLayout(3).bytes == 56, "gained [R] | totals [2] | flags u32[4]");
 
-int nearest_ready(ta_ctx* c) { return c ? transform_ready(c, c->near.seq, NO_RESULTS) : fail(TA_EINVAL, "ctx is NULL"); }
+bool nearest_current(const ta_ctx* c) { return pass_current(c, c->near.seq); }
 
 }  // namespace
 
@@ -66,7 +72,7 @@ TA_API int ta_nearest_extract(ta_ctx* c, uint32_t empty_label, uint32_t not_from
     TA_HIP(hipEventRecord(c->near.ev[1], c->stream));
     char* tp = (char*)c->near.table.p;
     ta::NearestTable t = {};
-    t.gained = (unsigned long long*)(tp + L.gained); t.totals = (unsigned long long*)(tp + L.totals); t.flags = (uint32_t*)(tp + L.flags);
+    t.gained = (unsigned long long*)(tp + L.gained.at); t.totals = (unsigned long long*)(tp + L.totals.at); t.flags = (uint32_t*)(tp + L.flags.at);
     t.max_label = c->max_label;
     TA_HIP(hipMemsetAsync(tp, 0, L.bytes, c->stream));
     launched[1] = ta::launch_nearest_count(c->stream, a, c->itemsize, t);
@@ -81,23 +87,18 @@ TA_API int ta_nearest_extract(ta_ctx* c, uint32_t empty_label, uint32_t not_from
 }
 
 TA_API int ta_nearest_get(ta_ctx* c, uint64_t* gained, uint64_t totals[2]) {
-    int rc = nearest_ready(c);
+    int rc = results_ready(c, nearest_current, NO_RESULTS);
     if (rc != TA_OK) return rc;
-    const uint64_t R = c->near.rows;
-    const NearestLayout L(R);
-    const char* tp = (const char*)c->near.table.p;
+    const NearestLayout L(c->near.rows);
     uint32_t flags[ta::NEAR_NFLAGS] = {0, 0, 0, 0};
-    TA_HIP(hipMemcpyAsync(flags, tp + L.flags, sizeof(flags), hipMemcpyDeviceToHost, c->stream));
-    if (gained) TA_HIP(hipMemcpyAsync(gained, tp + L.gained, 8 * R, hipMemcpyDeviceToHost, c->stream));
-    if (totals) TA_HIP(hipMemcpyAsync(totals, tp + L.totals, 16, hipMemcpyDeviceToHost, c->stream));
-    TA_HIP(hipStreamSynchronize(c->stream));
+    if ((rc = read_columns(c, c->near.table.p, {{flags, L.flags}, {gained, L.gained}, {totals, L.totals}})) != TA_OK) return rc;
     if (flags[ta::NEAR_FLAG_RANGE])
         return fail(TA_ERANGE, "the nearest-label pass met a label above max_label=%u (the volume changed since ta_extract)", c->max_label);
     return TA_OK;
 }
 
 TA_API int ta_nearest_image(ta_ctx* c, int64_t first_plane, int64_t nplanes, uint32_t* nearest, double* d2) {
-    int rc = nearest_ready(c);
+    int rc = results_ready(c, nearest_current, NO_RESULTS);
     if (rc != TA_OK) return rc;
     if ((rc = check_planes(c, first_plane, nplanes)) != TA_OK || !nplanes) return rc;
     const uint64_t plane = (uint64_t)c->mdims[1] * (uint64_t)c->mdims[2], from = (uint64_t)first_plane * plane, count = (uint64_t)nplanes * plane;
@@ -113,7 +114,7 @@ TA_API int ta_nearest_image(ta_ctx* c, int64_t first_plane, int64_t nplanes, uin
 }
 
 TA_API int ta_nearest_apply(ta_ctx* c) {
-    int rc = nearest_ready(c);
+    int rc = results_ready(c, nearest_current, NO_RESULTS);
     if (rc != TA_OK) return rc;
     const bool compact = c->ids.compact;
     (void)ta::launch_nearest_apply(c->stream, c->near.args, c->itemsize, const_cast<void*>(c->vol), compact ? c->ids.compact_vol.p : nullptr,
@@ -124,14 +125,14 @@ TA_API int ta_nearest_apply(ta_ctx* c) {
 }
 
 TA_API int ta_nearest_debug(ta_ctx* c, uint32_t out[4]) {
-    int rc = nearest_ready(c);
+    int rc = results_ready(c, nearest_current, NO_RESULTS);
     if (rc != TA_OK) return rc;
     if (out) std::copy(c->near.launched, c->near.launched + 4, out);
     return TA_OK;
 }
 
 TA_API int ta_nearest_timing(ta_ctx* c, double* ms_pass, double* ms_after) {
-    int rc = nearest_ready(c);
+    int rc = results_ready(c, nearest_current, NO_RESULTS);
     return rc != TA_OK ? rc : two_intervals_ms(c->near.ev, ms_pass, ms_after);
 }
 

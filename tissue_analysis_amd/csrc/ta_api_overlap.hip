@@ -7,6 +7,29 @@ namespace {
 
 constexpr CompanionKind B_VOLUME = {"B", 2, 4};        // uint16 or uint32
 constexpr int OV_MIN_LOG2 = 4, OV_MAX_LOG2 = 31;       // (the sort's values are u32 slot numbers)
+const char* const NO_TABLE = "no overlap table for the current volume and B (run ta_overlap_extract)";
+
+// where the parts of OverlapState::work lie, for the blocks of a table
+struct OverlapWork {
+    uint64_t counts, offsets, scratch, bytes;
+    explicit OverlapWork(uint64_t blocks) {
+        PartCursor at;
+        counts = at.take(blocks * 4).at; offsets = at.take(blocks * 8, 16).at; scratch = at.take(ta::scan_u32_scratch_bytes(blocks)).at;
+        bytes = at.end();
+    }
+};
+
+// the parts of OverlapState::rows for P pairs
+struct OverlapTable {
+    Part a, b, n;
+    uint64_t bytes = 0;
+    constexpr explicit OverlapTable(uint64_t P) {
+        PartCursor at;
+        a = at.take(4 * P); b = at.take(4 * P); n = at.take(8 * P);
+        bytes = at.end() + 16;
+    }
+};
+static_assert(OverlapTable(3).b.at == 12 && OverlapTable(3).n.at == 24 && OverlapTable(3).bytes == 64, "a u32[P] | b u32[P] | n u64[P]");
 
 uint64_t overlap_voxels(const ta_ctx* c) { return (uint64_t)(c->mdims[0] - c->first_owned) * (uint64_t)c->mdims[1] * (uint64_t)c->mdims[2]; }
 
@@ -30,8 +53,8 @@ int overlap_launch(ta_ctx* c) {
     int rc;
     if ((rc = c->ov.table.reserve(slots * 16)) != TA_OK) return rc;
     if ((rc = c->ov.small.reserve(32)) != TA_OK) return rc;
-    const uint64_t offsets_at = align16(blocks * 4), scratch_at = offsets_at + blocks * 8;
-    if ((rc = c->ov.work.reserve(scratch_at + ta::scan_u32_scratch_bytes(blocks))) != TA_OK) return rc;
+    const OverlapWork wl(blocks);
+    if ((rc = c->ov.work.reserve(wl.bytes)) != TA_OK) return rc;
     if ((rc = ensure_events(c->ov.ev)) != TA_OK) return rc;
     ta::OverlapArgs a;
     a.a = c->vol;                  // (the ids as the caller stored them: never the rank copy of a compacted context)
@@ -52,8 +75,8 @@ int overlap_launch(ta_ctx* c) {
     TA_HIP(hipGetLastError());
     TA_HIP(hipEventRecord(c->ov.ev[1], c->stream));
     char* w = (char*)c->ov.work.p;
-    ta::launch_overlap_count(c->stream, a.keys, slots, (uint32_t*)w);
-    ta::launch_scan_u32_exclusive(c->stream, (const uint32_t*)w, blocks, w + scratch_at, (uint64_t*)(w + offsets_at));
+    ta::launch_overlap_count(c->stream, a.keys, slots, (uint32_t*)(w + wl.counts));
+    ta::launch_scan_u32_exclusive(c->stream, (const uint32_t*)(w + wl.counts), blocks, w + wl.scratch, (uint64_t*)(w + wl.offsets));
     TA_HIP(hipGetLastError());
     TA_HIP(hipEventRecord(c->ov.ev[2], c->stream));
     c->ov.passes += 1;
@@ -63,15 +86,14 @@ int overlap_launch(ta_ctx* c) {
 // drain the stream; a table that overflowed is grown and the pass repeated; then the occupied slots become the sorted rows
 int overlap_settle(ta_ctx* c) {
     if (c->ov.state == 2) return TA_OK;
-    if (c->ov.state != 1) return fail(TA_EINVAL, "no overlap table for the current volume and B (run ta_overlap_extract)");
+    if (c->ov.state != 1) return fail(TA_EINVAL, NO_TABLE);
     int rc;
     uint64_t occupied = 0, top = 0;
     for (;;) {
-        const uint64_t slots = 1ull << c->ov.log2, blocks = ta::overlap_compact_blocks(slots);
-        const uint64_t scratch_at = align16(blocks * 4) + blocks * 8;
+        const uint64_t blocks = ta::overlap_compact_blocks(1ull << c->ov.log2);
         uint32_t small[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         TA_HIP(hipMemcpyAsync(small, c->ov.small.p, sizeof(small), hipMemcpyDeviceToHost, c->stream));
-        TA_HIP(hipMemcpyAsync(&occupied, ta::scan_u32_total((char*)c->ov.work.p + scratch_at, blocks), 8, hipMemcpyDeviceToHost, c->stream));
+        TA_HIP(hipMemcpyAsync(&occupied, ta::scan_u32_total((char*)c->ov.work.p + OverlapWork(blocks).scratch, blocks), 8, hipMemcpyDeviceToHost, c->stream));
         TA_HIP(hipStreamSynchronize(c->stream));
         memcpy(&top, &small[4], 8);
         c->ov.lds_spills = small[ta::OV_FLAG_LDS_SPILL];               // (of the run just read: in the end, of the last one)
@@ -86,12 +108,13 @@ int overlap_settle(ta_ctx* c) {
         if ((rc = overlap_launch(c)) != TA_OK) { c->ov.state = 0; return rc; }
     }
     const uint64_t slots = 1ull << c->ov.log2, blocks = ta::overlap_compact_blocks(slots);
-    const uint64_t offsets_at = align16(blocks * 4);
+    const uint64_t offsets_at = OverlapWork(blocks).offsets;
     const uint64_t P = occupied + (top ? 1 : 0);
     const uint64_t n = occupied;
     const SortLayout S(n, 8);
+    const OverlapTable tb(P);
     if ((rc = c->ov.sort.reserve(S.end + 16)) != TA_OK) return rc;
-    if ((rc = c->ov.rows.reserve(P * 16 + 16)) != TA_OK) return rc;
+    if ((rc = c->ov.rows.reserve(tb.bytes)) != TA_OK) return rc;
     char* q = (char*)c->ov.sort.p;
     uint64_t* k0 = (uint64_t*)(q + S.keys[0]); uint64_t* k1 = (uint64_t*)(q + S.keys[1]);
     uint32_t* i0 = (uint32_t*)(q + S.idx[0]); uint32_t* i1 = (uint32_t*)(q + S.idx[1]);
@@ -102,14 +125,20 @@ int overlap_settle(ta_ctx* c) {
     ta::launch_overlap_emit(c->stream, keys, slots, (const uint64_t*)((char*)c->ov.work.p + offsets_at), shift_b, k0, i0);
     uint64_t* ks = k0; uint32_t* is = i0;
     TA_HIP(ta::launch_radix_sort_u64(c->stream, n, k0, k1, i0, i1, temp, 8 * c->itemsize + shift_b, &ks, &is));
-    uint32_t* ra = (uint32_t*)c->ov.rows.p;
-    ta::launch_overlap_rows(c->stream, ks, is, n, keys + slots, shift_b, top, ra, ra + P, (uint64_t*)(ra + 2 * P));
+    char* rp = (char*)c->ov.rows.p;
+    ta::launch_overlap_rows(c->stream, ks, is, n, keys + slots, shift_b, top, (uint32_t*)(rp + tb.a.at), (uint32_t*)(rp + tb.b.at), (uint64_t*)(rp + tb.n.at));
     TA_HIP(hipGetLastError());
     TA_HIP(hipEventRecord(c->ov.ev[4], c->stream));
     TA_HIP(hipStreamSynchronize(c->stream));
     c->ov.npairs = P;
     c->ov.state = 2;
     return TA_OK;
+}
+
+// the checks every function behind the extract shares; settles
+int overlap_ready(ta_ctx* c) {
+    const int rc = results_ready(c, [](const ta_ctx* c) { return c->ov.state != 0; }, NO_TABLE);
+    return rc != TA_OK ? rc : overlap_settle(c);
 }
 
 }  // namespace
@@ -171,47 +200,26 @@ TA_API int ta_overlap_extract(ta_ctx* c) {
 TA_API int ta_overlap_size(ta_ctx* c, uint64_t* npairs) {
     if (!c) return fail(TA_EINVAL, "ctx is NULL");
     if (!npairs) return fail(TA_EINVAL, "NULL argument");
-    if (c->ov.state == 0) return fail(TA_EINVAL, "no overlap table for the current volume and B (run ta_overlap_extract)");
-    int rc = use_device(c);
-    if (rc != TA_OK) return rc;
-    if ((rc = overlap_settle(c)) != TA_OK) return rc;
-    *npairs = c->ov.npairs;
-    return TA_OK;
+    const int rc = overlap_ready(c);
+    if (rc == TA_OK) *npairs = c->ov.npairs;
+    return rc;
 }
 
 TA_API int ta_overlap_get(ta_ctx* c, uint32_t* a, uint32_t* b, uint64_t* n) {
-    if (!c) return fail(TA_EINVAL, "ctx is NULL");
-    if (c->ov.state == 0) return fail(TA_EINVAL, "no overlap table for the current volume and B (run ta_overlap_extract)");
-    int rc = use_device(c);
-    if (rc != TA_OK) return rc;
-    if ((rc = overlap_settle(c)) != TA_OK) return rc;
-    const uint64_t P = c->ov.npairs;
-    if (!P) return TA_OK;
-    const uint32_t* ra = (const uint32_t*)c->ov.rows.p;
-    if (a) TA_HIP(hipMemcpyAsync(a, ra, 4 * P, hipMemcpyDeviceToHost, c->stream));
-    if (b) TA_HIP(hipMemcpyAsync(b, ra + P, 4 * P, hipMemcpyDeviceToHost, c->stream));
-    if (n) TA_HIP(hipMemcpyAsync(n, ra + 2 * P, 8 * P, hipMemcpyDeviceToHost, c->stream));
-    TA_HIP(hipStreamSynchronize(c->stream));
-    return TA_OK;
+    const int rc = overlap_ready(c);
+    if (rc != TA_OK || !c->ov.npairs) return rc;
+    const OverlapTable tb(c->ov.npairs);
+    return read_columns(c, c->ov.rows.p, {{a, tb.a}, {b, tb.b}, {n, tb.n}});
 }
 
 TA_API int ta_overlap_debug(ta_ctx* c, uint32_t out[4]) {
-    if (!c) return fail(TA_EINVAL, "ctx is NULL");
-    if (c->ov.state == 0) return fail(TA_EINVAL, "no overlap table for the current volume and B (run ta_overlap_extract)");
-    int rc = use_device(c);
-    if (rc != TA_OK) return rc;
-    if ((rc = overlap_settle(c)) != TA_OK) return rc;
-    if (out) { out[0] = c->ov.lds_spills; out[1] = (uint32_t)c->ov.passes; out[2] = c->ov.plan.tiles_per_group; out[3] = c->ov.plan.groups; }
-    return TA_OK;
+    const int rc = overlap_ready(c);
+    if (rc == TA_OK) range_debug_words(out, c->ov.lds_spills, (uint32_t)c->ov.passes, c->ov.plan);
+    return rc;
 }
 
 TA_API int ta_overlap_timing(ta_ctx* c, double* ms) {
-    if (!c) return fail(TA_EINVAL, "ctx is NULL");
-    if (!ms) return fail(TA_EINVAL, "NULL argument");
-    if (c->ov.state == 0 || !c->ov.ev[1]) return fail(TA_EINVAL, "no overlap pass has been run");
-    int rc = use_device(c);
-    if (rc != TA_OK) return rc;
-    return interval_ms(c->ov.ev[0], c->ov.ev[1], ms);
+    return pass_timing(c, ms, [](ta_ctx* c) { return c->ov.state != 0 && c->ov.ev[1] ? c->ov.ev : nullptr; }, "no overlap pass has been run");
 }
 
 TA_API int ta_overlap_timing_compaction(ta_ctx* c, double* ms, int* passes) {

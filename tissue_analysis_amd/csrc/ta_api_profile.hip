@@ -12,34 +12,27 @@ static_assert(TA_PROF_MAX_BINS == ta::PROF_MAX_BINS, "the public header and the 
 static_assert(sizeof(ProfileState::edges) == 8 * (ta::PROF_MAX_BINS + 1), "ProfileState::edges holds K + 1 edges for the largest K");
 
 const char* const NO_RESULTS = "no distance-shell profile of the current distance map (run ta_profile_extract)";
+const char* const NOUN = "profile pass";
+static_assert(ta::PROF_NFLAGS == RANGE_NFLAGS && ta::PROF_FLAG_RANGE == RANGE_FLAG_RANGE && ta::PROF_FLAG_SPILL == RANGE_FLAG_SPILL,
+              "range_pass_finish reads these words");
 
 // the table belongs to the current extraction AND to the distance map the context holds (a new one ends it: profile_on_new_distance)
 bool profile_current(const ta_ctx* c) { return pass_current(c, c->prof.seq) && c->dist.seq == c->extract_seq; }
 
-// byte offsets of the parts of ProfileState::out for N = rows x bins entries; the signal columns only in a pass with signal
+// the parts of ProfileState::out for N = rows x bins entries; the buffer ends behind n in a pass without signal
 struct ProfileLayout {
-    uint64_t flags = 0, edges = 16, n, sum, sumsq, vmin, vmax, bytes;
-    ProfileLayout(uint64_t N, bool signal) {
-        n = align16(edges + 8 * (ta::PROF_MAX_BINS + 1)); sum = n + 8 * N; sumsq = sum + 8 * N; vmin = sumsq + 16 * N; vmax = vmin + 4 * N;
-        bytes = signal ? vmax + 4 * N : sum;
+    Part flags, edges, n, sum, sumsq, vmin, vmax;
+    uint64_t bytes = 0;
+    constexpr ProfileLayout(uint64_t N, bool signal) {
+        PartCursor at;
+        flags = at.take(16); edges = at.take(8 * (ta::PROF_MAX_BINS + 1)); n = at.take(8 * N, 16);
+        sum = at.take(8 * N); sumsq = at.take(16 * N); vmin = at.take(4 * N); vmax = at.take(4 * N);
+        bytes = signal ? at.end() : sum.at;
     }
 };
-
-int profile_ready(ta_ctx* c) {
-    if (!c) return fail(TA_EINVAL, "ctx is NULL");
-    if (!profile_current(c)) return fail(TA_EINVAL, NO_RESULTS);
-    return use_device(c);
-}
-
-// drain the stream and look at the pass's flag words
-int profile_finish(ta_ctx* c, uint32_t* spills = nullptr) {
-    uint32_t flags[ta::PROF_NFLAGS] = {0, 0, 0, 0};
-    if (const int rc = read_pass_flags<ta::PROF_NFLAGS>(c, c->prof.out.p, flags); rc != TA_OK) return rc;
-    if (flags[ta::PROF_FLAG_RANGE])
-        return fail(TA_ERANGE, "the profile pass met a label above max_label=%u (the volume changed since ta_extract)", c->max_label);
-    if (spills) *spills = flags[ta::PROF_FLAG_SPILL];
-    return TA_OK;
-}
+static_assert(ta::PROF_MAX_BINS == 64 && ProfileLayout(6, true).edges.at == 16 && ProfileLayout(6, true).n.at == 544 && ProfileLayout(6, true).sumsq.at == 640 &&
+              ProfileLayout(6, true).vmin.at == 736 && ProfileLayout(6, true).vmax.at == 760 && ProfileLayout(6, true).bytes == 784 &&
+              ProfileLayout(6, false).bytes == 592, "flags u32[4] | edges f64[65] | n [N] from a multiple of 16 | sum [N] | sumsq [N][2] | min u32[N] | max u32[N]");
 
 }  // namespace
 
@@ -74,7 +67,7 @@ TA_API int ta_profile_extract(ta_ctx* c, int nbins, const double* edges2, uint32
     if ((rc = ensure_events(c->prof.ev)) != TA_OK) return rc;
     char* o = (char*)c->prof.out.p;
     TA_HIP(hipMemsetAsync(o, 0, L.bytes, c->stream));
-    if (signal) TA_HIP(hipMemsetAsync(o + L.vmin, 0xff, 4 * N, c->stream));
+    if (signal) TA_HIP(hipMemsetAsync(o + L.vmin.at, 0xff, L.vmin.bytes, c->stream));
     ta::ProfileArgs a = {};
     a.vol = sweep_vol(c);
     a.d2 = (const double*)c->dist.d2.p;
@@ -82,15 +75,15 @@ TA_API int ta_profile_extract(ta_ctx* c, int nbins, const double* edges2, uint32
     a.n0 = c->mdims[0]; a.n1 = c->mdims[1]; a.n2 = c->mdims[2];
     a.max_label = c->max_label;
     a.bins = (uint32_t)nbins;
-    a.n = (unsigned long long*)(o + L.n);
-    a.sum = (unsigned long long*)(o + L.sum);
-    a.sumsq = (unsigned long long*)(o + L.sumsq);
-    a.vmin = (uint32_t*)(o + L.vmin);
-    a.vmax = (uint32_t*)(o + L.vmax);
+    a.n = (unsigned long long*)(o + L.n.at);
+    a.sum = (unsigned long long*)(o + L.sum.at);
+    a.sumsq = (unsigned long long*)(o + L.sumsq.at);
+    a.vmin = (uint32_t*)(o + L.vmin.at);
+    a.vmax = (uint32_t*)(o + L.vmax.at);
     a.flags = (uint32_t*)o;
     for (int k = 0; k <= ta::PROF_MAX_BINS; ++k) c->prof.edges[k] = k <= nbins ? edges2[k] : std::numeric_limits<double>::infinity();
-    TA_HIP(hipMemcpyAsync(o + L.edges, c->prof.edges, sizeof(c->prof.edges), hipMemcpyHostToDevice, c->stream));
-    a.edges = (const double*)(o + L.edges);
+    TA_HIP(hipMemcpyAsync(o + L.edges.at, c->prof.edges, sizeof(c->prof.edges), hipMemcpyHostToDevice, c->stream));
+    a.edges = (const double*)(o + L.edges.at);
     TA_HIP(hipEventRecord(c->prof.ev[0], c->stream));
     c->prof.plan = ta::launch_profile(c->stream, a, c->itemsize, signal ? c->sig.img.itemsize : 0);
     TA_HIP(hipGetLastError());
@@ -103,38 +96,25 @@ TA_API int ta_profile_extract(ta_ctx* c, int nbins, const double* edges2, uint32
 }
 
 TA_API int ta_profile_get(ta_ctx* c, uint64_t* n, uint64_t* sum, uint64_t* sumsq, uint32_t* vmin, uint32_t* vmax) {
-    int rc = profile_ready(c);
+    int rc = results_ready(c, profile_current, NO_RESULTS);
     if (rc != TA_OK) return rc;
     if (!c->prof.with_signal && (sum || sumsq || vmin || vmax))
         return fail(TA_EINVAL, "the profile pass ran without a signal (TA_PROF_SIGNAL): it has no sum, sumsq, min or max");
-    if ((rc = profile_finish(c)) != TA_OK) return rc;
-    const uint64_t N = (uint64_t)c->prof.rows * c->prof.bins;
-    const ProfileLayout L(N, c->prof.with_signal);
-    const char* o = (const char*)c->prof.out.p;
-    if (n) TA_HIP(hipMemcpyAsync(n, o + L.n, 8 * N, hipMemcpyDeviceToHost, c->stream));
-    if (sum) TA_HIP(hipMemcpyAsync(sum, o + L.sum, 8 * N, hipMemcpyDeviceToHost, c->stream));
-    if (sumsq) TA_HIP(hipMemcpyAsync(sumsq, o + L.sumsq, 16 * N, hipMemcpyDeviceToHost, c->stream));
-    if (vmin) TA_HIP(hipMemcpyAsync(vmin, o + L.vmin, 4 * N, hipMemcpyDeviceToHost, c->stream));
-    if (vmax) TA_HIP(hipMemcpyAsync(vmax, o + L.vmax, 4 * N, hipMemcpyDeviceToHost, c->stream));
-    TA_HIP(hipStreamSynchronize(c->stream));
-    return TA_OK;
+    if ((rc = range_pass_finish(c, c->prof.out.p, NOUN)) != TA_OK) return rc;
+    const ProfileLayout L((uint64_t)c->prof.rows * c->prof.bins, c->prof.with_signal);
+    return read_columns(c, c->prof.out.p, {{n, L.n}, {sum, L.sum}, {sumsq, L.sumsq}, {vmin, L.vmin}, {vmax, L.vmax}});
 }
 
 TA_API int ta_profile_debug(ta_ctx* c, uint32_t out[4]) {
-    int rc = profile_ready(c);
-    if (rc != TA_OK) return rc;
     uint32_t spills = 0;
-    if ((rc = profile_finish(c, &spills)) != TA_OK) return rc;
-    if (out) { out[0] = spills; out[1] = 0; out[2] = c->prof.plan.tiles_per_group; out[3] = c->prof.plan.groups; }
+    int rc = results_ready(c, profile_current, NO_RESULTS);
+    if (rc != TA_OK || (rc = range_pass_finish(c, c->prof.out.p, NOUN, &spills)) != TA_OK) return rc;
+    range_debug_words(out, spills, 0, c->prof.plan);
     return TA_OK;
 }
 
 TA_API int ta_profile_timing(ta_ctx* c, double* ms) {
-    if (!c) return fail(TA_EINVAL, "ctx is NULL");
-    if (!ms) return fail(TA_EINVAL, "NULL argument");
-    int rc = profile_ready(c);
-    if (rc != TA_OK) return rc;
-    return interval_ms(c->prof.ev[0], c->prof.ev[1], ms);
+    return pass_timing(c, ms, [](ta_ctx* c) { return profile_current(c) ? c->prof.ev : nullptr; }, NO_RESULTS);
 }
 
 }  // extern "C"

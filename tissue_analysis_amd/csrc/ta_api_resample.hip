@@ -170,18 +170,13 @@ TA_API int ta_resample_outside(ta_ctx* c, uint64_t* outside) {
 }
 
 TA_API int ta_resample_timing(ta_ctx* c, double* ms) {
-    if (!c) return fail(TA_EINVAL, "ctx is NULL");
-    if (!ms) return fail(TA_EINVAL, "NULL argument");
-    if (!c->rs.valid || !c->rs.ev[1]) return fail(TA_EINVAL, "no resample pass has been run");
-    int rc = use_device(c);
-    if (rc != TA_OK) return rc;
-    return interval_ms(c->rs.ev[0], c->rs.ev[1], ms);
+    return pass_timing(c, ms, [](ta_ctx* c) { return c->rs.valid && c->rs.ev[1] ? c->rs.ev : nullptr; }, "no resample pass has been run");
 }
 
 TA_API int ta_resample_debug(ta_ctx* c, uint32_t out[4]) {
     if (!c) return fail(TA_EINVAL, "ctx is NULL");
     if (!c->rs.valid) return fail(TA_EINVAL, NO_RESULT);
-    if (out) { out[0] = c->rs.vec ? 1u : 0u; out[1] = (uint32_t)c->rs.mode; out[2] = c->rs.plan.tiles_per_group; out[3] = c->rs.plan.groups; }
+    range_debug_words(out, c->rs.vec ? 1u : 0u, (uint32_t)c->rs.mode, c->rs.plan);
     return TA_OK;
 }
 

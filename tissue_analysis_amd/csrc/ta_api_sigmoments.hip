@@ -6,21 +6,24 @@
 namespace {
 
 const char* const NO_ROWS = "no signal moments of the current extraction (run ta_sigmom_extract)";
+const char* const NOUN = "signal-moment pass";
+static_assert(ta::SM_NFLAGS == RANGE_NFLAGS && ta::SM_FLAG_RANGE == RANGE_FLAG_RANGE && ta::SM_FLAG_SPILL == RANGE_FLAG_SPILL,
+              "range_pass_finish reads these words");
 
-// byte offsets of the parts of SigMomentState::out for R rows
+// the parts of SigMomentState::out for R rows
 struct SigMomLayout {
-    uint64_t flags = 0, n, w, m1, m2, bytes;
-    explicit SigMomLayout(uint64_t R) { n = 16; w = n + 8 * R; m1 = w + 8 * R; m2 = m1 + 24 * R; bytes = m2 + 96 * R; }
+    Part flags, n, w, m1, m2;
+    uint64_t bytes = 0;
+    constexpr explicit SigMomLayout(uint64_t R) {
+        PartCursor at;
+        flags = at.take(16); n = at.take(8 * R); w = at.take(8 * R); m1 = at.take(24 * R); m2 = at.take(96 * R);
+        bytes = at.end();
+    }
 };
+static_assert(SigMomLayout(3).n.at == 16 && SigMomLayout(3).w.at == 40 && SigMomLayout(3).m1.at == 64 && SigMomLayout(3).m2.at == 136 &&
+              SigMomLayout(3).bytes == 424, "flags u32[4] | n [R] | w [R] | m1 [R][3] | m2 [R][6][2]");
 
-// drain the stream and look at the pass's flag words; spills: records that missed a workgroup's LDS table
-int sigmom_finish(ta_ctx* c, uint32_t* spills = nullptr) {
-    uint32_t flags[ta::SM_NFLAGS] = {0, 0, 0, 0};
-    if (const int rc = read_pass_flags<ta::SM_NFLAGS>(c, c->sm.out.p, flags); rc != TA_OK) return rc;
-    if (flags[ta::SM_FLAG_RANGE]) return fail(TA_ERANGE, "the signal-moment pass met a label above max_label=%u (the volume changed since ta_extract)", c->max_label);
-    if (spills) *spills = flags[ta::SM_FLAG_SPILL];
-    return TA_OK;
-}
+bool sigmom_current(const ta_ctx* c) { return pass_current(c, c->sm.seq); }
 
 }  // namespace
 
@@ -32,7 +35,7 @@ extern "C" {
 
 TA_API int ta_sigmom_extract(ta_ctx* c) {
     if (!c) return fail(TA_EINVAL, "ctx is NULL");
-    int rc = signal_pass_preflight(c, "signal-moment pass");
+    int rc = signal_pass_preflight(c, NOUN);
     if (rc != TA_OK) return rc;
     c->sm.seq = 0;
     ta::RangePlan plan;
@@ -55,10 +58,10 @@ TA_API int ta_sigmom_extract(ta_ctx* c) {
     a.n0 = c->mdims[0]; a.n1 = c->mdims[1]; a.n2 = c->mdims[2];
     a.first_owned = c->first_owned;
     a.max_label = c->max_label;
-    a.n = (unsigned long long*)(o + L.n);
-    a.w = (unsigned long long*)(o + L.w);
-    a.m1 = (unsigned long long*)(o + L.m1);
-    a.m2 = (unsigned long long*)(o + L.m2);
+    a.n = (unsigned long long*)(o + L.n.at);
+    a.w = (unsigned long long*)(o + L.w.at);
+    a.m1 = (unsigned long long*)(o + L.m1.at);
+    a.m2 = (unsigned long long*)(o + L.m2.at);
     a.flags = (uint32_t*)o;
     a.tiles_per_group = 0;
     TA_HIP(hipEventRecord(c->sm.ev[0], c->stream));
@@ -72,40 +75,22 @@ TA_API int ta_sigmom_extract(ta_ctx* c) {
 }
 
 TA_API int ta_sigmom_get(ta_ctx* c, uint64_t* n, uint64_t* w, uint64_t* m1, uint64_t* m2) {
-    if (!c) return fail(TA_EINVAL, "ctx is NULL");
-    if (!pass_current(c, c->sm.seq)) return fail(TA_EINVAL, NO_ROWS);
-    int rc = use_device(c);
-    if (rc != TA_OK) return rc;
-    if ((rc = sigmom_finish(c)) != TA_OK) return rc;
-    const uint64_t R = c->sm.rows;
-    const SigMomLayout L(R);
-    const char* o = (const char*)c->sm.out.p;
-    if (n) TA_HIP(hipMemcpyAsync(n, o + L.n, 8 * R, hipMemcpyDeviceToHost, c->stream));
-    if (w) TA_HIP(hipMemcpyAsync(w, o + L.w, 8 * R, hipMemcpyDeviceToHost, c->stream));
-    if (m1) TA_HIP(hipMemcpyAsync(m1, o + L.m1, 24 * R, hipMemcpyDeviceToHost, c->stream));
-    if (m2) TA_HIP(hipMemcpyAsync(m2, o + L.m2, 96 * R, hipMemcpyDeviceToHost, c->stream));
-    TA_HIP(hipStreamSynchronize(c->stream));
-    return TA_OK;
+    int rc = results_ready(c, sigmom_current, NO_ROWS);
+    if (rc != TA_OK || (rc = range_pass_finish(c, c->sm.out.p, NOUN)) != TA_OK) return rc;
+    const SigMomLayout L(c->sm.rows);
+    return read_columns(c, c->sm.out.p, {{n, L.n}, {w, L.w}, {m1, L.m1}, {m2, L.m2}});
 }
 
 TA_API int ta_sigmom_debug(ta_ctx* c, uint32_t out[4]) {
-    if (!c) return fail(TA_EINVAL, "ctx is NULL");
-    if (!pass_current(c, c->sm.seq)) return fail(TA_EINVAL, NO_ROWS);
-    int rc = use_device(c);
-    if (rc != TA_OK) return rc;
     uint32_t spills = 0;
-    if ((rc = sigmom_finish(c, &spills)) != TA_OK) return rc;
-    if (out) { out[0] = spills; out[1] = 0; out[2] = c->sm.plan.tiles_per_group; out[3] = c->sm.plan.groups; }
+    int rc = results_ready(c, sigmom_current, NO_ROWS);
+    if (rc != TA_OK || (rc = range_pass_finish(c, c->sm.out.p, NOUN, &spills)) != TA_OK) return rc;
+    range_debug_words(out, spills, 0, c->sm.plan);
     return TA_OK;
 }
 
 TA_API int ta_sigmom_timing(ta_ctx* c, double* ms) {
-    if (!c) return fail(TA_EINVAL, "ctx is NULL");
-    if (!ms) return fail(TA_EINVAL, "NULL argument");
-    if (c->sm.seq == 0 || !c->sm.ev[1]) return fail(TA_EINVAL, "no signal-moment pass has been run");
-    int rc = use_device(c);
-    if (rc != TA_OK) return rc;
-    return interval_ms(c->sm.ev[0], c->sm.ev[1], ms);
+    return pass_timing(c, ms, [](ta_ctx* c) { return c->sm.seq != 0 && c->sm.ev[1] ? c->sm.ev : nullptr; }, "no signal-moment pass has been run");
 }
 
 }  // extern "C"

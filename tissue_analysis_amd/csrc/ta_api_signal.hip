@@ -7,14 +7,26 @@ namespace {
 
 constexpr CompanionKind SIGNAL = {"the signal", 1, 2};      // uint8 or uint16
 
-// byte offsets of the parts of SignalState::out for R rows and P pairs
+// the parts of SignalState::out for R rows and P pairs
 struct SignalLayout {
-    uint64_t flags = 0, n, sum, sumsq, vmin, vmax, side_lo, side_hi, bytes;
-    SignalLayout(uint64_t R, uint64_t P) {
-        n = 16; sum = n + 8 * R; sumsq = sum + 8 * R; vmin = sumsq + 16 * R; vmax = vmin + 4 * R;
-        side_lo = vmax + 4 * R; side_hi = side_lo + 8 * P; bytes = side_hi + 8 * P;
+    Part flags, n, sum, sumsq, vmin, vmax, side_lo, side_hi;
+    uint64_t bytes = 0;
+    constexpr SignalLayout(uint64_t R, uint64_t P) {
+        PartCursor at;
+        flags = at.take(16); n = at.take(8 * R); sum = at.take(8 * R); sumsq = at.take(16 * R); vmin = at.take(4 * R); vmax = at.take(4 * R);
+        side_lo = at.take(8 * P); side_hi = at.take(8 * P);
+        bytes = at.end();
     }
 };
+static_assert(SignalLayout(3, 2).n.at == 16 && SignalLayout(3, 2).sumsq.at == 64 && SignalLayout(3, 2).vmin.at == 112 && SignalLayout(3, 2).vmax.at == 124 &&
+              SignalLayout(3, 2).side_lo.at == 136 && SignalLayout(3, 2).side_hi.at == 152 && SignalLayout(3, 2).bytes == 168,
+              "flags u32[4] | n [R] | sum [R] | sumsq [R][2] | min u32[R] | max u32[R] | side_lo [P] | side_hi [P]");
+
+const char* const NO_LABELS = "no per-label signal results for the current extraction (run ta_signal_extract with TA_SIG_LABELS)";
+const char* const NO_WALLS = "no per-wall signal results for the current extraction (run ta_signal_extract with TA_SIG_WALLS)";
+bool signal_current(const ta_ctx* c) { return pass_current(c, c->sig.seq); }
+bool signal_labels_current(const ta_ctx* c) { return signal_current(c) && (c->sig.what & TA_SIG_LABELS); }
+bool signal_walls_current(const ta_ctx* c) { return signal_current(c) && (c->sig.what & TA_SIG_WALLS) && !c->exchanged; }
 
 // drain the stream and look at the pass's flag words; spills: label records, pair records that missed a workgroup's LDS tables
 int signal_finish(ta_ctx* c, uint32_t* spills = nullptr) {
@@ -95,19 +107,19 @@ TA_API int ta_signal_extract(ta_ctx* c, uint32_t what) {
     }
     char* o = (char*)c->sig.out.p;
     TA_HIP(hipMemsetAsync(o, 0, L.bytes, c->stream));
-    TA_HIP(hipMemsetAsync(o + L.vmin, 0xff, 4 * R, c->stream));
+    TA_HIP(hipMemsetAsync(o + L.vmin.at, 0xff, L.vmin.bytes, c->stream));
     a.vol = sweep_vol(c);
     a.sig = c->sig.img.p;
     a.n0 = c->mdims[0]; a.n1 = c->mdims[1]; a.n2 = c->mdims[2];
     a.first_owned = c->first_owned;
     a.max_label = c->max_label;
-    a.n = (unsigned long long*)(o + L.n);
-    a.sum = (unsigned long long*)(o + L.sum);
-    a.sumsq = (unsigned long long*)(o + L.sumsq);
-    a.vmin = (uint32_t*)(o + L.vmin);
-    a.vmax = (uint32_t*)(o + L.vmax);
-    a.side_lo = (unsigned long long*)(o + L.side_lo);
-    a.side_hi = (unsigned long long*)(o + L.side_hi);
+    a.n = (unsigned long long*)(o + L.n.at);
+    a.sum = (unsigned long long*)(o + L.sum.at);
+    a.sumsq = (unsigned long long*)(o + L.sumsq.at);
+    a.vmin = (uint32_t*)(o + L.vmin.at);
+    a.vmax = (uint32_t*)(o + L.vmax.at);
+    a.side_lo = (unsigned long long*)(o + L.side_lo.at);
+    a.side_hi = (unsigned long long*)(o + L.side_hi.at);
     a.flags = (uint32_t*)o;
     a.tiles_per_group = 0;
     TA_HIP(hipEventRecord(c->sig.ev[0], c->stream));
@@ -122,58 +134,29 @@ TA_API int ta_signal_extract(ta_ctx* c, uint32_t what) {
 }
 
 TA_API int ta_signal_get_labels(ta_ctx* c, uint64_t* n, uint64_t* sum, uint64_t* sumsq, uint32_t* vmin, uint32_t* vmax) {
-    if (!c) return fail(TA_EINVAL, "ctx is NULL");
-    if (!pass_current(c, c->sig.seq) || !(c->sig.what & TA_SIG_LABELS))
-        return fail(TA_EINVAL, "no per-label signal results for the current extraction (run ta_signal_extract with TA_SIG_LABELS)");
-    int rc = use_device(c);
-    if (rc != TA_OK) return rc;
-    if ((rc = signal_finish(c)) != TA_OK) return rc;
-    const uint64_t R = c->sig.rows;
-    const SignalLayout L(R, (uint64_t)c->sig.npairs);
-    const char* o = (const char*)c->sig.out.p;
-    if (n) TA_HIP(hipMemcpyAsync(n, o + L.n, 8 * R, hipMemcpyDeviceToHost, c->stream));
-    if (sum) TA_HIP(hipMemcpyAsync(sum, o + L.sum, 8 * R, hipMemcpyDeviceToHost, c->stream));
-    if (sumsq) TA_HIP(hipMemcpyAsync(sumsq, o + L.sumsq, 16 * R, hipMemcpyDeviceToHost, c->stream));
-    if (vmin) TA_HIP(hipMemcpyAsync(vmin, o + L.vmin, 4 * R, hipMemcpyDeviceToHost, c->stream));
-    if (vmax) TA_HIP(hipMemcpyAsync(vmax, o + L.vmax, 4 * R, hipMemcpyDeviceToHost, c->stream));
-    TA_HIP(hipStreamSynchronize(c->stream));
-    return TA_OK;
+    int rc = results_ready(c, signal_labels_current, NO_LABELS);
+    if (rc != TA_OK || (rc = signal_finish(c)) != TA_OK) return rc;
+    const SignalLayout L(c->sig.rows, (uint64_t)c->sig.npairs);
+    return read_columns(c, c->sig.out.p, {{n, L.n}, {sum, L.sum}, {sumsq, L.sumsq}, {vmin, L.vmin}, {vmax, L.vmax}});
 }
 
 TA_API int ta_signal_get_walls(ta_ctx* c, uint64_t* side_lo, uint64_t* side_hi) {
-    if (!c) return fail(TA_EINVAL, "ctx is NULL");
-    if (!pass_current(c, c->sig.seq) || !(c->sig.what & TA_SIG_WALLS) || c->exchanged)
-        return fail(TA_EINVAL, "no per-wall signal results for the current extraction (run ta_signal_extract with TA_SIG_WALLS)");
-    int rc = use_device(c);
-    if (rc != TA_OK) return rc;
-    if ((rc = signal_finish(c)) != TA_OK) return rc;
-    const uint64_t P = (uint64_t)c->sig.npairs;
-    const SignalLayout L(c->sig.rows, P);
-    const char* o = (const char*)c->sig.out.p;
-    if (side_lo && P) TA_HIP(hipMemcpyAsync(side_lo, o + L.side_lo, 8 * P, hipMemcpyDeviceToHost, c->stream));
-    if (side_hi && P) TA_HIP(hipMemcpyAsync(side_hi, o + L.side_hi, 8 * P, hipMemcpyDeviceToHost, c->stream));
-    TA_HIP(hipStreamSynchronize(c->stream));
-    return TA_OK;
+    int rc = results_ready(c, signal_walls_current, NO_WALLS);
+    if (rc != TA_OK || (rc = signal_finish(c)) != TA_OK) return rc;
+    const SignalLayout L(c->sig.rows, (uint64_t)c->sig.npairs);
+    return read_columns(c, c->sig.out.p, {{side_lo, L.side_lo}, {side_hi, L.side_hi}});
 }
 
 TA_API int ta_signal_debug(ta_ctx* c, uint32_t out[4]) {
-    if (!c) return fail(TA_EINVAL, "ctx is NULL");
-    if (!pass_current(c, c->sig.seq)) return fail(TA_EINVAL, "no signal results for the current extraction (run ta_signal_extract)");
-    int rc = use_device(c);
-    if (rc != TA_OK) return rc;
     uint32_t spills[2] = {0, 0};
-    if ((rc = signal_finish(c, spills)) != TA_OK) return rc;
-    if (out) { out[0] = spills[0]; out[1] = spills[1]; out[2] = c->sig.plan.tiles_per_group; out[3] = c->sig.plan.groups; }
+    int rc = results_ready(c, signal_current, "no signal results for the current extraction (run ta_signal_extract)");
+    if (rc != TA_OK || (rc = signal_finish(c, spills)) != TA_OK) return rc;
+    range_debug_words(out, spills[0], spills[1], c->sig.plan);
     return TA_OK;
 }
 
 TA_API int ta_signal_timing(ta_ctx* c, double* ms) {
-    if (!c) return fail(TA_EINVAL, "ctx is NULL");
-    if (!ms) return fail(TA_EINVAL, "NULL argument");
-    if (c->sig.seq == 0 || !c->sig.ev[1]) return fail(TA_EINVAL, "no signal pass has been run");
-    int rc = use_device(c);
-    if (rc != TA_OK) return rc;
-    return interval_ms(c->sig.ev[0], c->sig.ev[1], ms);
+    return pass_timing(c, ms, [](ta_ctx* c) { return c->sig.seq != 0 && c->sig.ev[1] ? c->sig.ev : nullptr; }, "no signal pass has been run");
 }
 
 }  // extern "C"

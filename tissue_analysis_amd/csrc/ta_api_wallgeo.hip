@@ -5,7 +5,21 @@
 
 namespace {
 
+const char* const NO_ROWS = "no wall-geometry rows for the current extraction (run ta_wallgeo_extract)";
+
 bool wallgeo_current(const ta_ctx* c) { return pass_current(c, c->wg.seq) && !c->exchanged; }
+
+// the parts of WallGeoState::out for P pairs
+struct WallGeoLayout {
+    Part flags, rows;
+    uint64_t bytes = 0;
+    constexpr explicit WallGeoLayout(uint64_t P) {
+        PartCursor at;
+        flags = at.take(16); rows = at.take(P * ta::WG_ROW * 8);
+        bytes = at.end();
+    }
+};
+static_assert(ta::WG_ROW == 15 && WallGeoLayout(2).rows.at == 16 && WallGeoLayout(2).bytes == 256, "flags u32[4] | rows u64[P][15]");
 
 // drain the stream and look at the pass's flag words
 int wallgeo_finish(ta_ctx* c, uint32_t* spills) {
@@ -40,18 +54,18 @@ TA_API int ta_wallgeo_extract(ta_ctx* c) {
             return fail(TA_ERANGE, "the second sums of a wall of this volume may not fit 64 bits (3 nvox (2 extent)^2 >= 2^64)");
     }
     const uint64_t P = (uint64_t)c->npairs;
-    const uint64_t bytes = 16 + P * ta::WG_ROW * 8;
-    if ((rc = c->wg.out.reserve(bytes)) != TA_OK) return rc;
+    const WallGeoLayout L(P);
+    if ((rc = c->wg.out.reserve(L.bytes)) != TA_OK) return rc;
     if ((rc = ensure_events(c->wg.ev)) != TA_OK) return rc;
     ta::WallGeoArgs a = {};
     if (P && (rc = build_pair_index(c, c->wg.hash, &a.hkeys, &a.hrows, &a.hmask)) != TA_OK) return rc;
     char* o = (char*)c->wg.out.p;
-    TA_HIP(hipMemsetAsync(o, 0, bytes, c->stream));
+    TA_HIP(hipMemsetAsync(o, 0, L.bytes, c->stream));
     a.vol = sweep_vol(c);
     a.n0 = c->mdims[0]; a.n1 = c->mdims[1]; a.n2 = c->mdims[2];
     a.first_owned = c->first_owned;
     a.origin0 = c->a_origin - c->first_owned;
-    a.rows = (unsigned long long*)(o + 16);
+    a.rows = (unsigned long long*)(o + L.rows.at);
     a.flags = (uint32_t*)o;
     TA_HIP(hipEventRecord(c->wg.ev[0], c->stream));
     // (a volume of one label has no pair and no row to add to: nothing to launch)
@@ -64,22 +78,16 @@ TA_API int ta_wallgeo_extract(ta_ctx* c) {
 }
 
 TA_API int ta_wallgeo_get(ta_ctx* c, uint64_t* fwd, uint64_t* rev, uint64_t* sum1, uint64_t* sum2) {
-    if (!c) return fail(TA_EINVAL, "ctx is NULL");
-    if (!wallgeo_current(c)) return fail(TA_EINVAL, "no wall-geometry rows for the current extraction (run ta_wallgeo_extract)");
-    int rc = use_device(c);
-    if (rc != TA_OK) return rc;
-    if ((rc = wallgeo_finish(c, nullptr)) != TA_OK) return rc;
+    int rc = results_ready(c, wallgeo_current, NO_ROWS);
+    if (rc != TA_OK || (rc = wallgeo_finish(c, nullptr)) != TA_OK) return rc;
     const uint64_t P = (uint64_t)c->wg.npairs;
     if (!P || (!fwd && !rev && !sum1 && !sum2)) return TA_OK;
     std::vector<uint64_t> h;
     try { h.resize(P * ta::WG_ROW); } catch (...) { return fail(TA_ENOMEM, "no host memory for %llu wall rows", (unsigned long long)P); }
-    TA_HIP(hipMemcpyAsync(h.data(), (const char*)c->wg.out.p + 16, P * ta::WG_ROW * 8, hipMemcpyDeviceToHost, c->stream));
-    TA_HIP(hipStreamSynchronize(c->stream));
+    if ((rc = read_columns(c, c->wg.out.p, {{h.data(), WallGeoLayout(P).rows}})) != TA_OK) return rc;
     // the device rows are in memory-axis order: to array axes
-    auto pair_slot = [](int x, int y) { if (x > y) std::swap(x, y); return x == 0 ? y : (x == 1 ? 2 + y : 5); };
-    static const int mem_pair[6][2] = {{0, 0}, {0, 1}, {0, 2}, {1, 1}, {1, 2}, {2, 2}};
     int slot[6];
-    for (int q = 0; q < 6; ++q) slot[q] = pair_slot(c->perm[mem_pair[q][0]], c->perm[mem_pair[q][1]]);
+    moment_slots(c, slot);
     for (uint64_t i = 0; i < P; ++i) {
         const uint64_t* r = h.data() + i * ta::WG_ROW;
         for (int k = 0; k < 3; ++k) {
@@ -93,31 +101,20 @@ TA_API int ta_wallgeo_get(ta_ctx* c, uint64_t* fwd, uint64_t* rev, uint64_t* sum
 }
 
 TA_API int ta_wallgeo_spills(ta_ctx* c, uint32_t* spills) {
-    if (!c) return fail(TA_EINVAL, "ctx is NULL");
-    if (!wallgeo_current(c)) return fail(TA_EINVAL, "no wall-geometry rows for the current extraction (run ta_wallgeo_extract)");
-    int rc = use_device(c);
-    if (rc != TA_OK) return rc;
-    return wallgeo_finish(c, spills);
+    const int rc = results_ready(c, wallgeo_current, NO_ROWS);
+    return rc != TA_OK ? rc : wallgeo_finish(c, spills);
 }
 
 TA_API int ta_wallgeo_debug(ta_ctx* c, uint32_t out[4]) {
-    if (!c) return fail(TA_EINVAL, "ctx is NULL");
-    if (!wallgeo_current(c)) return fail(TA_EINVAL, "no wall-geometry rows for the current extraction (run ta_wallgeo_extract)");
-    int rc = use_device(c);
-    if (rc != TA_OK) return rc;
     uint32_t spills = 0;
-    if ((rc = wallgeo_finish(c, &spills)) != TA_OK) return rc;
-    if (out) { out[0] = spills; out[1] = 0u; out[2] = c->wg.plan.tiles_per_group; out[3] = c->wg.plan.groups; }
+    int rc = results_ready(c, wallgeo_current, NO_ROWS);
+    if (rc != TA_OK || (rc = wallgeo_finish(c, &spills)) != TA_OK) return rc;
+    range_debug_words(out, spills, 0, c->wg.plan);
     return TA_OK;
 }
 
 TA_API int ta_wallgeo_timing(ta_ctx* c, double* ms) {
-    if (!c) return fail(TA_EINVAL, "ctx is NULL");
-    if (!ms) return fail(TA_EINVAL, "NULL argument");
-    if (c->wg.seq == 0 || !c->wg.ev[1]) return fail(TA_EINVAL, "no wall-geometry pass has been run");
-    int rc = use_device(c);
-    if (rc != TA_OK) return rc;
-    return interval_ms(c->wg.ev[0], c->wg.ev[1], ms);
+    return pass_timing(c, ms, [](ta_ctx* c) { return c->wg.seq != 0 && c->wg.ev[1] ? c->wg.ev : nullptr; }, "no wall-geometry pass has been run");
 }
 
 }  // extern "C"

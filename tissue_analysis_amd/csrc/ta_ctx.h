@@ -4,16 +4,20 @@
 // the rank exchange; ta_api_<feature>.hip a feature.  What crosses files is declared here, with the file that defines it; the small
 // checks that several features repeat are inline below the context (the plane range of a ta_*_image call, an id as the volume
 // stores it, a feature's timed intervals, what the passes over a settled extraction share -- the "current" predicate, the entry
-// checks, the read of a pass's flag words -- and the entry checks of the two separable transforms, whose column-pass geometry and
-// batch plan are in ta_separable.h; the launch plan of the range passes is in ta_range_plan.h).
+// checks, the read of a pass's flag words -- what the getters share -- one ready check, one read-back of the columns of a buffer
+// whose parts a layout struct names through the cursor of ta_parts.h, one timing path, the debug words of a range pass, the guard
+// of a host allocation, the two pieces of axis arithmetic -- and the entry checks of the two separable transforms, whose
+// column-pass geometry and batch plan are in ta_separable.h; the launch plan of the range passes is in ta_range_plan.h).
 #pragma once
 #include "../../include/tissue_scan.h"
 #include "ta_kernels.h"
 #include "ta_nearest.h"
+#include "ta_parts.h"
 
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <initializer_list>
 #include <string>
 #include <vector>
 
@@ -68,13 +72,15 @@ inline int interval_ms(hipEvent_t a, hipEvent_t b, double* ms) {      // (both r
     return elapsed_ms(a, b, ms);
 }
 
-// the workspace of launch_radix_sort_u32 / _u64 for n records, as byte offsets from `at`: keys (of key_bytes) x 2 | index u32 x 2 | temp
+// the workspace of launch_radix_sort_u32 / _u64 for n records, as byte offsets from `from` (a multiple of 16): keys (of key_bytes) x 2 |
+// index u32 x 2 | temp, each from a multiple of 16
 struct SortLayout {
     uint64_t keys[2], idx[2], temp, end;
-    SortLayout(uint64_t n, int key_bytes, uint64_t at = 0) {
-        for (auto& k : keys) { k = at; at += align16(n * key_bytes); }
-        for (auto& i : idx) { i = at; at += align16(n * 4); }
-        temp = at; end = at + align16(ta::wall_sort_temp_bytes(n));
+    SortLayout(uint64_t n, int key_bytes, uint64_t from = 0) {
+        PartCursor at(from);
+        for (auto& k : keys) k = at.take(n * key_bytes, 16).at;
+        for (auto& i : idx) i = at.take(n * 4, 16).at;
+        temp = at.take(ta::wall_sort_temp_bytes(n), 16).at; end = at.end(16);
     }
 };
 
@@ -418,6 +424,71 @@ template <int N> int read_pass_flags(ta_ctx* c, const void* dev, uint32_t* flags
     TA_HIP(hipStreamSynchronize(c->stream));
     return TA_OK;
 }
+// ... of a range pass whose words are RANGE = 0 (a label above max_label), SPILL = 1 (records that missed a workgroup's LDS table),
+// of `sets` (1 or 2) passes in a row at `dev`; `noun` is what the message calls the pass; spills: those of the last set
+constexpr int RANGE_NFLAGS = 4, RANGE_FLAG_RANGE = 0, RANGE_FLAG_SPILL = 1;
+inline int range_pass_finish(ta_ctx* c, const void* dev, const char* noun, uint32_t* spills = nullptr, int sets = 1) {
+    uint32_t f[2 * RANGE_NFLAGS] = {0, 0, 0, 0, 0, 0, 0, 0};
+    const int rc = sets == 2 ? read_pass_flags<2 * RANGE_NFLAGS>(c, dev, f) : read_pass_flags<RANGE_NFLAGS>(c, dev, f);
+    if (rc != TA_OK) return rc;
+    if (f[RANGE_FLAG_RANGE] || f[RANGE_NFLAGS + RANGE_FLAG_RANGE])
+        return fail(TA_ERANGE, "the %s met a label above max_label=%u (the volume changed since ta_extract)", noun, c->max_label);
+    if (spills) *spills = f[(sets - 1) * RANGE_NFLAGS + RANGE_FLAG_SPILL];
+    return TA_OK;
+}
+// the four words of a range pass's ta_*_debug: two of its own (spills first, where it counts them), then the launch plan
+inline void range_debug_words(uint32_t out[4], uint32_t first, uint32_t second, const ta::RangePlan& plan) {
+    if (out) { out[0] = first; out[1] = second; out[2] = plan.tiles_per_group; out[3] = plan.groups; }
+}
+
+// What the getters share.  results_ready: the entry checks of a getter whose results are tagged with an extraction (or a volume);
+// `current(c)` is the table's own predicate, asked only of a context that is there; `no_results` the feature's own message.
+template <class Current> int results_ready(ta_ctx* c, Current current, const char* no_results) {
+    if (!c) return fail(TA_EINVAL, "ctx is NULL");
+    if (!current(c)) return fail(TA_EINVAL, "%s", no_results);
+    return use_device(c);
+}
+// read_columns: the parts of the buffer at `base` into the host arrays that want them (a NULL destination, an empty part: skipped),
+// in list order, then one drain of the stream
+struct Column { void* dst; Part part; };
+inline int read_columns(ta_ctx* c, const void* base, std::initializer_list<Column> columns) {
+    for (const Column& col : columns)
+        if (col.dst && col.part.bytes)
+            TA_HIP(hipMemcpyAsync(col.dst, (const char*)base + col.part.at, col.part.bytes, hipMemcpyDeviceToHost, c->stream));
+    TA_HIP(hipStreamSynchronize(c->stream));
+    return TA_OK;
+}
+// pass_timing: a ta_*_timing of one interval; `events(c)` gives the two events of a pass that "has run" by the feature's own
+// rule, NULL otherwise (`none` is its message then)
+template <class Events> int pass_timing(ta_ctx* c, double* ms, Events events, const char* none) {
+    if (!c) return fail(TA_EINVAL, "ctx is NULL");
+    if (!ms) return fail(TA_EINVAL, "NULL argument");
+    hipEvent_t* ev = events(c);
+    if (!ev) return fail(TA_EINVAL, "%s", none);
+    const int rc = use_device(c);
+    return rc != TA_OK ? rc : interval_ms(ev[0], ev[1], ms);
+}
+// host_alloc: host allocations of an entry point run inside it, so that no exception leaves an extern "C" function
+template <class Allocate> int host_alloc(Allocate allocate) {
+    try { allocate(); } catch (...) { return fail(TA_ENOMEM, "out of host memory"); }
+    return TA_OK;
+}
+
+// Axis arithmetic.  moment_slots: second moments come in the order 00 01 02 11 12 22 of their axis pair; slot[q] is where the
+// q-th pair of MEMORY axes lies among the pairs of ARRAY axes.  array_key_strides: the stride of memory axis k in a key that
+// counts voxels in the C order of the ARRAY axes.
+inline void moment_slots(const ta_ctx* c, int slot[6]) {
+    auto pair_slot = [](int x, int y) { if (x > y) std::swap(x, y); return x == 0 ? y : (x == 1 ? 2 + y : 5); };
+    static const int mem_pair[6][2] = {{0, 0}, {0, 1}, {0, 2}, {1, 1}, {1, 2}, {2, 2}};
+    for (int q = 0; q < 6; ++q) slot[q] = pair_slot(c->perm[mem_pair[q][0]], c->perm[mem_pair[q][1]]);
+}
+inline void array_dims(const ta_ctx* c, int64_t dims[3]) { for (int k = 0; k < 3; ++k) dims[c->perm[k]] = c->mdims[k]; }
+inline void array_key_strides(const ta_ctx* c, uint64_t key_stride[3]) {
+    int64_t dims[3];
+    array_dims(c, dims);
+    const uint64_t array_stride[3] = {(uint64_t)dims[1] * (uint64_t)dims[2], (uint64_t)dims[2], 1ull};
+    for (int k = 0; k < 3; ++k) key_stride[k] = array_stride[c->perm[k]];
+}
 
 inline uint64_t voxels(const ta_ctx* c) { return (uint64_t)c->mdims[0] * (uint64_t)c->mdims[1] * (uint64_t)c->mdims[2]; }
 
@@ -452,7 +523,7 @@ inline int two_intervals_ms(hipEvent_t (&ev)[3], double* ms_first, double* ms_se
 
 // The whole-volume separable transforms (ta_api_distance.hip, ta_api_nearest.hip; `noun` is what their messages call the pass, "distance pass").
 // Their entry checks run in this order: check_spacing, then transform_preflight, which settles the extraction the pass reads and
-// fills w, the spacing of memory axis k.  transform_ready: a getter's context holds results of the current extraction (seq).
+// fills w, the spacing of memory axis k.
 inline int check_spacing(const double spacing[3]) {
     if (!spacing) return fail(TA_EINVAL, "spacing is NULL");
     for (int k = 0; k < 3; ++k)
@@ -467,10 +538,6 @@ inline int transform_preflight(ta_ctx* c, const char* noun, const double spacing
     if (rc != TA_OK) return rc;
     for (int k = 0; k < 3; ++k) w[k] = spacing[c->perm[k]];
     return TA_OK;
-}
-inline int transform_ready(ta_ctx* c, uint64_t seq, const char* no_results) {
-    if (!pass_current(c, seq)) return fail(TA_EINVAL, no_results);
-    return use_device(c);
 }
 inline int check_batch_option(const ta_ctx* c, int64_t columns) {
     if (!c) return fail(TA_EINVAL, "ctx is NULL");
