@@ -68,6 +68,11 @@ def component_plan(dims):
     return ComponentPlan(_ceil(n0, TP) * _ceil(n1, TR) * _ceil(n2, TC), rows, groups, _ceil(rows, groups), seams, _ceil(seams, THREADS))
 
 
+def component_waves(dims):
+    """The waves of the kernels that count and hand out the slots (the counts the scan takes): four per 1024 voxels."""
+    return 4 * _ceil(int(dims[0]) * int(dims[1]) * int(dims[2]), 1024)
+
+
 def column_seams_of_trip(dims, trip):
     """The columns c (the voxel behind a tile face along the fast axis) that the seam pass's threads reach in trip `trip` (from 0)."""
     n2 = int(dims[2])

@@ -83,6 +83,39 @@ def test_many_rows(name, dtype):
     assert p.seam_groups == ll.CC_SEAM_MAX_GROUPS < p.rows and p.seam_row_trips == 2       # fewer workgroups than rows
 
 
+SCAN_PER_BLOCK = 2048               # counts a workgroup of the scan of the per-wave root counts takes (csrc/ta_counted.h)
+# The count has ll.component_waves(dims) waves, four per 1024 voxels: the fewest voxels that give exactly SCAN_PER_BLOCK waves,
+# and the fewest that give more -- SCAN_PER_BLOCK + 4, for no volume has SCAN_PER_BLOCK + 1 -- in three factors each (2^19 + 1 =
+# 3 x 174763 has no third factor: the second volume is two voxels past the threshold)
+SCAN_EDGE_DIMS = {SCAN_PER_BLOCK: (5, 229, 457), SCAN_PER_BLOCK + 4: (37, 109, 130)}
+
+
+@functools.lru_cache(maxsize=None)
+def scan_edge_reference(waves):
+    V = synth.voronoi_labels(SCAN_EDGE_DIMS[waves], 200, waves)
+    V.setflags(write=False)
+    return V, ref.table(V)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("waves", sorted(SCAN_EDGE_DIMS))
+def test_a_count_of_one_scan_block_and_of_the_next_size(waves, dtype):
+    dims = SCAN_EDGE_DIMS[waves]
+    voxels = dims[0] * dims[1] * dims[2]
+    assert ll.component_waves(dims) == waves and 4 * ((voxels - 2 + 1023) // 1024) == waves - 4   # two voxels fewer: four waves fewer
+    V, want = scan_edge_reference(waves)
+    assert want[0][0].size >= 200
+    check(V.astype(dtype), want)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_a_volume_of_one_label_is_one_row(dtype):
+    V = np.full((4, 6, 72), 7, dtype=dtype)
+    want = ref.table(V)
+    assert want[0][0].tolist() == [7] and want[0][1].tolist() == [V.size]
+    check(V, want)
+
+
 @pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("make", [ll.runs_isolated, ll.runs_joined])
 def test_run_lengths(make, dtype):

@@ -79,6 +79,43 @@ def test_more_records_than_the_key_kernel_has_threads(dtype):
     assert groups == ll.JN_KEY_MAX_GROUPS < (records + 255) // 256 and trips == 2
 
 
+SCAN_PER_BLOCK = 2048               # counts a workgroup of the scan of the walk's per-task counts takes (csrc/ta_counted.h)
+# the smallest volumes with 2 x 2 x 2 blocks whose walk has exactly SCAN_PER_BLOCK tasks, and one more: a task is two rows of blocks
+SCAN_EDGE_DIMS = {SCAN_PER_BLOCK: (2, 4096, 2), SCAN_PER_BLOCK + 1: (2, 4098, 2)}
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("tasks", sorted(SCAN_EDGE_DIMS))
+def test_a_walk_of_one_scan_block_and_of_one_task_more(tasks, dtype):
+    dims = SCAN_EDGE_DIMS[tasks]
+    itemsize = np.dtype(dtype).itemsize
+    assert ll.junction_plan(dims, itemsize).tasks == tasks
+    assert ll.junction_plan((dims[0], dims[1] - 1, dims[2]), itemsize).tasks == tasks - 1     # (thinner: no 2 x 2 x 2 block is left)
+    V = np.random.default_rng(tasks).integers(1, 5, size=dims).astype(dtype)         # four labels: edges and vertices in every task
+    want = ref.tables(V)
+    assert want[0][1].size == 4 and want[1][1].size == 1 and int(want[1][1][0]) > tasks // 2 and want[2] == 0
+    ctx = _capi.Context(0)
+    try:
+        got, debug = run(ctx, V)
+    finally:
+        ctx.close()
+    same_tables(got, want)
+    assert debug == dict(tasks=tasks, edge_key_groups=ll.junction_key_groups(int(want[0][1].sum()))[0],
+                         vertex_key_groups=ll.junction_key_groups(int(want[1][1].sum()))[0])
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_a_volume_of_one_label_has_no_rows(dtype):
+    ctx = _capi.Context(0)
+    try:
+        got, debug = run(ctx, np.full((4, 6, 72), 7, dtype=dtype))
+    finally:
+        ctx.close()
+    (el, en, es), (vl, vn, vs), degenerate = got
+    assert el.shape == (0, 3) and vl.shape == (0, 4) and en.size == es.size == vn.size == vs.size == 0 and degenerate == 0
+    assert debug == dict(tasks=ll.junction_plan((4, 6, 72), np.dtype(dtype).itemsize).tasks, edge_key_groups=0, vertex_key_groups=0)
+
+
 def test_debug_is_valid_when_the_getters_are():
     V = synth.voronoi_labels((10, 12, 40), 30, 3, dtype=np.uint16)
     ctx = _capi.Context(0)

@@ -155,6 +155,23 @@ def test_a_context_after_its_table_grew():
         ctx.close()
 
 
+@pytest.mark.parametrize("dtype", [np.uint16, np.uint32], ids=["u16", "u32"])
+def test_the_sort_of_a_pair_list_with_one_bucket_more_than_a_scan_block(dtype):
+    """ta_adjacency_get sorts the pairs by counting them into max_label + 3 buckets and scanning the counts, 2048 a workgroup
+    (SCAN_PER_BLOCK of csrc/ta_counted.h): max_label = 2046 gives 2049 buckets, and the pairs of the largest label lie in the
+    second scan block."""
+    vol = voronoi((9, 12, 40), 6, 43, dtype)
+    top = int(vol.max())
+    vol[vol == top] = 2046
+    want = onepass_c.extract(vol)
+    assert int(want["max_label"]) + 3 == 2048 + 1 and int((want["pair_hi"] == 2046).sum()) > 0 and want["pair_lo"].size > 5
+    ctx = _context(8)
+    try:
+        _extract(ctx, vol, want, "2049 buckets %s" % np.dtype(dtype).name)
+    finally:
+        ctx.close()
+
+
 @pytest.mark.parametrize("dtype,shape", [(np.uint16, None), (np.uint32, 0), (np.uint32, 1)], ids=["u16", "u32-narrow", "u32-wide"])
 def test_the_spill_paths_insert_into_a_tiny_table(dtype, shape):
     """Thousands of cells of 30 voxels: a tile holds more labels and more pairs than its LDS tables, so the tile flush and both

@@ -150,9 +150,18 @@ def _flat_symmetric_walls():
     return v
 
 
+def _one_record_more_than_a_scan_block():
+    """2049 records: the scan that ranks the walls' first records takes 2048 flags a workgroup (SCAN_PER_BLOCK of csrc/ta_counted.h)."""
+    from helpers import brute_wall_records
+    v = voronoi((9, 11, 23), 10, 26, np.uint16)
+    assert brute_wall_records(v)[0].size == 2048 + 1
+    return v
+
+
 @pytest.mark.parametrize("make", [lambda: voronoi((36, 40, 44), 40, 71, np.uint16), lambda: voronoi((30, 28, 260), 50, 72, np.uint32),
-                                  _flat_symmetric_walls, lambda: random_blocks((14, 18, 30), 60, 73, np.uint32)],
-                         ids=["voronoi_u16", "voronoi_u32", "flat_symmetric", "blocks_u32"])
+                                  _flat_symmetric_walls, lambda: random_blocks((14, 18, 30), 60, 73, np.uint32),
+                                  _one_record_more_than_a_scan_block],
+                         ids=["voronoi_u16", "voronoi_u32", "flat_symmetric", "blocks_u32", "records_2049"])
 def test_wall_medians_on_the_device_equal_the_host_arithmetic(gpu_ctx, make):
     """ta_wall_medians (one wave a wall: the reference's Weiszfeld rules in IEEE double, sums in record order, truncation,
     nearest wall voxel) against geometry.median_voxels on the records the device grouped by pair: the same voxel for EVERY wall."""

@@ -19,7 +19,7 @@ SOURCES = ["ta_api.hip", "ta_api_walls.hip", "ta_api_sparse.hip", "ta_api_exchan
            "kernels_basic.hip", "kernels_scan.hip", "kernels_walls.hip", "kernels_wallsort.hip", "kernels_wallmedian.hip", "kernels_census.hip",
            "kernels_pairsort.hip", "kernels_signal.hip", "kernels_mesh.hip", "kernels_overlap.hip", "kernels_junctions.hip", "kernels_wallgeo.hip",
            "kernels_components.hip", "kernels_distance.hip", "kernels_nearest.hip", "kernels_profile.hip", "kernels_sighist.hip", "kernels_sigmoments.hip", "kernels_topology.hip", "kernels_resample.hip"]
-HEADERS = ["ta_ctx.h", "ta_parts.h", "ta_device.h", "ta_range_plan.h", "ta_kernels.h", "ta_sweep_common.h", "ta_sweep_switches.h", "ta_pin_tables.inc", "ta_signal.h", "ta_mesh.h", "ta_overlap.h", "ta_junctions.h", "ta_wallgeo.h", "ta_components.h", "ta_distance.h", "ta_nearest.h", "ta_separable.h", "ta_profile.h", "ta_sighist.h", "ta_sigmoments.h", "ta_topology.h", "ta_resample.h",
+HEADERS = ["ta_ctx.h", "ta_parts.h", "ta_counted.h", "ta_device.h", "ta_range_plan.h", "ta_kernels.h", "ta_sweep_common.h", "ta_sweep_switches.h", "ta_pin_tables.inc", "ta_signal.h", "ta_mesh.h", "ta_overlap.h", "ta_junctions.h", "ta_wallgeo.h", "ta_components.h", "ta_distance.h", "ta_nearest.h", "ta_separable.h", "ta_profile.h", "ta_sighist.h", "ta_sigmoments.h", "ta_topology.h", "ta_resample.h",
            os.path.join("..", "..", "include", "tissue_scan.h"), os.path.join("..", "..", "include", "tissue_scan_signal.h"),
            os.path.join("..", "..", "include", "tissue_scan_mesh.h"), os.path.join("..", "..", "include", "tissue_scan_overlap.h"),
            os.path.join("..", "..", "include", "tissue_scan_junctions.h"), os.path.join("..", "..", "include", "tissue_scan_wallgeo.h"),

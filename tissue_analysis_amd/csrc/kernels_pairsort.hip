@@ -6,7 +6,7 @@
 // unique inside a bucket, so the position of a pair is the number of pairs of its bucket with a smaller hi.  Every thread
 // of the rank kernel walks its own bucket; the threads of a wave mostly share one, so the walk is a broadcast read.
 // Seven small launches instead of the eight radix passes of a 64-bit library sort (round 2: hipCUB DeviceRadixSort).
-#include "ta_kernels.h"
+#include "ta_counted.h"
 
 namespace ta {
 
@@ -101,10 +101,19 @@ __global__ void __launch_bounds__(256) pairsort_rank_kernel(const uint64_t* keys
     }
 }
 
-uint64_t pairs_sort_scratch_bytes(uint64_t n, uint32_t max_label) {
-    const uint64_t rows = (uint64_t)max_label + 3;                       // buckets 0 .. max_label + 1, one more offset behind them
-    return 2 * ((rows * 4 + 15) & ~15ull) + ((rows * 8 + 15) & ~15ull) + scan_u32_scratch_bytes(rows) + n * 8 + n * 24 + 64;
-}
+// the scratch of the sort at `scratch` (NULL: for its size): the count/scan block of the buckets 0 .. max_label + 1, one more offset
+// behind them | cursor u32[rows] | bucketed keys u64[n] | bucketed faces u64[n][3]
+struct PairSortScratch {
+    ScanBlock buckets; uint32_t* cursor; uint64_t *keys_tmp, *faces_tmp, bytes;
+    PairSortScratch(void* scratch, uint64_t n, uint32_t max_label) : buckets((uint64_t)max_label + 3) {
+        PartCursor at(buckets.end);
+        const uintptr_t base = (uintptr_t)scratch;
+        cursor = (uint32_t*)(base + at.take(buckets.n * 4, 16).at); keys_tmp = (uint64_t*)(base + at.take(n * 8, 16).at); faces_tmp = (uint64_t*)(base + at.take(n * 24, 16).at);
+        bytes = at.end(16) + 64;
+    }
+};
+
+uint64_t pairs_sort_scratch_bytes(uint64_t n, uint32_t max_label) { return PairSortScratch(nullptr, n, max_label).bytes; }
 
 // keys / faces: the n unique pairs in any order.  keys_out / faces_out: the same pairs sorted by (lo, hi).  scratch:
 // pairs_sort_scratch_bytes(n, max_label) bytes of device memory; vol / itemsize / corner: where the label that holds the most
@@ -112,23 +121,17 @@ uint64_t pairs_sort_scratch_bytes(uint64_t n, uint32_t max_label) {
 hipError_t launch_pairs_sort(hipStream_t s, const uint64_t* keys, const uint64_t* faces, uint64_t n, uint32_t max_label, void* scratch,
                              uint64_t* keys_out, uint64_t* faces_out, const void* vol, int itemsize, int64_t corner) {
     if (n == 0) return hipSuccess;
-    const uint64_t rows = (uint64_t)max_label + 3;
-    char* p = (char*)scratch;
-    uint32_t* counts = (uint32_t*)p; p += (rows * 4 + 15) & ~15ull;
-    uint32_t* cursor = (uint32_t*)p; p += (rows * 4 + 15) & ~15ull;
-    uint64_t* offsets = (uint64_t*)p; p += (rows * 8 + 15) & ~15ull;
-    void* scan_scratch = p; p += scan_u32_scratch_bytes(rows);
-    uint64_t* keys_tmp = (uint64_t*)p; p += n * 8;
-    uint64_t* faces_tmp = (uint64_t*)p;
-    hipError_t e = hipMemsetAsync(counts, 0, rows * 4, s);
+    const PairSortScratch q(scratch, n, max_label);
+    uint32_t* counts = q.buckets.counts(scratch);
+    hipError_t e = hipMemsetAsync(counts, 0, q.buckets.n * 4, s);
     if (e != hipSuccess) return e;
     const unsigned blocks = (unsigned)((n + 255) / 256);
     hipLaunchKernelGGL(pairsort_count_kernel, dim3(blocks), dim3(256), 0, s, keys, n, counts, max_label, vol, itemsize, corner);
-    e = hipMemcpyAsync(cursor, counts, rows * 4, hipMemcpyDeviceToDevice, s);
+    e = hipMemcpyAsync(q.cursor, counts, q.buckets.n * 4, hipMemcpyDeviceToDevice, s);
     if (e != hipSuccess) return e;
-    launch_scan_u32_exclusive(s, counts, rows, scan_scratch, offsets);        // offsets[b] = pairs in the buckets before b; offsets[rows - 1] = n
-    hipLaunchKernelGGL(pairsort_scatter_kernel, dim3(blocks), dim3(256), 0, s, keys, faces, n, offsets, cursor, max_label, keys_tmp, faces_tmp, vol, itemsize, corner);
-    hipLaunchKernelGGL(pairsort_rank_kernel, dim3(blocks), dim3(256), 0, s, keys_tmp, faces_tmp, n, offsets, max_label, keys_out, faces_out);
+    q.buckets.scan(s, scratch);                                                    // offsets[b] = pairs in the buckets before b; offsets[rows - 1] = n
+    hipLaunchKernelGGL(pairsort_scatter_kernel, dim3(blocks), dim3(256), 0, s, keys, faces, n, q.buckets.offsets(scratch), q.cursor, max_label, q.keys_tmp, q.faces_tmp, vol, itemsize, corner);
+    hipLaunchKernelGGL(pairsort_rank_kernel, dim3(blocks), dim3(256), 0, s, q.keys_tmp, q.faces_tmp, n, q.buckets.offsets(scratch), max_label, keys_out, faces_out);
     return hipGetLastError();
 }
 

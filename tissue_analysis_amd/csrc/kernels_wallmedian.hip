@@ -10,7 +10,7 @@
 // last bit count on symmetric walls, whose median sits ON an integer), no fused multiply-add anywhere (numpy's ufuncs multiply
 // and add separately), correctly rounded sqrt and division.  The centroid is a sum of integers (exact in any order) divided
 // once.  One wave per wall: the terms of 64 voxels at a time in parallel, the sums lane-sequential.
-#include "ta_kernels.h"
+#include "ta_counted.h"
 
 #pragma clang fp contract(off)
 
@@ -117,21 +117,21 @@ __global__ void __launch_bounds__(64) wall_median_kernel(const uint2* pairs, con
     }
 }
 
-uint64_t wall_median_scratch_bytes(uint64_t n) { return ((n * 4 + 15) & ~15ull) + ((n * 8 + 15) & ~15ull) + scan_u32_scratch_bytes(n) + 64; }
+// the scratch of launch_wall_starts: one count/scan block -- the flags of the records are its counts, their ranks its offsets
+uint64_t wall_median_scratch_bytes(uint64_t n) { return ScanBlock(n).end + 64; }
 
 // pairs / coords: the n records grouped by pair (device).  scratch: wall_median_scratch_bytes(n).  starts: room for n entries.
-// Enqueues the flag + rank passes and leaves the number of walls in *nwalls_dev (uint64, device): the caller reads it back and
+// Enqueues the flag + rank passes and the read of the number of walls into *nwalls (host): the caller drains the stream and
 // then calls launch_wall_medians.
-void launch_wall_starts(hipStream_t s, const uint32_t* pairs, uint64_t n, void* scratch, uint32_t* starts, uint64_t** nwalls_dev) {
-    char* p = (char*)scratch;
-    uint32_t* flags = (uint32_t*)p; p += (n * 4 + 15) & ~15ull;
-    uint64_t* rank = (uint64_t*)p; p += (n * 8 + 15) & ~15ull;
+hipError_t launch_wall_starts(hipStream_t s, const uint32_t* pairs, uint64_t n, void* scratch, uint32_t* starts, uint64_t* nwalls) {
+    const ScanBlock b(n);
     unsigned blocks = (unsigned)((n + 255) / 256);
     if (blocks > 8192) blocks = 8192;
-    hipLaunchKernelGGL(wall_open_flags_kernel, dim3(blocks), dim3(256), 0, s, (const uint2*)pairs, n, flags);
-    launch_scan_u32_exclusive(s, flags, n, p, rank);
-    hipLaunchKernelGGL(wall_starts_kernel, dim3(blocks), dim3(256), 0, s, flags, rank, n, starts);
-    *nwalls_dev = scan_u32_total(p, n);              // (the scan leaves its total behind its block sums)
+    hipLaunchKernelGGL(wall_open_flags_kernel, dim3(blocks), dim3(256), 0, s, (const uint2*)pairs, n, b.counts(scratch));
+    b.scan(s, scratch);
+    hipLaunchKernelGGL(wall_starts_kernel, dim3(blocks), dim3(256), 0, s, b.counts(scratch), b.offsets(scratch), n, starts);
+    const hipError_t e = hipGetLastError();
+    return e != hipSuccess ? e : b.read_total(s, scratch, nwalls);
 }
 
 void launch_wall_medians(hipStream_t s, const uint32_t* pairs, const int32_t* coords, const uint32_t* starts, uint32_t nwalls, uint64_t n,

@@ -31,7 +31,7 @@
 // its region, or that holds a voxel with more than four neighbour labels, is NOT staged but listed: EMIT, the same
 // code with one listed cell per wave, recomputes exactly those cells and stores their records where they belong (a few
 // cells around points where five cells meet; noise volumes; a staging area sized for tissue, half a record per voxel).
-#include "ta_kernels.h"
+#include "ta_counted.h"
 #include "ta_sweep_common.h"
 
 namespace ta {
@@ -550,8 +550,7 @@ __global__ void __launch_bounds__(256) wall_copy_kernel(WallArgs A, uint32_t nce
 }
 
 // ---- exclusive scan of the (row, strip) counts: block sums, one block over the sums, apply ----------------------
-constexpr int SCAN_PER_BLOCK = 2048;   // 256 threads x 8
-
+// (SCAN_PER_BLOCK counts a workgroup, 256 threads x 8: ta_counted.h, with the format of the scratch)
 __global__ void __launch_bounds__(256) wall_scan_sums_kernel(const uint32_t* counts, uint64_t n, uint64_t* block_sums) {
     __shared__ uint64_t part[4];
     const uint64_t lo = (uint64_t)blockIdx.x * SCAN_PER_BLOCK;
@@ -618,16 +617,12 @@ __global__ void __launch_bounds__(256) wall_scan_apply_kernel(const uint32_t* co
     }
 }
 
-// the same three kernels as a general exclusive scan of uint32 counts (the adjacency sort buckets its pairs with it)
-uint64_t scan_u32_scratch_bytes(uint64_t n) { return ((n + SCAN_PER_BLOCK - 1) / SCAN_PER_BLOCK + 1) * 8 + 16; }
-
-uint64_t* scan_u32_total(void* scratch, uint64_t n) { return (uint64_t*)scratch + (n + SCAN_PER_BLOCK - 1) / SCAN_PER_BLOCK; }
-
+// the same three kernels as a general exclusive scan of uint32 counts (ScanBlock of ta_counted.h lays its buffers out and calls it)
 void launch_scan_u32_exclusive(hipStream_t s, const uint32_t* counts, uint64_t n, void* scratch, uint64_t* offsets) {
     if (n == 0) return;
-    const uint64_t blocks = (n + SCAN_PER_BLOCK - 1) / SCAN_PER_BLOCK;
+    const uint64_t blocks = scan_blocks(n);
     uint64_t* block_sums = (uint64_t*)scratch;
-    uint64_t* total = block_sums + blocks;
+    uint64_t* total = block_sums + scan_u32_total(n);
     hipLaunchKernelGGL(wall_scan_sums_kernel, dim3((unsigned)blocks), dim3(256), 0, s, counts, n, block_sums);
     hipLaunchKernelGGL(wall_scan_top_kernel, dim3(1), dim3(256), 0, s, block_sums, blocks, total);
     hipLaunchKernelGGL(wall_scan_apply_kernel, dim3((unsigned)blocks), dim3(256), 0, s, counts, n, block_sums, offsets);
@@ -641,7 +636,7 @@ WallPlan wall_plan(int64_t n0, int64_t n1, int64_t n2) {
     p.nstrips = (int32_t)((n2 + WSC - 1) / WSC);
     p.rows_per_wave = wall_rows_per_wave(n1);
     p.cells = (uint64_t)n0 * (uint64_t)n1 * (uint64_t)p.nstrips;
-    p.scan_blocks = (p.cells + SCAN_PER_BLOCK - 1) / SCAN_PER_BLOCK;
+    p.scan_blocks = scan_blocks(p.cells);
     const uint64_t chunks_b = (uint64_t)((n1 + p.rows_per_wave - 1) / p.rows_per_wave);
     p.waves = (uint64_t)n0 * chunks_b * (uint64_t)p.nstrips;
     return p;

@@ -7,18 +7,6 @@ namespace {
 
 const char* const NO_TABLES = "no component tables for the current volume (run ta_components_extract)";
 
-// where the parts of ComponentState::work lie, for W waves
-struct ComponentWork {
-    uint64_t counts, offsets, scratch, bytes;
-    explicit ComponentWork(uint64_t W) {
-        PartCursor at;
-        counts = at.take(W * 4, 16).at;
-        offsets = at.take(W * 8, 16).at;
-        scratch = at.take(ta::scan_u32_scratch_bytes(W), 16).at;
-        bytes = at.end(16) + 16;
-    }
-};
-
 // where the parts of ComponentState::slots lie, for S slots; [zero, fill) is zeroed, [fill, box) set to all ones, the box to 0x7F
 struct ComponentSlots {
     uint64_t root, row, zero, n, sum1, fill, first, box, bytes;
@@ -69,10 +57,9 @@ int components_settle(ta_ctx* c) {
     c->cc.state = 0;                               // (whatever fails below: no tables)
     int rc;
     const uint64_t nvox = voxels(c), W = c->cc.waves;
-    const ComponentWork w(W);
-    char* wp = (char*)c->cc.work.p;
+    const ScanBlock w(W);                          // ComponentState::work: the root counts of the waves
     uint64_t S = 0;
-    TA_HIP(hipMemcpyAsync(&S, ta::scan_u32_total(wp + w.scratch, W), 8, hipMemcpyDeviceToHost, c->stream));
+    TA_HIP(w.read_total(c->stream, c->cc.work.p, &S));
     TA_HIP(hipStreamSynchronize(c->stream));
     const ComponentSlots q(S);
     const SortLayout sl(S, 8);
@@ -90,7 +77,7 @@ int components_settle(ta_ctx* c) {
     TA_HIP(hipMemsetAsync(sp + q.fill, 0xFF, q.box - q.fill, c->stream));
     TA_HIP(hipMemsetAsync(sp + q.box, 0x7F, q.bytes - 16 - q.box, c->stream));
     TA_HIP(hipEventRecord(c->cc.ev[3], c->stream));
-    ta::launch_component_emit(c->stream, parent, nvox, (const uint64_t*)(wp + w.offsets), root_of_slot);
+    ta::launch_component_emit(c->stream, parent, nvox, w.offsets(c->cc.work.p), root_of_slot);
     ta::ComponentGeometry g = {};
     g.nvox = nvox;
     g.own_begin = (uint64_t)c->first_owned * (uint64_t)c->mdims[1] * (uint64_t)c->mdims[2];
@@ -102,17 +89,14 @@ int components_settle(ta_ctx* c) {
     TA_HIP(hipGetLastError());
     TA_HIP(hipEventRecord(c->cc.ev[4], c->stream));
     // the slots sorted by (label, first); those without an owned voxel sort behind every row
-    char* op = (char*)c->cc.sort.p;
-    uint64_t* k0 = (uint64_t*)(op + sl.keys[0]); uint64_t* k1 = (uint64_t*)(op + sl.keys[1]);
-    uint32_t* i0 = (uint32_t*)(op + sl.idx[0]); uint32_t* i1 = (uint32_t*)(op + sl.idx[1]);
-    c->cc.launched[3] = ta::launch_component_keys(c->stream, c->vol, c->itemsize, root_of_slot, stats, S, k0, i0, nonempty);
-    uint64_t* ks = k0; uint32_t* is = i0;
-    TA_HIP(ta::launch_radix_sort_u64(c->stream, S, k0, k1, i0, i1, op + sl.temp, 64, &ks, &is));
+    SortView<uint64_t> v(sl, c->cc.sort.p);
+    c->cc.launched[3] = ta::launch_component_keys(c->stream, c->vol, c->itemsize, root_of_slot, stats, S, v.keys(), v.idx(), nonempty);
+    TA_HIP(v.sort(c->stream, S, 64));
     char* tp = (char*)c->cc.rows.p;
     rows.label = (uint32_t*)(tp + tb.label.at); rows.n = (unsigned long long*)(tp + tb.n.at);
     rows.first = (int32_t*)(tp + tb.first.at); rows.bbox = (int32_t*)(tp + tb.bbox.at); rows.sum1 = (unsigned long long*)(tp + tb.sum1.at);
     rows.origin0 = c->a_origin - c->first_owned;
-    ta::launch_component_rows(c->stream, c->vol, c->itemsize, root_of_slot, stats, is, S, nonempty, (uint32_t*)(sp + q.row), rows);
+    ta::launch_component_rows(c->stream, c->vol, c->itemsize, root_of_slot, stats, v.idx(), S, nonempty, (uint32_t*)(sp + q.row), rows);
     TA_HIP(hipGetLastError());
     TA_HIP(hipEventRecord(c->cc.ev[5], c->stream));
     uint64_t R = 0;
@@ -151,22 +135,21 @@ TA_API int ta_components_extract(ta_ctx* c) {
     if (rc != TA_OK) return rc;
     c->cc.state = 0;
     c->cc.waves = ta::component_waves(nvox);
-    const ComponentWork w(c->cc.waves);
+    const ScanBlock w(c->cc.waves);
     if ((rc = c->cc.parent.reserve(nvox * 4 + 16)) != TA_OK) return rc;
-    if ((rc = c->cc.work.reserve(w.bytes)) != TA_OK) return rc;
+    if ((rc = c->cc.work.reserve(w.end + 16)) != TA_OK) return rc;
     if ((rc = c->cc.small.reserve(16)) != TA_OK) return rc;
     if ((rc = ensure_events(c->cc.ev)) != TA_OK) return rc;
     const ta::ComponentArgs a = component_args(c);
-    char* wp = (char*)c->cc.work.p;
     TA_HIP(hipEventRecord(c->cc.ev[0], c->stream));
     ta::launch_component_local(c->stream, a, c->itemsize);
     c->cc.launched[0] = (uint32_t)std::min<uint64_t>(ta::component_tiles(a), 0xFFFFFFFFull);
     c->cc.launched[1] = ta::launch_component_seams(c->stream, a, c->itemsize);
     c->cc.launched[2] = c->cc.launched[3] = 0u;
-    ta::launch_component_flatten(c->stream, a.parent, nvox, a.n1, a.n2, (uint32_t*)(wp + w.counts));
+    ta::launch_component_flatten(c->stream, a.parent, nvox, a.n1, a.n2, w.counts(c->cc.work.p));
     TA_HIP(hipGetLastError());
     TA_HIP(hipEventRecord(c->cc.ev[1], c->stream));
-    ta::launch_scan_u32_exclusive(c->stream, (const uint32_t*)(wp + w.counts), c->cc.waves, wp + w.scratch, (uint64_t*)(wp + w.offsets));
+    w.scan(c->stream, c->cc.work.p);
     TA_HIP(hipGetLastError());
     TA_HIP(hipEventRecord(c->cc.ev[2], c->stream));
     c->cc.state = 1;
@@ -239,12 +222,12 @@ TA_API int ta_components_timing(ta_ctx* c, double* ms_pass, double* ms_after) {
     if (c->cc.state != 2) return fail(TA_EINVAL, "no settled component tables (ask ta_components_size first)");
     int rc = use_device(c);
     if (rc != TA_OK) return rc;
-    TA_HIP(hipEventSynchronize(c->cc.ev[5]));
-    double find = 0.0, scan = 0.0, stats = 0.0, rest = 0.0;
-    if ((rc = elapsed_ms(c->cc.ev[0], c->cc.ev[1], &find)) != TA_OK || (rc = elapsed_ms(c->cc.ev[1], c->cc.ev[2], &scan)) != TA_OK ||
-        (rc = elapsed_ms(c->cc.ev[3], c->cc.ev[4], &stats)) != TA_OK || (rc = elapsed_ms(c->cc.ev[4], c->cc.ev[5], &rest)) != TA_OK) return rc;
-    if (ms_pass) *ms_pass = find + stats;
-    if (ms_after) *ms_after = scan + rest;
+    hipEvent_t* ev = c->cc.ev;                     // union-find + statistics | scan + the rest
+    double pass = 0.0, after = 0.0;
+    TA_HIP(summed_ms(ev[5], {{ev[0], ev[1]}, {ev[3], ev[4]}}, &pass));
+    TA_HIP(summed_ms(ev[5], {{ev[1], ev[2]}, {ev[4], ev[5]}}, &after));
+    if (ms_pass) *ms_pass = pass;
+    if (ms_after) *ms_after = after;
     return TA_OK;
 }
 

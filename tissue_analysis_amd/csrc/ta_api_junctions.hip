@@ -5,30 +5,14 @@
 
 namespace {
 
-// where the parts of JunctionState::work lie, for W waves
-struct JunctionWork {
-    uint64_t counts[2], offsets[2], scratch[2], bytes;
-    explicit JunctionWork(uint64_t W) {
-        PartCursor at;
-        for (auto& p : counts) p = at.take(W * 4, 16).at;
-        for (auto& p : offsets) p = at.take(W * 8, 16).at;
-        for (auto& p : scratch) p = at.take(ta::scan_u32_scratch_bytes(W), 16).at;
-        bytes = at.end(16) + 16;
-    }
-};
+// JunctionState::work for W waves: the count/scan block of the edge records, then the vertex records'
+ScanBlock junction_counts(uint64_t W, int k) { return ScanBlock(W, k ? ScanBlock(W).end : 0); }
 
-// where the parts of JunctionState::sort[k] lie, for N records
+// JunctionState::sort[k] for N records: the sort workspace, then the count/scan block of the rows that start in a block of records
 struct JunctionSort {
     SortLayout sort;
-    uint64_t counts, offsets, scratch, bytes;
-    explicit JunctionSort(uint64_t N) : sort(N, 8) {
-        const uint64_t B = ta::junction_row_blocks(N);
-        PartCursor at(sort.end);
-        counts = at.take(B * 4, 16).at;
-        offsets = at.take(B * 8, 16).at;
-        scratch = at.take(ta::scan_u32_scratch_bytes(B), 16).at;
-        bytes = at.end(16) + 16;
-    }
+    ScanBlock heads;
+    explicit JunctionSort(uint64_t N) : sort(N, 8), heads(ta::junction_row_blocks(N), sort.end) {}
 };
 
 // the parts of JunctionState::rows[k], for R rows of K labels
@@ -51,10 +35,9 @@ ta::JunctionArgs junction_args(ta_ctx* c) {
                                    //  the rows sort by id and need no translation)
     a.n0 = c->mdims[0]; a.n1 = c->mdims[1]; a.n2 = c->mdims[2];
     c->jn.waves = ta::junction_plan(a, c->itemsize);
-    const JunctionWork w(c->jn.waves);
-    char* p = (char*)c->jn.work.p;
-    a.wave_counts3 = (uint32_t*)(p + w.counts[0]); a.wave_counts4 = (uint32_t*)(p + w.counts[1]);
-    a.wave_offsets3 = (const uint64_t*)(p + w.offsets[0]); a.wave_offsets4 = (const uint64_t*)(p + w.offsets[1]);
+    const ScanBlock w3 = junction_counts(c->jn.waves, 0), w4 = junction_counts(c->jn.waves, 1);
+    a.wave_counts3 = w3.counts(c->jn.work.p); a.wave_counts4 = w4.counts(c->jn.work.p);
+    a.wave_offsets3 = w3.offsets(c->jn.work.p); a.wave_offsets4 = w4.offsets(c->jn.work.p);
     a.degenerate = (unsigned long long*)c->jn.small.p;
     return a;
 }
@@ -66,11 +49,8 @@ int junctions_settle(ta_ctx* c) {
     c->jn.state = 0;                               // (whatever fails below: no tables)
     int rc;
     ta::JunctionArgs a = junction_args(c);
-    const JunctionWork w(c->jn.waves);
-    char* wp = (char*)c->jn.work.p;
     uint64_t N[2] = {0, 0}, degenerate = 0;
-    for (int k = 0; k < 2; ++k)
-        TA_HIP(hipMemcpyAsync(&N[k], ta::scan_u32_total(wp + w.scratch[k], c->jn.waves), 8, hipMemcpyDeviceToHost, c->stream));
+    for (int k = 0; k < 2; ++k) TA_HIP(junction_counts(c->jn.waves, k).read_total(c->stream, c->jn.work.p, &N[k]));
     TA_HIP(hipMemcpyAsync(&degenerate, c->jn.small.p, 8, hipMemcpyDeviceToHost, c->stream));
     TA_HIP(hipStreamSynchronize(c->stream));
     for (int k = 0; k < 2; ++k)
@@ -81,7 +61,7 @@ int junctions_settle(ta_ctx* c) {
     const uint64_t lab_at[2] = {rec.take(N[0] * 12, 16).at, rec.take(N[1] * 16, 16).at};
     if ((rc = c->jn.rec.reserve(rec.end(16) + 16)) != TA_OK) return rc;
     for (int k = 0; k < 2; ++k)
-        if ((rc = c->jn.sort[k].reserve(JunctionSort(N[k]).bytes)) != TA_OK) return rc;
+        if ((rc = c->jn.sort[k].reserve(JunctionSort(N[k]).heads.end + 16)) != TA_OK) return rc;
     char* rp = (char*)c->jn.rec.p;
     uint64_t* origins[2] = {(uint64_t*)(rp + org_at[0]), (uint64_t*)(rp + org_at[1])};
     uint32_t* labels[2] = {(uint32_t*)(rp + lab_at[0]), (uint32_t*)(rp + lab_at[1])};
@@ -93,30 +73,25 @@ int junctions_settle(ta_ctx* c) {
     TA_HIP(hipEventRecord(c->jn.ev[4], c->stream));
     // stable sorts over the label columns from last to first, then the rows that start in every block of sorted records
     const int lb = 8 * c->itemsize;
-    uint32_t* order[2] = {nullptr, nullptr};
+    const uint32_t* order[2] = {nullptr, nullptr};
     uint64_t R[2] = {0, 0};
     for (int k = 0; k < 2; ++k) {
         const uint64_t n = N[k];
         c->jn.key_groups[k] = 0u;
         if (!n) continue;
         const JunctionSort q(n);
-        char* sp = (char*)c->jn.sort[k].p;
-        uint64_t* k0 = (uint64_t*)(sp + q.sort.keys[0]); uint64_t* k1 = (uint64_t*)(sp + q.sort.keys[1]);
-        uint32_t* i0 = (uint32_t*)(sp + q.sort.idx[0]); uint32_t* i1 = (uint32_t*)(sp + q.sort.idx[1]);
-        c->jn.key_groups[k] = ta::launch_junction_keys(c->stream, labels[k], K[k], n, nullptr, K[k] - 2, K[k] - 1, lb, k0, i0);
-        uint64_t* ks = k0; uint32_t* is = i0;
-        TA_HIP(ta::launch_radix_sort_u64(c->stream, n, k0, k1, i0, i1, sp + q.sort.temp, 2 * lb, &ks, &is));
+        void* sp = c->jn.sort[k].p;
+        SortView<uint64_t> v(q.sort, sp);
+        c->jn.key_groups[k] = ta::launch_junction_keys(c->stream, labels[k], K[k], n, nullptr, K[k] - 2, K[k] - 1, lb, v.keys(), v.idx());
+        TA_HIP(v.sort(c->stream, n, 2 * lb));
         // the leading columns of the records in that order, into the key buffer the order came out with
-        uint64_t* ko = ks == k0 ? k1 : k0; uint32_t* io = is == i0 ? i1 : i0;
-        ta::launch_junction_keys(c->stream, labels[k], K[k], n, is, K[k] == 4 ? 0 : -1, K[k] == 4 ? 1 : 0, lb, ks, nullptr);
-        uint64_t* ks2 = ks; uint32_t* is2 = is;
-        TA_HIP(ta::launch_radix_sort_u64(c->stream, n, ks, ko, is, io, sp + q.sort.temp, K[k] == 4 ? 2 * lb : lb, &ks2, &is2));
-        order[k] = is2;
-        const uint64_t B = ta::junction_row_blocks(n);
-        ta::launch_junction_heads(c->stream, labels[k], K[k], is2, n, (uint32_t*)(sp + q.counts));
-        ta::launch_scan_u32_exclusive(c->stream, (const uint32_t*)(sp + q.counts), B, sp + q.scratch, (uint64_t*)(sp + q.offsets));
+        ta::launch_junction_keys(c->stream, labels[k], K[k], n, v.idx(), K[k] == 4 ? 0 : -1, K[k] == 4 ? 1 : 0, lb, v.keys(), nullptr);
+        TA_HIP(v.sort(c->stream, n, K[k] == 4 ? 2 * lb : lb));
+        order[k] = v.idx();
+        ta::launch_junction_heads(c->stream, labels[k], K[k], order[k], n, q.heads.counts(sp));
+        q.heads.scan(c->stream, sp);
         TA_HIP(hipGetLastError());
-        TA_HIP(hipMemcpyAsync(&R[k], ta::scan_u32_total(sp + q.scratch, B), 8, hipMemcpyDeviceToHost, c->stream));
+        TA_HIP(q.heads.read_total(c->stream, sp, &R[k]));
     }
     TA_HIP(hipStreamSynchronize(c->stream));
     for (int k = 0; k < 2; ++k)
@@ -125,7 +100,6 @@ int junctions_settle(ta_ctx* c) {
         if (!N[k]) continue;
         const JunctionSort q(N[k]);
         const JunctionTable tb(R[k], K[k]);
-        char* sp = (char*)c->jn.sort[k].p;
         char* op = (char*)c->jn.rows[k].p;
         TA_HIP(hipMemsetAsync(op, 0, tb.labels.at, c->stream));
         ta::JunctionRows rows;
@@ -135,7 +109,7 @@ int junctions_settle(ta_ctx* c) {
         rows.n0 = c->mdims[0]; rows.n1 = c->mdims[1]; rows.n2 = c->mdims[2];
         rows.origin0 = c->a_origin - c->first_owned;
         for (int d = 0; d < 3; ++d) { rows.flat[d] = c->mdims[d] == 1 ? 1 : 0; rows.axis[d] = c->perm[d]; }
-        ta::launch_junction_reduce(c->stream, labels[k], origins[k], K[k], order[k], N[k], (const uint64_t*)(sp + q.offsets), rows);
+        ta::launch_junction_reduce(c->stream, labels[k], origins[k], K[k], order[k], N[k], q.heads.offsets(c->jn.sort[k].p), rows);
         TA_HIP(hipGetLastError());
     }
     TA_HIP(hipEventRecord(c->jn.ev[5], c->stream));
@@ -176,19 +150,16 @@ TA_API int ta_junctions_extract(ta_ctx* c) {
     {
         ta::JunctionArgs plan = {};
         plan.n0 = c->mdims[0]; plan.n1 = c->mdims[1]; plan.n2 = c->mdims[2];
-        if ((rc = c->jn.work.reserve(JunctionWork(ta::junction_plan(plan, c->itemsize)).bytes)) != TA_OK) return rc;
+        if ((rc = c->jn.work.reserve(junction_counts(ta::junction_plan(plan, c->itemsize), 1).end + 16)) != TA_OK) return rc;
     }
     if ((rc = ensure_events(c->jn.ev)) != TA_OK) return rc;
     const ta::JunctionArgs a = junction_args(c);
-    const JunctionWork w(c->jn.waves);
-    char* wp = (char*)c->jn.work.p;
     TA_HIP(hipMemsetAsync(c->jn.small.p, 0, 16, c->stream));
     TA_HIP(hipEventRecord(c->jn.ev[0], c->stream));
     ta::launch_junction_pass(c->stream, a, c->itemsize, false);
     TA_HIP(hipGetLastError());
     TA_HIP(hipEventRecord(c->jn.ev[1], c->stream));
-    for (int k = 0; k < 2; ++k)
-        ta::launch_scan_u32_exclusive(c->stream, (const uint32_t*)(wp + w.counts[k]), c->jn.waves, wp + w.scratch[k], (uint64_t*)(wp + w.offsets[k]));
+    for (int k = 0; k < 2; ++k) junction_counts(c->jn.waves, k).scan(c->stream, c->jn.work.p);
     TA_HIP(hipGetLastError());
     TA_HIP(hipEventRecord(c->jn.ev[2], c->stream));
     c->jn.state = 1;
@@ -223,12 +194,12 @@ TA_API int ta_junctions_timing(ta_ctx* c, double* ms_pass, double* ms_after) {
     if (c->jn.state != 2) return fail(TA_EINVAL, "no settled junction tables (ask ta_junctions_size first)");
     int rc = use_device(c);
     if (rc != TA_OK) return rc;
-    TA_HIP(hipEventSynchronize(c->jn.ev[5]));
-    double count = 0.0, scans = 0.0, emit = 0.0, rest = 0.0;
-    if ((rc = elapsed_ms(c->jn.ev[0], c->jn.ev[1], &count)) != TA_OK || (rc = elapsed_ms(c->jn.ev[1], c->jn.ev[2], &scans)) != TA_OK ||
-        (rc = elapsed_ms(c->jn.ev[3], c->jn.ev[4], &emit)) != TA_OK || (rc = elapsed_ms(c->jn.ev[4], c->jn.ev[5], &rest)) != TA_OK) return rc;
-    if (ms_pass) *ms_pass = count + emit;
-    if (ms_after) *ms_after = scans + rest;
+    hipEvent_t* ev = c->jn.ev;                     // count + emit | scans + the rest
+    double pass = 0.0, after = 0.0;
+    TA_HIP(summed_ms(ev[5], {{ev[0], ev[1]}, {ev[3], ev[4]}}, &pass));
+    TA_HIP(summed_ms(ev[5], {{ev[1], ev[2]}, {ev[4], ev[5]}}, &after));
+    if (ms_pass) *ms_pass = pass;
+    if (ms_after) *ms_after = after;
     return TA_OK;
 }
 

@@ -9,16 +9,12 @@ const char* const NO_MESH = "no mesh of the current extraction (run ta_mesh_extr
 
 bool mesh_current(const ta_ctx* c) { return pass_current(c, c->mesh.seq); }
 
-// byte offsets of the parts of MeshState::small for R rows and wf / wc waves of the face / corner kernels, each a multiple of 16
+// MeshState::small for R rows and wf / wc waves of the face / corner kernels: flags u32[4] | wanted u8[R] (from byte 16) | the
+// count/scan block of the faces | of the corners
 struct MeshSmall {
-    uint64_t flags, wanted, fcounts, ccounts, foffs, coffs, fscan, cscan, bytes;
-    MeshSmall(uint64_t R, uint64_t wf, uint64_t wc) {
-        PartCursor at;
-        flags = at.take(16).at; wanted = at.take(R, 16).at; fcounts = at.take(4 * wf, 16).at; ccounts = at.take(4 * wc, 16).at;
-        foffs = at.take(8 * wf, 16).at; coffs = at.take(8 * wc, 16).at;
-        fscan = at.take(ta::scan_u32_scratch_bytes(wf), 16).at; cscan = at.take(ta::scan_u32_scratch_bytes(wc), 16).at;
-        bytes = at.end(16);
-    }
+    static constexpr uint64_t wanted = 16;
+    ScanBlock faces, corners;
+    MeshSmall(uint64_t R, uint64_t wf, uint64_t wc) : faces(wf, align16(wanted + R)), corners(wc, faces.end) {}
 };
 // ... of MeshState::work for F faces and V vertex records
 struct MeshWork {
@@ -95,7 +91,7 @@ TA_API int ta_mesh_extract(ta_ctx* c, int sub_factor, const uint8_t* wanted_rows
     const uint64_t nvox = (uint64_t)a.m0 * a.m1 * a.m2, ncorner = (uint64_t)(a.m0 + 1) * (a.m1 + 1) * (a.m2 + 1);
     const uint64_t wf = ta::mesh_waves(nvox), wc = ta::mesh_waves(ncorner);
     const MeshSmall S(R, wf, wc);
-    if ((rc = c->mesh.small.reserve(S.bytes)) != TA_OK) return rc;
+    if ((rc = c->mesh.small.reserve(S.corners.end)) != TA_OK) return rc;
     char* sm = (char*)c->mesh.small.p;
     a.flags = (uint32_t*)sm;
     a.wanted = (const uint8_t*)(sm + S.wanted);
@@ -104,25 +100,20 @@ TA_API int ta_mesh_extract(ta_ctx* c, int sub_factor, const uint8_t* wanted_rows
     if (wanted_rows) TA_HIP(hipMemcpyAsync(sm + S.wanted, wanted_rows, R, hipMemcpyHostToDevice, c->stream));
     else TA_HIP(hipMemsetAsync(sm + S.wanted, 1, R, c->stream));
     // count -> scan: the totals are all the host needs before it sizes the output
-    uint32_t* fcounts = (uint32_t*)(sm + S.fcounts);
-    uint32_t* ccounts = (uint32_t*)(sm + S.ccounts);
-    uint64_t* foffs = (uint64_t*)(sm + S.foffs);
-    uint64_t* coffs = (uint64_t*)(sm + S.coffs);
     TA_HIP(hipEventRecord(c->mesh.ev[0], c->stream));
-    ta::launch_mesh_face_count(c->stream, a, c->itemsize, fcounts);
-    ta::launch_mesh_corner_count(c->stream, a, c->itemsize, ccounts);
-    ta::launch_scan_u32_exclusive(c->stream, fcounts, wf, sm + S.fscan, foffs);
-    ta::launch_scan_u32_exclusive(c->stream, ccounts, wc, sm + S.cscan, coffs);
+    ta::launch_mesh_face_count(c->stream, a, c->itemsize, S.faces.counts(sm));
+    ta::launch_mesh_corner_count(c->stream, a, c->itemsize, S.corners.counts(sm));
+    S.faces.scan(c->stream, sm);
+    S.corners.scan(c->stream, sm);
     TA_HIP(hipGetLastError());
     TA_HIP(hipEventRecord(c->mesh.ev[1], c->stream));
-    uint64_t tot[2] = {0, 0};
+    uint64_t F = 0, V = 0;
     uint32_t flags[ta::MESH_NFLAGS] = {0, 0, 0, 0};
-    if (wf) TA_HIP(hipMemcpyAsync(&tot[0], ta::scan_u32_total(sm + S.fscan, wf), 8, hipMemcpyDeviceToHost, c->stream));
-    if (wc) TA_HIP(hipMemcpyAsync(&tot[1], ta::scan_u32_total(sm + S.cscan, wc), 8, hipMemcpyDeviceToHost, c->stream));
+    TA_HIP(S.faces.read_total(c->stream, sm, &F));
+    TA_HIP(S.corners.read_total(c->stream, sm, &V));
     TA_HIP(hipMemcpyAsync(flags, sm, sizeof(flags), hipMemcpyDeviceToHost, c->stream));
     TA_HIP(hipStreamSynchronize(c->stream));
     if (flags[ta::MESH_FLAG_RANGE]) return fail(TA_ERANGE, "the mesh pass met a label above max_label=%u (the volume changed since ta_extract)", c->max_label);
-    const uint64_t F = tot[0], V = tot[1];
     if (V > 0xFFFFFFFFull) return fail(TA_ERANGE, "the meshes have %llu vertices: more than 2^32 - 1", (unsigned long long)V);
     if (F > 0xFFFFFFFFull) return fail(TA_ERANGE, "the meshes have %llu faces: more than 2^32 - 1", (unsigned long long)F);
     const MeshWork Wk(F, V);
@@ -134,25 +125,22 @@ TA_API int ta_mesh_extract(ta_ctx* c, int sub_factor, const uint8_t* wanted_rows
     uint64_t* frec = (uint64_t*)(w + Wk.frec);
     uint32_t* fnb = (uint32_t*)(w + Wk.fnb);
     uint64_t* corner = (uint64_t*)(w + Wk.corner);
-    uint32_t *keys0 = (uint32_t*)(w + Wk.sort.keys[0]), *keys1 = (uint32_t*)(w + Wk.sort.keys[1]);
-    uint32_t *idx0 = (uint32_t*)(w + Wk.sort.idx[0]), *idx1 = (uint32_t*)(w + Wk.sort.idx[1]);
-    void* temp = w + Wk.sort.temp;
+    SortView<uint32_t> vs(Wk.sort, w), fs(Wk.sort, w);      // (the vertex records', then the faces': both written into pair 0)
     uint64_t* vcorner = (uint64_t*)(o + O.vcorner.at);
     uint64_t *vbeg = (uint64_t*)(o + O.vbeg.at), *vend = (uint64_t*)(o + O.vend.at);
     uint64_t *fbeg = (uint64_t*)(o + O.fbeg.at), *fend = (uint64_t*)(o + O.fend.at);
     const int key_bits = c->max_label ? 32 - __builtin_clz(c->max_label) : 1;
-    uint32_t *skeys = nullptr, *sidx = nullptr;
     // emit -> group by cell -> resolve
     TA_HIP(hipEventRecord(c->mesh.ev[2], c->stream));
     TA_HIP(hipMemsetAsync(o + O.bounds.at, 0, O.bounds.bytes, c->stream));
-    ta::launch_mesh_corner_emit(c->stream, a, c->itemsize, coffs, V, corner, keys0, idx0);
-    TA_HIP(ta::launch_radix_sort_u32(c->stream, V, keys0, keys1, idx0, idx1, temp, key_bits, &skeys, &sidx));
-    ta::launch_mesh_bounds(c->stream, skeys, V, vbeg, vend);
-    ta::launch_mesh_gather(c->stream, corner, sidx, V, vcorner);
-    ta::launch_mesh_face_emit(c->stream, a, c->itemsize, foffs, F, frec, fnb, keys0, idx0);
-    TA_HIP(ta::launch_radix_sort_u32(c->stream, F, keys0, keys1, idx0, idx1, temp, key_bits, &skeys, &sidx));
-    ta::launch_mesh_bounds(c->stream, skeys, F, fbeg, fend);
-    ta::launch_mesh_resolve(c->stream, a, skeys, sidx, frec, fnb, F, vcorner, vbeg, vend, (uint32_t*)(o + O.tri.at),
+    ta::launch_mesh_corner_emit(c->stream, a, c->itemsize, S.corners.offsets(sm), V, corner, vs.keys(), vs.idx());
+    TA_HIP(vs.sort(c->stream, V, key_bits));
+    ta::launch_mesh_bounds(c->stream, vs.keys(), V, vbeg, vend);
+    ta::launch_mesh_gather(c->stream, corner, vs.idx(), V, vcorner);
+    ta::launch_mesh_face_emit(c->stream, a, c->itemsize, S.faces.offsets(sm), F, frec, fnb, fs.keys(), fs.idx());
+    TA_HIP(fs.sort(c->stream, F, key_bits));
+    ta::launch_mesh_bounds(c->stream, fs.keys(), F, fbeg, fend);
+    ta::launch_mesh_resolve(c->stream, a, fs.keys(), fs.idx(), frec, fnb, F, vcorner, vbeg, vend, (uint32_t*)(o + O.tri.at),
                             (uint32_t*)(o + O.tcell.at), (uint32_t*)(o + O.tnb.at));
     TA_HIP(hipGetLastError());
     TA_HIP(hipEventRecord(c->mesh.ev[3], c->stream));
@@ -214,15 +202,13 @@ TA_API int ta_mesh_get(ta_ctx* c, uint32_t* cells, uint64_t* vertex_offsets, uin
 }
 
 TA_API int ta_mesh_timing(ta_ctx* c, double* ms) {
-    if (!c) return fail(TA_EINVAL, "ctx is NULL");      // (two intervals with a gap between them: not pass_timing's shape)
+    if (!c) return fail(TA_EINVAL, "ctx is NULL");
     if (!ms) return fail(TA_EINVAL, "NULL argument");
     if (c->mesh.seq == 0 || !c->mesh.ev[3]) return fail(TA_EINVAL, "no mesh pass has been run");
-    int rc = use_device(c);
+    hipEvent_t* ev = c->mesh.ev;
+    const int rc = use_device(c);
     if (rc != TA_OK) return rc;
-    TA_HIP(hipEventSynchronize(c->mesh.ev[3]));
-    double t0 = 0.0, t1 = 0.0;
-    if ((rc = elapsed_ms(c->mesh.ev[0], c->mesh.ev[1], &t0)) != TA_OK || (rc = elapsed_ms(c->mesh.ev[2], c->mesh.ev[3], &t1)) != TA_OK) return rc;
-    *ms = t0 + t1;
+    TA_HIP(summed_ms(ev[3], {{ev[0], ev[1]}, {ev[2], ev[3]}}, ms));
     return TA_OK;
 }
 

@@ -9,16 +9,6 @@ constexpr CompanionKind B_VOLUME = {"B", 2, 4};        // uint16 or uint32
 constexpr int OV_MIN_LOG2 = 4, OV_MAX_LOG2 = 31;       // (the sort's values are u32 slot numbers)
 const char* const NO_TABLE = "no overlap table for the current volume and B (run ta_overlap_extract)";
 
-// where the parts of OverlapState::work lie, for the blocks of a table
-struct OverlapWork {
-    uint64_t counts, offsets, scratch, bytes;
-    explicit OverlapWork(uint64_t blocks) {
-        PartCursor at;
-        counts = at.take(blocks * 4).at; offsets = at.take(blocks * 8, 16).at; scratch = at.take(ta::scan_u32_scratch_bytes(blocks)).at;
-        bytes = at.end();
-    }
-};
-
 // the parts of OverlapState::rows for P pairs
 struct OverlapTable {
     Part a, b, n;
@@ -53,8 +43,8 @@ int overlap_launch(ta_ctx* c) {
     int rc;
     if ((rc = c->ov.table.reserve(slots * 16)) != TA_OK) return rc;
     if ((rc = c->ov.small.reserve(32)) != TA_OK) return rc;
-    const OverlapWork wl(blocks);
-    if ((rc = c->ov.work.reserve(wl.bytes)) != TA_OK) return rc;
+    const ScanBlock wl(blocks);                    // OverlapState::work: the occupied slots of the blocks of the table
+    if ((rc = c->ov.work.reserve(wl.end)) != TA_OK) return rc;
     if ((rc = ensure_events(c->ov.ev)) != TA_OK) return rc;
     ta::OverlapArgs a;
     a.a = c->vol;                  // (the ids as the caller stored them: never the rank copy of a compacted context)
@@ -74,9 +64,8 @@ int overlap_launch(ta_ctx* c) {
     c->ov.plan = ta::launch_overlap(c->stream, a, c->itemsize, c->ov.b.itemsize);
     TA_HIP(hipGetLastError());
     TA_HIP(hipEventRecord(c->ov.ev[1], c->stream));
-    char* w = (char*)c->ov.work.p;
-    ta::launch_overlap_count(c->stream, a.keys, slots, (uint32_t*)(w + wl.counts));
-    ta::launch_scan_u32_exclusive(c->stream, (const uint32_t*)(w + wl.counts), blocks, w + wl.scratch, (uint64_t*)(w + wl.offsets));
+    ta::launch_overlap_count(c->stream, a.keys, slots, wl.counts(c->ov.work.p));
+    wl.scan(c->stream, c->ov.work.p);
     TA_HIP(hipGetLastError());
     TA_HIP(hipEventRecord(c->ov.ev[2], c->stream));
     c->ov.passes += 1;
@@ -93,7 +82,7 @@ int overlap_settle(ta_ctx* c) {
         const uint64_t blocks = ta::overlap_compact_blocks(1ull << c->ov.log2);
         uint32_t small[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         TA_HIP(hipMemcpyAsync(small, c->ov.small.p, sizeof(small), hipMemcpyDeviceToHost, c->stream));
-        TA_HIP(hipMemcpyAsync(&occupied, ta::scan_u32_total((char*)c->ov.work.p + OverlapWork(blocks).scratch, blocks), 8, hipMemcpyDeviceToHost, c->stream));
+        TA_HIP(ScanBlock(blocks).read_total(c->stream, c->ov.work.p, &occupied));
         TA_HIP(hipStreamSynchronize(c->stream));
         memcpy(&top, &small[4], 8);
         c->ov.lds_spills = small[ta::OV_FLAG_LDS_SPILL];               // (of the run just read: in the end, of the last one)
@@ -108,25 +97,20 @@ int overlap_settle(ta_ctx* c) {
         if ((rc = overlap_launch(c)) != TA_OK) { c->ov.state = 0; return rc; }
     }
     const uint64_t slots = 1ull << c->ov.log2, blocks = ta::overlap_compact_blocks(slots);
-    const uint64_t offsets_at = OverlapWork(blocks).offsets;
     const uint64_t P = occupied + (top ? 1 : 0);
     const uint64_t n = occupied;
     const SortLayout S(n, 8);
     const OverlapTable tb(P);
     if ((rc = c->ov.sort.reserve(S.end + 16)) != TA_OK) return rc;
     if ((rc = c->ov.rows.reserve(tb.bytes)) != TA_OK) return rc;
-    char* q = (char*)c->ov.sort.p;
-    uint64_t* k0 = (uint64_t*)(q + S.keys[0]); uint64_t* k1 = (uint64_t*)(q + S.keys[1]);
-    uint32_t* i0 = (uint32_t*)(q + S.idx[0]); uint32_t* i1 = (uint32_t*)(q + S.idx[1]);
-    void* temp = q + S.temp;
+    SortView<uint64_t> v(S, c->ov.sort.p);
     const unsigned long long* keys = (const unsigned long long*)c->ov.table.p;
     const int shift_b = 8 * c->ov.b.itemsize;
     TA_HIP(hipEventRecord(c->ov.ev[3], c->stream));
-    ta::launch_overlap_emit(c->stream, keys, slots, (const uint64_t*)((char*)c->ov.work.p + offsets_at), shift_b, k0, i0);
-    uint64_t* ks = k0; uint32_t* is = i0;
-    TA_HIP(ta::launch_radix_sort_u64(c->stream, n, k0, k1, i0, i1, temp, 8 * c->itemsize + shift_b, &ks, &is));
+    ta::launch_overlap_emit(c->stream, keys, slots, ScanBlock(blocks).offsets(c->ov.work.p), shift_b, v.keys(), v.idx());
+    TA_HIP(v.sort(c->stream, n, 8 * c->itemsize + shift_b));
     char* rp = (char*)c->ov.rows.p;
-    ta::launch_overlap_rows(c->stream, ks, is, n, keys + slots, shift_b, top, (uint32_t*)(rp + tb.a.at), (uint32_t*)(rp + tb.b.at), (uint64_t*)(rp + tb.n.at));
+    ta::launch_overlap_rows(c->stream, v.keys(), v.idx(), n, keys + slots, shift_b, top, (uint32_t*)(rp + tb.a.at), (uint32_t*)(rp + tb.b.at), (uint64_t*)(rp + tb.n.at));
     TA_HIP(hipGetLastError());
     TA_HIP(hipEventRecord(c->ov.ev[4], c->stream));
     TA_HIP(hipStreamSynchronize(c->stream));
@@ -228,10 +212,8 @@ TA_API int ta_overlap_timing_compaction(ta_ctx* c, double* ms, int* passes) {
     if (c->ov.state != 2) return fail(TA_EINVAL, "no settled overlap table (ask ta_overlap_size first)");
     int rc = use_device(c);
     if (rc != TA_OK) return rc;
-    TA_HIP(hipEventSynchronize(c->ov.ev[4]));
-    double t0 = 0.0, t1 = 0.0;
-    if ((rc = elapsed_ms(c->ov.ev[1], c->ov.ev[2], &t0)) != TA_OK || (rc = elapsed_ms(c->ov.ev[3], c->ov.ev[4], &t1)) != TA_OK) return rc;
-    *ms = t0 + t1;
+    hipEvent_t* ev = c->ov.ev;
+    TA_HIP(summed_ms(ev[4], {{ev[1], ev[2]}, {ev[3], ev[4]}}, ms));
     if (passes) *passes = c->ov.passes;
     return TA_OK;
 }

@@ -235,17 +235,14 @@ TA_API int ta_wall_medians(ta_ctx* c, int max_iter, int64_t* nwalls, double* ms_
     uint64_t E = 0;
     uint32_t status = 0;
     if (rc == TA_OK) {
-        uint64_t* total_dev = nullptr;
-        ta::launch_wall_starts(c->stream, gpa, n, scratch.p, (uint32_t*)starts.p, &total_dev);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(&E, total_dev, sizeof(E), hipMemcpyDeviceToHost, c->stream);
+        e = ta::launch_wall_starts(c->stream, gpa, n, scratch.p, (uint32_t*)starts.p, &E);
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
         if (e == hipSuccess) rc = c->walls.medians.reserve(E * 24 + 16);
         if (e == hipSuccess && rc == TA_OK) {
             uint32_t* op = (uint32_t*)c->walls.medians.p;
             uint32_t* os = op + 2 * E;
             int32_t* om = (int32_t*)(os + E);
-            uint32_t* st = (uint32_t*)scratch.p;                          // (the flags are dead: their first word takes the status)
+            uint32_t* st = ScanBlock(n).counts(scratch.p);                // (the flags are dead: their first word takes the status)
             e = hipMemsetAsync(st, 0, 4, c->stream);
             if (e == hipSuccess) {
                 ta::launch_wall_medians(c->stream, gpa, gco, (const uint32_t*)starts.p, (uint32_t)E, n, max_iter, op, os, om, st);

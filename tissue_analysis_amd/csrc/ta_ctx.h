@@ -2,14 +2,13 @@
 // struct of state below and its entry points in a file of its own: ta_api.hip holds the core (context, volume, sweep, extraction)
 // and the sweep's tile shape; ta_api_walls.hip, ta_api_sparse.hip and ta_api_exchange.hip the wall voxels, the sparse label ids and
 // the rank exchange; ta_api_<feature>.hip a feature.  What crosses files is declared here, with the file that defines it; the small
-// checks that several features repeat are inline below the context (the plane range of a ta_*_image call, an id as the volume
-// stores it, a feature's timed intervals, what the passes over a settled extraction share -- the "current" predicate, the entry
-// checks, the read of a pass's flag words -- what the getters share -- one ready check, one read-back of the columns of a buffer
-// whose parts a layout struct names through the cursor of ta_parts.h, one timing path, the debug words of a range pass, the guard
-// of a host allocation, the two pieces of axis arithmetic -- and the entry checks of the two separable transforms, whose
-// column-pass geometry and batch plan are in ta_separable.h; the launch plan of the range passes is in ta_range_plan.h).
+// checks that several features repeat are inline here: a feature's timed intervals above the state structs; what the passes over a
+// settled extraction, the getters and the two separable transforms share below the context.  The formats that have a header of
+// their own: the parts of a buffer (ta_parts.h), the count/scan block and the sort workspace of the count-then-emit passes
+// (ta_counted.h), the launch plan of the range passes (ta_range_plan.h), the column passes and batches (ta_separable.h).
 #pragma once
 #include "../../include/tissue_scan.h"
+#include "ta_counted.h"
 #include "ta_kernels.h"
 #include "ta_nearest.h"
 #include "ta_parts.h"
@@ -72,18 +71,6 @@ inline int interval_ms(hipEvent_t a, hipEvent_t b, double* ms) {      // (both r
     return elapsed_ms(a, b, ms);
 }
 
-// the workspace of launch_radix_sort_u32 / _u64 for n records, as byte offsets from `from` (a multiple of 16): keys (of key_bytes) x 2 |
-// index u32 x 2 | temp, each from a multiple of 16
-struct SortLayout {
-    uint64_t keys[2], idx[2], temp, end;
-    SortLayout(uint64_t n, int key_bytes, uint64_t from = 0) {
-        PartCursor at(from);
-        for (auto& k : keys) k = at.take(n * key_bytes, 16).at;
-        for (auto& i : idx) i = at.take(n * 4, 16).at;
-        temp = at.take(ta::wall_sort_temp_bytes(n), 16).at; end = at.end(16);
-    }
-};
-
 // A companion volume: a second volume with the buffer dims and layout of the label volume (the signal image, the overlap's B).
 struct Companion {
     const void* p = nullptr;                            // device pointer (owned.p or adopted), NULL = none
@@ -109,7 +96,7 @@ struct SignalState {
 
 // cell meshes (include/tissue_scan_mesh.h)
 struct MeshState {
-    DevBuf small;                                       // flags u32[4] | wanted u8[R] | per-wave counts and offsets | scan scratch
+    DevBuf small;                                       // flags u32[4] | wanted u8[R] | count/scan block of the faces | of the corners
     DevBuf work;                                        // face records u64[F] | neighbours u32[F] | corners u64[V] | sort keys, values x 2 | sort temp
     DevBuf out;                                         // vertex corners u64[V] | vbeg, vend, fbeg, fend u64[R] | triangles u32[2F][3] | cell, neighbour u32[2F]
     uint64_t seq = 0;                                   // extract_seq of the extraction the mesh belongs to, 0 = none
@@ -128,7 +115,7 @@ struct OverlapState {
     Companion b;
     DevBuf table;                                       // the device-global pair table: keys u64[slots] | counts u64[slots]
     DevBuf small;                                       // flags u32[4] | voxels of the pair (2^32 - 1, 2^32 - 1) u64
-    DevBuf work;                                        // compaction: block counts u32[B] | block offsets u64[B] | scan scratch
+    DevBuf work;                                        // compaction: the count/scan block of the blocks of the table
     DevBuf sort;                                        // sort keys u64[P] x 2 | slots u32[P] x 2 | radix temp
     DevBuf rows;                                        // the sorted table: a u32[P] | b u32[P] | n u64[P]
     int opt_log2 = 0;                                   // ta_overlap_set_capacity: 0 = automatic
@@ -146,9 +133,9 @@ struct OverlapState {
 // cell junctions (include/tissue_scan_junctions.h): index 0 = edges (3 labels), 1 = vertices (4 labels)
 struct JunctionState {
     DevBuf small;                                       // blocks of order >= 5 u64
-    DevBuf work;                                        // per wave: counts u32[W] x 2 | offsets u64[W] x 2 | scan scratch x 2
+    DevBuf work;                                        // per wave: the count/scan block of the edge records | of the vertex records
     DevBuf rec;                                         // records: origins u64[N3] | origins u64[N4] | labels u32[N3][3] | labels u32[N4][4]
-    DevBuf sort[2];                                     // sort keys u64[N] x 2 | order u32[N] x 2 | radix temp | row counts, offsets, scan scratch
+    DevBuf sort[2];                                     // sort keys u64[N] x 2 | order u32[N] x 2 | radix temp | count/scan block of the row heads
     DevBuf rows[2];                                     // the table: n u64[R] | sums u64[R][3] | labels u32[R][K]
     int state = 0;                                      // 0 = no tables, 1 = counting walk enqueued, 2 = settled
     uint64_t waves = 0;                                 // waves (= tasks) of a walk
@@ -172,7 +159,7 @@ struct WallGeoState {
 // connected components of the labels (include/tissue_scan_components.h)
 struct ComponentState {
     DevBuf parent;                                      // u32[voxels]: the union-find forest, then root / flagged slot: the row image's source
-    DevBuf work;                                        // per wave: root counts u32[W] | slot offsets u64[W] | scan scratch
+    DevBuf work;                                        // per wave: the count/scan block of the roots (offsets: the first slot of a wave)
     DevBuf slots;                                       // per slot: root u32[S] | row u32[S] | n u64[S] | sum1 u64[S][3] | first u64[S] | box i32[S][6]
     DevBuf sort;                                        // sort keys u64[S] x 2 | order u32[S] x 2 | radix temp
     DevBuf rows;                                        // the table, S rows of room: label u32 | n u64 | first i32[3] | bbox i32[6] | sum1 u64[3]

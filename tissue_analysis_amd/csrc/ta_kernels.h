@@ -81,14 +81,13 @@ hipError_t launch_radix_sort_u32(hipStream_t s, uint64_t n, uint32_t* keys0, uin
 hipError_t launch_radix_sort_u64(hipStream_t s, uint64_t n, uint64_t* keys0, uint64_t* keys1, uint32_t* idx0, uint32_t* idx1,
                                  void* temp, int key_bits, uint64_t** keys_out, uint32_t** idx_out);
 
-// kernels_walls.hip (continued): exclusive scan of uint32 counts into uint64 offsets (three small kernels)
-uint64_t scan_u32_scratch_bytes(uint64_t n);
+// kernels_walls.hip (continued): exclusive scan of uint32 counts into uint64 offsets (three small kernels); its callers go through
+// the ScanBlock of ta_counted.h, which states the format of the scratch
 void launch_scan_u32_exclusive(hipStream_t s, const uint32_t* counts, uint64_t n, void* scratch, uint64_t* offsets);
-uint64_t* scan_u32_total(void* scratch, uint64_t n);        // where that scan leaves the sum of all counts (device)
 
 // kernels_wallmedian.hip -- the median voxel of every wall, from the records grouped by pair (one wave per wall)
 uint64_t wall_median_scratch_bytes(uint64_t n);
-void launch_wall_starts(hipStream_t s, const uint32_t* pairs, uint64_t n, void* scratch, uint32_t* starts, uint64_t** nwalls_dev);
+hipError_t launch_wall_starts(hipStream_t s, const uint32_t* pairs, uint64_t n, void* scratch, uint32_t* starts, uint64_t* nwalls);
 void launch_wall_medians(hipStream_t s, const uint32_t* pairs, const int32_t* coords, const uint32_t* starts, uint32_t nwalls, uint64_t n,
                          int max_iter, uint32_t* out_pairs, uint32_t* out_sizes, int32_t* out_medians, uint32_t* status);
 
