@@ -191,6 +191,12 @@ DECLARED = {
         "ta_resample_as_overlap": (_ci, [_vp]),
         "ta_resample_as_signal": (_ci, [_vp]),
     },
+    "tissue_scan_extents.h": {
+        "ta_extents_extract": (_ci, [_vp, _P(_f64), _u32]),
+        "ta_extents_get": (_ci, [_vp, _vp, _vp]),
+        "ta_extents_debug": (_ci, [_vp, _P(_u32)]),
+        "ta_extents_timing": (_ci, [_vp, _P(_f64)]),
+    },
 }
 
 SYMBOLS = tuple(DECLARED["tissue_scan.h"])          # (kept apart from the feature headers' lists: this is tissue_scan.h's)
@@ -242,6 +248,10 @@ TOPOLOGY_MAX_GROUPS = 1024             # TP_MAX_GROUPS: workgroups of the pass a
 RESAMPLE_SYMBOLS = tuple(DECLARED["tissue_scan_resample.h"])
 RS_NEAREST, RS_LINEAR = 0, 1           # TA_RS_NEAREST / TA_RS_LINEAR
 RESAMPLE_DTYPES = (np.uint8, np.uint16, np.uint32)
+
+EXTENT_SYMBOLS = tuple(DECLARED["tissue_scan_extents.h"])
+EXTENT_SLOTS = 768                     # EX_SLOTS of csrc/ta_extents.h: rows of a workgroup's LDS table
+EXTENT_MAX_GROUPS = 1024               # EX_MAX_GROUPS: workgroups of the pass at most (the plan: tests/extent_reference.py)
 
 
 def exchange_words(capacity_pairs):
@@ -1052,6 +1062,33 @@ class Context(object):
         _check(self._lib.ta_resample_as_signal(self._h))
         self._keep_sig = None
         self._signal_itemsize = self.resample_device()[1]
+
+    # -- oriented extents (include/tissue_scan_extents.h)
+    def extents_extract(self, weights):
+        """Enqueue the extent pass over the current extraction: weights f64[R, 3, 3], per row of labels() three directions k with
+        one weight per MEMORY axis d (unit direction times voxel size; `memory_axes()` has the array axis of each d)."""
+        w = np.ascontiguousarray(weights, dtype=np.float64)
+        if w.ndim != 3 or w.shape[1:] != (3, 3):
+            raise ValueError("weights must be [rows, 3, 3], not %s" % (w.shape,))
+        _check(self._lib.ta_extents_extract(self._h, w.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), int(w.shape[0])))
+        self._extent_rows = int(w.shape[0])
+
+    def extents_rows(self):
+        """(lo f64[R, 3], hi f64[R, 3]): the smallest and the largest projection of every row's voxels per direction, +inf and
+        -inf for a row without voxels."""
+        R = getattr(self, "_extent_rows", 1)                   # (no pass yet: the library answers TA_EINVAL)
+        lo, hi = np.zeros((R, 3), dtype=np.float64), np.zeros((R, 3), dtype=np.float64)
+        _check(self._lib.ta_extents_get(self._h, lo.ctypes.data, hi.ctypes.data))
+        return lo, hi
+
+    def extents_debug(self):
+        """Diagnostics of the last extent pass: records that missed a workgroup's LDS table (spills) and the launch plan
+        (tiles_per_group, groups)."""
+        out = self._debug_words(self._lib.ta_extents_debug)
+        return dict(spills=out[0], tiles_per_group=out[2], groups=out[3])
+
+    def extents_timing(self):
+        return self._doubles(self._lib.ta_extents_timing, 1)[0]
 
     def memory_axes(self):
         """perm[k] = the array axis of memory axis k of the resident volume (slowest first), as the library orders them."""

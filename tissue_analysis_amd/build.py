@@ -15,11 +15,11 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJDIR = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "libtissue_scan.so")
-SOURCES = ["ta_api.hip", "ta_api_walls.hip", "ta_api_sparse.hip", "ta_api_exchange.hip", "ta_api_signal.hip", "ta_api_mesh.hip", "ta_api_overlap.hip", "ta_api_junctions.hip", "ta_api_wallgeo.hip", "ta_api_components.hip", "ta_api_distance.hip", "ta_api_nearest.hip", "ta_api_profile.hip", "ta_api_sighist.hip", "ta_api_sigmoments.hip", "ta_api_topology.hip", "ta_api_resample.hip",
+SOURCES = ["ta_api.hip", "ta_api_walls.hip", "ta_api_sparse.hip", "ta_api_exchange.hip", "ta_api_signal.hip", "ta_api_mesh.hip", "ta_api_overlap.hip", "ta_api_junctions.hip", "ta_api_wallgeo.hip", "ta_api_components.hip", "ta_api_distance.hip", "ta_api_nearest.hip", "ta_api_profile.hip", "ta_api_sighist.hip", "ta_api_sigmoments.hip", "ta_api_topology.hip", "ta_api_extents.hip", "ta_api_resample.hip",
            "kernels_basic.hip", "kernels_scan.hip", "kernels_walls.hip", "kernels_wallsort.hip", "kernels_wallmedian.hip", "kernels_census.hip",
            "kernels_pairsort.hip", "kernels_signal.hip", "kernels_mesh.hip", "kernels_overlap.hip", "kernels_junctions.hip", "kernels_wallgeo.hip",
-           "kernels_components.hip", "kernels_distance.hip", "kernels_nearest.hip", "kernels_profile.hip", "kernels_sighist.hip", "kernels_sigmoments.hip", "kernels_topology.hip", "kernels_resample.hip"]
-HEADERS = ["ta_ctx.h", "ta_parts.h", "ta_counted.h", "ta_device.h", "ta_range_plan.h", "ta_kernels.h", "ta_sweep_common.h", "ta_sweep_switches.h", "ta_pin_tables.inc", "ta_signal.h", "ta_mesh.h", "ta_overlap.h", "ta_junctions.h", "ta_wallgeo.h", "ta_components.h", "ta_distance.h", "ta_nearest.h", "ta_separable.h", "ta_profile.h", "ta_sighist.h", "ta_sigmoments.h", "ta_topology.h", "ta_resample.h",
+           "kernels_components.hip", "kernels_distance.hip", "kernels_nearest.hip", "kernels_profile.hip", "kernels_sighist.hip", "kernels_sigmoments.hip", "kernels_topology.hip", "kernels_extents.hip", "kernels_resample.hip"]
+HEADERS = ["ta_ctx.h", "ta_parts.h", "ta_counted.h", "ta_device.h", "ta_range_plan.h", "ta_kernels.h", "ta_sweep_common.h", "ta_sweep_switches.h", "ta_pin_tables.inc", "ta_signal.h", "ta_mesh.h", "ta_overlap.h", "ta_junctions.h", "ta_wallgeo.h", "ta_components.h", "ta_distance.h", "ta_nearest.h", "ta_separable.h", "ta_profile.h", "ta_sighist.h", "ta_sigmoments.h", "ta_topology.h", "ta_extents.h", "ta_resample.h",
            os.path.join("..", "..", "include", "tissue_scan.h"), os.path.join("..", "..", "include", "tissue_scan_signal.h"),
            os.path.join("..", "..", "include", "tissue_scan_mesh.h"), os.path.join("..", "..", "include", "tissue_scan_overlap.h"),
            os.path.join("..", "..", "include", "tissue_scan_junctions.h"), os.path.join("..", "..", "include", "tissue_scan_wallgeo.h"),
@@ -27,7 +27,7 @@ HEADERS = ["ta_ctx.h", "ta_parts.h", "ta_counted.h", "ta_device.h", "ta_range_pl
            os.path.join("..", "..", "include", "tissue_scan_nearest.h"),
            os.path.join("..", "..", "include", "tissue_scan_profile.h"), os.path.join("..", "..", "include", "tissue_scan_sighist.h"),
            os.path.join("..", "..", "include", "tissue_scan_sigmoments.h"), os.path.join("..", "..", "include", "tissue_scan_topology.h"),
-           os.path.join("..", "..", "include", "tissue_scan_resample.h")]
+           os.path.join("..", "..", "include", "tissue_scan_resample.h"), os.path.join("..", "..", "include", "tissue_scan_extents.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden",
          "-Wall", "-Wno-unused-function", "-DTA_BUILD"]
 # Per-source extra flags.  (The sweep kernels live on a hand-set VGPR budget -- the plane in flight is pinned above it -- and
@@ -36,7 +36,9 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hi
 # is the way out that was needed for one of round 4's variants and measured 0 - 2 % slower.  Not needed by the code as it is.)
 # kernels_resample.hip: the rounding order of its coordinate arithmetic is part of the ABI (include/tissue_scan_resample.h), so
 # nothing in it may be contracted into a fused multiply-add; the file says so itself with a pragma, the flag says it again.
-EXTRA_FLAGS = {"kernels_resample.hip": ["-ffp-contract=off"]}
+# kernels_extents.hip: every projection is three products and two sums, each rounded on its own (include/tissue_scan_extents.h); neither
+# the pragma nor __dmul_rn / __dadd_rn keeps -O3 from fusing them on gfx950, the flag does.
+EXTRA_FLAGS = {"kernels_resample.hip": ["-ffp-contract=off"], "kernels_extents.hip": ["-ffp-contract=off"]}
 
 
 def _hipcc():

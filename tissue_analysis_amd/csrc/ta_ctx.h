@@ -247,6 +247,18 @@ struct TopologyState {
     void release() { out.release(); destroy_events(ev); }
 };
 
+// oriented extents (include/tissue_scan_extents.h)
+struct ExtentState {
+    DevBuf out;                                         // flags u32[4] | keys of lo u64[R][3] | keys of hi u64[R][3]
+    DevBuf weights;                                     // f64[R][3][3]: the table of the last pass
+    std::vector<double> h_weights;                      // what that table was copied to the device from
+    uint64_t seq = 0;                                   // extract_seq of the extraction the rows belong to, 0 = none
+    uint32_t rows = 0;                                  // max_label + 1 of that extraction
+    ta::RangePlan plan;                                 // what the last pass was launched with (ta_extents_debug)
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    void release() { out.release(); weights.release(); destroy_events(ev); }
+};
+
 // resampling a second volume onto the label grid (include/tissue_scan_resample.h)
 struct ResampleState {
     const void* src = nullptr;                          // device pointer (owned_src.p or adopted), NULL = none
@@ -381,6 +393,7 @@ struct ta_ctx {
     SigHistState sh;
     SigMomentState sm;
     TopologyState tp;
+    ExtentState ex;
     ResampleState rs;
 };
 
@@ -565,6 +578,7 @@ void sighist_on_new_signal(ta_ctx* c);                // a new signal image: bot
 void sigmom_on_new_volume(ta_ctx* c);
 void sigmom_on_new_signal(ta_ctx* c);                 // a new signal image: the rows read the old one.  ta_api_sigmoments.hip
 void topology_on_new_volume(ta_ctx* c);
+void extents_on_new_volume(ta_ctx* c);
 void resample_on_new_volume(ta_ctx* c);               // a grid of other dims drops source and result.  ta_api_resample.hip
 // ta_resample_extract is about to write into `buf` (or, now == NULL, has let go of it): a B / a signal adopted from it by
 // ta_resample_as_overlap / _as_signal holds new contents -- its tables are stale -- and is dropped when the buffer moved to `now`

@@ -1,4 +1,4 @@
-// ta_range_plan.h -- the launch plan of the range passes: kernels_signal, _overlap, _wallgeo, _profile, _sighist, _sigmoments.hip
+// ta_range_plan.h -- the launch plan of the range passes: kernels_signal, _overlap, _wallgeo, _profile, _sighist, _sigmoments, _extents.hip
 // and, over block positions, kernels_topology.hip (plain host C++, no HIP).  A tile is `waves` rows x (64 lanes x VPL columns) x `planes` planes, VPL = 16 / sizeof(label) voxels a
 // lane; a workgroup takes `tiles_per_group` consecutive tiles (column blocks first, then row blocks, then plane blocks) and keeps
 // its LDS tables for the whole range.  Each kernel file states its RangeShape; tests/range_tiles.py restates the arithmetic, once.

@@ -327,6 +327,10 @@ class SlabJob(object):
         raise NotImplementedError("the Euler numbers (tissue_scan_topology.h) do not run on a slab: a 2 x 2 x 2 block at a seam "
                                   "belongs to two buffers")
 
+    def cell_extents(self, *args, **kwargs):
+        raise NotImplementedError("the oriented extents (tissue_scan_extents.h) do not run on a slab: the pass counts its "
+                                  "coordinates from the volume's first plane")
+
     def owned_view(self):
         return self.vol[1:] if self.has_low_halo else self.vol
 
@@ -614,6 +618,10 @@ class PipelinedSlabJob(object):
     def topology(self, *args, **kwargs):
         raise NotImplementedError("the Euler numbers (tissue_scan_topology.h) do not run on a slab: a 2 x 2 x 2 block at a seam "
                                   "belongs to two buffers")
+
+    def cell_extents(self, *args, **kwargs):
+        raise NotImplementedError("the oriented extents (tissue_scan_extents.h) do not run on a slab: the pass counts its "
+                                  "coordinates from the volume's first plane")
 
     def owned_view(self):
         return self.jobs[0].owned_view()

@@ -599,6 +599,13 @@ class ResidentVolume(object):
         from .cell_topology import resident_topology
         return self._timed("topology", resident_topology, self, voxelsize)
 
+    def cell_extents(self, axes=None, voxelsize=(1.0, 1.0, 1.0)):
+        """How far every label of the resident volume reaches along three directions of its own (`axes`: None = its principal
+        axes; one direction, one frame, a frame per row or {label: frame}, in array axes and physical space): a `CellExtents`
+        whose rows line up with the last extraction (swept first when there is none).  One pass over the labels on the GPU."""
+        from .cell_extents import resident_cell_extents
+        return self._timed("cell_extents", resident_cell_extents, self, axes, voxelsize)
+
     def meshes(self, labels=None, sub_factor=1, voxelsize=(1.0, 1.0, 1.0)):
         """The exact voxel-face surface meshes of the cells `labels` (ids; None = every label, background included) of
         host[::s, ::s, ::s]: a `CellMeshes`.  Count, scan and emit on the GPU, over the current extraction (swept first when

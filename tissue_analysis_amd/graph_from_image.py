@@ -135,7 +135,8 @@ def tissue_tables(analysis, labels, background, properties, property_as_real=Tru
     the face-connected blobs the label consists of, `analysis.label_components()`) runs the component pass, likewise;
     'euler_number' (vertex: `analysis.euler_number()`, 6-connectivity) the Euler-number pass; and so do
     'inscribed_radius' (vertex: `analysis.inscribed_radius()`) and 'depth' (vertex: `analysis.cell_depth()`, which needs a
-    background) with the distance pass, in real units with `property_as_real`."""
+    background) with the distance pass, in real units with `property_as_real`; 'principal_lengths' (vertex:
+    `analysis.cell_lengths()`, major, middle, minor) and 'box_fill' (vertex: `analysis.box_fill()`) the extent pass."""
     x = analysis.extraction
     ids = np.asarray(labels, dtype=np.int64).reshape(-1)
     pairs = _PairView(analysis, ids, min_contact_area)
@@ -241,6 +242,10 @@ def tissue_tables(analysis, labels, background, properties, property_as_real=Tru
         graph.set_vertex_column('inscribed_radius', analysis.wall_distance(real=real).of_labels(ids, 'max2'), asked)
     if 'depth' in properties:
         graph.set_vertex_column('depth', analysis.distance_from(real=real).of_labels(ids, 'min2'), asked)
+    if 'principal_lengths' in properties:
+        graph.set_vertex_column('principal_lengths', analysis.cell_extents(real=real).of_labels(ids, 'lengths'), asked, _show_vector)
+    if 'box_fill' in properties:
+        graph.set_vertex_column('box_fill', analysis.cell_extents().of_labels(ids, 'fill'), asked)
     return graph
 
 

@@ -208,6 +208,7 @@ class AbstractSpatialImageAnalysis(object):
         self._wall_geometry = None
         self._components = None
         self._topology = None
+        self._extents = {}
         self._distance_cache = {}
         try:
             self.filepath, self.filename = split(image.info["Filename"])
@@ -273,6 +274,7 @@ class AbstractSpatialImageAnalysis(object):
         self._wall_geometry = None
         self._components = None
         self._topology = None
+        self._extents = {}
         self._distance_cache = {}
         self._voxel_layer1 = None
         self._voxel_layer18 = None
@@ -779,6 +781,44 @@ class AbstractSpatialImageAnalysis(object):
         without those in `exclude`.  For 6-connectivity only: the components are face-connected."""
         from .cell_topology import topological_defects
         return topological_defects(self.cell_topology(), self.label_components(), exclude)
+
+    # -- oriented extents: length, width, depth (include/tissue_scan_extents.h; one pass over the resident volume on the GPU)
+    def cell_extents(self, axes=None, real=True):
+        """How far every label reaches along three directions of its own: a `CellExtents` (lengths, oriented box, fill) in the
+        ids of the image, with this analysis' voxel size (ones with real=False).  axes: None = every cell's principal axes, those
+        of its PHYSICAL covariance from the sweep's exact moments, by decreasing eigenvalue; or one direction (completed to a
+        frame), one [3, 3] frame for every cell, or {label: [3, 3]} (the other labels take the image axes), in array axes.
+        Nothing is excluded here.  With axes=None cached per `real` until `refresh()` or an edit of the image; not cached with
+        axes of the caller's."""
+        vs = tuple(float(v) for v in self._voxelsize) if real else (1.0, 1.0, 1.0)
+        if axes is not None:
+            return self._resident_rows().cell_extents(axes, vs)
+        cache = getattr(self, "_extents", None)
+        if cache is None:
+            cache = self._extents = {}
+        if bool(real) not in cache:
+            cache[bool(real)] = self._resident_rows().cell_extents(None, vs)
+        return cache[bool(real)]
+
+    def cell_lengths(self, labels=None, real=True):
+        """Per label its extents along its principal axes, ordered major, middle, minor axis: how long, wide and thick the cell
+        is (the exact extent of the union of its voxel boxes; NaN for a label without voxels).  Returned like center_of_mass()."""
+        labels = self.label_request(labels)
+        values = self.cell_extents(real=real).of_labels(labels, "lengths")
+        if len(labels) == 1:
+            return values[0]
+        return self.convert_return(values if self.return_type == NPLIST else list(values), labels)
+
+    def cell_extent_along(self, direction, labels=None, real=True):
+        """Per label its extent along `direction` (array axes; say, the organ axis); returned like volume()."""
+        labels = self.label_request(labels)
+        return self.convert_return(self.cell_extents(direction, real).of_labels(labels, "lengths")[:, 0], labels)
+
+    def box_fill(self, labels=None):
+        """Per label the share of its oriented box (along its principal axes) that the cell fills: 1 for a cuboid, 0.52 for a
+        ball; returned like volume()."""
+        labels = self.label_request(labels)
+        return self.convert_return(self.cell_extents().of_labels(labels, "fill"), labels)
 
     # -- exact Euclidean distance maps (include/tissue_scan_distance.h; three passes over the resident volume on the GPU)
     def _distance_map(self, mode, label, edge, real):
