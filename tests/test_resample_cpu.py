@@ -62,7 +62,9 @@ def test_library_exports_the_resample_symbols_and_they_reject_a_null_context():
 def test_build_recipe_lists_the_new_files():
     from tissue_analysis_amd import build
     assert "kernels_resample.hip" in build.SOURCES and "ta_api_resample.hip" in build.SOURCES
-    assert "ta_resample.h" in build.HEADERS and any(h.endswith("tissue_scan_resample.h") for h in build.HEADERS)
+    assert "ta_resample.h" in build.dependencies("kernels_resample.hip")        # (a change of the header rebuilds the feature)
+    host = build.dependencies("ta_api_resample.hip")
+    assert "ta_resample.h" in host and any(h.endswith("tissue_scan_resample.h") for h in host)
     assert "-ffp-contract=off" in build.EXTRA_FLAGS["kernels_resample.hip"]
     assert "#pragma clang fp contract(off)" in open(os.path.join(build.CSRC, "kernels_resample.hip")).read()
 

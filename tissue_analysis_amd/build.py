@@ -3,11 +3,18 @@
     python -m tissue_analysis_amd.build [--force] [--save-temps]
 
 hipcc cross-compiles without a GPU; the built .so is git-ignored but travels with the tree.
+
+Every *.hip file of csrc/ is a source; build(), build_sanitized() and scripts/build_variant.py are calls of compile_and_link,
+which says what makes an object current.  `--save-temps` is part of the recorded command like any flag: asking for it
+recompiles everything, and so does the next plain build.  dependencies(source) answers why a change rebuilt an object.
 """
 from __future__ import annotations
 
+import concurrent.futures
+import json
 import os
 import re
+import shutil
 import subprocess
 import sys
 
@@ -15,19 +22,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJDIR = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "libtissue_scan.so")
-SOURCES = ["ta_api.hip", "ta_api_walls.hip", "ta_api_sparse.hip", "ta_api_exchange.hip", "ta_api_signal.hip", "ta_api_mesh.hip", "ta_api_overlap.hip", "ta_api_junctions.hip", "ta_api_wallgeo.hip", "ta_api_components.hip", "ta_api_distance.hip", "ta_api_nearest.hip", "ta_api_profile.hip", "ta_api_sighist.hip", "ta_api_sigmoments.hip", "ta_api_topology.hip", "ta_api_extents.hip", "ta_api_resample.hip",
-           "kernels_basic.hip", "kernels_scan.hip", "kernels_walls.hip", "kernels_wallsort.hip", "kernels_wallmedian.hip", "kernels_census.hip",
-           "kernels_pairsort.hip", "kernels_signal.hip", "kernels_mesh.hip", "kernels_overlap.hip", "kernels_junctions.hip", "kernels_wallgeo.hip",
-           "kernels_components.hip", "kernels_distance.hip", "kernels_nearest.hip", "kernels_profile.hip", "kernels_sighist.hip", "kernels_sigmoments.hip", "kernels_topology.hip", "kernels_extents.hip", "kernels_resample.hip"]
-HEADERS = ["ta_ctx.h", "ta_parts.h", "ta_counted.h", "ta_device.h", "ta_range_plan.h", "ta_kernels.h", "ta_sweep_common.h", "ta_sweep_switches.h", "ta_pin_tables.inc", "ta_signal.h", "ta_mesh.h", "ta_overlap.h", "ta_junctions.h", "ta_wallgeo.h", "ta_components.h", "ta_distance.h", "ta_nearest.h", "ta_separable.h", "ta_profile.h", "ta_sighist.h", "ta_sigmoments.h", "ta_topology.h", "ta_extents.h", "ta_resample.h",
-           os.path.join("..", "..", "include", "tissue_scan.h"), os.path.join("..", "..", "include", "tissue_scan_signal.h"),
-           os.path.join("..", "..", "include", "tissue_scan_mesh.h"), os.path.join("..", "..", "include", "tissue_scan_overlap.h"),
-           os.path.join("..", "..", "include", "tissue_scan_junctions.h"), os.path.join("..", "..", "include", "tissue_scan_wallgeo.h"),
-           os.path.join("..", "..", "include", "tissue_scan_components.h"), os.path.join("..", "..", "include", "tissue_scan_distance.h"),
-           os.path.join("..", "..", "include", "tissue_scan_nearest.h"),
-           os.path.join("..", "..", "include", "tissue_scan_profile.h"), os.path.join("..", "..", "include", "tissue_scan_sighist.h"),
-           os.path.join("..", "..", "include", "tissue_scan_sigmoments.h"), os.path.join("..", "..", "include", "tissue_scan_topology.h"),
-           os.path.join("..", "..", "include", "tissue_scan_resample.h"), os.path.join("..", "..", "include", "tissue_scan_extents.h")]
+SOURCES = sorted(f for f in os.listdir(CSRC) if f.endswith(".hip"))
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden",
          "-Wall", "-Wno-unused-function", "-DTA_BUILD"]
 # Per-source extra flags.  (The sweep kernels live on a hand-set VGPR budget -- the plane in flight is pinned above it -- and
@@ -39,6 +34,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hi
 # kernels_extents.hip: every projection is three products and two sums, each rounded on its own (include/tissue_scan_extents.h); neither
 # the pragma nor __dmul_rn / __dadd_rn keeps -O3 from fusing them on gfx950, the flag does.
 EXTRA_FLAGS = {"kernels_resample.hip": ["-ffp-contract=off"], "kernels_extents.hip": ["-ffp-contract=off"]}
+SAVE_TEMPS = ["-save-temps=obj", "-Rpass-analysis=kernel-resource-usage"]      # after -o: intermediates and the resource-usage remarks
 
 
 def _hipcc():
@@ -112,57 +108,140 @@ def pinned_violations(asm, variants):
     return bad
 
 
-def _check_pinned(hipcc, verbose=False):
-    """Refuse a build in which compiler-allocated code reaches the hand-pinned registers (pinned_violations)."""
-    asm = os.path.join(OBJDIR, "kernels_scan.check.s")
-    cmd = [hipcc] + FLAGS + EXTRA_FLAGS.get("kernels_scan.hip", []) + ["--cuda-device-only", "-S", os.path.join(CSRC, "kernels_scan.hip"), "-o", asm]
+def _check_pinned(hipcc, objdir, flags, verbose=False):
+    """Refuse a build in which compiler-allocated code reaches the hand-pinned registers (pinned_violations): kernels_scan.hip
+    compiled to assembly in `objdir` with the `flags` its object there was made with."""
+    asm = os.path.join(objdir, "kernels_scan.check.s")
+    cmd = [hipcc] + flags + ["--cuda-device-only", "-S", os.path.join(CSRC, "kernels_scan.hip"), "-o", asm]
     if verbose:
         print(" ".join(cmd))
-    subprocess.check_call(cmd, cwd=OBJDIR)
+    subprocess.check_call(cmd, cwd=objdir)
     bad = pinned_violations(open(asm).read(), read_variants())
     if bad:
         raise RuntimeError("compiler-allocated VGPRs reach the hand-pinned registers in kernels_scan.hip:\n  %s"
                            % "\n  ".join(bad[:10]))
 
 
-def build(force=False, save_temps=False, verbose=False):
-    """Compile every HIP source for gfx950 and link libtissue_scan.so. Returns its path."""
+def _jobs():
+    """How many compilers run at a time: $MAX_JOBS, 16 by default and at the most."""
+    try:
+        return max(1, min(16, int(os.environ.get("MAX_JOBS", "16"))))
+    except ValueError:
+        return 16
+
+
+def _current(target, record, argv, compiler, base):
+    """Whether `record` says that `target` was made by exactly `argv` under this `compiler`, and nothing it was made from
+    (paths relative to `base`) is missing or newer than it.  A target without a record is never current."""
+    try:
+        rec = json.load(open(record))
+        t = os.path.getmtime(target)
+    except (OSError, ValueError):
+        return False
+    deps = [os.path.join(base, d) for d in rec.get("deps", [])]
+    return (rec.get("argv") == argv and rec.get("compiler") == compiler
+            and all(os.path.exists(d) and os.path.getmtime(d) <= t for d in deps))
+
+
+def _write_record(record, argv, compiler, deps):
+    with open(record, "w") as f:
+        json.dump({"argv": argv, "compiler": compiler, "deps": deps}, f, indent=1)
+
+
+def _parse_deps(rule, cwd, base):
+    """The prerequisites of the make rule that `-MM` printed when run in `cwd`, as paths relative to `base`."""
+    words = re.split(r"(?<!\\)\s+", rule.replace("\\\n", " ").split(":", 1)[1].strip())
+    return [os.path.relpath(os.path.join(cwd, w.replace("\\ ", " ")), base) for w in words if w]
+
+
+def compile_and_link(srcdir, sources, objdir, lib, flags, link_flags=(), extra_flags=None, defines=(), tail=None,
+                     force=False, verbose=False, pin_check=False, report=None):
+    """Compile those of `sources` (names in `srcdir`) whose objects in `objdir` are not current, at most $MAX_JOBS at a time, and
+    link `lib` from all of them if it is not current.  Returns the sources it compiled.
+
+    A source's command is hipcc + flags + extra_flags[source] + defines + -c/-o + tail[source], run in `objdir`; the link's is
+    hipcc --offload-arch=gfx950 -shared -fPIC + link_flags + -o lib + the objects in the order of `sources`.  Each object has a
+    record beside it (NAME.o.json): that argv with the resolved compiler in front, the compiler's version, and the files the
+    source was preprocessed from, which a `--cuda-host-only -MM` run with the same flags and defines names while the
+    compile runs.  (Not -MMD on the compile itself: the compiler derives the HIP compilation-unit id from its command line, so
+    that would change every object.)  An object is current when its record says what would run now and none of those files is
+    missing or newer than it.  The record is removed before the compile and written after it succeeded, so a failed compile is
+    never skipped by the next call.  The library's record, in `objdir` too, does the same for the link, which also runs whenever
+    an object was compiled.  `report(source, text)` gets what each successful compile printed; `pin_check` runs _check_pinned
+    on the kernels_scan.hip of CSRC."""
     hipcc = _hipcc()
-    os.makedirs(OBJDIR, exist_ok=True)
-    hdrs = [os.path.join(CSRC, h) for h in HEADERS]
-    procs, objs = [], []
-    for src in SOURCES:
-        s = os.path.join(CSRC, src)
-        o = os.path.join(OBJDIR, src.replace(".hip", ".o"))
+    resolved = os.path.realpath(shutil.which(hipcc) or hipcc)
+    version = subprocess.check_output([hipcc, "--version"]).decode(errors="replace")
+    compiler = " / ".join(line.strip() for line in version.splitlines() if "version" in line)
+    extra_flags, tail = extra_flags or {}, tail or {}
+    os.makedirs(objdir, exist_ok=True)
+    objs, todo = [], []
+    for src in sources:
+        s = os.path.join(srcdir, src)
+        o = os.path.join(objdir, src.replace(".hip", ".o"))
         objs.append(o)
-        if force or _stale(o, [s] + hdrs):
-            cmd = [hipcc] + FLAGS + EXTRA_FLAGS.get(src, []) + ["-c", s, "-o", o]
-            if save_temps:
-                cmd += ["-save-temps=obj", "-Rpass-analysis=kernel-resource-usage"]
+        front = [hipcc] + list(flags) + extra_flags.get(src, []) + list(defines)
+        cmd = front + ["-c", s, "-o", o] + tail.get(src, [])
+        if force or not _current(o, o + ".json", [resolved] + cmd[1:], compiler, srcdir):
+            todo.append((src, o, cmd, front + ["--cuda-host-only", "-MM", s]))
+    failed = False
+    with concurrent.futures.ThreadPoolExecutor(_jobs()) as pool:
+        runs = []
+        for src, o, cmd, deps_cmd in todo:
+            if os.path.exists(o + ".json"):
+                os.remove(o + ".json")
             if verbose:
                 print(" ".join(cmd))
-            procs.append((src, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT,
-                                                cwd=OBJDIR)))
-    failed = False
-    for src, p in procs:
-        out = p.communicate()[0].decode(errors="replace")
-        if p.returncode != 0:
-            failed = True
-            sys.stderr.write("hipcc failed on %s:\n%s\n" % (src, out))
-        elif out.strip() and (verbose or save_temps):
-            print(out)
+            runs.append((pool.submit(subprocess.run, cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, cwd=objdir),
+                         pool.submit(subprocess.run, deps_cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, cwd=objdir)))
+        for (src, o, cmd, _), (compiled, listed) in zip(todo, runs):
+            compiled, listed = compiled.result(), listed.result()
+            out = compiled.stdout.decode(errors="replace")
+            if compiled.returncode or listed.returncode:
+                failed = True
+                said = out if compiled.returncode else listed.stderr.decode(errors="replace")
+                sys.stderr.write("hipcc failed on %s:\n%s\n" % (src, said))
+                continue
+            _write_record(o + ".json", [resolved] + cmd[1:], compiler, _parse_deps(listed.stdout.decode(), objdir, srcdir))
+            if report:
+                report(src, out)
     if failed:
         raise RuntimeError("hipcc compilation failed")
-    stamp = os.path.join(OBJDIR, "kernels_scan.check.ok")       # (a failed check must not be skipped by the next call)
-    if _stale(stamp, [os.path.join(OBJDIR, "kernels_scan.o")]):
-        _check_pinned(hipcc, verbose)
-        open(stamp, "w").write("ok\n")
-    if force or procs or _stale(LIB, objs):
-        cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB] + objs
+    if pin_check:
+        stamp = os.path.join(objdir, "kernels_scan.check.ok")       # (a failed check must not be skipped by the next call)
+        if _stale(stamp, [os.path.join(objdir, "kernels_scan.o")]):
+            _check_pinned(hipcc, objdir, list(flags) + extra_flags.get("kernels_scan.hip", []) + list(defines), verbose)
+            open(stamp, "w").write("ok\n")
+    cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC"] + list(link_flags) + ["-o", lib] + objs
+    record = os.path.join(objdir, os.path.basename(lib) + ".json")
+    if force or todo or not _current(lib, record, [resolved] + cmd[1:], compiler, objdir):
+        if os.path.exists(record):
+            os.remove(record)
         if verbose:
             print(" ".join(cmd))
         subprocess.check_call(cmd)
+        _write_record(record, [resolved] + cmd[1:], compiler, objs)
+    return [src for src, _, _, _ in todo]
+
+
+def build(force=False, save_temps=False, verbose=False):
+    """Compile every HIP source for gfx950 and link libtissue_scan.so. Returns its path."""
+    def show(src, out):
+        if out.strip():
+            print(out)
+    compile_and_link(CSRC, SOURCES, OBJDIR, LIB, FLAGS, extra_flags=EXTRA_FLAGS,
+                     tail={s: SAVE_TEMPS for s in SOURCES} if save_temps else None,
+                     force=force, verbose=verbose, pin_check=True, report=show if verbose or save_temps else None)
     return LIB
+
+
+def dependencies(source_name):
+    """The files the product build's object of `source_name` was made from, as its record has them: paths relative to CSRC,
+    the source itself first.  A change of any of them recompiles that source, and of nothing else but the command."""
+    record = os.path.join(OBJDIR, source_name.replace(".hip", ".o") + ".json")
+    if not os.path.exists(record):
+        raise RuntimeError("%s has no build record: run build() first" % source_name)
+    return json.load(open(record))["deps"]
 
 
 ASAN_DIR = os.path.join(OBJDIR, "asan")
@@ -181,28 +260,10 @@ def build_sanitized(force=False, verbose=False):
     """HOST side of the same SOURCES under -fsanitize=address,undefined (the device side cannot be
     instrumented on this pool and is compiled as usual): the library the CPU suite loads to walk the C ABI's
     argument checks and failure paths.  Never the product build."""
-    hipcc = _hipcc()
-    os.makedirs(ASAN_DIR, exist_ok=True)
-    hdrs = [os.path.join(CSRC, h) for h in HEADERS]
     flags = [f for f in FLAGS if f != "-O3"] + ["-O1", "-g", "-fno-omit-frame-pointer",
                                                 "-fsanitize=address,undefined", "-Wno-option-ignored"]
-    procs, objs = [], []
-    for src in SOURCES:
-        s = os.path.join(CSRC, src)
-        o = os.path.join(ASAN_DIR, src.replace(".hip", ".o"))
-        objs.append(o)
-        if force or _stale(o, [s] + hdrs):
-            cmd = [hipcc] + flags + EXTRA_FLAGS.get(src, []) + ["-c", s, "-o", o]
-            if verbose:
-                print(" ".join(cmd))
-            procs.append((src, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, cwd=ASAN_DIR)))
-    for src, p in procs:
-        out = p.communicate()[0].decode(errors="replace")
-        if p.returncode != 0:
-            raise RuntimeError("hipcc (sanitized) failed on %s:\n%s" % (src, out))
-    if force or procs or _stale(ASAN_LIB, objs):
-        subprocess.check_call([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-fsanitize=address,undefined",
-                               "-shared-libsan", "-o", ASAN_LIB] + objs)
+    compile_and_link(CSRC, SOURCES, ASAN_DIR, ASAN_LIB, flags, ["-fsanitize=address,undefined", "-shared-libsan"],
+                     extra_flags=EXTRA_FLAGS, force=force, verbose=verbose)
     return ASAN_LIB
 
 
