@@ -198,8 +198,8 @@ TA_API int ta_read_probe(ta_ctx* ctx, const void* dev_ptr, uint64_t bytes, int r
 
 /* Diagnostics of the last ta_extract: out[0] = label-range flag, out[1] = adjacency-table overflow
  * flag, out[2] = run records that missed the workgroup LDS label table (went to global atomics),
- * out[3] = face records that missed the LDS pair table, out[4..15] reserved (cycle stamps of
- * diagnostic builds). */
+ * out[3] = face records that missed the LDS pair table, out[4..15] reserved (record counts and
+ * cycle stamps of the TA_RECCOUNT / TA_BARSTAMP diagnostic builds). */
 TA_API int ta_debug_counters(ta_ctx* ctx, uint32_t out[16]);
 
 /* ---- device-side views for the multi-GPU reduce (RCCL runs on these in place) -------------

@@ -1,6 +1,6 @@
-"""Build a VARIANT of libtissue_scan.so with extra -D flags (experiments, ablations, stamps) into scratch/:
+"""Build a VARIANT of libtissue_scan.so with extra -D flags (experiments, ablations, instrumentation) into scratch/:
 
-    python scripts/build_variant.py NAME -DTA_STAMPS [-DTA_FCAP=128 ...]     ->  scratch/libNAME.so
+    python scripts/build_variant.py NAME -DTA_RECCOUNT [-DTA_FCAP=128 ...]     ->  scratch/libNAME.so
 
 Run anything against it with TISSUE_SCAN_LIB=$PWD/scratch/libNAME.so (the product never loads a variant by itself).
 `--no-pin-check` skips the check that compiler-allocated registers stay clear of the hand-pinned ones (ablations whose

@@ -31,11 +31,10 @@ done
 #   noflush = the tile tables are not flushed; hot1 = ... and the top-of-plane drains add nothing to the tables; hot2 = ... and run
 #   no probe rounds; hot4 = ... and read neither keys nor records; noslow = ... and the in-plane drains / the end of the tile consume
 #   nothing; abl1 = nothing is consumed anywhere (records produced and stored); abl3 = not even placed (compares + counts + scan);
-#   nf01 (not cumulative) = no axis-0 / axis-1 face records; nomask = the pre-round-5 record stores (trash slot, five VALU a position);
-#   nohalo1 = a workgroup's first wave reads no row above (12.5 % fewer bytes fetched); notr = the flush adds a label's sums lane = label
+#   nf01 (not cumulative) = no axis-0 / axis-1 face records; nohalo1 = a workgroup's first wave reads no row above (12.5 % fewer bytes fetched)
 OUT=gpurun_out/${TAG}_ablations.txt
 : > $OUT
-for a in base noflush hot1 hot2 hot4 noslow abl1 abl3 nf01 nomask nohalo1 notr base; do
+for a in base noflush hot1 hot2 hot4 noslow abl1 abl3 nf01 nohalo1 base; do
   if [ "$a" = base ] || [ -f scratch/lib$a.so ]; then
     echo "ablation $a" >> $OUT
     if [ "$a" = base ]; then unset TISSUE_SCAN_LIB; else export TISSUE_SCAN_LIB=$R/scratch/lib$a.so; fi

@@ -15,10 +15,11 @@
 //
 // How the (sparse: ~2 of 64 lanes per compare) events reach the dense 64-wide consumer:
 //   * per row every lane counts its events (one v_addc per compare), ONE packed DPP add-scan over the
-//     lanes gives each lane the offset of its first record, and every lane then stores at every compare
-//     without touching the exec mask: at its own running offset when the compare fired, into a trash slot
-//     when it did not.  No per-compare ballot / mask-prefix / popcount / SGPR cursor arithmetic, no live
-//     64-bit masks; the axis-0 faces of a plane ride on the scan of its first row;
+//     lanes gives each lane the offset of its first record, and every compare is then made once more as a
+//     v_cmpx that writes the exec mask itself: the lanes where it fired store at their own running offset
+//     and step it, one scalar move puts the mask back (the predicated stores below).  No per-compare
+//     ballot / mask-prefix / popcount / SGPR cursor arithmetic, no live 64-bit masks; the axis-0 faces of a
+//     plane ride on the scan of its first row;
 //   * the per-wave buffers are LINEAR and drained completely (no ring wrap arithmetic); the drain is
 //     checked once per row, BEFORE the row is emitted, from the totals the scan produced (one scalar test);
 //   * records of a row land sorted by column, so a run record only carries the column where its run
@@ -34,9 +35,7 @@
 
 namespace ta {
 
-// the hot (most common) label of the volume gets a private row per workgroup, also with adjacency
 constexpr int FCAP = TA_FCAP, RCAP = TA_RCAP;           // record capacities of a wave's buffers
-constexpr int FTRASH = FCAP, RTRASH = RCAP + 1;          // the trash slots of the branch-free stores, behind the buffers
 constexpr uint32_t ROWID_MASK = 0x7FFFFC00u;            // bits of a run code that name the row (b, a, and the zero bits above)
 constexpr uint32_t ROW_END = 0x80000000u;               // code bit of the record that closes a row's last run (no voxel to its right)
 constexpr uint32_t NO_ROW = 0xFFFFFFFFu;                // code of the sentinel: never equal to a record's row
@@ -45,8 +44,9 @@ typedef __attribute__((address_space(3))) uint32_t* lds_u32;
 
 template <bool ADJ>
 struct __attribute__((aligned(16))) ScanWaveLds {
-    uint2 frec[ADJ ? FCAP + 1 : 1];                     // faces of axis 0/1: voxel, neighbour | axis << 30; [FCAP] = trash slot
-    uint32_t cql[RCAP + 2], cqc[RCAP + 2];              // runs; record i lives in slot i + 1, slot 0 = sentinel / carry, slot RCAP + 1 = trash
+    uint2 frec[ADJ ? FCAP + 1 : 1];                     // faces of axis 0/1: voxel, neighbour | axis << 30; [FCAP] is spare (nothing writes it)
+    uint32_t cql[RCAP + 2], cqc[RCAP + 2];              // runs; record i lives in slot i + 1, slot 0 = sentinel / carry; slot RCAP + 1 is spare
+                                                        // (nothing writes it: the drain reads it behind a full buffer's last record and ignores it)
 };
 
 // NW packed words of sums per label slot (SumPack)
@@ -90,43 +90,9 @@ __device__ __forceinline__ uint32_t wave_scan_add(uint32_t x) {
 // LDS / VALU instructions that run under it; DPP instructions are the exception -- emit_done() pads for them.)
 // FULL: every lane of the wave is live at the call (EXEC is put back to all ones), else `live` is the mask to put back
 #define TA_CMPX(a, b) "v_cmpx_ne_u32_e32 vcc, " a ", " b "\n\t"
-#define TA_CMPX_PART(a, b) TA_CMPX(a, b)
-template <bool FULL>
-__device__ __forceinline__ void store_face_if_ne(uint32_t& off, const uint32_t v, const uint32_t pv, const uint64_t live) {
-    if constexpr (FULL)
-        asm volatile(TA_CMPX("%1", "%2") "ds_write2_b32 %0, %1, %2 offset1:1\n\tv_add_u32_e32 %0, 8, %0\n\ts_mov_b64 exec, -1"
-                     : "+v"(off) : "v"(v), "v"(pv) : "vcc", "memory");
-    else
-        asm volatile(TA_CMPX_PART("%1", "%2") "ds_write2_b32 %0, %1, %2 offset1:1\n\tv_add_u32_e32 %0, 8, %0\n\ts_mov_b64 exec, %3"
-                     : "+v"(off) : "v"(v), "v"(pv), "s"(live) : "vcc", "memory");
-}
-// ... the neighbour word tagged with the axis (`tag`: wave-uniform)
-template <bool FULL>
-__device__ __forceinline__ void store_face_tagged_if_ne(uint32_t& off, const uint32_t v, const uint32_t pv, const uint32_t tag, const uint64_t live) {
-    uint32_t t;
-    if constexpr (FULL)
-        asm volatile(TA_CMPX("%2", "%3") "v_or_b32_e32 %1, %4, %3\n\tds_write2_b32 %0, %2, %1 offset1:1\n\tv_add_u32_e32 %0, 8, %0\n\ts_mov_b64 exec, -1"
-                     : "+v"(off), "=&v"(t) : "v"(v), "v"(pv), "s"(tag) : "vcc", "memory");
-    else
-        asm volatile(TA_CMPX_PART("%2", "%3") "v_or_b32_e32 %1, %4, %3\n\tds_write2_b32 %0, %2, %1 offset1:1\n\tv_add_u32_e32 %0, 8, %0\n\ts_mov_b64 exec, %5"
-                     : "+v"(off), "=&v"(t) : "v"(v), "v"(pv), "s"(tag), "s"(live) : "vcc", "memory");
-}
-// a run record {closing label, code0 | J} where v != pcv; the two run arrays lie STRIDE dwords apart
-template <bool FULL, int J, int STRIDE>
-__device__ __forceinline__ void store_run_if_ne(uint32_t& off, const uint32_t v, const uint32_t pcv, const uint32_t code0, const uint64_t live) {
-    static_assert(STRIDE < 256, "ds_write2_b32 offsets are 8 bits of dwords");
-    uint32_t t;
-    if constexpr (FULL)
-        asm volatile(TA_CMPX("%2", "%3") "v_or_b32_e32 %1, %5, %4\n\tds_write2_b32 %0, %3, %1 offset1:%6\n\tv_add_u32_e32 %0, 4, %0\n\ts_mov_b64 exec, -1"
-                     : "+v"(off), "=&v"(t) : "v"(v), "v"(pcv), "v"(code0), "n"(J), "n"(STRIDE) : "vcc", "memory");
-    else
-        asm volatile(TA_CMPX_PART("%2", "%3") "v_or_b32_e32 %1, %5, %4\n\tds_write2_b32 %0, %3, %1 offset1:%6\n\tv_add_u32_e32 %0, 4, %0\n\ts_mov_b64 exec, %7"
-                     : "+v"(off), "=&v"(t) : "v"(v), "v"(pcv), "v"(code0), "n"(J), "n"(STRIDE), "s"(live) : "vcc", "memory");
-}
 // Four positions in ONE asm statement (between separate statements the compiler pads a wait state it cannot rule out: an s_nop per
 // position).  `EX`: what EXEC is put back to after each position.
 #define TA_FACE_POS(v, pv, EX) TA_CMPX(v, pv) "ds_write2_b32 %0, " v ", " pv " offset1:1\n\tv_add_u32_e32 %0, 8, %0\n\ts_mov_b64 exec, " EX "\n\t"
-#define TA_FACE_POS_PART(v, pv, EX) TA_CMPX_PART(v, pv) "ds_write2_b32 %0, " v ", " pv " offset1:1\n\tv_add_u32_e32 %0, 8, %0\n\ts_mov_b64 exec, " EX "\n\t"
 template <bool FULL>
 __device__ __forceinline__ void store_faces4_if_ne(uint32_t& off, const uint32_t v0, const uint32_t p0, const uint32_t v1, const uint32_t p1,
                                                    const uint32_t v2, const uint32_t p2, const uint32_t v3, const uint32_t p3, const uint64_t live) {
@@ -134,12 +100,11 @@ __device__ __forceinline__ void store_faces4_if_ne(uint32_t& off, const uint32_t
         asm volatile(TA_FACE_POS("%1", "%2", "-1") TA_FACE_POS("%3", "%4", "-1") TA_FACE_POS("%5", "%6", "-1") TA_FACE_POS("%7", "%8", "-1")
                      : "+v"(off) : "v"(v0), "v"(p0), "v"(v1), "v"(p1), "v"(v2), "v"(p2), "v"(v3), "v"(p3) : "vcc", "memory");
     else
-        asm volatile(TA_FACE_POS_PART("%1", "%2", "%9") TA_FACE_POS_PART("%3", "%4", "%9") TA_FACE_POS_PART("%5", "%6", "%9") TA_FACE_POS_PART("%7", "%8", "%9")
+        asm volatile(TA_FACE_POS("%1", "%2", "%9") TA_FACE_POS("%3", "%4", "%9") TA_FACE_POS("%5", "%6", "%9") TA_FACE_POS("%7", "%8", "%9")
                      : "+v"(off) : "v"(v0), "v"(p0), "v"(v1), "v"(p1), "v"(v2), "v"(p2), "v"(v3), "v"(p3), "s"(live) : "vcc", "memory");
 }
 // ... the neighbour words tagged with the axis (%1: scratch, %10: the tag)
 #define TA_TFACE_POS(v, pv, EX) TA_CMPX(v, pv) "v_or_b32_e32 %1, %10, " pv "\n\tds_write2_b32 %0, " v ", %1 offset1:1\n\tv_add_u32_e32 %0, 8, %0\n\ts_mov_b64 exec, " EX "\n\t"
-#define TA_TFACE_POS_PART(v, pv, EX) TA_CMPX_PART(v, pv) "v_or_b32_e32 %1, %10, " pv "\n\tds_write2_b32 %0, " v ", %1 offset1:1\n\tv_add_u32_e32 %0, 8, %0\n\ts_mov_b64 exec, " EX "\n\t"
 template <bool FULL>
 __device__ __forceinline__ void store_faces4_tagged_if_ne(uint32_t& off, const uint32_t v0, const uint32_t p0, const uint32_t v1, const uint32_t p1,
                                                           const uint32_t v2, const uint32_t p2, const uint32_t v3, const uint32_t p3,
@@ -149,13 +114,12 @@ __device__ __forceinline__ void store_faces4_tagged_if_ne(uint32_t& off, const u
         asm volatile(TA_TFACE_POS("%2", "%3", "-1") TA_TFACE_POS("%4", "%5", "-1") TA_TFACE_POS("%6", "%7", "-1") TA_TFACE_POS("%8", "%9", "-1")
                      : "+v"(off), "=&v"(t) : "v"(v0), "v"(p0), "v"(v1), "v"(p1), "v"(v2), "v"(p2), "v"(v3), "v"(p3), "s"(tag) : "vcc", "memory");
     else
-        asm volatile(TA_TFACE_POS_PART("%2", "%3", "%11") TA_TFACE_POS_PART("%4", "%5", "%11") TA_TFACE_POS_PART("%6", "%7", "%11") TA_TFACE_POS_PART("%8", "%9", "%11")
+        asm volatile(TA_TFACE_POS("%2", "%3", "%11") TA_TFACE_POS("%4", "%5", "%11") TA_TFACE_POS("%6", "%7", "%11") TA_TFACE_POS("%8", "%9", "%11")
                      : "+v"(off), "=&v"(t) : "v"(v0), "v"(p0), "v"(v1), "v"(p1), "v"(v2), "v"(p2), "v"(v3), "v"(p3), "s"(tag), "s"(live) : "vcc", "memory");
 }
 // ... four run records: positions J .. J + 3 of the strip; v_k against the voxel before it (p0 = the voxel left of v0); %1: scratch,
 // %7: code0, %8 .. %11: J .. J + 3, %12: the dword stride between the two run arrays
 #define TA_RUN_POS(v, pv, j, EX) TA_CMPX(v, pv) "v_or_b32_e32 %1, " j ", %7\n\tds_write2_b32 %0, " pv ", %1 offset1:%12\n\tv_add_u32_e32 %0, 4, %0\n\ts_mov_b64 exec, " EX "\n\t"
-#define TA_RUN_POS_PART(v, pv, j, EX) TA_CMPX_PART(v, pv) "v_or_b32_e32 %1, " j ", %7\n\tds_write2_b32 %0, " pv ", %1 offset1:%12\n\tv_add_u32_e32 %0, 4, %0\n\ts_mov_b64 exec, " EX "\n\t"
 template <bool FULL, int J, int STRIDE>
 __device__ __forceinline__ void store_runs4_if_ne(uint32_t& off, const uint32_t p0, const uint32_t v0, const uint32_t v1, const uint32_t v2, const uint32_t v3,
                                                   const uint32_t code0, const uint64_t live) {
@@ -166,7 +130,7 @@ __device__ __forceinline__ void store_runs4_if_ne(uint32_t& off, const uint32_t 
                      : "+v"(off), "=&v"(t) : "v"(p0), "v"(v0), "v"(v1), "v"(v2), "v"(v3), "v"(code0), "n"(J), "n"(J + 1), "n"(J + 2), "n"(J + 3), "n"(STRIDE)
                      : "vcc", "memory");
     else
-        asm volatile(TA_RUN_POS_PART("%3", "%2", "%8", "%13") TA_RUN_POS_PART("%4", "%3", "%9", "%13") TA_RUN_POS_PART("%5", "%4", "%10", "%13") TA_RUN_POS_PART("%6", "%5", "%11", "%13")
+        asm volatile(TA_RUN_POS("%3", "%2", "%8", "%13") TA_RUN_POS("%4", "%3", "%9", "%13") TA_RUN_POS("%5", "%4", "%10", "%13") TA_RUN_POS("%6", "%5", "%11", "%13")
                      : "+v"(off), "=&v"(t) : "v"(p0), "v"(v0), "v"(v1), "v"(v2), "v"(v3), "v"(code0), "n"(J), "n"(J + 1), "n"(J + 2), "n"(J + 3), "n"(STRIDE), "s"(live)
                      : "vcc", "memory");
 }
@@ -438,7 +402,6 @@ __device__ __forceinline__ void drain_buffers(const SweepArgs* kp, LDS& S, WLDS&
 // (Per-lane branches are what made the probe loops of drain_buffers slow: ~100 scalar / branch instructions a round.)
 template <typename LDS>
 __device__ __forceinline__ uint64_t pair_probe_issue(LDS& S, const bool pend, uint32_t& slot, const uint64_t k, const uint64_t key) {
-#if TA_PROBE_NORTN
     // a compare-and-swap that returns nothing where the slot was EMPTY, then a plain read of the slot (the same one, or the
     // next one where another key sits): LDS keeps a wave's operations in order, so the read sees what the swap left
     if (pend && k == EMPTY_KEY) (void)atomicCAS((unsigned long long*)&S.pkeys[slot], (unsigned long long)EMPTY_KEY, (unsigned long long)key);
@@ -446,27 +409,14 @@ __device__ __forceinline__ uint64_t pair_probe_issue(LDS& S, const bool pend, ui
     uint64_t r = k;
     if (pend) r = S.pkeys[slot];
     return r;
-#else
-    slot = (pend && k != EMPTY_KEY) ? ((slot + 1u) & (PSLOTS - 1)) : slot;
-    uint64_t r = k;
-    if (pend) r = atomicCAS((unsigned long long*)&S.pkeys[slot], (unsigned long long)EMPTY_KEY, (unsigned long long)key);
-    return r;
-#endif
 }
 template <typename LDS>
 __device__ __forceinline__ uint32_t label_probe_issue(LDS& S, const bool pend, uint32_t& slot, const uint32_t k, const uint32_t label) {
-#if TA_PROBE_NORTN
     if (pend && k == INVALID_LABEL) (void)atomicCAS(&S.lkeys[slot], INVALID_LABEL, label);
     slot = (pend && k != INVALID_LABEL) ? ((slot + 1u) & (LSLOTS - 1)) : slot;
     uint32_t r = k;
     if (pend) r = S.lkeys[slot];
     return r;
-#else
-    slot = (pend && k != INVALID_LABEL) ? ((slot + 1u) & (LSLOTS - 1)) : slot;
-    uint32_t r = k;
-    if (pend) r = atomicCAS(&S.lkeys[slot], INVALID_LABEL, label);
-    return r;
-#endif
 }
 
 // TA_ABL_HOT (ablations of the hot drains, cumulative, results wrong by construction): 1 = nothing is added to the tables
@@ -525,13 +475,12 @@ __device__ __forceinline__ void drain_face_groups(const SweepArgs* kp, LDS& S, W
     for (uint32_t round = 1u; __builtin_amdgcn_ballot_w64(pend[0] | pend[NF - 1]); ++round) {
         if (round >= (uint32_t)PPROBE) { spill = true; break; }
         const uint64_t r0 = pair_probe_issue(S, pend[0], slot[0], k[0], key[0]);
-        // (a compare-and-swap that gave EMPTY back has put the key there; a plain read that gives EMPTY has found a free slot)
+        // (a plain read that gives EMPTY has found a free slot: the next round's compare-and-swap goes there)
         if constexpr (NF == 2) {
-            const uint64_t r1 = pair_probe_issue(S, pend[1], slot[1], k[1], key[1]);
-            k[1] = (!TA_PROBE_NORTN && r1 == EMPTY_KEY) ? key[1] : r1;
+            k[1] = pair_probe_issue(S, pend[1], slot[1], k[1], key[1]);
             pend[1] = pend[1] && k[1] != key[1];
         }
-        k[0] = (!TA_PROBE_NORTN && r0 == EMPTY_KEY) ? key[0] : r0;
+        k[0] = r0;
         pend[0] = pend[0] && k[0] != key[0];
     }
 #endif
@@ -609,9 +558,8 @@ __device__ __forceinline__ void drain_run_group(const SweepArgs* kp, LDS& S, WLD
 #pragma nounroll
     for (uint32_t round = 1u; __builtin_amdgcn_ballot_w64(ppend | lpend); ++round) {
         if (round >= (uint32_t)LPROBE) { spill = true; break; }          // (LPROBE <= PPROBE: both give up together)
-        const uint64_t rp = pair_probe_issue(S, ppend, pslot, pk, pkey);
-        const uint32_t rl = label_probe_issue(S, lpend, lslot, lk, label);
-        pk = (!TA_PROBE_NORTN && rp == EMPTY_KEY) ? pkey : rp; lk = (!TA_PROBE_NORTN && rl == INVALID_LABEL) ? label : rl;
+        pk = pair_probe_issue(S, ppend, pslot, pk, pkey);
+        lk = label_probe_issue(S, lpend, lslot, lk, label);
         ppend = ppend && pk != pkey; lpend = lpend && lk != label;
     }
 #endif
@@ -668,30 +616,17 @@ __device__ __forceinline__ void drain_run_group(const SweepArgs* kp, LDS& S, WLD
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
 }
 
-// strip load of this file: like load_strip, but the scalar path of edge tiles also reports a REAL voxel that
-// equals the outside-the-volume filler (0xFFFFFFFF in a uint32 volume: above any max_label)
+// the strip load of the plain edge tiles: voxel by voxel with bounds, the filler INVALID_LABEL for positions outside the volume;
+// `bad` reports a REAL voxel that equals the filler (0xFFFFFFFF in a uint32 volume: above any max_label)
 template <typename T, int VPL>
-__device__ __forceinline__ void scan_load_strip(const bool EDGE, const T* row_c0, bool row_ok, uint32_t lane_off,
-                                                int64_t c, int64_t n2, uint32_t (&dst)[VPL], bool& bad) {
-    if (!EDGE) {
-        const uint4 x = *reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(row_c0) + lane_off);
-        if (sizeof(T) == 4) {
-            dst[0] = x.x; dst[1] = x.y; dst[2] = x.z; dst[3] = x.w;
-        } else {
-            dst[0] = x.x & 0xffffu; dst[1] = x.x >> 16; dst[2] = x.y & 0xffffu; dst[3] = x.y >> 16;
-            if (VPL > 4) {           // (VPL = 4 of a uint16 volume: the lane's strip is the first half of what it loaded)
-                dst[4 % VPL] = x.z & 0xffffu; dst[5 % VPL] = x.z >> 16;
-                dst[6 % VPL] = x.w & 0xffffu; dst[7 % VPL] = x.w >> 16;
-            }
-        }
-    } else {
-        const T* lane_p = reinterpret_cast<const T*>(reinterpret_cast<const char*>(row_c0) + lane_off);
+__device__ __forceinline__ void scan_load_strip(const T* row_c0, bool row_ok, uint32_t lane_off, int64_t c, int64_t n2,
+                                                uint32_t (&dst)[VPL], bool& bad) {
+    const T* lane_p = reinterpret_cast<const T*>(reinterpret_cast<const char*>(row_c0) + lane_off);
 #pragma unroll
-        for (int j = 0; j < VPL; ++j) {
-            const bool ok = row_ok && c + j < n2;
-            dst[j] = ok ? (uint32_t)lane_p[j] : INVALID_LABEL;
-            if (sizeof(T) == 4) bad |= ok && dst[j] == INVALID_LABEL;
-        }
+    for (int j = 0; j < VPL; ++j) {
+        const bool ok = row_ok && c + j < n2;
+        dst[j] = ok ? (uint32_t)lane_p[j] : INVALID_LABEL;
+        if (sizeof(T) == 4) bad |= ok && dst[j] == INVALID_LABEL;
     }
 }
 
@@ -750,6 +685,42 @@ __device__ __forceinline__ void unpack_strip(const u32x4& x, uint32_t (&dst)[VPL
         }
     }
 }
+// the voxel above cur[r][j]: in the row before, or in the halo row above the wave's first row
+template <int RB, int VPL>
+__device__ __forceinline__ uint32_t voxel_above(const uint32_t (&cur)[RB][VPL], const uint32_t (&up)[VPL], const int r, const int j) {
+    return r > 0 ? cur[r > 0 ? r - 1 : 0][j] : up[j];
+}
+// two landed quads -> the eight uint32 voxels of a lane's strip
+__device__ __forceinline__ void unpack_quads(const u32x4& lo, const u32x4& hi, uint32_t (&dst)[8]) {
+    dst[0] = lo.x; dst[1] = lo.y; dst[2] = lo.z; dst[3] = lo.w;
+    dst[4] = hi.x; dst[5] = hi.y; dst[6] = hi.z; dst[7] = hi.w;
+}
+
+// The end of a tile: its `nlead` leading rows of TC voxels that are one label from end to end were never records; they are added
+// here in one closed form (one lane calls).  Rows in (plane, row) order: P full planes of RB rows, then R rows of plane P.
+template <bool MOM2, int RB, int TC, typename LDS>
+__device__ __forceinline__ void add_leading_rows(const SweepArgs* kp, LDS& S, const int w, const uint32_t label, const uint32_t nlead) {
+    const uint64_t P = nlead / RB, R = nlead % RB, nc = TC, b0 = (uint64_t)w * RB;
+    const uint64_t t1c = range_sum1(0, nc), t2c = range_sum2(0, nc);
+    const uint64_t rows = P * RB + R;                                        // = nlead
+    const uint64_t sa_rows = range_sum1(0, P) * RB + P * R;                  // sum of a over the rows
+    const uint64_t saa_rows = range_sum2(0, P) * RB + P * P * R;
+    const uint64_t sb_rows = P * range_sum1(b0, RB) + range_sum1(b0, R);
+    const uint64_t sbb_rows = P * range_sum2(b0, RB) + range_sum2(b0, R);
+    const uint64_t sab_rows = range_sum1(0, P) * range_sum1(b0, RB) + P * range_sum1(b0, R);
+    LocalSums L;
+    L.n = rows * nc; L.sa = sa_rows * nc; L.sb = sb_rows * nc; L.sc = rows * t1c;
+    if (MOM2) {
+        L.saa = saa_rows * nc; L.sab = sab_rows * nc; L.sbb = sbb_rows * nc;
+        L.sac = sa_rows * t1c; L.sbc = sb_rows * t1c; L.scc = rows * t2c;
+    } else {
+        L.saa = L.sab = L.sac = L.sbb = L.sbc = L.scc = 0;
+    }
+    const uint32_t mxa = (uint32_t)(R ? P : P - 1u);
+    const uint32_t mxb = (uint32_t)(b0 + (P ? RB : R) - 1u);
+    const uint32_t fh = scan_label_hash(label);
+    scan_label_add<MOM2, LDS, LocalSums>(kp, S, label, L, 0u, mxa, (uint32_t)b0, mxb, 0u, (uint32_t)(nc - 1), fh, S.lkeys[fh]);
+}
 
 // EDGE: the tile may hold positions outside the volume (they carry the filler INVALID_LABEL) and may lack a row above / a
 // column to the left.  PINB: 0 = plain guarded loads (volumes whose rows are not 16-byte aligned), else the first of the
@@ -763,17 +734,7 @@ __device__ __forceinline__ void wave_scan(const SweepArgs& A, const SweepArgs* k
     static_assert(TC <= 512, "the run code holds the end column in 10 bits");
     static_assert(FCAP >= RB * VPL && RCAP >= VPL + 1, "the records of one lane must fit a buffer");
     auto& W = S.wave[w];
-    // the hot drain sites take every record of a buffer at once (drain_faces_all / drain_runs_all); the rare ones -- a row too
-    // big for the buffers placed in pieces, the end of the tile -- keep the compact group-by-group drain_buffers
-// TA_FDRAIN1: tiles of eight voxels a lane put twice the records of a plane step into the same buffers; with 64 .. 127 faces
-// left after a step, the next one's often do not fit and the whole buffer goes through the in-plane drain (29 % of C4's face
-// records, 43 % of the tissue-filled volume's, against 13 / 14 % with four voxels a lane).  With one group of 64 leaving at
-// the top of the plane those shares fall to 7 / 16 % -- and the sweep takes the same time (C4 1.01 / 1.02 vs 1.01 / 1.02 ms,
-// filled 1.38 - 1.44 vs 1.39 - 1.46, C5 6.79 / 6.83 vs 6.78 / 6.86): where a record is drained does not matter.  On since
-// round 5 (with the predicated stores: C4 0.972 -> 0.965, filled 1.392 -> 1.367 / 1.390 ms in one call -- within the noise, and
-// the in-plane drain with its per-lane probe loops becomes the rare path it is meant to be).
-    constexpr bool DRAIN_ALL = ADJ && TA_DRAIN_ALL && FCAP % 64 == 0 && RCAP % 64 == 0 && (TA_DRAIN_ALL_U16 || VPL == 4) && RB == 2 && !EDGE;
-
+    // ---- 1. tile geometry and addresses ------------------------------------------------------------------------------
     const T* vol = reinterpret_cast<const T*>(A.vol);
     const int64_t n1 = A.n1, n2 = A.n2, plane = n1 * n2;
     const int64_t b_wave0 = (int64_t)b_tile0 + (int64_t)w * RB;
@@ -787,6 +748,7 @@ __device__ __forceinline__ void wave_scan(const SweepArgs& A, const SweepArgs* k
     const bool has_prev = ADJ && p_lo > 0;
     const uint32_t lane_c = (uint32_t)lane * VPL;
     constexpr bool PAD = EDGE && PINB != 0;
+    constexpr bool WIDE8 = sizeof(T) == 4 && VPL == 8;       // eight uint32 voxels a lane: two 16-byte quads a strip
     // PADDED: a lane whose strip lies past the end of the row loads the tile's first strip instead (a strip that straddles
     // the end is loaded where it is: the few bytes past the row are the next row's, or the slack behind the library's own
     // volume buffer); a row past the last one loads the wave's first row (the last row of the volume when the whole wave
@@ -798,15 +760,34 @@ __device__ __forceinline__ void wave_scan(const SweepArgs& A, const SweepArgs* k
     bool row_in[RB];
 #pragma unroll
     for (int r = 0; r < RB; ++r) row_in[r] = !PAD || b_wave0 + r < n1;
+    // the hand-issued loads of the interior and padded tiles (part 2): one running pointer walks the planes
+    const uint32_t rowbytes = (uint32_t)(n2 * (int64_t)sizeof(T));
+    const uint32_t left_off = (uint32_t)(PAD && b_wave0 + (lane & (RB - 1)) >= n1 ? 0 : (lane & (RB - 1))) * rowbytes;    // (the VGPR offset of a load is unsigned)
+    const int64_t plane_bytes = plane * (int64_t)sizeof(T);
+    const char* next_row0 = reinterpret_cast<const char*>(vol + (int64_t)(has_prev ? p_lo - 1 : p_lo) * plane + b_base * n2 + c_tile0);
+    using Zone = Pin<(PINB ? PINB : PIN_scan_kernel)>;     // the landing zone of the plane in flight (PINB = 0 issues nothing into it)
 
     // The working set of a lane: the RB x VPL voxels of the CURRENT plane, the strip of the row above, the voxel to
     // the left.  The previous plane is never kept: its faces with the current one are taken at the moment the new
     // plane lands, while both are in registers (that is what leaves room for a fifth wave per SIMD).
     uint32_t cur[RB][VPL], up[VPL];
+    uint32_t old[RB][VPL];                                 // the plane before, kept until the new plane's first row is done (its axis-0 faces)
     uint32_t leftv = INVALID_LABEL;                        // lane r: the voxel left of row r of the tile
     static_assert(RB == 2 || RB == 4, "the pinned-register layout is written out for 2 and 4 rows");
     bool bad = false;
+    uint32_t fcount = 0u, rcount = 0u;                    // records in the buffers (wave-uniform)
+    if (lane == 0) W.cqc[0] = NO_ROW;
+    // LDS byte offsets of the wave's buffers (the low half of a flat LDS address is the LDS offset)
+    const uint32_t fbase = (uint32_t)(uintptr_t)&W.frec[0];
+    const uint32_t rbase = (uint32_t)(uintptr_t)&W.cql[1];
+    constexpr uint32_t RSTRIDE = (RCAP + 2) * 4u;         // bytes between the two run arrays
+    // Leading rows of the tile that are one label (the label of its first voxel) from end to end are not records:
+    // they are counted and added in closed form at the end -- that is the whole cost of background.
+    uint32_t first_label = INVALID_LABEL;
+    bool leading = true;
+    uint32_t nlead = 0u;
 
+    // ---- 2. the plane loader: issue, land, unpack, pad; the prologue ------------------------------------------------------
     // -- edge tiles: plain loads with bounds, the compiler waits as it sees fit
     auto load_rows = [&](int64_t p, uint32_t (&d)[RB][VPL]) {
         const T* pbase = vol + p * plane;
@@ -815,7 +796,7 @@ __device__ __forceinline__ void wave_scan(const SweepArgs& A, const SweepArgs* k
             const int64_t b = b_wave0 + r;
             const bool row_ok = b < n1;
             const T* row = pbase + (row_ok ? b : 0) * n2 + c_tile0;
-            scan_load_strip<T, VPL>(true, row, row_ok, lane_off, c0g, n2, d[r], bad);
+            scan_load_strip<T, VPL>(row, row_ok, lane_off, c0g, n2, d[r], bad);
         }
     };
     auto load_halo = [&](int64_t p, uint32_t (&dup)[VPL], uint32_t& dl) {
@@ -827,23 +808,20 @@ __device__ __forceinline__ void wave_scan(const SweepArgs& A, const SweepArgs* k
         if (has_up) {
             const bool row_ok = (b_wave0 - 1) < n1;
             const T* row = pbase + (row_ok ? (b_wave0 - 1) : 0) * n2 + c_tile0;
-            scan_load_strip<T, VPL>(true, row, row_ok, lane_off, c0g, n2, dup, bad);
+            scan_load_strip<T, VPL>(row, row_ok, lane_off, c0g, n2, dup, bad);
         }
     };
     // -- interior tiles: every load is unconditional, RB + 2 loads per plane.  A tile without a row above / a column
     //    to the left reads its own first row / column instead: those compares can never fire, so the hot loop does
-    //    not test has_up / has_left at all.  One running pointer walks the planes.
-    const uint32_t rowbytes = (uint32_t)(n2 * (int64_t)sizeof(T));
-    const uint32_t left_off = (uint32_t)(PAD && b_wave0 + (lane & (RB - 1)) >= n1 ? 0 : (lane & (RB - 1))) * rowbytes;    // (the VGPR offset of a load is unsigned)
-    const int64_t plane_bytes = plane * (int64_t)sizeof(T);
-    const char* next_row0 = reinterpret_cast<const char*>(vol + (int64_t)(has_prev ? p_lo - 1 : p_lo) * plane + b_base * n2 + c_tile0);
-    using Zone = Pin<(PINB ? PINB : PIN_scan_kernel)>;     // the landing zone of the plane in flight (PINB = 0 issues nothing into it)
+    //    not test has_up / has_left at all.
     auto issue_plane = [&]() {                            // issues the plane at `next_row0` into the landing zone and steps it
         const char* row0 = next_row0;
 #ifndef TA_ABL_L2
         next_row0 += plane_bytes;
 #endif
-        if constexpr (sizeof(T) == 4 && VPL == 8) {      // 32-byte strips: two quads a row, two rows, two quads the row above
+        // `up_there`, in each branch behind the loads of the tile's own rows (once in front of them, or in a lambda, the padded kernels come out in
+        // other registers).  PADDED, the whole wave past the last row: row0 is the last row of the volume; the row "above" it is not asked for.
+        if constexpr (WIDE8) {                            // 32-byte strips: two quads a row, two rows, two quads the row above
             static_assert(RB == 2 && ADJ, "eight uint32 voxels a lane: two rows a wave, the 25-register landing zone");
             const char* row1 = row_in[1] ? row0 + rowbytes : row0;
             Zone::template issue_strip<0>(lane_off, row0);
@@ -854,7 +832,6 @@ __device__ __forceinline__ void wave_scan(const SweepArgs& A, const SweepArgs* k
             const char* upr = up_there ? row0 - rowbytes : row0;
             Zone::template issue_strip<4>(lane_off, upr);
             Zone::template issue_strip<5>(lane_off, upr + 16);
-            Zone::template issue_voxel<T, RB>(left_off, has_left ? row0 - sizeof(T) : row0);
         } else if constexpr (sizeof(T) == 2 && VPL == 4) {      // 8-byte strips: the first half of each landing quad
             static_assert(RB == 2, "four uint16 voxels a lane: the two-row tiles");
             Zone::template issue_half<0>(lane_off, row0);
@@ -862,23 +839,44 @@ __device__ __forceinline__ void wave_scan(const SweepArgs& A, const SweepArgs* k
             if (ADJ) {
                 const bool up_there = has_up && (!PAD || b_wave0 < n1);
                 Zone::template issue_half<2>(lane_off, up_there ? row0 - rowbytes : row0);
-                Zone::template issue_voxel<T, RB>(left_off, has_left ? row0 - sizeof(T) : row0);
             }
         } else {
-        Zone::template issue_strip<0>(lane_off, row0);
-        Zone::template issue_strip<1>(lane_off, row_in[1] ? row0 + rowbytes : row0);
-        if (RB > 2) {
-            Zone::template issue_strip<2>(lane_off, row_in[RB > 2 ? 2 : 0] ? row0 + 2 * (int64_t)rowbytes : row0);
-            Zone::template issue_strip<3>(lane_off, row_in[RB > 3 ? 3 : 0] ? row0 + 3 * (int64_t)rowbytes : row0);
+            Zone::template issue_strip<0>(lane_off, row0);
+            Zone::template issue_strip<1>(lane_off, row_in[1] ? row0 + rowbytes : row0);
+            if (RB > 2) {
+                Zone::template issue_strip<2>(lane_off, row_in[RB > 2 ? 2 : 0] ? row0 + 2 * (int64_t)rowbytes : row0);
+                Zone::template issue_strip<3>(lane_off, row_in[RB > 3 ? 3 : 0] ? row0 + 3 * (int64_t)rowbytes : row0);
+            }
+            if (ADJ) {
+                const bool up_there = has_up && (!PAD || b_wave0 < n1);
+                Zone::template issue_strip<RB>(lane_off, up_there ? row0 - rowbytes : row0);       // (the quad behind the rows')
+            }
         }
-        if (ADJ) {       // (without adjacency nobody looks at the row above or the voxel to the left)
-            // (PADDED, the whole wave past the last row: row0 is the last row of the volume; the row "above" it is not asked for)
-            const bool up_there = has_up && (!PAD || b_wave0 < n1);
-            if (RB > 2) Zone::template issue_strip<4>(lane_off, up_there ? row0 - rowbytes : row0);
-            else        Zone::template issue_strip<2>(lane_off, up_there ? row0 - rowbytes : row0);
-            Zone::template issue_voxel<T, RB>(left_off, has_left ? row0 - sizeof(T) : row0);
+        // (without adjacency nobody looks at the row above or the voxel to the left)
+        if (ADJ) Zone::template issue_voxel<T, RB>(left_off, has_left ? row0 - sizeof(T) : row0);
+    };
+
+    uint32_t nxt[RB][VPL], nxt_up[VPL], nxt_leftv = INVALID_LABEL;           // edge tiles: the plane in flight, unpacked
+    u32x4 nraw[RB], nup_raw;                                                  // interior tiles: the plane just read back
+    u32x4 nraw_hi[RB], nup_hi;                                                // (eight uint32 voxels a lane: their second halves)
+    auto land = [&]() {                                    // the plane in flight -> nraw / nup_raw / nxt_leftv
+        if constexpr (PINB == 0) {
+            // (edge tiles load with bounds: nothing lands)
+        } else if constexpr (WIDE8) {
+            u32x4 t[6];
+            Zone::landed_wide(t, nxt_leftv);
+            nraw[0] = t[0]; nraw_hi[0] = t[1]; nraw[RB - 1] = t[2]; nraw_hi[RB - 1] = t[3]; nup_raw = t[4]; nup_hi = t[5];
+        } else {
+            Zone::template landed<RB>(nraw, nup_raw, nxt_leftv);
         }
-        }
+    };
+    auto unpack_row = [&](const int r, uint32_t (&dst)[VPL]) {
+        if constexpr (WIDE8) unpack_quads(nraw[r], nraw_hi[r], dst);
+        else unpack_strip<T, VPL>(nraw[r], dst);
+    };
+    auto unpack_up = [&](uint32_t (&dst)[VPL]) {
+        if constexpr (WIDE8) unpack_quads(nup_raw, nup_hi, dst);
+        else unpack_strip<T, VPL>(nup_raw, dst);
     };
 
     // PADDED: what landed for positions outside the volume is overwritten with the filler; a REAL voxel equal to the
@@ -903,37 +901,69 @@ __device__ __forceinline__ void wave_scan(const SweepArgs& A, const SweepArgs* k
         }
     };
 
-    uint32_t fcount = 0u, rcount = 0u;                    // records in the buffers (wave-uniform)
-#ifdef TA_STAMPS
-    uint64_t tk_cmp = 0, tk_emit = 0, tk_drain = 0, tk_adv = 0, tk_land = 0, tk_evrows = 0, tk_drains = 0;
+    // -- prologue: the plane before the tile (another tile's, or the slab's halo plane) only gives faces
+#pragma unroll
+    for (int j = 0; j < VPL; ++j) { up[j] = INVALID_LABEL; nxt_up[j] = INVALID_LABEL; }
+    if constexpr (PINB == 0) {
+        if (has_prev) load_rows(p_lo - 1, cur);
+        load_rows(p_lo, nxt); load_halo(p_lo, nxt_up, nxt_leftv);
+    } else {
+        if constexpr (!PAD && RB == 2 && VPL == 8) {       // (the tiles of eight voxels a lane: C5 6.79 -> 6.63 ms, C4 unchanged; the narrow tiles measured +1 %: not there)
+            // The plane BEFORE the tile and the tile's first plane in flight TOGETHER (round 4 landed one, then issued the other:
+            // a workgroup began its life with two memory latencies back to back, ~13 k cycles of a background tile's 210 k).
+            // The older plane goes into ordinary registers -- by hand-issued loads as well: a load the compiler knows about in
+            // front of this loop makes it wait for `vmcnt(0)` inside every iteration, behind the next plane's hand-issued loads
+            // (measured: +6 ... +9 %) -- and ONE counted wait lets the landing zone's loads, which are younger, stay in flight.
+            if (has_prev) {
+                const char* row0 = next_row0;
+#ifndef TA_ABL_L2
+                next_row0 += plane_bytes;
 #endif
-    if (lane == 0) W.cqc[0] = NO_ROW;
-    // LDS byte offsets of the wave's buffers (the low half of a flat LDS address is the LDS offset)
-    const uint32_t fbase = (uint32_t)(uintptr_t)&W.frec[0];
-    const uint32_t rbase = (uint32_t)(uintptr_t)&W.cql[1];
-    constexpr uint32_t RSTRIDE = (RCAP + 2) * 4u;         // bytes between the two run arrays
-    [[maybe_unused]] const uint32_t ftrash = (uint32_t)(uintptr_t)&W.frec[FTRASH];   // where the stores of compares that did not fire go (TA_MASKED_STORES: nowhere)
-    [[maybe_unused]] const uint32_t rtrash = (uint32_t)(uintptr_t)&W.cql[RTRASH];
+                constexpr int NQ = WIDE8 ? 2 : 1;                    // 16-byte quads a row
+                u32x4 t[RB * NQ];
+#pragma unroll
+                for (int r = 0; r < RB; ++r)
+#pragma unroll
+                    for (int q = 0; q < NQ; ++q)
+                        asm volatile("global_load_dwordx4 %0, %1, %2" : "=&v"(t[r * NQ + q]) : "v"(lane_off), "s"(row0 + (int64_t)r * rowbytes + 16 * q) : "memory");
+                issue_plane();
+                // the landing zone's loads: eight voxels a lane 6 strips + the left voxel, else two rows + the row above + the left voxel
+                if constexpr (WIDE8) asm volatile("s_waitcnt vmcnt(7)" : "+v"(t[0]), "+v"(t[1]), "+v"(t[NQ]), "+v"(t[2 * NQ - 1]) :: "memory");
+                else                 asm volatile("s_waitcnt vmcnt(4)" : "+v"(t[0]), "+v"(t[RB - 1]) :: "memory");
+#pragma unroll
+                for (int r = 0; r < RB; ++r) {
+                    if constexpr (WIDE8) unpack_quads(t[r * NQ], t[r * NQ + NQ - 1], cur[r]);
+                    else unpack_strip<T, VPL>(t[r * NQ], cur[r]);
+                }
+            } else {
+                issue_plane();
+            }
+        } else if (has_prev) {
+            issue_plane();
+            land();
+#pragma unroll
+            for (int r = 0; r < RB; ++r) unpack_row(r, cur[r]);
+            if constexpr (PAD) {
+                uint32_t dump_up[VPL], dump_l = 0u;
+#pragma unroll
+                for (int j = 0; j < VPL; ++j) dump_up[j] = 0u;
+                pad_plane(cur, dump_up, dump_l);
+            }
+            issue_plane();
+        } else {
+            issue_plane();
+        }
+    }
 
-    // Leading rows of the tile that are one label (the label of its first voxel) from end to end are not records:
-    // they are counted and added in closed form at the end -- that is the whole cost of background.
-    uint32_t first_label = INVALID_LABEL;
-    bool leading = true;
-    uint32_t nlead = 0u;
+    // ---- 3. the record placer ----------------------------------------------------------------------------------------
     auto drain = [&](const bool may_keep) {
 #ifdef TA_ABL_NOSLOW      // (ablation, results wrong by construction: the in-plane drains and the end of the tile consume nothing)
         fcount = 0u; rcount = 0u; if (lane == 0) W.cqc[0] = NO_ROW; return;
-#endif
-#ifdef TA_STAMPS
-        const uint64_t td0 = __builtin_amdgcn_s_memtime();
 #endif
 #ifdef TA_RECCOUNT
         if (lane == 0) { atomicAdd(&cold_args(kp)->flags[8], fcount); atomicAdd(&cold_args(kp)->flags[9], rcount); atomicAdd(&cold_args(kp)->flags[10], 1u); }
 #endif
         drain_buffers<ADJ, MOM2, LDS>(kp, S, W, EDGE, lane, fcount, rcount, first_label, may_keep);
-#ifdef TA_STAMPS
-        tk_drain += __builtin_amdgcn_s_memtime() - td0; tk_drains += 1;
-#endif
     };
     // A set of records too big even for empty buffers (a flat wall between two planes: up to RB * VPL faces per lane; noise)
     // goes a lane range at a time: halve the range until its records fit, place them, go on with the rest; the buffers are
@@ -981,9 +1011,9 @@ __device__ __forceinline__ void wave_scan(const SweepArgs& A, const SweepArgs* k
         fcount += rowf; rcount += rowr;
         if (TA_ABLATE < 2) emit(offf, offr, std::true_type{});      // (straight-line code: every lane is live)
     };
+    // ---- 4. the plane and row step -----------------------------------------------------------------------------------
     // A new plane has landed: its faces with the plane before it (axis 0) are counted and stored TOGETHER with the events of
     // its first row -- one scan of the lanes' counts instead of two (`old` = the plane before, kept until that row is done).
-    uint32_t old[RB][VPL];
     auto count_plane_faces = [&]() {
         uint32_t cf = 0u;
 #ifndef TA_ABL_NOFACE0
@@ -999,127 +1029,15 @@ __device__ __forceinline__ void wave_scan(const SweepArgs& A, const SweepArgs* k
 #pragma unroll
         for (int r = 0; r < RB; ++r)
 #pragma unroll
-            for (int j = 0; j < VPL; ++j) {
-#if TA_MASKED_STORES & 1
-                if constexpr (VPL % 4 == 0) {
-                    if (j % 4 == 0)
-                        store_faces4_if_ne<decltype(full)::value>(offf, cur[r][j], old[r][j], cur[r][(j + 1) % VPL], old[r][(j + 1) % VPL],
-                                                                 cur[r][(j + 2) % VPL], old[r][(j + 2) % VPL], cur[r][(j + 3) % VPL], old[r][(j + 3) % VPL], live);
-                } else {
-                    store_face_if_ne<decltype(full)::value>(offf, cur[r][j], old[r][j], live);
-                }
-                continue;
-#endif
-                uint32_t v = cur[r][j];
-                asm volatile("" : "+v"(v));               // (compare again: see the row emission)
-                const bool f = v != old[r][j];
-                const uint32_t at = f ? offf : ftrash;
-                *(lds_u32)(uintptr_t)at = v; *(lds_u32)(uintptr_t)(at + 4u) = old[r][j];
-                offf += f ? 8u : 0u;
-            }
+            for (int j = 0; j < VPL; j += 4)
+                store_faces4_if_ne<decltype(full)::value>(offf, cur[r][j], old[r][j], cur[r][j + 1], old[r][j + 1],
+                                                         cur[r][j + 2], old[r][j + 2], cur[r][j + 3], old[r][j + 3], live);
 #endif
     };
 
-    // ---- prologue: the plane before the tile (another tile's, or the slab's halo plane) only gives faces
-    uint32_t nxt[RB][VPL], nxt_up[VPL], nxt_leftv = INVALID_LABEL;           // edge tiles: the plane in flight, unpacked
-    u32x4 nraw[RB], nup_raw;                                                  // interior tiles: the plane just read back
-    u32x4 nraw_hi[RB], nup_hi;                                                // (eight uint32 voxels a lane: their second halves)
-    constexpr bool WIDE8 = sizeof(T) == 4 && VPL == 8;
-    auto land = [&]() {                                    // the plane in flight -> nraw / nup_raw / nxt_leftv
-        if constexpr (PINB == 0) {
-            // (edge tiles load with bounds: nothing lands)
-        } else if constexpr (WIDE8) {
-            u32x4 t[6];
-            Zone::landed_wide(t, nxt_leftv);
-            nraw[0] = t[0]; nraw_hi[0] = t[1]; nraw[RB - 1] = t[2]; nraw_hi[RB - 1] = t[3]; nup_raw = t[4]; nup_hi = t[5];
-        } else {
-            Zone::template landed<RB>(nraw, nup_raw, nxt_leftv);
-        }
-    };
-    auto unpack_row = [&](const int r, uint32_t (&dst)[VPL]) {
-        if constexpr (WIDE8) {
-            dst[0] = nraw[r].x; dst[1] = nraw[r].y; dst[2] = nraw[r].z; dst[3] = nraw[r].w;
-            dst[4 % VPL] = nraw_hi[r].x; dst[5 % VPL] = nraw_hi[r].y; dst[6 % VPL] = nraw_hi[r].z; dst[7 % VPL] = nraw_hi[r].w;
-        } else {
-            unpack_strip<T, VPL>(nraw[r], dst);
-        }
-    };
-    auto unpack_up = [&](uint32_t (&dst)[VPL]) {
-        if constexpr (WIDE8) {
-            dst[0] = nup_raw.x; dst[1] = nup_raw.y; dst[2] = nup_raw.z; dst[3] = nup_raw.w;
-            dst[4 % VPL] = nup_hi.x; dst[5 % VPL] = nup_hi.y; dst[6 % VPL] = nup_hi.z; dst[7 % VPL] = nup_hi.w;
-        } else {
-            unpack_strip<T, VPL>(nup_raw, dst);
-        }
-    };
-#pragma unroll
-    for (int j = 0; j < VPL; ++j) { up[j] = INVALID_LABEL; nxt_up[j] = INVALID_LABEL; }
-    if constexpr (PINB == 0) {
-        if (has_prev) load_rows(p_lo - 1, cur);
-        load_rows(p_lo, nxt); load_halo(p_lo, nxt_up, nxt_leftv);
-    } else {
-        if constexpr (!PAD && TA_PROLOGUE_OVERLAP && RB == 2 && VPL == 8) {       // (the tiles of eight voxels a lane: C5 6.79 -> 6.63 ms, C4 unchanged; the narrow tiles measured +1 %: not there)
-            // The plane BEFORE the tile and the tile's first plane in flight TOGETHER (round 4 landed one, then issued the other:
-            // a workgroup began its life with two memory latencies back to back, ~13 k cycles of a background tile's 210 k).
-            // The older plane goes into ordinary registers -- by hand-issued loads as well: a load the compiler knows about in
-            // front of this loop makes it wait for `vmcnt(0)` inside every iteration, behind the next plane's hand-issued loads
-            // (measured: +6 ... +9 %) -- and ONE counted wait lets the landing zone's loads, which are younger, stay in flight.
-            if (has_prev) {
-                const char* row0 = next_row0;
-#ifndef TA_ABL_L2
-                next_row0 += plane_bytes;
-#endif
-                constexpr int NQ = WIDE8 ? 2 : 1;                    // 16-byte quads a row
-                u32x4 t[RB * NQ];
-#pragma unroll
-                for (int r = 0; r < RB; ++r)
-#pragma unroll
-                    for (int q = 0; q < NQ; ++q)
-                        asm volatile("global_load_dwordx4 %0, %1, %2" : "=&v"(t[r * NQ + q]) : "v"(lane_off), "s"(row0 + (int64_t)r * rowbytes + 16 * q) : "memory");
-                issue_plane();
-                // the landing zone's loads: eight voxels a lane 6 strips + the left voxel, else two rows + the row above + the left voxel
-                if constexpr (WIDE8) asm volatile("s_waitcnt vmcnt(7)" : "+v"(t[0]), "+v"(t[1]), "+v"(t[NQ]), "+v"(t[2 * NQ - 1]) :: "memory");
-                else                 asm volatile("s_waitcnt vmcnt(4)" : "+v"(t[0]), "+v"(t[RB - 1]) :: "memory");
-#pragma unroll
-                for (int r = 0; r < RB; ++r) {
-                    if constexpr (WIDE8) {
-                        const u32x4 a = t[r * NQ], c4 = t[r * NQ + NQ - 1];
-                        cur[r][0] = a.x; cur[r][1] = a.y; cur[r][2] = a.z; cur[r][3] = a.w;
-                        cur[r][4 % VPL] = c4.x; cur[r][5 % VPL] = c4.y; cur[r][6 % VPL] = c4.z; cur[r][7 % VPL] = c4.w;
-                    } else {
-                        unpack_strip<T, VPL>(t[r * NQ], cur[r]);
-                    }
-                }
-            } else {
-                issue_plane();
-            }
-        } else if (has_prev) {
-            issue_plane();
-            land();
-#pragma unroll
-            for (int r = 0; r < RB; ++r) unpack_row(r, cur[r]);
-            if constexpr (PAD) {
-                uint32_t dump_up[VPL], dump_l = 0u;
-#pragma unroll
-                for (int j = 0; j < VPL; ++j) dump_up[j] = 0u;
-                pad_plane(cur, dump_up, dump_l);
-            }
-            issue_plane();
-        } else {
-            issue_plane();
-        }
-    }
-
-#ifdef TA_STAMPS
-    const uint64_t tk_begin = __builtin_amdgcn_s_memtime();
-#define TA_T() __builtin_amdgcn_s_memtime()
-#endif
     // `process_plane(p)`: plane p has landed (interior tiles: in `nraw` / `nup_raw` / `nxt_leftv`; edge tiles: in `nxt`...)
     auto process_plane = [&](const int32_t p) {
         const uint32_t ploc = (uint32_t)(p - p_lo);
-#ifdef TA_STAMPS
-        const uint64_t t4 = TA_T();
-#endif
         if constexpr (PINB == 0) {
 #pragma unroll
             for (int r = 0; r < RB; ++r)
@@ -1148,15 +1066,9 @@ __device__ __forceinline__ void wave_scan(const SweepArgs& A, const SweepArgs* k
         if (p == p_lo) first_label = __builtin_amdgcn_readfirstlane(cur[0][0]);
         const bool with_plane_faces = ADJ && (p > p_lo || has_prev);
         const uint32_t cf_plane = with_plane_faces ? count_plane_faces() : 0u;
-#ifdef TA_STAMPS
-        tk_adv += TA_T() - t4;
-#endif
 #pragma unroll
         for (int r = 0; r < RB; ++r) {
             const uint32_t bloc = (uint32_t)(w * RB + r);
-#ifdef TA_STAMPS
-            const uint64_t t0 = TA_T();
-#endif
             // ---- 1. compares + per-lane event counts
             uint32_t pcv[VPL];
             uint32_t cf = 0u, cr = 0u;
@@ -1170,7 +1082,7 @@ __device__ __forceinline__ void wave_scan(const SweepArgs& A, const SweepArgs* k
                 cr += fc ? 1u : 0u;
                 const uint64_t mc = __builtin_amdgcn_ballot_w64(fc);
                 inner |= j == 0 ? (mc & ~1ull) : mc;
-                if (ADJ && (r > 0 || !EDGE || has_up)) cf += (v != (r > 0 ? cur[r > 0 ? r - 1 : 0][j] : up[j])) ? 1u : 0u;
+                if (ADJ && (r > 0 || !EDGE || has_up)) cf += (v != voxel_above(cur, up, r, j)) ? 1u : 0u;
             }
 #ifdef TA_ABL_NOFACE1
             cf = 0u;                                      // (ablation: results wrong by construction)
@@ -1184,15 +1096,7 @@ __device__ __forceinline__ void wave_scan(const SweepArgs& A, const SweepArgs* k
             if (!EDGE && uniform && rowlab == INVALID_LABEL) bad = true;      // not a filler: a voxel above any max_label
             if (need_end && lane == 63) cr += 1u;
             const uint32_t cnt = cf | (cr << 16);         // faces in the low half, runs in the high half
-#ifdef TA_STAMPS
-            const bool anyev_ = __builtin_amdgcn_ballot_w64(cnt != 0u) != 0ull;
-            const uint64_t t1 = TA_T();
-            tk_cmp += t1 - t0;
-            if (!anyev_) continue;
-            tk_evrows += 1;
-#else
             if (__builtin_amdgcn_ballot_w64(cnt != 0u) == 0ull) continue;       // the common case: one branch per row
-#endif
             // ---- 2. + 3. offsets, then a firing lane stores at its own offset and steps it
             place_records(cnt, [&](uint32_t offf, uint32_t offr, auto full) {
                 // (laundered: keeps the tagged / coded copies of the row's registers out of long-lived registers)
@@ -1208,134 +1112,68 @@ __device__ __forceinline__ void wave_scan(const SweepArgs& A, const SweepArgs* k
                 if (!FULL) asm volatile("" : "+s"(live));
                 if (ADJ && r == 0) { if (with_plane_faces) emit_plane_faces(offf, live, full); }
                 const uint32_t code0 = lane_c | rowcode;
+                // The row's axis-1 faces, four positions a statement.  (Every j with the `j % 4` test inside: in steps of four, or with the test outside,
+                // the narrow kernels compile to other registers.  The indices wrap: the iterations the test removes name no element past the strip.)
 #pragma unroll
-                for (int j = 0; j < VPL; ++j) {
+                for (int j = 0; j < VPL; ++j)
 #ifndef TA_ABL_NOFACE1
-                    if (ADJ && (r > 0 || !EDGE || has_up))
+                    if (ADJ && (r > 0 || !EDGE || has_up) && j % 4 == 0)
 #else
                     if (false)
 #endif
-                    {
-                        const uint32_t pv = r > 0 ? cur[r > 0 ? r - 1 : 0][j] : up[j];
-#if TA_MASKED_STORES & 2
-                        if constexpr (VPL % 4 == 0) {
-                            if (j % 4 == 0) {
-                                const uint32_t pv1 = r > 0 ? cur[r > 0 ? r - 1 : 0][(j + 1) % VPL] : up[(j + 1) % VPL];
-                                const uint32_t pv2 = r > 0 ? cur[r > 0 ? r - 1 : 0][(j + 2) % VPL] : up[(j + 2) % VPL];
-                                const uint32_t pv3 = r > 0 ? cur[r > 0 ? r - 1 : 0][(j + 3) % VPL] : up[(j + 3) % VPL];
-                                store_faces4_tagged_if_ne<FULL>(offf, cur[r][j], pv, cur[r][(j + 1) % VPL], pv1, cur[r][(j + 2) % VPL], pv2,
-                                                                cur[r][(j + 3) % VPL], pv3, tag1, live);
-                            }
-                        } else {
-                            store_face_tagged_if_ne<FULL>(offf, cur[r][j], pv, tag1, live);
-                        }
-#else
-                        // (every lane stores at every compare without touching the exec mask: at its own offset when the compare
-                        //  fired, into a trash slot when it did not -- the pre-round-5 stores, kept for comparison)
-                        uint32_t v = cur[r][j];
-                        asm volatile("" : "+v"(v));
-                        const bool f = v != pv;
-                        const uint32_t at = f ? offf : ftrash;
-                        *(lds_u32)(uintptr_t)at = v; *(lds_u32)(uintptr_t)(at + 4u) = pv | tag1;
-                        offf += f ? 8u : 0u;
-#endif
-                    }
-                }
+                        store_faces4_tagged_if_ne<FULL>(offf, cur[r][j], voxel_above(cur, up, r, j), cur[r][(j + 1) % VPL], voxel_above(cur, up, r, (j + 1) % VPL),
+                                                        cur[r][(j + 2) % VPL], voxel_above(cur, up, r, (j + 2) % VPL), cur[r][(j + 3) % VPL],
+                                                        voxel_above(cur, up, r, (j + 3) % VPL), tag1, live);
                 // (the runs behind the faces; records of a row in column order)
-#if TA_MASKED_STORES & 4
-                static_assert(VPL == 4 || VPL == 8, "the run stores are written out for four or eight voxels a lane");
-                store_runs4_if_ne<FULL, 0, (int)(RSTRIDE / 4u)>(offr, pcv[0], cur[r][0], cur[r][1 % VPL], cur[r][2 % VPL], cur[r][3 % VPL], code0, live);
+                static_assert(VPL == 4 || VPL == 8, "the record stores are written out for four or eight voxels a lane");
+                store_runs4_if_ne<FULL, 0, (int)(RSTRIDE / 4u)>(offr, pcv[0], cur[r][0], cur[r][1], cur[r][2], cur[r][3], code0, live);
                 if constexpr (VPL == 8)
-                    store_runs4_if_ne<FULL, 4, (int)(RSTRIDE / 4u)>(offr, cur[r][3 % VPL], cur[r][4 % VPL], cur[r][5 % VPL], cur[r][6 % VPL], cur[r][7 % VPL], code0, live);
-                static_assert(VPL <= 8, "the run stores are written out for eight voxels a lane");
-#else
-#pragma unroll
-                for (int j = 0; j < VPL; ++j) {
-                    uint32_t v = cur[r][j];
-                    asm volatile("" : "+v"(v));
-                    const bool g = v != pcv[j];
-                    const uint32_t at = g ? offr : rtrash;
-                    *(lds_u32)(uintptr_t)at = pcv[j];
-                    *(lds_u32)(uintptr_t)(at + RSTRIDE) = code0 | (uint32_t)j;
-                    offr += g ? 4u : 0u;
-                }
-#endif
-                if (TA_MASKED_STORES) emit_done();
+                    store_runs4_if_ne<FULL, 4, (int)(RSTRIDE / 4u)>(offr, cur[r][3], cur[r][4], cur[r][5], cur[r][6], cur[r][7], code0, live);
+                emit_done();
                 if (need_end && lane == 63) {
                     *(lds_u32)(uintptr_t)offr = cur[r][VPL - 1];
                     *(lds_u32)(uintptr_t)(offr + RSTRIDE) = (uint32_t)TC | rowcode | ROW_END;
                 }
             });
-#ifdef TA_STAMPS
-            tk_emit += TA_T() - t1;
-#endif
         }
     };
-    // ---- the planes of the tile: the plane in flight lands (it was issued a whole plane of compute ago), the next one is
-    //      issued into the registers it leaves, the landed one is processed.  (Measured and dropped: TWO planes in flight for
-    //      the two-row tiles of uint16 volumes, in the two halves of the sixteen pinned registers -- C2 stayed at 0.070 ms:
-    //      that kernel is bound by its instructions per voxel, not by the bytes it has in flight.)
+    // The hot drains, at the top of a plane (drain_face_groups, drain_run_group): full groups of 64, every lookup in flight together.
+    // The rare sites -- a row too big for the buffers placed in pieces, the end of the tile -- keep the group-by-group drain_buffers.
+    // One group of 64 faces leaves from 64 on in the tiles of eight voxels a lane: they put twice the records of a plane step into
+    // the same buffers; with 64 .. 127 faces left after a step, the next one's often do not fit and the whole buffer goes through the
+    // in-plane drain (29 % of C4's face records, 43 % of the tissue-filled volume's, against 13 / 14 % with four voxels a lane).  With
+    // one group leaving at the top of the plane those shares fall to 7 / 16 % -- and the sweep takes the same time (C4 1.01 / 1.02 vs
+    // 1.01 / 1.02 ms, filled 1.38 - 1.44 vs 1.39 - 1.46, C5 6.79 / 6.83 vs 6.78 / 6.86): where a record is drained does not matter.  On
+    // since round 5 (with the predicated stores: C4 0.972 -> 0.965, filled 1.392 -> 1.367 / 1.390 ms in one call -- within the noise,
+    // and the in-plane drain with its per-lane probe loops becomes the rare path it is meant to be).
+    constexpr bool DRAIN_ALL = ADJ && FCAP % 64 == 0 && RCAP % 64 == 0 && RB == 2 && !EDGE;
+    // -- the planes of the tile: the plane in flight lands (it was issued a whole plane of compute ago), the next one is
+    //    issued into the registers it leaves, the landed one is processed.  (Measured and dropped: TWO planes in flight for
+    //    the two-row tiles of uint16 volumes, in the two halves of the sixteen pinned registers -- C2 stayed at 0.070 ms:
+    //    that kernel is bound by its instructions per voxel, not by the bytes it has in flight.)
     for (int32_t p = p_lo; p < p_hi; ++p) {
         if constexpr (DRAIN_ALL) {
-            // the hot drains: between two planes a wave holds nothing but the plane before (and the next one is in flight)
+            // (between two planes a wave holds nothing but the plane before, and the next one is in flight)
 #ifdef TA_RECCOUNT
             if (lane == 0 && fcount >= (uint32_t)TA_FDRAIN) atomicAdd(&cold_args(kp)->flags[11], 128u);
-            else if (lane == 0 && TA_FDRAIN1 && VPL == 8 && fcount >= 64u) atomicAdd(&cold_args(kp)->flags[11], 64u);
+            else if (lane == 0 && VPL == 8 && fcount >= 64u) atomicAdd(&cold_args(kp)->flags[11], 64u);
             if (lane == 0 && rcount > 64u) atomicAdd(&cold_args(kp)->flags[12], 64u);
 #endif
             if (fcount >= (uint32_t)TA_FDRAIN) drain_face_groups<2, LDS>(kp, S, W, lane, fcount);
-            else if (TA_FDRAIN1 && VPL == 8 && fcount >= 64u) drain_face_groups<1, LDS>(kp, S, W, lane, fcount);
+            else if (VPL == 8 && fcount >= 64u) drain_face_groups<1, LDS>(kp, S, W, lane, fcount);
             if (rcount > 64u) drain_run_group<MOM2, LDS>(kp, S, W, EDGE, lane, rcount, first_label);
         }
         if constexpr (PINB != 0) {
-#ifdef TA_STAMPS
-            const uint64_t t4 = TA_T();
-#endif
             land();
-#ifdef TA_STAMPS
-            tk_land += TA_T() - t4;
-#endif
             if (p + 1 < p_hi) issue_plane();
         }
         process_plane(p);
     }
-#ifdef TA_STAMPS
-    if (lane == 0) {
-        uint32_t* fl = cold_args(kp)->flags;
-        atomicAdd(&fl[8], (uint32_t)(tk_cmp >> 8)); atomicAdd(&fl[9], (uint32_t)(tk_emit >> 8));
-        atomicAdd(&fl[10], (uint32_t)(tk_drain >> 8)); atomicAdd(&fl[11], (uint32_t)(tk_adv >> 8));
-        atomicAdd(&fl[12], (uint32_t)((TA_T() - tk_begin) >> 8));
-        atomicAdd(&fl[13], (uint32_t)(tk_land >> 8)); atomicAdd(&fl[14], (uint32_t)tk_evrows); atomicAdd(&fl[15], (uint32_t)tk_drains);
-    }
-#endif
 
-    // ---- end of tile: drain the buffers, then the leading one-label rows in one closed form
+    // ---- 5. the end of the tile: drain the buffers, then the leading one-label rows in one closed form
     drain(false);
     if (__builtin_amdgcn_ballot_w64(bad)) { if (lane == 0) atomicOr(&cold_args(kp)->flags[FLAG_RANGE], 1u); }
-    if (lane == 0 && nlead != 0u && first_label != INVALID_LABEL) {
-        // rows in (plane, row) order: P full planes of RB rows, then R rows of plane P
-        const uint64_t P = nlead / RB, R = nlead % RB, nc = TC, b0 = (uint64_t)w * RB;
-        const uint64_t t1c = range_sum1(0, nc), t2c = range_sum2(0, nc);
-        const uint64_t rows = P * RB + R;                                        // = nlead
-        const uint64_t sa_rows = range_sum1(0, P) * RB + P * R;                  // sum of a over the rows
-        const uint64_t saa_rows = range_sum2(0, P) * RB + P * P * R;
-        const uint64_t sb_rows = P * range_sum1(b0, RB) + range_sum1(b0, R);
-        const uint64_t sbb_rows = P * range_sum2(b0, RB) + range_sum2(b0, R);
-        const uint64_t sab_rows = range_sum1(0, P) * range_sum1(b0, RB) + P * range_sum1(b0, R);
-        LocalSums L;
-        L.n = rows * nc; L.sa = sa_rows * nc; L.sb = sb_rows * nc; L.sc = rows * t1c;
-        if (MOM2) {
-            L.saa = saa_rows * nc; L.sab = sab_rows * nc; L.sbb = sbb_rows * nc;
-            L.sac = sa_rows * t1c; L.sbc = sb_rows * t1c; L.scc = rows * t2c;
-        } else {
-            L.saa = L.sab = L.sac = L.sbb = L.sbc = L.scc = 0;
-        }
-        const uint32_t mxa = (uint32_t)(R ? P : P - 1u);
-        const uint32_t mxb = (uint32_t)(b0 + (P ? RB : R) - 1u);
-        const uint32_t fh = scan_label_hash(first_label);
-        scan_label_add<MOM2, LDS, LocalSums>(kp, S, first_label, L, 0u, mxa, (uint32_t)b0, mxb, 0u,
-                                             (uint32_t)(nc - 1), fh, S.lkeys[fh]);
-    }
+    if (lane == 0 && nlead != 0u && first_label != INVALID_LABEL) add_leading_rows<MOM2, RB, TC, LDS>(kp, S, w, first_label, nlead);
 }
 
 // Tiles of a volume: `fc` x `fb` full tiles per plane band go to the interior kernel (hand-issued 16-byte loads, no
@@ -1409,7 +1247,7 @@ __device__ __forceinline__ void scan_kernel_body(const SweepArgs& A, const ScanS
         else { t -= strip; tc = t % sp.fc; tb = sp.fb + t / sp.fc; }                                    // the last tile row(s)
     }
     // (the private hot-label row of a tile: numbered by the tile)
-    if (TA_HOT_ADJ || !ADJ) hot_row_init(A, tid, wg0 + tile);
+    hot_row_init(A, tid, wg0 + tile);
     const uint32_t c_tile0 = tc * TC, b_tile0 = tb * TB;
     const int32_t p_lo = A.first_owned + (int32_t)band * A.tile_planes;
     int32_t p_hi = p_lo + A.tile_planes;
@@ -1436,8 +1274,8 @@ __device__ __forceinline__ void scan_kernel_body(const SweepArgs& A, const ScanS
     const SweepArgs& Ac = ka.a;
     const uint32_t wg_ = ka.wg0 + tile;
 #ifndef TA_ABL_NOFLUSH
-    flush_tables<NW, ADJ, MOM2, (TA_HOT_ADJ || !ADJ), LDS>(Ac, S, threadIdx.x, (uint64_t)S.frame[0], (uint64_t)S.frame[1], (uint64_t)S.frame[2],
-                                      (TA_HOT_ADJ || !ADJ) ? hot_label_of<T>(Ac) : 0u, wg_);
+    flush_tables<NW, ADJ, MOM2, true, LDS>(Ac, S, threadIdx.x, (uint64_t)S.frame[0], (uint64_t)S.frame[1], (uint64_t)S.frame[2],
+                                           hot_label_of<T>(Ac), wg_);
 #else
     if (wg_ == 0xffffffffu) S.frame[3] = 1;
 #endif

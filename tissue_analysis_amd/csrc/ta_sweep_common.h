@@ -153,7 +153,6 @@ __device__ __forceinline__ void hot_row_init(const SweepArgs& A, const int tid, 
         rows[(uint64_t)wg * HOTW + tid] = tid < NSUM ? 0ull : imax2;
     }
 }
-__device__ __forceinline__ void hot_row_init(const SweepArgs& A, const int tid) { hot_row_init(A, tid, blockIdx.x); }
 
 // HOT = false compiles the hot-row path out (the naive cross-check kernel's rows; the sweep uses it for every mask).
 //
@@ -201,16 +200,16 @@ __device__ __forceinline__ void flush_tables(const SweepArgs& A, LDS& S, const i
     __syncthreads();
     const int nl = (int)S.fcnt[0], np = ADJ ? (int)S.fcnt[1] : 0;
 
-    // TRANSPOSED label flush (TA_FLUSH_TRANSPOSE): a label's NSUM sums are consecutive u64 words of one global row, and a global atomic
-    // is a request to the memory side per cache line a wave instruction touches.  Lane = label sends every add of an instruction to a
+    // TRANSPOSED label flush (kernels with adjacency: the sums are staged in the pair table's space).  A label's NSUM sums are consecutive
+    // u64 words of one global row, and a global atomic is a request to the memory side per cache line a wave instruction touches.  Lane = label sends every add of an instruction to a
     // different row (64 requests, ten instructions a label); lane = (label, word) sends 64 consecutive words of ~6 rows.  The sums go
     // through LDS for that: the pair table's keys and counts are read into registers first (two pairs a thread at most; their home
     // slots' global reads are in flight from then on), the sums are staged where the pair table was, and the pairs' adds go last.
     constexpr int NS = MOM2 ? NSUM : 4;
-    constexpr bool TR = ADJ && TA_FLUSH_TRANSPOSE != 0 && PSLOTS <= 2 * NT &&
-                        (size_t)LSLOTS * NSUM * 8 <= sizeof(S.pkeys) + sizeof(S.pcnt);
-    if constexpr (TR) {
-        static_assert(!TR || offsetof(LDS, pcnt) == offsetof(LDS, pkeys) + sizeof(S.pkeys), "the staged sums run from the pair keys on into the pair counts");
+    static_assert(!ADJ || (PSLOTS <= 2 * NT && (size_t)LSLOTS * NSUM * 8 <= sizeof(S.pkeys) + sizeof(S.pcnt)),
+                  "the flush takes two pairs a thread and stages the labels' sums where the pair table was");
+    if constexpr (ADJ) {
+        static_assert(offsetof(LDS, pcnt) == offsetof(LDS, pkeys) + sizeof(S.pkeys), "the staged sums run from the pair keys on into the pair counts");
         uint64_t pkey[2], gkey[2]; uint32_t pf[2][3], ghome[2]; bool plive[2];
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
@@ -283,24 +282,7 @@ __device__ __forceinline__ void flush_tables(const SweepArgs& A, LDS& S, const i
             if (plive[q])
                 pair_add_global_from(A.pairs, (uint32_t)(pkey[q] >> 32), (uint32_t)pkey[q], pf[q][0], pf[q][1], pf[q][2], A.flags, ghome[q], gkey[q]);
     } else {
-    // -- the pairs, from the last thread down: the home slot of the pair in the device-global table is READ first and looked
-    //    at afterwards (the first global round trip of the probe is in flight while the rest is prepared)
-#ifdef TA_ABL_NOFLUSH_PAIRS
-    if (false) {
-#else
-    if (ADJ) {
-#endif
-        for (int j = NT - 1 - tid; j < np; j += NT) {
-            const int i = plist[j];
-            const uint64_t key = S.pkeys[i];
-            const uint32_t lo = (uint32_t)(key >> 32), hi = (uint32_t)key;
-            const uint32_t gh = hash_pair(lo, hi) & A.pairs.mask;
-            const uint64_t gk = __hip_atomic_load(&A.pairs.keys[gh], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const uint32_t f0 = S.pcnt[i * 3 + 0], f1 = S.pcnt[i * 3 + 1], f2 = S.pcnt[i * 3 + 2];
-            pair_add_global_from(A.pairs, lo, hi, f0, f1, f2, A.flags, gh, gk);
-        }
-    }
-    // -- the labels, from the first thread up
+    // -- without adjacency there are no pairs: the labels, from the first thread up, lane = label
     uint64_t* const hot_rows = HOT ? hot_rows_of(A) : nullptr;
 #ifdef TA_ABL_NOFLUSH_LABELS
     for (int j = tid; j < 0; j += NT) {
@@ -332,7 +314,6 @@ __device__ __forceinline__ void flush_tables(const SweepArgs& A, LDS& S, const i
         // their minima -- so a skip decided on it is always safe; the price is one more round trip in a flush that waits for several.
         const int32_t m0 = (int32_t)(A0 + bx0), m1 = (int32_t)(B0 + bx1), m2 = (int32_t)(C0 + bx2);
         const int32_t m3 = -(int32_t)(A0 + bx3), m4 = -(int32_t)(B0 + bx4), m5 = -(int32_t)(C0 + bx5);
-#if TA_FLUSH_BOX_READ
         const int2 g01 = *reinterpret_cast<const int2*>(box), g23 = *reinterpret_cast<const int2*>(box + 2), g45 = *reinterpret_cast<const int2*>(box + 4);
         if (m0 < g01.x) flush_min(box + 0, m0);
         if (m1 < g01.y) flush_min(box + 1, m1);
@@ -340,19 +321,8 @@ __device__ __forceinline__ void flush_tables(const SweepArgs& A, LDS& S, const i
         if (m3 < g23.y) flush_min(box + 3, m3);
         if (m4 < g45.x) flush_min(box + 4, m4);
         if (m5 < g45.y) flush_min(box + 5, m5);
-#else
-        flush_min(box + 0, m0); flush_min(box + 3, m3);
-        flush_min(box + 1, m1); flush_min(box + 4, m4);
-        flush_min(box + 2, m2); flush_min(box + 5, m5);
-#endif
     }
     }
-}
-
-template <int NW, bool ADJ, bool MOM2, bool HOT, typename LDS>
-__device__ __forceinline__ void flush_tables(const SweepArgs& A, LDS& S, const int tid, const uint64_t A0,
-                                             const uint64_t B0, const uint64_t C0, const uint32_t hot) {
-    flush_tables<NW, ADJ, MOM2, HOT, LDS>(A, S, tid, A0, B0, C0, hot, blockIdx.x);
 }
 
 }  // namespace ta
