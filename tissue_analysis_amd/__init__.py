@@ -18,6 +18,7 @@ from .extraction import Extraction, extract_volume
 from .signal_stats import SignalStats
 from .signal_quantiles import SignalHistogram, SignalQuantiles
 from .signal_moments import SignalMoments
+from .channel_pair import ChannelPairStats
 from .cell_topology import CellTopology
 from .cell_extents import CellExtents
 from .cell_meshes import CellMeshes
@@ -33,7 +34,7 @@ from .property_graph import PropertyGraph
 from .graph_from_image import graph_from_image, property_graph_to_dataframe
 
 __all__ = ["SpatialImage", "NPLIST", "LIST", "DICT", "AbstractSpatialImageAnalysis",
-           "SpatialImageAnalysis3D", "SpatialImageAnalysis", "Extraction", "extract_volume", "SignalStats", "SignalHistogram", "SignalQuantiles", "SignalMoments", "CellTopology", "CellExtents", "CellMeshes",
+           "SpatialImageAnalysis3D", "SpatialImageAnalysis", "Extraction", "extract_volume", "SignalStats", "SignalHistogram", "SignalQuantiles", "SignalMoments", "ChannelPairStats", "CellTopology", "CellExtents", "CellMeshes",
            "LabelOverlap", "label_overlap", "lineage_from_images", "Resampled", "index_matrix", "transform_points", "CellJunctions", "cell_junctions", "WallGeometry", "wall_geometry",
            "LabelComponents", "label_components", "DistanceMap", "distance_map", "NearestLabels", "ShellProfile",
            "dilation", "dilation_by", "real_indices", "return_list_of_vectors", "hollow_out_cells", "wall", "contact_surface",

@@ -173,6 +173,15 @@ DECLARED = {
         "ta_sigmom_debug": (_ci, [_vp, _P(_u32)]),
         "ta_sigmom_timing": (_ci, [_vp, _P(_f64)]),
     },
+    "tissue_scan_cosignal.h": {
+        "ta_cosignal_set": (_ci, [_vp, _vp, _ci, _P(_i64), _P(_i64)]),
+        "ta_cosignal_set_device": (_ci, [_vp, _vp, _ci]),
+        "ta_cosignal_extract": (_ci, [_vp, _u32, _u32]),
+        "ta_cosignal_get": (_ci, [_vp] + [_vp] * 11),
+        "ta_cosignal_debug": (_ci, [_vp, _P(_u32)]),
+        "ta_cosignal_timing": (_ci, [_vp, _P(_f64)]),
+        "ta_cosignal_thresholds": (_ci, [_vp, _P(_u32), _P(_u32)]),
+    },
     "tissue_scan_topology.h": {
         "ta_topology_extract": (_ci, [_vp]),
         "ta_topology_get": (_ci, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -240,6 +249,11 @@ SIGHIST_MAX_GROUPS = 65536             # TA_SH_MAX_GROUPS: workgroups of the dig
 SIGMOM_SYMBOLS = tuple(DECLARED["tissue_scan_sigmoments.h"])
 SIGMOM_SLOTS = 448                     # SM_SLOTS of csrc/ta_sigmoments.h: rows of a workgroup's LDS table
 SIGMOM_MAX_GROUPS = 1024               # SM_MAX_GROUPS: workgroups of the pass at most (the plan: tests/sigmoment_reference.py)
+
+COSIGNAL_SYMBOLS = tuple(DECLARED["tissue_scan_cosignal.h"])
+COSIGNAL_COLUMNS = ("n", "sum_a", "sum_b", "sq_aa", "sq_bb", "sq_ab", "n_a", "n_b", "n_ab", "sum_a_over", "sum_b_over")   # ta_cosignal_get's order
+COSIG_SLOTS = 512                      # COSIG_SLOTS of csrc/ta_cosignal.h: rows of a workgroup's LDS table
+COSIG_MAX_GROUPS = 1024                # COSIG_MAX_GROUPS: workgroups of the pass at most (the plan: that of the signal pass)
 
 TOPOLOGY_SYMBOLS = tuple(DECLARED["tissue_scan_topology.h"])
 TOPOLOGY_SLOTS = 768                   # TP_SLOTS of csrc/ta_topology.h: rows of a workgroup's LDS table
@@ -970,6 +984,50 @@ class Context(object):
 
     def sigmom_timing(self):
         return self._doubles(self._lib.ta_sigmom_timing, 1)[0]
+
+    # -- two-channel statistics (include/tissue_scan_cosignal.h): channel A is the signal image, channel B is set here
+    def set_cosignal(self, array):
+        """Upload channel B: a uint8 / uint16 intensity image of the label volume's shape.  One stored in another axis permutation
+        than the labels is copied into the labels' layout first."""
+        a = np.asarray(array)
+        if a.dtype not in SIGNAL_DTYPES:
+            raise TypeError("signal images must be uint8 or uint16, not %s" % a.dtype)
+        a = self._in_label_layout(a, ("its second signal", "second signal's"))
+        _check(self._lib.ta_cosignal_set(self._h, ctypes.c_void_p(a.ctypes.data), a.dtype.itemsize, _i64x3(a.shape), _i64x3(a.strides)))
+        self._keep_cosig = None
+
+    def set_cosignal_device(self, dev_ptr, itemsize, keep=None):
+        """Adopt a device-resident channel B: dense C order with the label volume's buffer dims (halo plane included)."""
+        _check(self._lib.ta_cosignal_set_device(self._h, ctypes.c_void_p(int(dev_ptr)), int(itemsize)))
+        self._keep_cosig = keep
+
+    def cosignal_extract(self, thr_a=0, thr_b=0):
+        """Enqueue the two-channel pass over the current extraction, the signal image (A) and channel B; a voxel is over in a
+        channel when its value is > the threshold."""
+        _check(self._lib.ta_cosignal_extract(self._h, int(thr_a), int(thr_b)))
+        self._cosig_rows = self._max_label + 1
+
+    def cosignal_rows(self):
+        """A dict of COSIGNAL_COLUMNS, rows as labels(): uint64 [R], the three sq_* columns uint64 [R, 2] (lo, hi words)."""
+        R = getattr(self, "_cosig_rows", 1)                    # (no pass yet: the library answers TA_EINVAL)
+        cols = dict((k, np.zeros((R, 2) if k.startswith("sq_") else R, dtype=np.uint64)) for k in COSIGNAL_COLUMNS)
+        _check(self._lib.ta_cosignal_get(self._h, *[cols[k].ctypes.data for k in COSIGNAL_COLUMNS]))
+        return cols
+
+    def cosignal_debug(self):
+        """Diagnostics of the last two-channel pass: records that missed a workgroup's LDS table (spills) and the launch plan
+        (tiles_per_group, groups)."""
+        out = self._debug_words(self._lib.ta_cosignal_debug)
+        return dict(spills=out[0], tiles_per_group=out[2], groups=out[3])
+
+    def cosignal_timing(self):
+        return self._doubles(self._lib.ta_cosignal_timing, 1)[0]
+
+    def cosignal_thresholds(self):
+        """(thr_a, thr_b) of the last two-channel pass."""
+        a, b = ctypes.c_uint32(0), ctypes.c_uint32(0)
+        _check(self._lib.ta_cosignal_thresholds(self._h, ctypes.byref(a), ctypes.byref(b)))
+        return int(a.value), int(b.value)
 
     # -- Euler numbers (include/tissue_scan_topology.h)
     def topology_extract(self):

@@ -329,6 +329,7 @@ static void voxels_changed(ta_ctx* c) {          // what every change of the vox
     profile_on_new_volume(c);
     sighist_on_new_volume(c);
     sigmom_on_new_volume(c);
+    cosig_on_new_volume(c);
     topology_on_new_volume(c);
     extents_on_new_volume(c);
 }
@@ -427,7 +428,7 @@ TA_API int ta_ctx_destroy(ta_ctx* c) {
     c->small.release();
     c->hot_rows.release(); c->sort_buf.release(); c->h_pairs.release();
     c->walls.release(); c->ids.release(); c->shape.release();
-    c->sig.release(); c->mesh.release(); c->ov.release(); c->jn.release(); c->wg.release(); c->cc.release(); c->dist.release(); c->near.release(); c->prof.release(); c->sh.release(); c->sm.release(); c->tp.release(); c->ex.release(); c->rs.release();
+    c->sig.release(); c->mesh.release(); c->ov.release(); c->jn.release(); c->wg.release(); c->cc.release(); c->dist.release(); c->near.release(); c->prof.release(); c->sh.release(); c->sm.release(); c->co.release(); c->tp.release(); c->ex.release(); c->rs.release();
     if (c->h_small) (void)hipHostFree(c->h_small);
     destroy_events(c->ev);
     for (auto& e : c->ring) if (e) (void)hipEventDestroy(e);

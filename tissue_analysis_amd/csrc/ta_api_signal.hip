@@ -68,7 +68,7 @@ void signal_on_new_volume(ta_ctx* c) {
 // the resample pass rewrites (or has moved) the buffer the signal was adopted from: its results are stale, a signal that is gone is dropped
 void signal_on_resampled(ta_ctx* c, const void* buf, const void* now, int itemsize) {
     if (!buf || c->sig.img.p != buf || c->sig.img.owned.p) return;
-    c->sig.seq = 0; profile_on_new_signal(c); sighist_on_new_signal(c); sigmom_on_new_signal(c);
+    c->sig.seq = 0; profile_on_new_signal(c); sighist_on_new_signal(c); sigmom_on_new_signal(c); cosig_on_new_signal(c);
     if (now != buf || itemsize != c->sig.img.itemsize) { c->sig.img.p = nullptr; c->sig.img.itemsize = 0; }
 }
 
@@ -77,14 +77,14 @@ extern "C" {
 TA_API int ta_signal_set(ta_ctx* c, const void* host_ptr, int itemsize, const int64_t dims[3], const int64_t strides_bytes[3]) {
     if (!c) return fail(TA_EINVAL, "ctx is NULL");
     const int rc = companion_set_host(c, c->sig.img, SIGNAL, host_ptr, itemsize, dims, strides_bytes);
-    if (rc == TA_OK) { c->sig.seq = 0; profile_on_new_signal(c); sighist_on_new_signal(c); sigmom_on_new_signal(c); }     // (the results are stale only once a new signal is in place: deliberate, as inherited)
+    if (rc == TA_OK) { c->sig.seq = 0; profile_on_new_signal(c); sighist_on_new_signal(c); sigmom_on_new_signal(c); cosig_on_new_signal(c); }     // (the results are stale only once a new signal is in place: deliberate, as inherited)
     return rc;
 }
 
 TA_API int ta_signal_set_device(ta_ctx* c, const void* dev_ptr, int itemsize) {
     if (!c) return fail(TA_EINVAL, "ctx is NULL");
     const int rc = companion_set_device(c, c->sig.img, SIGNAL, dev_ptr, itemsize);
-    if (rc == TA_OK) { c->sig.seq = 0; profile_on_new_signal(c); sighist_on_new_signal(c); sigmom_on_new_signal(c); }
+    if (rc == TA_OK) { c->sig.seq = 0; profile_on_new_signal(c); sighist_on_new_signal(c); sigmom_on_new_signal(c); cosig_on_new_signal(c); }
     return rc;
 }
 

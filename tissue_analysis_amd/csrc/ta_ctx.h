@@ -237,6 +237,18 @@ struct SigMomentState {
     void release() { out.release(); destroy_events(ev); }
 };
 
+// two-channel statistics (include/tissue_scan_cosignal.h): channel A is SignalState::img
+struct CoSignalState {
+    Companion b;                                        // channel B
+    DevBuf out;                                         // flags u32[4] | n | sum_a | sum_b u64[R] | sq_aa | sq_bb | sq_ab u64[R][2] | n_a | n_b | n_ab | over_a | over_b u64[R]
+    uint64_t seq = 0;                                   // extract_seq of the extraction the rows belong to, 0 = none
+    uint32_t rows = 0;                                  // max_label + 1 of that extraction
+    uint32_t thr[2] = {0, 0};                           // the thresholds of the last pass (ta_cosignal_thresholds)
+    ta::RangePlan plan;                                 // what the last pass was launched with (ta_cosignal_debug)
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    void release() { b.owned.release(); out.release(); destroy_events(ev); }
+};
+
 // Euler numbers (include/tissue_scan_topology.h)
 struct TopologyState {
     DevBuf out;                                         // flags u32[4] | mixed blocks u64 | n0 u64[R] | n1 u64[R][3] | n2 u64[R][3] | n3 u64[R] | v u64[R] | e u64[R][3]
@@ -392,6 +404,7 @@ struct ta_ctx {
     ProfileState prof;
     SigHistState sh;
     SigMomentState sm;
+    CoSignalState co;
     TopologyState tp;
     ExtentState ex;
     ResampleState rs;
@@ -577,6 +590,8 @@ void sighist_on_new_volume(ta_ctx* c);
 void sighist_on_new_signal(ta_ctx* c);                // a new signal image: both tables read the old one.  ta_api_sighist.hip
 void sigmom_on_new_volume(ta_ctx* c);
 void sigmom_on_new_signal(ta_ctx* c);                 // a new signal image: the rows read the old one.  ta_api_sigmoments.hip
+void cosig_on_new_volume(ta_ctx* c);                  // ... and a B of other dims is dropped.  ta_api_cosignal.hip
+void cosig_on_new_signal(ta_ctx* c);                  // a new signal image: the rows read the old one as their channel A.  ta_api_cosignal.hip
 void topology_on_new_volume(ta_ctx* c);
 void extents_on_new_volume(ta_ctx* c);
 void resample_on_new_volume(ta_ctx* c);               // a grid of other dims drops source and result.  ta_api_resample.hip

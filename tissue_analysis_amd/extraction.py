@@ -592,6 +592,15 @@ class ResidentVolume(object):
         signal = self._signal_on_grid(signal, matrix, order, fill)
         return self._timed("signal_moments", resident_signal_moments, self, signal, voxelsize)
 
+    def signal_pair(self, a, b, thresholds=(0, 0)):
+        """Two intensity images `a`, `b` (uint8 / uint16 each, the shape of the labels, on their grid) per label: a
+        `ChannelPairStats` (ratio, covariance, Pearson's r, Manders' M1 / M2 for `thresholds` = (t_a, t_b), all from exact integer
+        sums) whose rows line up with the last extraction.  One upload per channel and one pass over labels + both channels on the
+        GPU.  A channel on another grid is resampled first (`resample`): the resample pass owns one result buffer, so there is no
+        `matrix=` here."""
+        from .channel_pair import resident_channel_pair
+        return self._timed("signal_pair", resident_channel_pair, self, a, b, thresholds)
+
     def topology(self, voxelsize=(1.0, 1.0, 1.0)):
         """The Euler numbers of the labels of the resident volume, for 6- and for 26-connectivity, and the intrinsic volumes of
         their voxel solids: a `CellTopology` (twelve exact block counts per label) whose rows line up with the last extraction

@@ -124,13 +124,15 @@ def _wall_median_columns(graph, analysis, pairs, background):
         graph.set_vertex_column(name, value, valid, _show_point)
 
 
-def tissue_tables(analysis, labels, background, properties, property_as_real=True, min_contact_area=None, signal=None):
+def tissue_tables(analysis, labels, background, properties, property_as_real=True, min_contact_area=None, signal=None,
+                  reference_signal=None):
     """The vertex / edge tables of the tissue graph from the sweep results held by `analysis`.
     `labels`: the vertex ids (any order, distinct).  Returns a PropertyGraph whose columns are plain numpy arrays.
     With an intensity image `signal`, 'mean_signal' (vertex: cell_signal's mean), 'median_signal' (vertex: signal_median) and
     'wall_signal' (edge: wall_signal's face-weighted mean) can be asked for too, and 'signal_barycenter' and 'signal_polarity'
     (vertex: signal_center_of_mass and the vector of signal_polarity, which run the signal-moment pass; a property list without
-    them does not).  'wall_centroid', 'wall_normal' and 'wall_projected_area' (edge: the columns of
+    them does not).  With a second image `reference_signal` beside it, 'signal_ratio' and 'signal_correlation' (vertex:
+    `analysis.signal_ratio(signal, reference_signal)` and `.signal_correlation`) run the two-channel pass.  'wall_centroid', 'wall_normal' and 'wall_projected_area' (edge: the columns of
     `analysis.wall_geometry()`) run the wall-geometry pass; a property list without them does not.  'n_components' (vertex:
     the face-connected blobs the label consists of, `analysis.label_components()`) runs the component pass, likewise;
     'euler_number' (vertex: `analysis.euler_number()`, 6-connectivity) the Euler-number pass; and so do
@@ -221,6 +223,12 @@ def tissue_tables(analysis, labels, background, properties, property_as_real=Tru
             graph.set_vertex_column('signal_barycenter', moments.of_labels(ids, 'centroid', real), asked, _show_vector)
         if 'signal_polarity' in properties:
             graph.set_vertex_column('signal_polarity', moments.of_labels(ids, 'polarity', real), asked, _show_vector)
+    if signal is not None and reference_signal is not None and ('signal_ratio' in properties or 'signal_correlation' in properties):
+        pair = analysis._channel_pair(signal, reference_signal)
+        if 'signal_ratio' in properties:
+            graph.set_vertex_column('signal_ratio', pair.of_labels(ids, 'ratio'), asked)
+        if 'signal_correlation' in properties:
+            graph.set_vertex_column('signal_correlation', pair.of_labels(ids, 'pearson'), asked)
     wall_geometry_columns = [p for p in ('wall_centroid', 'wall_normal', 'wall_projected_area') if p in properties]
     if wall_geometry_columns:
         geo = analysis.wall_geometry()
@@ -250,7 +258,7 @@ def tissue_tables(analysis, labels, background, properties, property_as_real=Tru
 
 
 def _graph_from_image(image, labels, background, default_properties, property_as_real, ignore_cells_at_stack_margins,
-                      min_contact_area, signal=None):
+                      min_contact_area, signal=None, reference_signal=None):
     """TGI:77-244: which analysis object, which labels are ignored, which become vertices -- then the tables."""
     if isinstance(image, AbstractSpatialImageAnalysis):
         analysis = image
@@ -271,23 +279,24 @@ def _graph_from_image(image, labels, background, default_properties, property_as
             labels.remove(background)                                      # the caller's list, as in the reference
         ids = np.asarray(labels, dtype=np.int64)
         analysis.add2ignoredlabels(np.setdiff1d(np.asarray(analysis.labels(), dtype=np.int64), ids))
-    return tissue_tables(analysis, ids, background, default_properties, property_as_real, min_contact_area, signal)
+    return tissue_tables(analysis, ids, background, default_properties, property_as_real, min_contact_area, signal, reference_signal)
 
 
 def graph_from_image2D(image, labels, background, spatio_temporal_properties, property_as_real,
-                       ignore_cells_at_stack_margins, min_contact_area, signal=None):
+                       ignore_cells_at_stack_margins, min_contact_area, signal=None, reference_signal=None):
     return _graph_from_image(image, labels, background, spatio_temporal_properties, property_as_real,
-                             ignore_cells_at_stack_margins, min_contact_area, signal)
+                             ignore_cells_at_stack_margins, min_contact_area, signal, reference_signal)
 
 
 graph_from_image3D = graph_from_image2D        # (the reference's two entry points run the same body, TGI:247-258)
 
 
 def graph_from_image(image, labels=None, background=1, spatio_temporal_properties=None, property_as_real=True,
-                     ignore_cells_at_stack_margins=True, min_contact_area=None, signal=None):
+                     ignore_cells_at_stack_margins=True, min_contact_area=None, signal=None, reference_signal=None):
     """TGI:260-284.  `image`: a label image or an analysis object of this package.  `signal`: an intensity image (uint8 /
     uint16) of the same shape, which makes the properties 'mean_signal', 'median_signal', 'signal_barycenter', 'signal_polarity'
-    (vertex) and 'wall_signal' (edge) available."""
+    (vertex) and 'wall_signal' (edge) available; with `reference_signal`, a second one, also 'signal_ratio' and 'signal_correlation'
+    (vertex: sum(signal) / sum(reference_signal) and Pearson's r of the two over the cell)."""
     if isinstance(image, AbstractSpatialImageAnalysis):
         shape = np.shape(image.image)
         if labels is None:
@@ -299,7 +308,7 @@ def graph_from_image(image, labels=None, background=1, spatio_temporal_propertie
         spatio_temporal_properties = spatio_temporal_properties2D if flat else spatio_temporal_properties3D
     build = graph_from_image2D if flat else graph_from_image3D
     return build(image, labels, background, spatio_temporal_properties, property_as_real, ignore_cells_at_stack_margins,
-                 min_contact_area, signal)
+                 min_contact_area, signal, reference_signal)
 
 
 # ----------------------------------------------------------------------------- helpers of TGI:30-60, 309-398, by name

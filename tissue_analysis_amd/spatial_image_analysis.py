@@ -269,6 +269,7 @@ class AbstractSpatialImageAnalysis(object):
         self._wall_medians = None
         self._signal_cache = None
         self._sigmom_cache = None
+        self._pair_cache = None
         self._mesh_cache = {}
         self._junctions = None
         self._wall_geometry = None
@@ -675,6 +676,42 @@ class AbstractSpatialImageAnalysis(object):
             return vecs, vals
         axes = [list(v) for v in vecs]
         return self.convert_return(axes, labels), self.convert_return(list(vals), labels)
+
+    # -- two channels per cell (include/tissue_scan_cosignal.h; one pass over labels + both channels on the GPU)
+    def _channel_pair(self, a, b, thresholds=(0, 0)):
+        """ChannelPairStats of the channels `a`, `b` over this image: uploaded and reduced once per pair of array OBJECTS and
+        thresholds, like `_signal_stats`."""
+        thresholds = (int(thresholds[0]), int(thresholds[1]))
+        cache = getattr(self, "_pair_cache", None)
+        if cache is not None and cache[0] is a and cache[1] is b and cache[2] == thresholds:
+            return cache[3]
+        bb = np.asarray(b)
+        pair = self._resident_rows().signal_pair(bb if a is b else np.asarray(a), bb, thresholds)
+        self._pair_cache = (a, b, thresholds, pair)
+        return pair
+
+    def signal_ratio(self, a, b, labels=None):
+        """Per label the ratio sum(a) / sum(b) of two intensity images (uint8 / uint16 each, the image's shape) over the label's
+        voxels -- the read-out of a ratiometric reporter; NaN where sum(b) == 0.  Returned like volume().  Both channels lie on
+        this image's grid: one on another grid goes through resample_onto_grid(order=1) first (there is no `transform=` here:
+        the resample pass owns one result buffer)."""
+        labels = self.label_request(labels)
+        return self.convert_return(self._channel_pair(a, b).of_labels(labels, "ratio"), labels)
+
+    def signal_correlation(self, a, b, labels=None):
+        """Per label Pearson's correlation coefficient of the two intensity images over the label's voxels; NaN for a label of
+        fewer than two voxels or with a constant channel.  Returned like volume()."""
+        labels = self.label_request(labels)
+        return self.convert_return(self._channel_pair(a, b).of_labels(labels, "pearson"), labels)
+
+    def signal_colocalisation(self, a, b, thresholds, labels=None):
+        """Per label Manders' coefficients (M1, M2) for thresholds = (t_a, t_b): M1 the fraction of sum(a) that lies in voxels with
+        b > t_b, M2 the fraction of sum(b) in voxels with a > t_a.  One pair per label, returned like volume() (NPLIST: an array
+        [labels, 2])."""
+        labels = self.label_request(labels)
+        pair = self._channel_pair(a, b, thresholds)
+        values = np.stack([pair.of_labels(labels, "manders_m1"), pair.of_labels(labels, "manders_m2")], axis=1)
+        return self.convert_return(values if self.return_type == NPLIST else [tuple(v) for v in values.tolist()], labels)
 
     # -- exact histograms, medians and quantiles of a signal image (include/tissue_scan_sighist.h; radix select on the GPU)
     def signal_quantiles(self, signal, q, labels=None, method='linear', transform=None, voxelsize=None):
