@@ -163,6 +163,7 @@ void launch_max_label(hipStream_t s, const void* vol, int itemsize, uint64_t nvo
 // Each block owns a contiguous slot range: count its occupied slots, reserve output space with
 // ONE returning atomic per block (a single hot word sustains only ~88 atomics/us), then write.
 constexpr int COLLECT_PER_THREAD = 8;
+constexpr PairSlot FREE_SLOT = {EMPTY_KEY, {0ull, 0ull, 0ull}};
 // `publish`: host-mapped mirror of the flag words (+ cursor): written by a kernel whose predecessors have fixed them, so the
 // step needs no device-to-host copy (a blit kernel + a queue barrier) afterwards.
 __device__ __forceinline__ void publish_small(const uint32_t* small, uint32_t* publish, int nwords, int tid) {
@@ -179,16 +180,16 @@ __device__ __forceinline__ void pairs_collect_block(const PairTable& pt, uint64_
     const uint64_t cap = (uint64_t)pt.mask + 1;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const uint64_t lo = (uint64_t)block * (256 * COLLECT_PER_THREAD);
-    // the thread's keys are read ONCE, all loads in flight together (coalesced 8-byte reads), and kept in registers
-    uint64_t k[COLLECT_PER_THREAD];
+    // the thread's slots are read ONCE, whole (32 bytes: the key and the three counts), all loads in flight together, and kept in registers
+    PairSlot s[COLLECT_PER_THREAD];
     uint32_t mine = 0;
 #pragma unroll
     for (int i = 0; i < COLLECT_PER_THREAD; ++i) {
         const uint64_t h = lo + (uint64_t)i * 256 + tid;
-        k[i] = h < cap ? pt.keys[h] : EMPTY_KEY;
+        s[i] = h < cap ? pt.slots[h] : FREE_SLOT;
     }
 #pragma unroll
-    for (int i = 0; i < COLLECT_PER_THREAD; ++i) mine += k[i] != EMPTY_KEY;
+    for (int i = 0; i < COLLECT_PER_THREAD; ++i) mine += s[i].key != EMPTY_KEY;
     // wave inclusive scan, then block offsets
     uint32_t incl = mine;
 #pragma unroll
@@ -208,15 +209,14 @@ __device__ __forceinline__ void pairs_collect_block(const PairTable& pt, uint64_
     // emit and self-clean (order inside the list does not matter: the host getter sorts)
 #pragma unroll
     for (int i = 0; i < COLLECT_PER_THREAD; ++i) {
-        if (k[i] == EMPTY_KEY) continue;
+        if (s[i].key == EMPTY_KEY) continue;
         const uint64_t h = lo + (uint64_t)i * 256 + tid;
-        out_keys[pos] = k[i];
-        out_faces[3ull * pos + 0] = pt.faces[3 * h + 0];
-        out_faces[3ull * pos + 1] = pt.faces[3 * h + 1];
-        out_faces[3ull * pos + 2] = pt.faces[3 * h + 2];
+        out_keys[pos] = s[i].key;
+        out_faces[3ull * pos + 0] = s[i].f[0];
+        out_faces[3ull * pos + 1] = s[i].f[1];
+        out_faces[3ull * pos + 2] = s[i].f[2];
         ++pos;
-        pt.keys[h] = EMPTY_KEY;                              // leave the table clean for the next call
-        pt.faces[3 * h + 0] = 0; pt.faces[3 * h + 1] = 0; pt.faces[3 * h + 2] = 0;
+        pt.slots[h] = FREE_SLOT;                             // leave the table clean for the next call: one 32-byte store
     }
 }
 
@@ -376,8 +376,7 @@ __global__ void __launch_bounds__(256) pairs_clear_kernel(PairTable pt) {
     const uint64_t cap = (uint64_t)pt.mask + 1;
     for (uint64_t h = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; h < cap;
          h += (uint64_t)gridDim.x * blockDim.x) {
-        pt.keys[h] = EMPTY_KEY;
-        pt.faces[3 * h + 0] = 0; pt.faces[3 * h + 1] = 0; pt.faces[3 * h + 2] = 0;
+        pt.slots[h] = FREE_SLOT;
     }
 }
 

@@ -234,13 +234,8 @@ __device__ __forceinline__ void scan_label_add(const SweepArgs* kp, LDS& S,
             atomicMax(box + 3, mxa); atomicMax(box + 4, mxb); atomicMax(box + 5, mxc);
         }
     } else {                                       // table full: straight to the global rows
-        const SweepArgs* A = cold_args(kp);
-        LocalSums Lc;
-        Lc.n = L.n; Lc.sa = L.sa; Lc.sb = L.sb; Lc.sc = L.sc; Lc.saa = L.saa; Lc.sab = L.sab;
-        Lc.sac = L.sac; Lc.sbb = L.sbb; Lc.sbc = L.sbc; Lc.scc = L.scc;
-        uint32_t bx[6];
-        bx[0] = mna; bx[1] = mnb; bx[2] = mnc; bx[3] = mxa; bx[4] = mxb; bx[5] = mxc;
-        label_spill_global(A->sums, A->boxes, A->flags, A->max_label, label, &Lc, S.frame[0], S.frame[1], S.frame[2], bx);
+        label_spill_global(cold_args(kp), label, L.n, L.sa, L.sb, L.sc, L.saa, L.sab, L.sac, L.sbb, L.sbc, L.scc,
+                           S.frame[0], S.frame[1], S.frame[2], pack_box3(mna, mnb, mnc), pack_box3(mxa, mxb, mxc));
     }
 }
 
@@ -603,13 +598,8 @@ __device__ __forceinline__ void drain_run_group(const SweepArgs* kp, LDS& S, WLD
     if (spill) {              // (wave-uniform: the probe limit was reached with lookups still open)
         if (ppend) { const SweepArgs* A = cold_args(kp); pair_spill_global(A->pairs, A->flags, plo, phi, 2u, 1u); }
         if (lpend) {
-            const SweepArgs* A = cold_args(kp);
-            LocalSums Lc;
-            Lc.n = L.n; Lc.sa = L.sa; Lc.sb = L.sb; Lc.sc = L.sc; Lc.saa = L.saa; Lc.sab = L.sab;
-            Lc.sac = L.sac; Lc.sbb = L.sbb; Lc.sbc = L.sbc; Lc.scc = L.scc;
-            uint32_t bx[6];
-            bx[0] = al; bx[1] = bl; bx[2] = c0; bx[3] = al; bx[4] = bl; bx[5] = kk - 1u;
-            label_spill_global(A->sums, A->boxes, A->flags, A->max_label, label, &Lc, S.frame[0], S.frame[1], S.frame[2], bx);
+            label_spill_global(cold_args(kp), label, L.n, L.sa, L.sb, L.sc, L.saa, L.sab, L.sac, L.sbb, L.sbc, L.scc,
+                               S.frame[0], S.frame[1], S.frame[2], pack_box3(al, bl, c0), pack_box3(al, bl, kk - 1u));
         }
     }
     rcount = rem;

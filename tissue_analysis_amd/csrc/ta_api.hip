@@ -23,11 +23,10 @@ int fail(int code, const char* fmt, ...) {
 namespace {
 
 int ensure_pair_table(ta_ctx* c, int log2cap) {
-    if (c->pair_log2 == log2cap && c->pkeys.p) return TA_OK;
+    if (c->pair_log2 == log2cap && c->pslots.p) return TA_OK;
     const uint64_t cap = 1ull << log2cap;
     int rc;
-    if ((rc = c->pkeys.reserve(cap * 8)) != TA_OK) return rc;
-    if ((rc = c->pfaces.reserve(cap * 24)) != TA_OK) return rc;
+    if ((rc = c->pslots.reserve(cap * sizeof(ta::PairSlot))) != TA_OK) return rc;
     if ((rc = c->out_keys.reserve(cap * 8)) != TA_OK) return rc;
     if ((rc = c->out_faces.reserve(cap * 24)) != TA_OK) return rc;
     c->pair_log2 = log2cap;
@@ -424,7 +423,7 @@ TA_API int ta_ctx_destroy(ta_ctx* c) {
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     c->owned_vol.release(); c->own_sums.release(); c->own_boxes.release();
-    c->pkeys.release(); c->pfaces.release(); c->out_keys.release(); c->out_faces.release();
+    c->pslots.release(); c->out_keys.release(); c->out_faces.release();
     c->small.release();
     c->hot_rows.release(); c->sort_buf.release(); c->h_pairs.release();
     c->walls.release(); c->ids.release(); c->shape.release();
@@ -521,7 +520,7 @@ TA_API int ta_ctx_get_option(ta_ctx* c, int key, int64_t* value) {
                 c->shape.density >= WIDE_SHORTER_TILES_DENSITY && planes > 28) planes = 28;      // (the rule of run_extract)
             *value = planes; return TA_OK;
         }
-        case TA_OPT_PAIR_SLOTS: *value = c->pkeys.p ? c->pair_log2 : c->opt_pair_log2; return TA_OK;
+        case TA_OPT_PAIR_SLOTS: *value = c->pslots.p ? c->pair_log2 : c->opt_pair_log2; return TA_OK;
         default: return fail(TA_EINVAL, "unknown option key %d", key);
     }
 }
@@ -754,8 +753,8 @@ TA_API int ta_extract(ta_ctx* c, uint32_t feature_mask, uint32_t max_label) {
     {
         const bool adj = feature_mask & TA_F_ADJACENCY;
         // never below a size the table has already grown to (a fixed TA_OPT_PAIR_SLOTS is a starting size)
-        int want = c->opt_pair_log2 ? std::max(c->opt_pair_log2, c->pkeys.p ? c->pair_log2 : 0)
-                                    : std::max(c->pkeys.p ? c->pair_log2 : 4, adj ? auto_pair_log2(max_label) : 4);
+        int want = c->opt_pair_log2 ? std::max(c->opt_pair_log2, c->pslots.p ? c->pair_log2 : 0)
+                                    : std::max(c->pslots.p ? c->pair_log2 : 4, adj ? auto_pair_log2(max_label) : 4);
         if ((rc = ensure_pair_table(c, want)) != TA_OK) return rc;
     }
     c->extracted = true;

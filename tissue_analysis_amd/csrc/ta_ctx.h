@@ -364,7 +364,7 @@ struct ta_ctx {
     uint32_t max_label = 0;
 
     // adjacency
-    DevBuf pkeys, pfaces, out_keys, out_faces, small;   // small: flags[NFLAGS] | cursor | maxlabel
+    DevBuf pslots, out_keys, out_faces, small;         // small: flags[NFLAGS] | cursor | maxlabel
     DevBuf hot_rows;                                    // [workgroups][16] private rows of the hot label
     DevBuf sort_buf;                                    // scratch of ta_adjacency_get's device sort (kept between calls)
     int pair_log2 = 0;                                  // current table log2 capacity
@@ -565,8 +565,8 @@ inline uint32_t* cursor_dev(ta_ctx* c) { return (uint32_t*)c->small.p + ta::NFLA
 inline uint32_t* maxlab_dev(ta_ctx* c) { return (uint32_t*)c->small.p + ta::NFLAGS + 1; }
 inline ta::PairTable pair_table(ta_ctx* c) {
     ta::PairTable pt;
-    pt.keys = (uint64_t*)c->pkeys.p;
-    pt.faces = (uint64_t*)c->pfaces.p;
+    pt.slots = (ta::PairSlot*)c->pslots.p;       // (device allocations are aligned far beyond a slot's 32 bytes)
+    pt.unused = 0;
     pt.mask = (uint32_t)((1ull << c->pair_log2) - 1);
     return pt;
 }

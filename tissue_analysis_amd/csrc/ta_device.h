@@ -29,9 +29,14 @@ constexpr uint64_t XSTATUS_RANGE = 1, XSTATUS_PAIR_OVERFLOW = 2;
 // of the table initialisation (ta_distance.h), and the launches of the column kernel along both axes together.
 struct DistanceLaunch { uint32_t row_groups = 0, voxel_groups = 0, init_groups = 0, column_launches = 0; };
 
-struct PairTable {           // device-global open-addressing hash: key = lo<<32|hi
-    uint64_t* keys;          // [cap], EMPTY_KEY when free
-    uint64_t* faces;         // [cap][3] per memory axis
+// One slot of the adjacency hash is one 32-byte sector of one cache line: the key read of a probe brings the counts' line to where
+// the adds that follow are performed, the collect reads a slot with one load and cleans it with one store.  (The counts stay u64:
+// a pair's faces along one axis are only bounded by the voxel count, which passes 2^32 on a 2048^3 volume.)
+struct alignas(32) PairSlot { uint64_t key; uint64_t f[3]; };     // key = lo<<32|hi, EMPTY_KEY when free; faces per memory axis
+static_assert(sizeof(PairSlot) == 32, "a slot is one 32-byte sector");
+struct PairTable {           // device-global open-addressing hash
+    PairSlot* slots;         // [cap]
+    uint64_t unused;         // (where the second array's pointer was: every word of the sweep kernels' argument block keeps its offset)
     uint32_t mask;           // cap - 1 (cap is a power of two)
 };
 
@@ -79,19 +84,19 @@ __device__ __forceinline__ void pair_add_global_from(const PairTable& pt, uint32
     const uint64_t key = ((uint64_t)lo << 32) | hi;
     for (uint32_t probe = 0; probe < 512u; ++probe) {
         if (k == EMPTY_KEY) {
-            k = atomicCAS((unsigned long long*)&pt.keys[h], (unsigned long long)EMPTY_KEY,
+            k = atomicCAS((unsigned long long*)&pt.slots[h].key, (unsigned long long)EMPTY_KEY,
                           (unsigned long long)key);
             if (k == EMPTY_KEY) k = key;
         }
         if (k == key) {
-            unsigned long long* f = (unsigned long long*)&pt.faces[3ull * h];
+            unsigned long long* f = (unsigned long long*)pt.slots[h].f;      // (the three adds go out back to back, to one sector)
             if (f0) flush_add(f + 0, (unsigned long long)f0);
             if (f1) flush_add(f + 1, (unsigned long long)f1);
             if (f2) flush_add(f + 2, (unsigned long long)f2);
             return;
         }
         h = (h + 1) & pt.mask;
-        k = __hip_atomic_load(&pt.keys[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        k = __hip_atomic_load(&pt.slots[h].key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     atomicOr(&flags[FLAG_PAIR_OVERFLOW], 1u);
 }
@@ -101,14 +106,14 @@ __device__ inline void pair_add_global(const PairTable& pt, uint32_t lo, uint32_
     const uint64_t key = ((uint64_t)lo << 32) | hi;
     uint32_t h = hash_pair(lo, hi) & pt.mask;
     for (uint32_t probe = 0; probe < 512u; ++probe) {
-        uint64_t k = __hip_atomic_load(&pt.keys[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        uint64_t k = __hip_atomic_load(&pt.slots[h].key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (k == EMPTY_KEY) {
-            k = atomicCAS((unsigned long long*)&pt.keys[h], (unsigned long long)EMPTY_KEY,
+            k = atomicCAS((unsigned long long*)&pt.slots[h].key, (unsigned long long)EMPTY_KEY,
                           (unsigned long long)key);
             if (k == EMPTY_KEY) k = key;
         }
         if (k == key) {
-            unsigned long long* f = (unsigned long long*)&pt.faces[3ull * h];
+            unsigned long long* f = (unsigned long long*)pt.slots[h].f;
             if (f0) atomicAdd(f + 0, (unsigned long long)f0);
             if (f1) atomicAdd(f + 1, (unsigned long long)f1);
             if (f2) atomicAdd(f + 2, (unsigned long long)f2);

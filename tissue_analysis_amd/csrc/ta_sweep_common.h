@@ -104,19 +104,26 @@ __device__ __forceinline__ void local_to_global(const LocalSums& L, uint64_t A0,
 }
 
 // ---- rare spill paths, kept out of line so they do not bloat the hot loops ------------------
-static __device__ __noinline__ void label_spill_global(uint64_t* sums, int32_t* boxes, uint32_t* flags,
-                                                uint32_t max_label, uint32_t label, const LocalSums* L,
-                                                uint64_t A0, uint64_t B0, uint64_t C0, const uint32_t* box) {
+// (Everything travels in registers: a struct of more than 64 bytes, or a pointer to a local, is passed through the stack, and the one
+//  stack frame of a sweep kernel -- 112 bytes a lane -- was this function's.  So: the kernel's arguments by their address, the ten sums as
+//  ten words, the tile-local box -- a <= 64, b < 16, c < 512 -- as two: mins / maxs = a | b << 8 | c << 16.  28 argument registers.)
+__device__ __forceinline__ uint32_t pack_box3(uint32_t a, uint32_t b, uint32_t c) { return a | (b << 8) | (c << 16); }
+static __device__ __noinline__ void label_spill_global(const SweepArgs* A, uint32_t label, uint64_t n, uint64_t sa, uint64_t sb, uint64_t sc,
+                                                uint64_t saa, uint64_t sab, uint64_t sac, uint64_t sbb, uint64_t sbc, uint64_t scc,
+                                                uint32_t A0, uint32_t B0, uint32_t C0, uint32_t mins, uint32_t maxs) {
+    uint32_t* const flags = A->flags;
     atomicAdd(&flags[FLAG_LDS_LABEL_SPILL], 1u);
-    if (label > max_label) { atomicOr(&flags[FLAG_RANGE], 1u); return; }
+    if (label > A->max_label) { atomicOr(&flags[FLAG_RANGE], 1u); return; }
+    const LocalSums L = {n, sa, sb, sc, saa, sab, sac, sbb, sbc, scc};
     uint64_t g[NSUM];
-    local_to_global(*L, A0, B0, C0, g);
-    unsigned long long* row = (unsigned long long*)&sums[(uint64_t)label * NSUM];
+    local_to_global(L, A0, B0, C0, g);
+    unsigned long long* row = (unsigned long long*)&A->sums[(uint64_t)label * NSUM];
+#pragma unroll
     for (int k = 0; k < NSUM; ++k) if (g[k]) atomicAdd(row + k, (unsigned long long)g[k]);
-    int32_t* gb = &boxes[(uint64_t)label * NBOX];
-    atomicMin(gb + 0, (int32_t)(A0 + box[0])); atomicMin(gb + 3, -(int32_t)(A0 + box[3]));
-    atomicMin(gb + 1, (int32_t)(B0 + box[1])); atomicMin(gb + 4, -(int32_t)(B0 + box[4]));
-    atomicMin(gb + 2, (int32_t)(C0 + box[2])); atomicMin(gb + 5, -(int32_t)(C0 + box[5]));
+    int32_t* gb = &A->boxes[(uint64_t)label * NBOX];
+    atomicMin(gb + 0, (int32_t)(A0 + (mins & 255u)));         atomicMin(gb + 3, -(int32_t)(A0 + (maxs & 255u)));
+    atomicMin(gb + 1, (int32_t)(B0 + ((mins >> 8) & 255u)));  atomicMin(gb + 4, -(int32_t)(B0 + ((maxs >> 8) & 255u)));
+    atomicMin(gb + 2, (int32_t)(C0 + (mins >> 16)));          atomicMin(gb + 5, -(int32_t)(C0 + (maxs >> 16)));
 }
 
 static __device__ __noinline__ void pair_spill_global(PairTable pt, uint32_t* flags, uint32_t lo, uint32_t hi,
@@ -205,6 +212,8 @@ __device__ __forceinline__ void flush_tables(const SweepArgs& A, LDS& S, const i
     // different row (64 requests, ten instructions a label); lane = (label, word) sends 64 consecutive words of ~6 rows.  The sums go
     // through LDS for that: the pair table's keys and counts are read into registers first (two pairs a thread at most; their home
     // slots' global reads are in flight from then on), the sums are staged where the pair table was, and the pairs' adds go last.
+    // (A global slot is one 32-byte sector, key and counts together: the early read of the key also brings the line the three adds
+    //  go to.  Its 8 bytes are all that is loaded -- the flush needs no count -- and a neighbour's key is never among a slot's bytes.)
     constexpr int NS = MOM2 ? NSUM : 4;
     static_assert(!ADJ || (PSLOTS <= 2 * NT && (size_t)LSLOTS * NSUM * 8 <= sizeof(S.pkeys) + sizeof(S.pcnt)),
                   "the flush takes two pairs a thread and stages the labels' sums where the pair table was");
@@ -221,7 +230,7 @@ __device__ __forceinline__ void flush_tables(const SweepArgs& A, LDS& S, const i
                 const int i = plist[j];
                 pkey[q] = S.pkeys[i];
                 ghome[q] = hash_pair((uint32_t)(pkey[q] >> 32), (uint32_t)pkey[q]) & A.pairs.mask;
-                gkey[q] = __hip_atomic_load(&A.pairs.keys[ghome[q]], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                gkey[q] = __hip_atomic_load(&A.pairs.slots[ghome[q]].key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 pf[q][0] = S.pcnt[i * 3 + 0]; pf[q][1] = S.pcnt[i * 3 + 1]; pf[q][2] = S.pcnt[i * 3 + 2];
             }
 #endif

@@ -54,6 +54,10 @@
 //   ... for the full tiles of uint16 volumes too (with the predicated stores, C2 0.137 -> 0.134 ms).  Without: 0.143 - 0.144 against 0.140 - 0.143 ms.
 //   Eight voxels a lane: one group of 64 faces leaves at the top of a plane from 64 on.  From 128 on only: equal time, 29 % instead of 7 %
 //   of C4's face records through the in-plane drain.
+//   The global pair table is one array of 32-byte slots {key, f0, f1, f2}.  Keys u64[cap] and counts u64[cap][3] in two arrays: sweep
+//   0.976 / 1.26 against 0.968 / 1.27 ms (inside the noise), the collect 0.027 / 0.037 against 0.021 / 0.027 ms (profiles/pair_slots_ab.txt).
+//   The out-of-line label spill takes its sums and box in registers.  By pointer to a stack frame (112 bytes of scratch a lane in every
+//   sweep kernel): equal time, 0.968 / 1.27 against 0.966 / 1.25 ms.
 
 // ---- ablations (results WRONG by construction; only the time matters) and instrumentation ---------------------------------------
 //   TA_ABLATE = 1 records produced and stored, nothing consumed; 2 = placed, not stored; 3 = not even placed
