@@ -15,76 +15,38 @@ profiles/junctions_bench.jsonl.
 The parent's implementation of the same 2 x 2 x 2 walk is the corner-count kernel of the mesh extraction: take its time from
     rocprofv3 --kernel-trace --stats -- python scripts/bench_mesh.py --configs C4 --reps 3 --no-cpu
 in a process of its own."""
-import argparse
-import json
-import os
 import statistics
-import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
-from tissue_analysis_amd import synth  # noqa: E402
-from tissue_analysis_amd import device as dev  # noqa: E402
-
-TBS = 8e12
+import featbench as fb
 
 
-def run(name, dims, dtype, n_cells, seed, reps):
-    import torch
-    dtype = np.dtype(dtype)
-    ctx = dev.torch_context(0)
-    v, _ = dev.synth_slab(ctx, dims, dtype, n_cells, seed)
-    torch.cuda.synchronize()
-    ctx.set_volume_device(v.data_ptr(), dtype.itemsize, v.shape, keep=v)
-    vol_bytes = v.numel() * v.element_size()
-    probe_ms = ctx.read_probe(v.data_ptr(), vol_bytes, repeats=5)
-    for _ in range(3):
-        ctx.junctions_extract()
-        ctx.junctions_size()
-    walks, after = [], []
-    for _ in range(reps):
-        ctx.junctions_extract()
-        E, V, degenerate = ctx.junctions_size()
-        a, b = ctx.junctions_timing()
-        walks.append(a)
-        after.append(b)
-    (el, en, es), (vl, vn, vs), _ = ctx.junctions_get()
+def run(cfg, a):
+    with fb.resident(cfg) as (ctx, v, _):
+        vol_bytes = v.numel() * v.element_size()
+        probe_ms, probe_bps = fb.read_probe(ctx, v)
+        last = {}
+
+        def junctions():
+            ctx.junctions_extract()
+            last["size"] = ctx.junctions_size()
+
+        walks, after = zip(*fb.timed(junctions, ctx.junctions_timing, a.reps))
+        E, V, degenerate = last["size"]
+        (el, en, es), (vl, vn, vs), _ = ctx.junctions_get()
     k = statistics.median(walks)
     nbytes = 2 * vol_bytes
-    blocks = int(np.prod([max(int(d) - 1, 1) for d in dims]))
-    line = dict(config=name, dims=list(dims), labels=dtype.name, pass_ms=round(k, 4), pass_ms_min=round(min(walks), 4),
-                pass_ms_max=round(max(walks), 4), after_ms=round(statistics.median(after), 4), reps=reps, blocks=blocks,
-                records3=int(en.sum()), records4=int(vn.sum()), edges=int(E), vertices=int(V), degenerate=int(degenerate),
-                bytes=nbytes, tb_per_s=round(nbytes / (k * 1e-3) / 1e12, 3), frac_8tbs=round(nbytes / (k * 1e-3) / TBS, 4),
-                read_probe_ms=round(probe_ms, 4), read_probe_tbs=round(vol_bytes / (probe_ms * 1e-3) / 1e12, 3),
-                pass_over_probe=round(k / probe_ms, 3))
-    ctx.close()
-    del v
-    torch.cuda.empty_cache()
-    return line
+    blocks = int(np.prod([max(int(d) - 1, 1) for d in cfg.dims]))
+    return dict(config=cfg.name, dims=list(cfg.dims), labels=cfg.dtype.name, **fb.spread("pass_ms", walks),
+                after_ms=round(statistics.median(after), 4), reps=a.reps, blocks=blocks, records3=int(en.sum()), records4=int(vn.sum()),
+                edges=int(E), vertices=int(V), degenerate=int(degenerate), bytes=nbytes, tb_per_s=round(nbytes / (k * 1e-3) / 1e12, 3),
+                frac_8tbs=round(nbytes / (k * 1e-3) / fb.TBS, 4), read_probe_ms=round(probe_ms, 4),
+                read_probe_tbs=round(probe_bps / 1e12, 3), pass_over_probe=round(k / probe_ms, 3))
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=30)
-    ap.add_argument("--configs", default="C4,512^3")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "junctions_bench.jsonl"))
-    a = ap.parse_args()
-    lines = []
-    for name in a.configs.split(","):
-        if name == "C4":
-            c = synth.CONFIGS["C4"]
-            lines.append(run("C4", c["dims"], c["dtype"], c["n_cells"], c["seed"], a.reps))
-        else:
-            c = synth.CONFIGS["C2"]
-            lines.append(run("512^3", c["dims"], "uint16", c["n_cells"], c["seed"], a.reps))
-        print(json.dumps(lines[-1]), flush=True)
-    with open(a.out, "w") as f:
-        for d in lines:
-            f.write(json.dumps(d) + "\n")
+    fb.main(run, reps=30, configs="C4,512^3", out="profiles/junctions_bench.jsonl", mode="w")
 
 
 if __name__ == "__main__":

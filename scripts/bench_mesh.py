@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Cell-mesh throughput (include/tissue_scan_mesh.h): one JSON line per configuration.
 
-    python scripts/bench_mesh.py [--reps 10] [--configs C4,512^3] [--no-cpu]
+    python scripts/bench_mesh.py [--reps 10] [--configs C4,512^3] [--no-cpu] [--out FILE]
 
   device_ms        median over --reps extractions of ta_mesh_timing: the count kernels + the emit / sort / resolve kernels
                    (the one read-back of the totals between them is not counted)
@@ -10,8 +10,7 @@
   model_bytes      bytes read plus written by all kernels (byte model below); frac_8tbs = model_bytes / device_ms against 8 TB/s
 Configurations: C4 (1024^3 uint32, 50k seeds) and 512^3 uint16 (5k seeds), each at sub_factor 1 and 4 and a labels subset of
 1 % at sub_factor 1; and, for context, the NumPy restatement (tests/mesh_reference.py) on the central 256^3 crop of C4 on one CPU core."""
-import argparse
-import json
+import ctypes
 import os
 import statistics
 import sys
@@ -19,13 +18,11 @@ import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import featbench as fb
+from tissue_analysis_amd import _capi
 
-from tissue_analysis_amd import _capi, synth  # noqa: E402
-from tissue_analysis_amd import device as dev  # noqa: E402
-
-TBS = 8e12
+CASES = (("all cells", 1, None), ("all cells", 4, None), ("1% of cells", 1, 0.01))
+CROP = []                       # C4's central 256^3, for the CPU line
 
 
 def byte_model(dims, s, L, F, V, key_bits):
@@ -49,44 +46,31 @@ def byte_model(dims, s, L, F, V, key_bits):
     )
 
 
-def run(name, dims, ldtype, n_cells, seed, reps, cases):
-    ldtype = np.dtype(ldtype)
-    ctx = dev.torch_context(0)
-    vol, L = dev.synth_slab(ctx, dims, ldtype, n_cells, seed)
-    ctx.set_volume_device(vol.data_ptr(), ldtype.itemsize, vol.shape, keep=vol)
-    ctx.extract(_capi.F_ALL, L)
-    count = ctx.labels()[0]
-    present = np.flatnonzero(count)
-    key_bits = max(1, int(L).bit_length())
-    out = []
-    for what, s, frac in cases:
-        wanted = None
-        nreq = present.size
-        if frac is not None:
-            pick = present[1::max(1, int(round(1 / frac)))]
-            wanted = np.zeros(L + 1, dtype=np.uint8)
-            wanted[pick] = 1
-            nreq = pick.size
-        ms = []
-        for i in range(reps + 2):
-            _check_extract(ctx, s, wanted)
-            if i >= 2:
-                ms.append(ctx.mesh_timing())
-        C, V, T = _size(ctx)
-        F = T // 2
-        model = byte_model(dims, s, ldtype.itemsize, F, V, key_bits)
-        mb = sum(model.values())
-        k = statistics.median(ms)
-        out.append(dict(config=name, what=what, dims=list(dims), labels=ldtype.name, sub_factor=s, cells_requested=int(nreq),
-                        cells=int(C), vertices=int(V), triangles=int(T), device_ms=round(k, 4), device_ms_min=round(min(ms), 4),
-                        reps=reps, out_bytes=int(8 * V + 12 * T + 8 * T), model_bytes=int(mb),
-                        frac_8tbs=round(mb / (k * 1e-3) / TBS, 4), model_by_kernel=model))
-    crop = vol[384:640, 384:640, 384:640].cpu().numpy().view(ldtype) if name == "C4" else None
-    ctx.close()
-    del vol
-    import torch
-    torch.cuda.empty_cache()
-    return out, crop
+def run(cfg, a):
+    with fb.resident(cfg) as (ctx, vol, L):
+        ctx.extract(_capi.F_ALL, L)
+        count = ctx.labels()[0]
+        present = np.flatnonzero(count)
+        key_bits = max(1, int(L).bit_length())
+        for what, s, frac in CASES:
+            wanted = None
+            nreq = present.size
+            if frac is not None:
+                pick = present[1::max(1, int(round(1 / frac)))]
+                wanted = np.zeros(L + 1, dtype=np.uint8)
+                wanted[pick] = 1
+                nreq = pick.size
+            ms = fb.timed(lambda: _check_extract(ctx, s, wanted), ctx.mesh_timing, a.reps, warmup=2)
+            C, V, T = _size(ctx)
+            F = T // 2
+            model = byte_model(cfg.dims, s, cfg.dtype.itemsize, F, V, key_bits)
+            mb = sum(model.values())
+            yield dict(config=cfg.name, what=what, dims=list(cfg.dims), labels=cfg.dtype.name, sub_factor=s, cells_requested=int(nreq),
+                       cells=int(C), vertices=int(V), triangles=int(T), **fb.spread("device_ms", ms, ("min",)), reps=a.reps,
+                       out_bytes=int(8 * V + 12 * T + 8 * T), model_bytes=int(mb),
+                       frac_8tbs=round(mb / (statistics.median(ms) * 1e-3) / fb.TBS, 4), model_by_kernel=model)
+        if cfg.name == "C4":
+            CROP[:] = [vol[384:640, 384:640, 384:640].cpu().numpy().view(cfg.dtype)]
 
 
 def _check_extract(ctx, s, wanted):
@@ -96,39 +80,28 @@ def _check_extract(ctx, s, wanted):
 
 
 def _size(ctx):
-    import ctypes
     C, V, T = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
     _capi._check(ctx._lib.ta_mesh_size(ctx._h, ctypes.byref(C), ctypes.byref(V), ctypes.byref(T)))
     return C.value, V.value, T.value
 
 
+def cpu_line(a):
+    if not CROP or a.no_cpu:
+        return []
+    sys.path.insert(0, os.path.join(fb.ROOT, "tests"))
+    import mesh_reference
+    crop = CROP.pop()                                 # taken: a later call in this process starts without a crop
+    labels = np.unique(crop)[1:]
+    t0 = time.perf_counter()
+    r = mesh_reference.mesh(crop, labels=labels)
+    cpu = (time.perf_counter() - t0) * 1e3
+    return dict(config="C4 central crop 256^3", what="NumPy restatement (tests/mesh_reference.py), 1 CPU core",
+                cells=int(labels.size), triangles=int(len(r["triangles"])), cpu_ms=round(cpu, 1))
+
+
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=10)
-    ap.add_argument("--configs", default="C4,512^3")
-    ap.add_argument("--no-cpu", action="store_true")
-    a = ap.parse_args()
-    cases = (("all cells", 1, None), ("all cells", 4, None), ("1% of cells", 1, 0.01))
-    lines, crop = [], None
-    for name in a.configs.split(","):
-        if name == "C4":
-            c = synth.CONFIGS["C4"]
-            got, crop = run("C4", c["dims"], c["dtype"], c["n_cells"], c["seed"], a.reps, cases)
-        else:
-            c = synth.CONFIGS["C2"]
-            got, _ = run("512^3", c["dims"], "uint16", c["n_cells"], c["seed"], a.reps, cases)
-        for d in got:
-            print(json.dumps(d), flush=True)
-        lines += got
-    if crop is not None and not a.no_cpu:
-        sys.path.insert(0, os.path.join(ROOT, "tests"))
-        import mesh_reference
-        labels = np.unique(crop)[1:]
-        t0 = time.perf_counter()
-        r = mesh_reference.mesh(crop, labels=labels)
-        cpu = (time.perf_counter() - t0) * 1e3
-        print(json.dumps(dict(config="C4 central crop 256^3", what="NumPy restatement (tests/mesh_reference.py), 1 CPU core",
-                              cells=int(labels.size), triangles=int(len(r["triangles"])), cpu_ms=round(cpu, 1))))
+    fb.main(run, reps=10, configs="C4,512^3", out=None, mode="w", after=cpu_line,
+            extra_args=[("--no-cpu", dict(action="store_true"))])
 
 
 if __name__ == "__main__":

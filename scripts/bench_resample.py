@@ -2,7 +2,7 @@
 """Resample-pass throughput (include/tissue_scan_resample.h): one JSON line per configuration and map, also written to
 profiles/resample_bench.jsonl.
 
-    python scripts/bench_resample.py [--reps 20] [--lut-stats kernel_stats.csv] [--out profiles/resample_bench.jsonl]
+    python scripts/bench_resample.py [--reps 20] [--configs 512^3,C4] [--lut-stats kernel_stats.csv] [--out profiles/resample_bench.jsonl]
     rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python scripts/bench_resample.py --lut-only
 
   kernel_ms        median of the gather kernel's HIP-event durations (ta_resample_timing) over --reps passes, after 3 warm-up passes
@@ -16,23 +16,18 @@ profiles/resample_bench.jsonl.
   read_probe_ms    ta_read_probe on the label buffer in this run (read only), for context
 Configurations: 512^3 uint16 and 1024^3 uint32 targets from equal-size sources (a second frame of the synthetic tissue), nearest
 neighbour; identity, a 10 degree rotation about each axis through the centre, a 2 x zoom; 512^3 also trilinear (uint16)."""
-import argparse
 import csv
 import json
-import os
 import statistics
-import sys
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import featbench as fb
+from tissue_analysis_amd import _capi
+from tissue_analysis_amd import device as dev
 
-from tissue_analysis_amd import _capi, synth  # noqa: E402
-from tissue_analysis_amd import device as dev  # noqa: E402
-
-CONFIGS = (("512^3", "C2", "uint16"), ("1024^3", "C4", "uint32"))
+NAMES = {"C4": "1024^3"}        # the `config` of the lines where it is not the configuration's own name
 
 
 def about_centre(linear, dims):
@@ -73,85 +68,55 @@ def lut_stats(path):
     return out
 
 
-def volumes(cfg, dtype):
-    import torch
-    c = synth.CONFIGS[cfg]
-    ctx = dev.torch_context(0)
-    labels, _ = dev.synth_slab(ctx, c["dims"], dtype, c["n_cells"], c["seed"])
-    torch.cuda.synchronize()
-    ctx.set_volume_device(labels.data_ptr(), np.dtype(dtype).itemsize, labels.shape, keep=labels)
-    return ctx, labels, c
-
-
-def lut_only(reps):
-    """The LUT sweep alone, `reps` calls a configuration: for a kernel trace around this process."""
-    for name, cfg, dtype in CONFIGS:
-        ctx, labels, c = volumes(cfg, dtype)
-        lut = np.arange(c["n_cells"] + 2, dtype=dtype)
-        like = np.empty(tuple(c["dims"]), dtype=dtype)
+def lut_only(cfg, reps):
+    """The LUT sweep alone, `reps` calls: for a kernel trace around this process.  Its line is printed, not kept."""
+    with fb.resident(cfg) as (ctx, labels, _):
+        lut = np.arange(cfg.n_cells + 2, dtype=cfg.dtype)
+        like = np.empty(cfg.dims, dtype=cfg.dtype)
         wall = []
         for _ in range(reps):
             t0 = time.perf_counter()
             ctx.map_labels(lut, 0, like)
             wall.append((time.perf_counter() - t0) * 1e3)
-        print(json.dumps(dict(config=name, what="ta_volume_map, whole call (allocation, sweep, copy to the host)", wall_ms=round(min(wall), 2))))
-        ctx.close()
-        del labels
+    print(json.dumps(dict(config=NAMES.get(cfg.name, cfg.name), what="ta_volume_map, whole call (allocation, sweep, copy to the host)",
+                          wall_ms=round(min(wall), 2))))
 
 
-def run(name, cfg, dtype, order, reps, lut):
+def run(cfg, a, order=_capi.RS_NEAREST):
     import torch
-    dtype = np.dtype(dtype)
-    ctx, labels, c = volumes(cfg, dtype)
-    dims = tuple(c["dims"])
-    src, _ = dev.synth_slab(ctx, dims, dtype, c["n_cells"], c["seed"] + 100)
-    torch.cuda.synchronize()
-    nbytes_vol = int(np.prod(dims)) * dtype.itemsize
-    probe_ms = ctx.read_probe(labels.data_ptr(), nbytes_vol, repeats=5)
-    ctx.set_resample_source_device(src.data_ptr(), dtype.itemsize, dims, keep=src)
-    y = lut.get(dtype.name)
-    lines = []
-    for what, A in maps(dims):
-        for _ in range(3):
-            ctx.resample_extract(A, order)
-            ctx.synchronize()
-        ms = []
-        for _ in range(reps):
-            ctx.resample_extract(A, order)
-            ms.append(ctx.resample_timing())
-        k = statistics.median(ms)
-        d = ctx.resample_debug()
-        lines.append(dict(config=name, dtype=dtype.name, mode="linear" if order else "nearest", map=what, kernel_ms=round(k, 4),
-                          kernel_ms_min=round(min(ms), 4), kernel_ms_max=round(max(ms), 4), reps=reps, outside=ctx.resample_outside(),
-                          bytes=2 * nbytes_vol, gb_per_s=round(2 * nbytes_vol / (k * 1e-3) / 1e9, 1),
-                          lut_sweep_ms=None if y is None else round(y["ms"], 4), lut_sweep_calls=None if y is None else y["calls"],
-                          ratio_to_lut=None if y is None else round(k / y["ms"], 3), read_probe_ms=round(probe_ms, 4),
-                          tiles_per_group=d["tiles_per_group"], groups=d["groups"], vector=d["vector"]))
-        print(json.dumps(lines[-1]), flush=True)
-    ctx.close()
-    del labels, src
-    torch.cuda.empty_cache()
-    return lines
+    if a.lut_only:
+        lut_only(cfg, min(a.reps, 5))
+        return
+    y = lut_stats(a.lut_stats).get(cfg.dtype.name)
+    with fb.resident(cfg) as (ctx, labels, _):
+        src, _ = dev.synth_slab(ctx, cfg.dims, cfg.dtype, cfg.n_cells, cfg.seed + 100)
+        torch.cuda.synchronize()
+        nbytes_vol = int(np.prod(cfg.dims)) * cfg.dtype.itemsize
+        probe_ms, _ = fb.read_probe(ctx, labels)
+        ctx.set_resample_source_device(src.data_ptr(), cfg.dtype.itemsize, cfg.dims, keep=src)
+        for what, A in maps(cfg.dims):
+            for _ in range(3):
+                ctx.resample_extract(A, order)
+                ctx.synchronize()
+            ms = fb.timed(lambda: ctx.resample_extract(A, order), ctx.resample_timing, a.reps, warmup=0)
+            k = statistics.median(ms)
+            d = ctx.resample_debug()
+            yield dict(config=NAMES.get(cfg.name, cfg.name), dtype=cfg.dtype.name, mode="linear" if order else "nearest", map=what,
+                       **fb.spread("kernel_ms", ms), reps=a.reps, outside=ctx.resample_outside(), bytes=2 * nbytes_vol,
+                       gb_per_s=round(2 * nbytes_vol / (k * 1e-3) / 1e9, 1),
+                       lut_sweep_ms=None if y is None else round(y["ms"], 4), lut_sweep_calls=None if y is None else y["calls"],
+                       ratio_to_lut=None if y is None else round(k / y["ms"], 3), read_probe_ms=round(probe_ms, 4),
+                       tiles_per_group=d["tiles_per_group"], groups=d["groups"], vector=d["vector"])
+
+
+def trilinear(a):
+    """After the nearest-neighbour runs: 512^3 once more, trilinear."""
+    return () if a.lut_only or "512^3" not in a.configs.split(",") else run(fb.config("512^3"), a, _capi.RS_LINEAR)
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=20)
-    ap.add_argument("--lut-only", action="store_true")
-    ap.add_argument("--lut-stats", default=None)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "resample_bench.jsonl"))
-    a = ap.parse_args()
-    if a.lut_only:
-        lut_only(min(a.reps, 5))
-        return
-    lut = lut_stats(a.lut_stats)
-    lines = []
-    for name, cfg, dtype in CONFIGS:
-        lines += run(name, cfg, dtype, _capi.RS_NEAREST, a.reps, lut)
-    lines += run("512^3", "C2", "uint16", _capi.RS_LINEAR, a.reps, lut)
-    with open(a.out, "w") as f:
-        for d in lines:
-            f.write(json.dumps(d) + "\n")
+    fb.main(run, reps=20, configs="512^3,C4", out="profiles/resample_bench.jsonl", mode="w", after=trilinear,
+            extra_args=[("--lut-only", dict(action="store_true")), ("--lut-stats", dict(default=None))])
 
 
 if __name__ == "__main__":

@@ -16,116 +16,72 @@ signal content, also written to profiles/sighist_bench.jsonl.
                    the last digit pass of the select
   signal           'random': uniform over the type; 'constant': one value everywhere -- the two ends of the contention range
   variant          the library the numbers come from when it is not the product build (TISSUE_SCAN_LIB, scripts/build_variant.py)"""
-import argparse
-import json
-import os
 import statistics
-import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
-from tissue_analysis_amd import _capi, synth  # noqa: E402
-from tissue_analysis_amd import device as dev  # noqa: E402
+import featbench as fb
+from tissue_analysis_amd import _capi
 
 
-def run(name, dims, dtype, n_cells, seed, reps, variant):
+def run(cfg, a):
     import torch
-    dtype = np.dtype(dtype)
-    ctx = dev.torch_context(0)
-    v, _ = dev.synth_slab(ctx, dims, dtype, n_cells, seed)
-    torch.cuda.synchronize()
-    ctx.set_volume_device(v.data_ptr(), dtype.itemsize, v.shape, keep=v)
-    nvox = v.numel()
-    ctx.extract(_capi.F_VOLUME, ctx.max_label())
-    count = ctx.labels()[0]
-    present = count > 0
-    top = np.where(present, count - np.uint64(1), np.uint64(0))
-    ranks = np.stack([top // np.uint64(2), (top + np.uint64(1)) // np.uint64(2)], axis=1)
-    ranks[~present] = np.uint64(0xFFFFFFFFFFFFFFFF)
-    probe_labels = ctx.read_probe(v.data_ptr(), nvox * dtype.itemsize, repeats=5)
-    lines = []
-    for sbytes in (1, 2):
-        for content in ("random", "constant"):
-            if sbytes == 1:
-                sig = (torch.randint(0, 256, tuple(v.shape), dtype=torch.uint8, device=v.device) if content == "random"
-                       else torch.full(tuple(v.shape), 200, dtype=torch.uint8, device=v.device))
-            else:
-                sig = (torch.randint(-32768, 32767, tuple(v.shape), dtype=torch.int16, device=v.device) if content == "random"
-                       else torch.full(tuple(v.shape), 20000, dtype=torch.int16, device=v.device))
-            torch.cuda.synchronize()
-            probe_ms = probe_labels + ctx.read_probe(sig.data_ptr(), nvox * sbytes, repeats=5)
-            ctx.set_signal_device(sig.data_ptr(), sbytes, keep=sig)
-            ctx.signal_extract(_capi.SIG_LABELS)
-            ctx.signal_timing()
-            signal_ms = []
-            for _ in range(reps):
-                ctx.signal_extract(_capi.SIG_LABELS)
-                signal_ms.append(ctx.signal_timing())
-            signal_ms = statistics.median(signal_ms)
-            width = 8 * sbytes - 8
-            ctx.sighist_extract(width)
-            ctx.sighist_timing()
-            hist = []
-            for _ in range(reps):
+    with fb.resident(cfg) as (ctx, v, _):
+        nvox = v.numel()
+        ctx.extract(_capi.F_VOLUME, ctx.max_label())
+        count = ctx.labels()[0]
+        present = count > 0
+        top = np.where(present, count - np.uint64(1), np.uint64(0))
+        ranks = np.stack([top // np.uint64(2), (top + np.uint64(1)) // np.uint64(2)], axis=1)
+        ranks[~present] = np.uint64(0xFFFFFFFFFFFFFFFF)
+        probe_labels = fb.read_probe(ctx, v)[0]
+        for sbytes in (1, 2):
+            for content in ("random", "constant"):
+                if sbytes == 1:
+                    sig = (torch.randint(0, 256, tuple(v.shape), dtype=torch.uint8, device=v.device) if content == "random"
+                           else torch.full(tuple(v.shape), 200, dtype=torch.uint8, device=v.device))
+                else:
+                    sig = (torch.randint(-32768, 32767, tuple(v.shape), dtype=torch.int16, device=v.device) if content == "random"
+                           else torch.full(tuple(v.shape), 20000, dtype=torch.int16, device=v.device))
+                torch.cuda.synchronize()
+                probe_ms = probe_labels + fb.read_probe(ctx, sig)[0]
+                ctx.set_signal_device(sig.data_ptr(), sbytes, keep=sig)
+                labels_only = lambda: ctx.signal_extract(_capi.SIG_LABELS)
+                labels_only()
+                ctx.signal_timing()
+                signal_ms = statistics.median(fb.timed(labels_only, ctx.signal_timing, a.reps, warmup=0))
+                width = 8 * sbytes - 8
                 ctx.sighist_extract(width)
-                hist.append(ctx.sighist_timing()[0])
-            counts = ctx.sighist_get()
-            hdebug = ctx.sighist_debug()
-            assert np.array_equal(counts.sum(axis=1), count)
-            ctx.sigrank_extract(ranks)
-            ctx.sighist_timing()
-            rank = []
-            for _ in range(reps):
+                ctx.sighist_timing()
+                hist = fb.timed(lambda: ctx.sighist_extract(width), lambda: ctx.sighist_timing()[0], a.reps, warmup=0)
+                counts = ctx.sighist_get()
+                hdebug = ctx.sighist_debug()
+                assert np.array_equal(counts.sum(axis=1), count)
                 ctx.sigrank_extract(ranks)
-                rank.append(ctx.sighist_timing()[1])
-            values = ctx.sigrank_get()
-            rdebug = ctx.sighist_debug()
-            assert (values[present] != _capi.SIGRANK_NONE).all()
-            h, r = statistics.median(hist), statistics.median(rank)
-            nbytes = nvox * (dtype.itemsize + sbytes)
-            lines.append(dict(config=name, dims=list(dims), labels_dtype=dtype.name, signal_dtype="uint%d" % (8 * sbytes), signal=content,
-                              variant=variant, slots=_capi.SIGHIST_SLOTS if variant is None else None,
-                              hist_ms=round(h, 4), hist_ms_min=round(min(hist), 4), hist_ms_max=round(max(hist), 4),
-                              rank_ms=round(r, 4), rank_ms_min=round(min(rank), 4), rank_ms_max=round(max(rank), 4), reps=reps,
-                              bytes=nbytes, bytes_per_voxel=nbytes // nvox, hist_tbs=round(nbytes / (h * 1e-3) / 1e12, 3),
-                              read_probe_ms=round(probe_ms, 4), read_probe_tbs=round(nbytes / (probe_ms * 1e-3) / 1e12, 3),
-                              hist_over_probe=round(h / probe_ms, 3), rank_over_probe=round(r / probe_ms, 3),
-                              signal_pass_ms=round(signal_ms, 4), hist_over_signal=round(h / signal_ms, 3),
-                              rank_over_signal=round(r / signal_ms, 3), voxels=nvox, rows_in_use=int(present.sum()),
-                              counters_in_use=int((counts > 0).sum()), spills=hdebug["spills"], rank_spills=rdebug["spills"],
-                              tiles_per_group=hdebug["tiles_per_group"], groups=hdebug["groups"]))
-            del sig
-            torch.cuda.empty_cache()
-    ctx.close()
-    del v
-    torch.cuda.empty_cache()
-    return lines
+                ctx.sighist_timing()
+                rank = fb.timed(lambda: ctx.sigrank_extract(ranks), lambda: ctx.sighist_timing()[1], a.reps, warmup=0)
+                values = ctx.sigrank_get()
+                rdebug = ctx.sighist_debug()
+                assert (values[present] != _capi.SIGRANK_NONE).all()
+                h, r = statistics.median(hist), statistics.median(rank)
+                nbytes = nvox * (cfg.dtype.itemsize + sbytes)
+                yield dict(config=cfg.name, dims=list(cfg.dims), labels_dtype=cfg.dtype.name, signal_dtype="uint%d" % (8 * sbytes),
+                           signal=content, variant=a.variant, slots=_capi.SIGHIST_SLOTS if a.variant is None else None,
+                           **fb.spread("hist_ms", hist), **fb.spread("rank_ms", rank), reps=a.reps, bytes=nbytes,
+                           bytes_per_voxel=nbytes // nvox, hist_tbs=round(nbytes / (h * 1e-3) / 1e12, 3),
+                           read_probe_ms=round(probe_ms, 4), read_probe_tbs=round(nbytes / (probe_ms * 1e-3) / 1e12, 3),
+                           hist_over_probe=round(h / probe_ms, 3), rank_over_probe=round(r / probe_ms, 3),
+                           signal_pass_ms=round(signal_ms, 4), hist_over_signal=round(h / signal_ms, 3),
+                           rank_over_signal=round(r / signal_ms, 3), voxels=nvox, rows_in_use=int(present.sum()),
+                           counters_in_use=int((counts > 0).sum()), spills=hdebug["spills"], rank_spills=rdebug["spills"],
+                           tiles_per_group=hdebug["tiles_per_group"], groups=hdebug["groups"])
+                del sig
+                torch.cuda.empty_cache()
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=10)
-    ap.add_argument("--configs", default="C4,512^3")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "sighist_bench.jsonl"))
-    ap.add_argument("--variant", default=None, help="a name for the library under TISSUE_SCAN_LIB, recorded with every line")
-    a = ap.parse_args()
-    lines = []
-    for name in a.configs.split(","):
-        if name == "C4":
-            c = synth.CONFIGS["C4"]
-            new = run(name, c["dims"], c["dtype"], c["n_cells"], c["seed"], a.reps, a.variant)
-        else:
-            c = synth.CONFIGS["C2"]
-            new = run("512^3", c["dims"], "uint16", c["n_cells"], c["seed"], a.reps, a.variant)
-        for d in new:
-            print(json.dumps(d), flush=True)
-        lines += new
-    with open(a.out, "w") as f:
-        for d in lines:
-            f.write(json.dumps(d) + "\n")
+    fb.main(run, reps=10, configs="C4,512^3", out="profiles/sighist_bench.jsonl", mode="w",
+            extra_args=[("--variant", dict(default=None, help="a name for the library under TISSUE_SCAN_LIB, recorded with every line"))])
 
 
 if __name__ == "__main__":

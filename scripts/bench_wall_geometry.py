@@ -13,87 +13,40 @@ this one process on the same resident volume and extraction; every figure is a m
   ratio            median geo_ms / median signal_walls_ms
   spread           (max - min) / median of each pass's per-round medians
   pairs, faces     rows of the table, faces they hold; spills: records that missed the LDS table in the last pass"""
-import argparse
-import json
-import os
 import statistics
-import sys
 
-import numpy as np
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
-from tissue_analysis_amd import _capi, synth  # noqa: E402
-from tissue_analysis_amd import device as dev  # noqa: E402
-
-TBS = 8e12
+import featbench as fb
+from tissue_analysis_amd import _capi
 
 
-def run(name, dims, dtype, n_cells, seed, reps, rounds):
+def run(cfg, a):
     import torch
-    dtype = np.dtype(dtype)
-    ctx = dev.torch_context(0)
-    vol, L = dev.synth_slab(ctx, dims, dtype, n_cells, seed)
-    g = torch.Generator(device="cuda").manual_seed(seed)
-    sig = torch.randint(0, 256, tuple(dims), generator=g, device="cuda", dtype=torch.int32).to(torch.uint8)
-    torch.cuda.synchronize()
-    ctx.set_volume_device(vol.data_ptr(), dtype.itemsize, vol.shape, keep=vol)
-    ctx.set_signal_device(sig.data_ptr(), 1, keep=sig)
-    ctx.extract(_capi.F_ALL, L)
-    pairs = ctx.adjacency_size()
-    vol_bytes = vol.numel() * vol.element_size()
-    geo, walls, probe = [], [], []
-    for _ in range(rounds):
-        for _ in range(3):
-            ctx.wallgeo_extract()
-        ms = []
-        for _ in range(reps):
-            ctx.wallgeo_extract()
-            ms.append(ctx.wallgeo_timing())
-        geo.append(statistics.median(ms))
-        for _ in range(3):
-            ctx.signal_extract(_capi.SIG_WALLS)
-        ms = []
-        for _ in range(reps):
-            ctx.signal_extract(_capi.SIG_WALLS)
-            ms.append(ctx.signal_timing())
-        walls.append(statistics.median(ms))
-        probe.append(ctx.read_probe(vol.data_ptr(), vol_bytes, repeats=5))
-    spills = ctx.wallgeo_spills()
-    fwd, rev, _, _ = ctx.wallgeo_get()
+    with fb.resident(cfg) as (ctx, vol, L):
+        sig = fb.random_signal(cfg.dims, 1, torch.Generator(device="cuda").manual_seed(cfg.seed))
+        torch.cuda.synchronize()
+        ctx.set_signal_device(sig.data_ptr(), 1, keep=sig)
+        ctx.extract(_capi.F_ALL, L)
+        pairs = ctx.adjacency_size()
+        vol_bytes = vol.numel() * vol.element_size()
+        geo, walls, probe = [], [], []
+        for _ in range(a.rounds):
+            geo.append(statistics.median(fb.timed(ctx.wallgeo_extract, ctx.wallgeo_timing, a.reps)))
+            walls.append(statistics.median(fb.timed(lambda: ctx.signal_extract(_capi.SIG_WALLS), ctx.signal_timing, a.reps)))
+            probe.append(fb.read_probe(ctx, vol)[0])
+        spills = ctx.wallgeo_spills()
+        fwd, rev, _, _ = ctx.wallgeo_get()
     k, w = statistics.median(geo), statistics.median(walls)
-    line = dict(config=name, dims=list(dims), labels=dtype.name, reps=reps, rounds=rounds,
+    return dict(config=cfg.name, dims=list(cfg.dims), labels=cfg.dtype.name, reps=a.reps, rounds=a.rounds,
                 geo_ms=[round(v, 4) for v in geo], signal_walls_ms=[round(v, 4) for v in walls],
                 read_probe_ms=[round(v, 4) for v in probe], geo_ms_median=round(k, 4), signal_walls_ms_median=round(w, 4),
                 ratio=round(k / w, 3), geo_spread=round((max(geo) - min(geo)) / k, 4), signal_spread=round((max(walls) - min(walls)) / w, 4),
                 pairs=int(pairs), faces=int(fwd.sum() + rev.sum()), spills=int(spills), bytes=vol_bytes,
-                frac_8tbs=round(vol_bytes / (k * 1e-3) / TBS, 4), geo_over_probe=round(k / statistics.median(probe), 3))
-    ctx.close()
-    del vol, sig
-    torch.cuda.empty_cache()
-    return line
+                frac_8tbs=round(vol_bytes / (k * 1e-3) / fb.TBS, 4), geo_over_probe=round(k / statistics.median(probe), 3))
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=30)
-    ap.add_argument("--rounds", type=int, default=2)
-    ap.add_argument("--configs", default="C4,512^3")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "wall_geometry_bench.jsonl"))
-    a = ap.parse_args()
-    lines = []
-    for name in a.configs.split(","):
-        if name == "C4":
-            c = synth.CONFIGS["C4"]
-            lines.append(run("C4", c["dims"], c["dtype"], c["n_cells"], c["seed"], a.reps, a.rounds))
-        else:
-            c = synth.CONFIGS["C2"]
-            lines.append(run("512^3", c["dims"], "uint16", c["n_cells"], c["seed"], a.reps, a.rounds))
-        print(json.dumps(lines[-1]), flush=True)
-    with open(a.out, "w") as f:
-        for d in lines:
-            f.write(json.dumps(d) + "\n")
+    fb.main(run, reps=30, configs="C4,512^3", out="profiles/wall_geometry_bench.jsonl", mode="w",
+            extra_args=[("--rounds", dict(type=int, default=2))])
 
 
 if __name__ == "__main__":
